@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the MI355X back end (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 Primary metric   : SE(3) edges optimised / s   on BASELINE config 2 (1k nodes / 5k edges, 20 LM iterations)
 `secondary`      : node pairs matched / s      on BASELINE config 3 (512 pairs x 1000 ORB-256, 500 hypotheses)
@@ -20,6 +20,9 @@ the figure WITH that memory is reported beside it as `repeat_identical`, the fir
 
 Output: the full record goes to stderr and to gpurun_out/bench_full.json; the LAST line on stdout - the only one - is the compact record
 (`compact_record`, < 6 KB, no prose) the driver parses.
+--dump-outputs DIR writes what the primary's last timed step computed, as a caller of uzl_pgo_store receives it (`pgo_outputs`: the
+errors of the edges that entered the solve, no NaN markers of skipped ones; `dump_outputs`), so that two builds can be compared output
+for output: the inputs are seeded, identical from run to run for the same arguments.
 With --gpus N > 1 (one rank per GPU under torch.distributed.run; when RANK is not set this script starts the ranks itself, before
 anything touches the GPU) every rank solves its own independent graph / its own shard of node pairs: the path partitions into
 independent units, so there is no data-path collective and scaling is weak; torch.distributed is used only for the barrier and
@@ -74,10 +77,15 @@ def parse():
     ap.add_argument("--sharded-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--online-cpu-seconds", type=float, default=25.0, help="budget of the CPU replay of config 5 (online_c5.cpu_baseline)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="budget of each CPU-baseline sample of the primary / secondary block")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the primary's last timed step's outputs to DIR/<name>.npy (float32 / float64, <= 64 MB in all)")
     ap.add_argument("--rehearse-gloo", action="store_true",
                     help="rehearsal of the N > 1 code paths on a box with fewer GPUs than ranks: process group over gloo, rank r on device "
                          "r %% device_count (RCCL refuses two ranks on one device); the numbers mean nothing")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def spawn_ranks(a):
@@ -215,6 +223,34 @@ def estimate_phases(applies):
                 fraction={k: round(us[n] / tot, 4) for k, n in zip(short, names)}, bound=bound)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays, limit=DUMP_LIMIT_BYTES):
+    """`--dump-outputs DIR`: every array as DIR/<name>.npy, float64 kept, anything else as float32.  Above `limit` bytes in all, the
+    same fixed, seeded sample of leading-axis rows is taken of every array over 64 KB (their row indices in DIR/<name>_rows.npy)."""
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, np.float64 if np.asarray(v).dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    sampled = sum(v.nbytes + 8 * len(v) for v in arrays.values() if v.ndim > 0)          # a sampled row costs its bytes + its f64 index
+    for k, v in arrays.items():
+        if total > limit and v.ndim > 0 and v.nbytes > 1 << 16:
+            keep = max(1, int(len(v) * (limit * 0.9 / sampled)))
+            rows = np.sort(np.random.default_rng(20240607).choice(len(v), keep, replace=False))
+            np.save(os.path.join(d, k + "_rows.npy"), rows.astype(np.float64))
+            v = v[rows]
+        np.save(os.path.join(d, k + ".npy"), v)
+    return sorted(arrays)
+
+
+def pgo_outputs(stored, st):
+    """What a caller of the primary's path receives from one solve, as `--dump-outputs` writes it: poses (n x 12), edge_used (1 = the
+    input edge entered the solve), edge_error = ||e|| of the edges that entered the solve, in input order (uzl_pgo_store marks a
+    skipped edge's error NaN; edge_used says which those are), and chi2 = (initial, final) of the solve."""
+    poses, err, used = stored
+    return dict(poses=poses, edge_error=err[used != 0], edge_used=used, chi2=np.array([st["chi2_initial"], st["chi2_final"]]))
+
+
 def roof(kernel, bound, achieved, peak, unit, **extra):
     d = dict(kernel=kernel, bound=bound, achieved=round(achieved, 3), peak=peak, unit=unit, frac=round(achieved / peak, 5) if peak else None)
     d.update(extra)
@@ -247,9 +283,9 @@ def pgo_block(capi, synth, dist, dev, a, nodes, edges, steps, warmup, seed, xy=F
     work["edges"] = 0
     t = timed(dist, step, steps)
     t0 = time.perf_counter()
-    poses = pgo.store()[0]
+    stored = pgo.store()                                                      # (poses, edge errors, edge used) of the last timed step
     d2h_ms = 1e3 * (time.perf_counter() - t0)
-    out = dict(g=g, pgo=pgo, t=t, edges=work["edges"], st=dict(work["last"]), h2d_ms=h2d_ms, d2h_ms=d2h_ms, poses=poses,
+    out = dict(g=g, pgo=pgo, t=t, edges=work["edges"], st=dict(work["last"]), h2d_ms=h2d_ms, d2h_ms=d2h_ms, poses=stored[0], stored=stored,
                first=dict(first_solve_ms=round(first_ms, 3), structure_ms=round(st_first["structure_ms"], 3), lm_passes=st_first["lm_passes"]))
     if repeat:
         pgo.set_config(pass_history=0)
@@ -1272,6 +1308,8 @@ def main():
         for k, v in (("batched", batched), ("formats", formats), ("c4_1gpu", c4), ("online_c5", online_c5), ("sharded_c4", sharded_c4)):
             if v is not None:
                 out[k] = v
+        if a.dump_outputs:
+            out["dumped_outputs"] = dump_outputs(a.dump_outputs, pgo_outputs(B["stored"], st))
         emit(out)
     pgo.close()
     if matcher is not None:

@@ -7,6 +7,7 @@ may import this package.  PARITY UNPINNED: the reference ships no golden vectors
 import ctypes as C
 import os
 import subprocess
+import tempfile
 
 import numpy as np
 
@@ -84,13 +85,24 @@ def lib():
 _native = None
 
 
+def native_dir():
+    """oracle/_native/ when this process may write there; otherwise (a checkout the running user cannot write to) a directory of
+    this user's own under the system temporary directory.  The build is made where it runs, so it cannot be prepared in advance."""
+    d = os.path.join(_HERE, "_native")
+    if os.access(d if os.path.isdir(d) else _HERE, os.W_OK):
+        return d
+    return os.path.join(tempfile.gettempdir(), "uzl_oracle_native-%d" % os.getuid())
+
+
 def native_lib():
-    """The same C sources built on THIS machine with -O3 -march=native -fopenmp (oracle/Makefile target `native`): the CPU
-    baseline of bench.py.  Never used as a checker (the portable build is), never shipped (oracle/_native/ is ignored)."""
+    """The same C sources built on THIS machine with -O3 -march=native -fopenmp (oracle/Makefile target `native`, into
+    `native_dir()`): the CPU baseline of bench.py.  Never used as a checker (the portable build is), never shipped
+    (oracle/_native/ is ignored)."""
     global _native
     if _native is None:
-        subprocess.check_call(["make", "-s", "-C", _HERE, "native"])
-        _native = C.CDLL(os.path.join(_HERE, "_native", "libuzl_oracle_native.so"))
+        d = native_dir()
+        subprocess.check_call(["make", "-s", "-C", _HERE, "native", "NATIVE_DIR=" + d])
+        _native = C.CDLL(os.path.join(d, "libuzl_oracle_native.so"))
         _native.uzlo_pgo_optimize.restype = C.c_int32
         _native.uzlo_has_openmp.restype = C.c_int32
     return _native

@@ -187,6 +187,36 @@ def wire_fixture():
     np.savez_compressed(os.path.join(HERE, "wire_msgs.npz"), **z)
 
 
+def hamming_fixture():
+    """Known-answer vectors of the reference's own Hamming functor (cv::HammingSse, graph_slam_common/thirdparty/include/
+    graph_slam_tools/hammingsse.hpp), evaluated through oracle/_ref/libref_hamming.so (make -C oracle ref, where the reference tree
+    exists).  Per descriptor size: query / train rows and the functor's distance for every (query, train) pair."""
+    import ctypes
+    so = os.path.join(ROOT, "oracle", "_ref", "libref_hamming.so")
+    ref = ctypes.CDLL(so)
+    ref.ref_hamming.restype = ctypes.c_int
+    ref.ref_hamming.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+    rng = np.random.default_rng(2024)
+    z = {}
+    for nbytes in (32, 64, 16):
+        # 16-byte aligned rows (the functor uses aligned 128-bit loads)
+        def aligned(n):
+            raw = np.zeros(n * nbytes + 16, np.uint8)
+            off = (-raw.ctypes.data) % 16
+            return raw[off:off + n * nbytes].reshape(n, nbytes)
+        q = aligned(40); t = aligned(57)
+        q[:] = rng.integers(0, 256, q.shape, dtype=np.uint8); t[:] = rng.integers(0, 256, t.shape, dtype=np.uint8)
+        t[3] = q[5]; t[9] = ~q[5]; q[7] = 0; t[11] = 255              # distance 0, all bits, sparse / dense rows
+        d = np.array([[ref.ref_hamming(q[i].ctypes.data, t[j].ctypes.data, nbytes) for j in range(len(t))] for i in range(len(q))], np.int32)
+        assert np.array_equal(d, np.unpackbits(q[:, None, :] ^ t[None, :, :], axis=2).sum(axis=2)), "functor != popcount of XOR"
+        z[f"q{nbytes}"] = np.array(q); z[f"t{nbytes}"] = np.array(t); z[f"dist{nbytes}"] = d
+    np.savez_compressed(os.path.join(HERE, "hamming_ref.npz"), **z)
+
+
 if __name__ == "__main__":
     match_fixture(); match_deployed_fixture(); ransac_fixture(); pgo_fixture(); filter_fixture(); wire_fixture()
+    if os.path.exists(os.path.join(ROOT, "oracle", "_ref", "libref_hamming.so")):
+        hamming_fixture()
+    else:
+        print("oracle/_ref/libref_hamming.so not built: hamming_ref.npz left as it is")
     print("golden fixtures written to", HERE)

@@ -78,3 +78,53 @@ def test_every_traffic_key_the_bench_reads_is_in_traffic_json():
     have = json.load(open(os.path.join(ROOT, "profiles", "traffic.json")))
     missing = sorted(k for k in keys if not (isinstance(have.get(k), (int, float)) and have[k] > 0))
     assert not missing, missing
+
+
+def test_dump_outputs_types_size_cap_and_fixed_sample(tmp_path):
+    """`--dump-outputs DIR`: one DIR/<name>.npy per array, float64 kept and every other type as float32; above the cap the same seeded
+    row sample of every large array, so that two runs (two builds) compare element for element."""
+    import numpy as np
+    import bench
+    poses = np.random.default_rng(3).random((5000, 12)); used = (poses[:, 0] > 0.5).astype(np.uint8); chi2 = np.array([2.5, 1.25])
+    names = bench.dump_outputs(str(tmp_path / "small"), dict(poses=poses, edge_used=used, chi2=chi2))
+    assert names == ["chi2", "edge_used", "poses"]
+    got = {n: np.load(tmp_path / "small" / (n + ".npy")) for n in names}
+    assert got["poses"].dtype == np.float64 and np.array_equal(got["poses"], poses)
+    assert got["edge_used"].dtype == np.float32 and np.array_equal(got["edge_used"], used)
+    assert np.array_equal(got["chi2"], chi2)
+    limit = 200_000
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), dict(poses=poses, edge_used=used, chi2=chi2), limit=limit)
+        assert sum(f.stat().st_size for f in (tmp_path / run).iterdir()) <= limit
+    for f in ("poses.npy", "poses_rows.npy", "edge_used.npy", "chi2.npy"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+    rows = np.load(tmp_path / "a" / "poses_rows.npy").astype(np.int64)
+    assert 0 < len(rows) < len(poses) and np.array_equal(np.load(tmp_path / "a" / "poses.npy"), poses[rows])
+    assert np.array_equal(np.load(tmp_path / "a" / "chi2.npy"), chi2)                       # small arrays stay whole
+
+
+def test_steps_and_dump_outputs_arguments():
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=60)
+    assert r.returncode != 0 and "--steps" in r.stderr
+    import bench
+    sys.argv, argv = ["bench.py", "--steps", "7", "--warmup", "0", "--dump-outputs", "d"], sys.argv
+    try:
+        a = bench.parse()
+    finally:
+        sys.argv = argv
+    assert a.steps == 7 and a.warmup == 0 and a.dump_outputs == "d"
+
+
+def test_dumped_pgo_outputs_are_finite():
+    """uzl_pgo_store reports NaN as the error of an edge that did not enter the solve; the dump keeps the errors of the edges that did
+    (edge_used, full length, says which), so every dumped value is finite and each error still maps to its input edge."""
+    import numpy as np
+    import bench
+    poses = np.arange(36.).reshape(3, 12)
+    err = np.array([np.nan, 0.5, 0.25, np.nan, 1.0]); used = np.array([0, 1, 1, 0, 1], np.uint8)
+    o = bench.pgo_outputs((poses, err, used), dict(chi2_initial=4.0, chi2_final=1.5))
+    assert sorted(o) == ["chi2", "edge_error", "edge_used", "poses"]
+    assert np.array_equal(o["edge_error"], [0.5, 0.25, 1.0]) and np.array_equal(o["edge_used"], used)
+    assert np.array_equal(o["chi2"], [4.0, 1.5]) and np.array_equal(o["poses"], poses)
+    assert all(np.isfinite(np.asarray(v, np.float64)).all() for v in o.values())

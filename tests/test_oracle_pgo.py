@@ -179,3 +179,25 @@ def test_odom_convert_known_answers(oracle):
     # no elapsed time: wheel velocities are zero, so is the motion
     assert np.array_equal(oracle.odom_convert(0.3, 0.1, 0.2, 0.0), [0.0, 0.0, 0.0])
     assert np.array_equal(oracle.odom_convert(0.3, 0.1, 0.0, 0.0), [0.0, 0.0, 0.0])
+
+
+def test_native_baseline_builds_where_it_runs(oracle, tmp_path, monkeypatch):
+    """bench.py's CPU baseline (oracle.native_lib: the same sources, -march=native -fopenmp) is compiled by the process that runs it:
+    into oracle/_native/ when the checkout is writable, else into a directory of the user's own under the temporary directory.  Its
+    solve agrees with the portable checker's."""
+    import os
+    from uzliti_slam_amd import synth
+    real_access = os.access
+    monkeypatch.setattr(oracle.os, "access", lambda p, m: False if os.path.realpath(p).startswith(oracle._HERE) else real_access(p, m))
+    monkeypatch.setattr(oracle.tempfile, "gettempdir", lambda: str(tmp_path))
+    assert oracle.native_dir() == os.path.join(str(tmp_path), "uzl_oracle_native-%d" % os.getuid())
+    monkeypatch.undo()
+    g = synth.make_pose_graph(100, 300)
+    fl = oracle.flatten_graph(g["nodes_pose"], g["nodes_fixed"], g["edges"])
+    fixed, _ = oracle.set_fixed_nodes(fl["fixed"], fl["ij"])
+    args = (fl["poses"], fixed, fl["ij"], fl["meas"], fl["info"], fl["robust"])
+    P, st = oracle.pgo_optimize(*args, iterations=10)
+    Pn, stn = oracle.pgo_optimize(*args, iterations=10, native_threads=2)
+    assert os.path.exists(os.path.join(oracle.native_dir(), "libuzl_oracle_native.so"))
+    assert (stn["iterations_done"], stn["lm_trials"]) == (st["iterations_done"], st["lm_trials"])
+    assert np.allclose(Pn, P, rtol=0, atol=1e-9) and abs(stn["chi2_final"] - st["chi2_final"]) <= 1e-9 * st["chi2_final"]
