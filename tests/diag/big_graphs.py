@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Diagnostic: solve time of very large loopy graphs (beyond BASELINE's sizes) - where the dense level-2 operator (UZL_ML_COMP4_MAX in the
-diagnostic build) stops paying.   python tests/diag/big_graphs.py [n:e ...]"""
+"""Diagnostic: solve time of very large loopy graphs (beyond BASELINE's sizes) - where the dense level-2 operator (kComp4Max, uzl_pgo.hip)
+stops paying.   python tests/diag/big_graphs.py [n:e ...]"""
 import os
 import sys
 import time

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Diagnostic (diagnostic build, UZL_ML_REFRESH_REL in the environment): solve time and PCG iterations of a list of graph shapes - the
-lazy-refresh threshold's effect beyond the two benchmark graphs.   UZL_ML_REFRESH_REL=3e-2 python tests/diag/refresh_shapes.py"""
+"""Diagnostic: solve time and PCG iterations of a list of graph shapes beyond the two benchmark graphs.
+   python tests/diag/refresh_shapes.py"""
 import os
 import sys
 import time

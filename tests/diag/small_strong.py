@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Diagnostic: small chain-like graphs with the reduced system in row order / by strong aggregates (UZL_SCHUR_STRONG_MIN lowered, diagnostic build)."""
+"""Diagnostic: small chain-like graphs with the reduced system in row order / by strong aggregates (uzl_pgo_cfg::reduced_numbering 1 / 2)."""
 import os
 import sys
 import time

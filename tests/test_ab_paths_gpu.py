@@ -27,7 +27,7 @@ def _run(**env):
 def test_alternative_kernel_paths_agree():
     ref = _run()
     # the shipped library ignores the switches: same digests as the diagnostic build without any switch set
-    e = dict(os.environ, UZL_KNN2_VALU="1", UZL_VOTE_VALU="1", UZL_ML_NO_COMP4="1", UZL_ML_ADDITIVE="1")
+    e = dict(os.environ, UZL_KNN2_VALU="1", UZL_VOTE_VALU="1", UZL_ML_NO_COMP4="1")
     e.pop("UZL_LIB", None)
     out = subprocess.run([sys.executable, os.path.join(HERE, "_ab_worker.py")], env=e, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]

@@ -103,10 +103,7 @@ __global__ __launch_bounds__(kGateBlock) void gate_kernel(GateArgs a)
 {
     const int k = blockIdx.x * kGateBlock + threadIdx.x;
     if (k >= a.n_query) return;
-    if (!a.run[k]) {
-        if (!a.keep_unrun) { a.pre_ok[k] = 0; a.heur_ok[k] = 0; a.dist[k] = -1.; }
-        return;
-    }
+    if (!a.run[k]) return;                                  // (its outputs hold gate_wave_kernel's / gate_bound_kernel's verdicts)
     a.pre_ok[k] = 0; a.heur_ok[k] = 0; a.dist[k] = -1.;
     const uzl_gate_edge c = a.cand[k];
     if (!(c.matching_score >= a.min_score)) return;                                  // :798

@@ -29,7 +29,6 @@ struct GateArgs {
     uint8_t* heur_ok;               // checkEdgeHeuristic (:1064-1085)
     double* dist;                   // astar path length, DBL_MAX = not reachable, -1 = not searched
     int32_t* overflow;              // set when a heap ran out of space
-    int32_t keep_unrun;             // 1: leave the outputs of candidates with run == 0 alone (they hold gate_wave_kernel's verdicts)
     int32_t skip_decided;           // 1: no search for a candidate whose verdict the straight-line distance already decides (dist = -2)
 };
 

@@ -1,9 +1,9 @@
 // match_kernels.hip — gfx950 kernels of the edge-estimation half.
 //
-//   knn2_kernel      M1  brute-force 2-NN Hamming match (feature_transformation_estimator.cpp:38,58):
-//                        one lane per query descriptor (registers), train descriptors streamed through
-//                        the scalar cache (wave-uniform address -> s_load), v_xor + v_bcnt accumulate,
-//                        top-2 kept as packed (distance<<20 | trainIdx) keys with v_med3/v_min.
+//   knn2_mfma_kernel M1  brute-force 2-NN Hamming match (feature_transformation_estimator.cpp:38,58) on the
+//                        matrix cores (int8 MFMA emits the sort key); knn2_lds_kernel is its vector-ALU twin
+//                        (v_xor + v_bcnt), knn2_generic_kernel serves other descriptor widths.  Top-2 kept as
+//                        packed (distance << kIdxBits | trainIdx) keys with v_med3/v_min.
 //   estimate_kernel  M2..M9  one workgroup per node pair: sensor-pair selection (:73-86), ratio test
 //                        (:65-71), 3-D filter (:101-112), sort by (distance, queryIdx) (:114), gather into
 //                        an LDS tile (:118-124), PROSAC with one hypothesis per lane and LDS-broadcast
@@ -45,40 +45,6 @@ constexpr int kBlock = 256;
 __device__ __forceinline__ uint32_t second_of(uint32_t best1, uint32_t best2, uint32_t key)
 {
     return min(best2, max(best1, key));
-}
-
-template <int W>
-__global__ __launch_bounds__(kBlock) void knn2_kernel(const uint32_t* __restrict__ arena,
-                                                      const Combo* __restrict__ combos,
-                                                      uint2* __restrict__ knn)
-{
-    const Combo c = combos[blockIdx.y];
-    if (c.words != W) return;                                  // other instantiation's combo
-    const int q0 = blockIdx.x * kBlock;
-    if (q0 >= c.nq) return;                                    // wave-uniform
-    const int q = q0 + (int)threadIdx.x;
-    const int qc = q < c.nq ? q : c.nq - 1;
-    const uint32_t* __restrict__ qd = arena + c.desc_to_off + (size_t)qc * W;
-    uint32_t qw[W];
-#pragma unroll
-    for (int k = 0; k < W; k += 4) {
-        const uint4 v = *reinterpret_cast<const uint4*>(qd + k);
-        qw[k] = v.x; qw[k + 1] = v.y; qw[k + 2] = v.z; qw[k + 3] = v.w;
-    }
-    uint32_t best1 = 0xffffffffu, best2 = 0xffffffffu;
-    const uint32_t* __restrict__ td = arena + c.desc_from_off;  // wave-uniform base
-    const int nt = c.nt;
-#pragma unroll 4
-    for (int t = 0; t < nt; ++t) {
-        const uint32_t* __restrict__ tr = td + (size_t)t * W;   // wave-uniform -> scalar loads
-        uint32_t d = 0;
-#pragma unroll
-        for (int k = 0; k < W; ++k) d += __popc(qw[k] ^ tr[k]);
-        const uint32_t key = (d << kIdxBits) | (uint32_t)t;
-        best2 = second_of(best1, best2, key);
-        best1 = min(best1, key);
-    }
-    if (q < c.nq) knn[c.knn_off + q] = make_uint2(best1, best2);
 }
 
 // LDS variant: the train set is staged tile by tile in LDS (coalesced 16-B loads) and every lane reads each train
@@ -181,9 +147,7 @@ __device__ __forceinline__ int med3_i32(int a, int b, int c) { return max(min(a,
 constexpr int kKeyBits = 12, kSweep = 1 << kKeyBits;
 constexpr int kMmInvalid = 1023 << kKeyBits;      // key of a padded train row before |q| is added: above every real key
 
-// RB: 32-row train blocks a wave works on side by side (the same query fragments against two row fragments): with UT = 1 (W = 16: the
-// query fragments of one 32-query tile already take 64 VGPRs) a wave would otherwise run ONE chain of sixteen dependent MFMAs per block.
-template <int W, int UT, int RB = 1>
+template <int W, int UT>
 __global__ __launch_bounds__(kBlock) void knn2_mfma_kernel(const uint32_t* __restrict__ arena,
                                                            const Combo* __restrict__ combos,
                                                            uint2* __restrict__ knn)
@@ -259,41 +223,34 @@ __global__ __launch_bounds__(kBlock) void knn2_mfma_kernel(const uint32_t* __res
             }
             __syncthreads();
             const int rows_here = min(TR, nt_s - t0);
-            static_assert(TR % (32 * RB) == 0, "a chunk holds whole groups of row blocks (rows past the train set carry the invalid key)");
-            for (int r0 = 0; r0 < rows_here; r0 += 32 * RB) {
+            static_assert(TR % 32 == 0, "a chunk holds whole row blocks (rows past the train set carry the invalid key)");
+            for (int r0 = 0; r0 < rows_here; r0 += 32) {
                 // rows of this lane's registers: 8 (reg>>2) + 4 h + (reg&3): their accumulators start at the rows' key words
-                v16i32 acc[RB][UT];
+                v16i32 acc[UT];
 #pragma unroll
-                for (int rb = 0; rb < RB; rb++)
+                for (int g4 = 0; g4 < 4; g4++) {
+                    const v4i32 rr = *reinterpret_cast<const v4i32*>(sR + r0 + 8 * g4 + 4 * h);
 #pragma unroll
-                    for (int g4 = 0; g4 < 4; g4++) {
-                        const v4i32 rr = *reinterpret_cast<const v4i32*>(sR + r0 + 32 * rb + 8 * g4 + 4 * h);
+                    for (int j = 0; j < 4; j++)
 #pragma unroll
-                        for (int j = 0; j < 4; j++)
-#pragma unroll
-                            for (int u = 0; u < UT; u++) acc[rb][u][4 * g4 + j] = rr[j];
-                    }
+                        for (int u = 0; u < UT; u++) acc[u][4 * g4 + j] = rr[j];
+                }
                 const uint8_t* arow = sA + (r0 + col) * ROWB + 16 * h;
 #pragma unroll
                 for (int s_ = 0; s_ < W; s_++) {
+                    const v4i32 a = *reinterpret_cast<const v4i32*>(arow + 32 * s_);
 #pragma unroll
-                    for (int rb = 0; rb < RB; rb++) {
-                        const v4i32 a = *reinterpret_cast<const v4i32*>(arow + 32 * rb * ROWB + 32 * s_);
-#pragma unroll
-                        for (int u = 0; u < UT; u++) acc[rb][u] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, bf[u][s_], acc[rb][u], 0, 0, 0);
-                    }
+                    for (int u = 0; u < UT; u++) acc[u] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, bf[u][s_], acc[u], 0, 0, 0);
                 }
 #pragma unroll
-                for (int rb = 0; rb < RB; rb++)
+                for (int k = 0; k < 16; k++) {
 #pragma unroll
-                    for (int k = 0; k < 16; k++) {
-#pragma unroll
-                        for (int u = 0; u < UT; u++) {
-                            const int kk = acc[rb][u][k];                           // (|t| - 2 <t, q>) << 12 | t: the matrix cores built the key
-                            b2[u] = med3_i32(b1[u], b2[u], kk);
-                            b1[u] = min(b1[u], kk);
-                        }
+                    for (int u = 0; u < UT; u++) {
+                        const int kk = acc[u][k];                                   // (|t| - 2 <t, q>) << 12 | t: the matrix cores built the key
+                        b2[u] = med3_i32(b1[u], b2[u], kk);
+                        b1[u] = min(b1[u], kk);
                     }
+                }
             }
         }
         // ---- this sweep's winners as full keys (padded rows stay the missing-neighbour sentinel), merged into the winners so far
@@ -1089,27 +1046,15 @@ void launch_knn2(const uint32_t* arena, const Combo* combos, int n_combos, int m
 {
     if (n_combos <= 0 || max_nq <= 0) return;
     dim3 grid((max_nq + kBlock - 1) / kBlock, n_combos);
-    static const bool scalar_path = diag_flag("UZL_KNN2_SCALAR");   // A/B switch: train rows by scalar loads
-    static const bool valu_path = diag_flag("UZL_KNN2_VALU");       // A/B switch: xor / popcount on the vector ALU (LDS-staged)
-    if (scalar_path) {
-        if (has8) hipLaunchKernelGGL(knn2_kernel<8>, grid, dim3(kBlock), 0, s, arena, combos, knn);
-        if (has16) hipLaunchKernelGGL(knn2_kernel<16>, grid, dim3(kBlock), 0, s, arena, combos, knn);
-    } else if (valu_path) {
+    static const bool valu_path = diag_flag("UZL_KNN2_VALU");       // xor / popcount on the vector ALU (LDS-staged): the bit-exactness reference
+    if (valu_path) {
         if (has8) hipLaunchKernelGGL((knn2_lds_kernel<8, 1>), grid, dim3(kBlock), 0, s, arena, combos, knn);
         if (has16) hipLaunchKernelGGL((knn2_lds_kernel<16, 1>), grid, dim3(kBlock), 0, s, arena, combos, knn);
     } else {
-        // matrix-core path: 256 (W = 8) / 128 (W = 16) queries per workgroup
-        static const int ut8 = diag_int("UZL_KNN2_UT", 2);                     // A/B switch: 32-query tiles per wave (W = 8)
-        if (has8 && ut8 == 4) hipLaunchKernelGGL((knn2_mfma_kernel<8, 4>), dim3((max_nq + 511) / 512, n_combos), dim3(kBlock), 0, s, arena, combos, knn);
-        else if (has8 && ut8 == 3) hipLaunchKernelGGL((knn2_mfma_kernel<8, 3>), dim3((max_nq + 383) / 384, n_combos), dim3(kBlock), 0, s, arena, combos, knn);
-        else if (has8) hipLaunchKernelGGL((knn2_mfma_kernel<8, 2>), dim3((max_nq + 255) / 256, n_combos), dim3(kBlock), 0, s, arena, combos, knn);
-        // A/B switch (diagnostic build): two 32-row blocks side by side for W = 16, i.e. two independent MFMA chains per wave instead of one.
-        // Measured slower (512 pairs, 64-byte descriptors: 300 keypoints 0.0422 -> 0.0464 ms, 1000 keypoints 0.262 -> 0.309 ms): the single
-        // chain was not what the kernel waited for - at 1000 keypoints W = 16 reaches the same 0.40 of the int8 peak as W = 8 with two chains
-        // (vector ALU and LDS port beside the matrix pipe: DESIGN_APPENDIX.md, round 5)
-        static const int rb16 = diag_int("UZL_KNN2_RB16", 1);
-        if (has16 && rb16 == 2) hipLaunchKernelGGL((knn2_mfma_kernel<16, 1, 2>), dim3((max_nq + 127) / 128, n_combos), dim3(kBlock), 0, s, arena, combos, knn);
-        else if (has16) hipLaunchKernelGGL((knn2_mfma_kernel<16, 1>), dim3((max_nq + 127) / 128, n_combos), dim3(kBlock), 0, s, arena, combos, knn);
+        // matrix-core path: 256 (W = 8: two 32-query tiles per wave) / 128 (W = 16: one tile per wave, one MFMA chain per row block;
+        // two chains side by side measured slower, DESIGN_APPENDIX.md round 5) queries per workgroup
+        if (has8) hipLaunchKernelGGL((knn2_mfma_kernel<8, 2>), dim3((max_nq + 255) / 256, n_combos), dim3(kBlock), 0, s, arena, combos, knn);
+        if (has16) hipLaunchKernelGGL((knn2_mfma_kernel<16, 1>), dim3((max_nq + 127) / 128, n_combos), dim3(kBlock), 0, s, arena, combos, knn);
     }
     if (has_generic) hipLaunchKernelGGL(knn2_generic_kernel, grid, dim3(kBlock), 0, s, arena, combos, knn);
 }

@@ -234,8 +234,12 @@ int batch_optimize_lm(LmRun*& R, const std::vector<uzl_pgo*>& hs, int resident, 
 constexpr int kSchurStrongOneMax = 256;                // strong aggregates: up to this many groups as ONE level (level-1 path), beyond in blocks of 4 (pgo_schur.hpp)
 constexpr int kSchurStrongMin = 32;                   // separators from which on the reduced system is numbered by strong aggregates
 extern const int kUpperNs;                            // Newton-Schulz steps of the dense levels above the composite level
-extern const bool kAlwaysRefresh;                     // A/B switches (diagnostic build)
-extern const double kRefreshRel, kRefreshRelSync, kLambdaRetake;
-extern const int kGraphPairs;                         // one long PCG replay = 2 x kGraphPairs iterations
+// lazy refresh of the multilevel preconditioner (lm_refresh): rebuilt when the last step moved chi2 by more than kRefreshRel ... and,
+// where the rebuild is synchronous (large loopy graphs: its GEMMs are 1.4 ms at 10k / 50k, 7 ms at 20k / 100k, in front of the solve),
+// by the chi2 rule only while the problem still changes wholesale (kRefreshRelSync), the PCG-rate rule (kRateDrop, pgo_lm.hpp) from then on
+constexpr double kRefreshRel = 1e-3;
+constexpr double kRefreshRelSync = 3e-2;
+constexpr double kLambdaRetake = 32.;                 // lambda grown by this factor since the inverses were taken: take them again
+constexpr int kGraphPairs = 8;                        // one long PCG replay = 2 x kGraphPairs iterations
 constexpr int kShortPairs = 2;                        // ... a short one 2 x kShortPairs
 }  // namespace uzl

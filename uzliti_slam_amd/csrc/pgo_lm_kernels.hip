@@ -33,7 +33,7 @@ __device__ __forceinline__ void lm_head_decide(const LmSlot& S, LmDev* lm, int p
         }
         lm->adopted = 0;
         if (lm->pending) { lm->ix ^= 1; lm->pending = 0; lm->adopted = 1; }      // the copy built during the last iteration
-        if (lm_refresh(lm->it, lm->iterations, lm->always_refresh != 0, lm->sync_rebuild != 0, lm->last_rel, lm->refresh_rel, lm->rate_ref, lm->rate_last, lm->rate_drop)) {
+        if (lm_refresh(lm->it, lm->iterations, lm->sync_rebuild != 0, lm->last_rel, lm->refresh_rel, lm->rate_ref, lm->rate_last, lm->rate_drop)) {
             lm->st_precond_builds++;
             need |= (lm->it == 0 || lm->sync_rebuild) ? (kNeedNumeric | kNeedTrial) : kNeedRebuild;
         }
@@ -202,7 +202,7 @@ __global__ __launch_bounds__(kTailBlk) void lm_tail_kernel(const LmSlot* __restr
         // (Round 4 sent seq_begin ahead behind a fence of its own.)
         __hip_atomic_store(&S.pub->seq_begin, s_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
-    publish_wait_own_stores();                              // this lane's stores have been acknowledged (uzl_common.hpp: gfx9 only without a fence)
+    publish_wait_own_stores();                              // this lane's stores have been acknowledged (pgo_device.hpp: gfx9 only without a fence)
     __syncthreads();
     if (tid == 0) __hip_atomic_store(&S.pub->seq, s_seq, UZL_PUBLISH_SEQ_ORDER, __HIP_MEMORY_SCOPE_SYSTEM);
 }

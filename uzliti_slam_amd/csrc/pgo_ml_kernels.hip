@@ -2464,8 +2464,7 @@ hipError_t k_ml_cg(const PgoDev& D, const MlHot& ml, int agg, const double* p, c
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) dev = 0;
     const bool comp4 = agg != 1 && ml.Cmat != nullptr;
     const bool ypre = comp4 && ml.levels >= 2 && 6 * ml.n[2] <= 4 * 32 * kYU;       // the six rows of Y_2 fit the registers
-    static const bool no_vpre = diag_flag("UZL_NO_VPRE");                            // A/B switch (diagnostic build)
-    const bool vpre = comp4 && !ypre && !init && ml.Vg != nullptr && !no_vpre;      // alpha and rg - alpha Sg prepared once, by ml_alpha_kernel
+    const bool vpre = comp4 && !ypre && !init && ml.Vg != nullptr;                  // alpha and rg - alpha Sg prepared once, by ml_alpha_kernel
     // COMP stages nothing but the gather-level vector: asking for the LDS of the full restrict / top / chain walk (52 KB at 20k
     // vertices) held the kernel at two workgroups per CU - 625 workgroups ran in two rounds
     if (comp4) lds = ml_comp4_lds(ml.n[2]);
@@ -2802,22 +2801,16 @@ static void kl_ml_spmv_t(SLOT sl, const LmShape& sh, int parity, hipStream_t s, 
     if (sh.batch_geometry && ev_a) hipExtLaunchKernelGGL((ml_spmv_lm_kernel<1, kSpmvBatchRpw, kSpmvBatchWaves, SLOT>), dim3(sh.g_spmv, 1, sh.nslots), dim3(64 * kSpmvBatchWaves), 0, s, ev_a, ev_b, 0, sl, parity);
     else if (sh.batch_geometry) hipLaunchKernelGGL((ml_spmv_lm_kernel<1, kSpmvBatchRpw, kSpmvBatchWaves, SLOT>), dim3(sh.g_spmv, 1, sh.nslots), dim3(64 * kSpmvBatchWaves), 0, s, sl, parity);
     else if (sh.agg == 1) {
-        // one row per wave (8 waves) or two (4 waves: half the waves to launch, the same 8 rows per workgroup, the same bits);
-        // UZL_SPMV1_RPW (diagnostic build) picks
-        static const int rpw1 = diag_int("UZL_SPMV1_RPW", 1);
-        if (rpw1 == 2) hipLaunchKernelGGL((ml_spmv_lm_kernel<1, 2, 4, SLOT>), dim3(sh.g_spmv, 1, sh.nslots), dim3(256), 0, s, sl, parity);
-        else hipLaunchKernelGGL((ml_spmv_lm_kernel<1, 1, 8, SLOT>), dim3(sh.g_spmv, 1, sh.nslots), dim3(512), 0, s, sl, parity);
+        // one row per wave, 8 waves (two rows per wave on 4 waves: the same bits, config 2 5.68 -> 6.06 ms)
+        hipLaunchKernelGGL((ml_spmv_lm_kernel<1, 1, 8, SLOT>), dim3(sh.g_spmv, 1, sh.nslots), dim3(512), 0, s, sl, parity);
     }
     else {
         // rows per wave of the AGG = 4 geometry (16 rows per workgroup; the same bits either way).  Up to two such workgroups per CU the
         // kernel is a latency chain per row and twice the lanes per row shorten it (5k / 25k 23.4 -> 21.8 ms, 6k / 30k 25.5 -> 23.8, 8k / 24k
         // 35.8 -> 34.2); beyond, four rows per wave keep three workgroups on a CU (10k / 50k: 626 workgroups in one round; 47.0 -> 49.2 ms
-        // at two rows per wave).  tests/diag/knob_sweep.sh; UZL_SPMV4_RPW (diagnostic build) fixes it
-        static const int rpw_env = diag_int("UZL_SPMV4_RPW", 0);
+        // at two rows per wave)
         static const int two_per_cu = [] { int dev = 0, cu = 256; if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev); return 2 * cu; }();
-        const int rpw = rpw_env ? rpw_env : (sh.g_spmv <= two_per_cu ? 2 : 4);
-        if (rpw == 2) hipLaunchKernelGGL((ml_spmv_lm_kernel<4, 2, 8, SLOT>), dim3(sh.g_spmv, 1, sh.nslots), dim3(512), 0, s, sl, parity);
-        else if (rpw == 1) hipLaunchKernelGGL((ml_spmv_lm_kernel<4, 1, 16, SLOT>), dim3(sh.g_spmv, 1, sh.nslots), dim3(1024), 0, s, sl, parity);
+        if (sh.g_spmv <= two_per_cu) hipLaunchKernelGGL((ml_spmv_lm_kernel<4, 2, 8, SLOT>), dim3(sh.g_spmv, 1, sh.nslots), dim3(512), 0, s, sl, parity);
         else hipLaunchKernelGGL((ml_spmv_lm_kernel<4, 4, kSpmvWaves4, SLOT>), dim3(sh.g_spmv, 1, sh.nslots), dim3(64 * kSpmvWaves4), 0, s, sl, parity);
     }
 }
@@ -2831,7 +2824,6 @@ static hipError_t kl_ml_init_t(SLOT sl, const LmShape& sh, hipStream_t s)
 // which ml_cg kernel serves a hierarchy (the choice k_ml_cg makes per launch), and its dynamic LDS
 void ml_cg_variant(const MlHot& ml, int agg, size_t lds_full, int32_t* variant, int32_t* comp_u, uint64_t* lds)
 {
-    static const bool no_vpre = diag_flag("UZL_NO_VPRE");                            // A/B switch (diagnostic build)
     *comp_u = 0; *lds = lds_full;
     if (agg == 1) {
         if (!ml.Cmat) { *variant = kCgPlain1; return; }
@@ -2843,7 +2835,7 @@ void ml_cg_variant(const MlHot& ml, int agg, size_t lds_full, int32_t* variant, 
     if (!ml.Cmat) { *variant = kCgPlain4; return; }
     *lds = ml_comp4_lds(ml.n[2]);                                                    // COMP stages nothing but the gather-level vector
     const bool ypre = ml.levels >= 2 && 6 * ml.n[2] <= 4 * 32 * kYU;
-    *variant = ypre ? kCgComp4Ypre : ((ml.Vg != nullptr && !no_vpre) ? kCgComp4Vpre : kCgComp4);
+    *variant = ypre ? kCgComp4Ypre : (ml.Vg != nullptr ? kCgComp4Vpre : kCgComp4);
 }
 // x = 0, r = b, first application of the preconditioner - for the graphs whose solve starts in this pass.  by_value: the pass has one
 // graph and `host_slot` is its slot (the device table `sl` is what every other twin reads)

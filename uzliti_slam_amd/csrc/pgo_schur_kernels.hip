@@ -201,23 +201,8 @@ SchurPlan schur_plan(int nb, const std::vector<int32_t>& row_ptr, const std::vec
         if (one_level) { g2.resize((size_t)n1); for (int a1 = 0; a1 < n1; a1++) g2[a1] = a1; n2 = n1; }
         else {
             g2 = strong_groups(n1, E, kMlFanout2, theta, 4, &n2);
-            // A/B switch (diagnostic build): blocks that stayed below four groups are packed together in the order of their lowest group,
-            // tie or no tie - fewer, fuller blocks (every block is 32 rows of every PCG kernel's work, filled or not).  Measured on config
-            // 5 (round 5, tests/diag/online_passes.py): 35 % fewer rows (3328 -> 2176 at the first interval on this layout), 6 % more PCG
-            // iterations (57.3 k -> 61.0 k), optimize 1.39 -> 1.36 s: the kernels are latency-bound, the rows were nearly free.  Off.
-            static const int pack = diag_int("UZL_SCHUR_BLOCK_PACK", 0);
-            if (pack) {
-                std::vector<int32_t> bsize((size_t)n2, 0), nid((size_t)n2, -1);
-                for (int a1 = 0; a1 < n1; a1++) bsize[g2[a1]]++;
-                int cnt = 0, open_id = -1, open_fill = 0;
-                for (int b = 0; b < n2; b++) {                                      // blocks are numbered by their lowest group
-                    if (bsize[b] >= kMlFanout2) { nid[b] = cnt++; continue; }
-                    if (open_id < 0 || open_fill + bsize[b] > kMlFanout2) { open_id = cnt++; open_fill = 0; }
-                    nid[b] = open_id; open_fill += bsize[b];
-                }
-                for (int a1 = 0; a1 < n1; a1++) g2[a1] = nid[g2[a1]];
-                n2 = cnt;
-            }
+            // Blocks that stayed below four groups are not packed together: packing gave 35 % fewer rows on config 5 but 6 % more PCG
+            // iterations and no gain (the kernels are latency-bound, the rows were nearly free; DESIGN_APPENDIX.md, round 5).
             static const bool verbose_plan = diag_flag("UZL_SCHUR_PLAN_DBG");
             if (verbose_plan) fprintf(stderr, "[uzl] schur plan: %d separators, %d groups, %d blocks -> %d rows\n", P.n_sep, n1, n2, n2 * kMlFanout * kMlFanout2);
         }
@@ -311,7 +296,7 @@ struct SchurWaveLds { double D[36], Di[36], C[36], E[36], T[36], W[36], g[6], u[
 // The LDS matrices of a half are private to its wave: what one lane writes the wave's other lanes read a few instructions later.  A wave's
 // LDS operations execute in program order, so all that is needed between the write and the reads is that the COMPILER keeps that order -
 // no s_barrier.  (Round 5: the elimination's 19 workgroup barriers per step made its two waves march in lock step; without them 37.9 ->
-// 34.5 us at 20k / 21.7k - tests/diag/r5_schur_ab.sh; the step is a chain of ~60 LDS round trips and six divisions either way.)
+// 34.5 us at 20k / 21.7k, DESIGN_APPENDIX.md; the step is a chain of ~60 LDS round trips and six divisions either way.)
 __device__ __forceinline__ void wave_sync()
 {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");

@@ -199,8 +199,8 @@ struct LmDev {
     int32_t build_pass, build_ix, build_cur, need;          // rebuild of copy build_ix from the poses in buffer build_cur; need: LmNeed bits
     int32_t it, qmax, iterations, max_it;                   // LM iteration, trial of it, iterations asked for, PCG iteration cap per solve
     int32_t pending, adopted, fresh, pcg_last;              // a rebuilt copy waits to be adopted / was adopted this iteration / this trial runs on fresh inverses
-    int32_t always_refresh, sync_rebuild, guarded, tails;   // constants of the solve; tails: lm_tail_kernel launches seen (= sequence word of LmHost)
-    int32_t st_pcg_iterations, st_lm_trials, st_precond_builds, st_iterations_done, st_terminated_early, anomaly_code, pad0, pad1;
+    int32_t sync_rebuild, guarded, tails;                   // constants of the solve; tails: lm_tail_kernel launches seen (= sequence word of LmHost)
+    int32_t st_pcg_iterations, st_lm_trials, st_precond_builds, st_iterations_done, st_terminated_early, anomaly_code, pad0;
     double lambda, ni, chi_cur, last_rel;
     double lambda_setup[2];    // lambda the inverses of each hierarchy copy were taken at
     double rate_ref, rate_last;
@@ -210,7 +210,7 @@ struct LmDev {
 };
 // what the host sees after a pass: an image of the LM state and of PgoDev::scal[0..8), written by lm_tail_kernel into pinned coherent
 // memory (one 8-byte word per lane); seq_begin with the fields, seq (= LmDev::tails) after every lane's stores have been acknowledged
-// (publish_wait_own_stores, uzl_common.hpp - no fence on gfx9).  The host copies a snapshot before it enqueues the pass whose tail writes
+// (publish_wait_own_stores, pgo_device.hpp - no fence on gfx9).  The host copies a snapshot before it enqueues the pass whose tail writes
 // the next one: that ordering, not the two words, keeps a copy whole; seq_begin == seq around it is the cross-check
 struct LmHost {
     LmDev lm;

@@ -14,12 +14,22 @@
 
 namespace uzl {
 
-// A/B switches (alternative kernels, preconditioner variants, scheduling constants) exist for measurements and for the tests that
-// prove the variants agree.  They are read from the environment ONLY in the diagnostic build (`make diag` -> libuzl_mi355x_diag.so,
-// -DUZL_DIAG; tests and tests/diag scripts select it with UZL_LIB); in the shipped library every one of them is a compile-time
-// constant.  Two run-time switches remain in both builds because a profiler / a debugging session needs them on the product:
-// UZL_NO_GRAPH=1 (eager launches: rocprofv3's kernel tracer cannot follow hipGraph replays on this image) and UZL_VERBOSE=1.
+// Run-time switches.  Most are read from the environment ONLY in the diagnostic build (`make diag` -> libuzl_mi355x_diag.so, -DUZL_DIAG;
+// tests and tests/diag scripts select it with UZL_LIB); in the shipped library each is a compile-time constant.  Every one of them is
+// there because a test or a profiling session depends on it:
+//   UZL_KNN2_VALU, UZL_VOTE_VALU           the vector-ALU matcher / vote loop: tests/test_ab_paths_gpu.py holds the matrix-core ones to
+//                                          their bits
+//   UZL_ML_SYNC_REBUILD, UZL_ML_NO_COMP4   synchronous rebuilds / the walked hierarchy instead of the dense level-2 operator: same test
+//                                          (poses agree, the dense operator halves the PCG count)
+//   UZL_BATCH_LANES=1                      a batch as one launch sequence (tests/test_batch_gpu.py)
+//   UZL_BATCH_FORCE_ANOMALY_N              sends graphs of that many nodes down the batch's anomaly fallback (tests/test_batch_gpu.py)
+//   UZL_PHASES, UZL_PHASES_EACH, UZL_GATE_DBG, UZL_STREAM_DBG, UZL_SCHUR_PLAN_DBG, -DUZL_STAMPS
+//                                          observation only: they time or print and choose no path
+// Three are read in both builds because a profiler / a debugging session needs them on the product: UZL_NO_GRAPH=1 (eager launches:
+// rocprofv3's kernel tracer cannot follow hipGraph replays), UZL_VERBOSE=1, and UZL_STREAM_PROBE=0 (uzl_streams.hip).
 // Test hooks (uzl_debug_*) exist in the diagnostic build only; the product library exports include/uzl_mi355x.h and nothing else.
+// The tuning constants chosen by measurement are named constexpr values beside the code that uses them (DESIGN_APPENDIX.md has the
+// measurements).
 #define UZL_DIAG_EXPORT __attribute__((visibility("default")))
 #ifdef UZL_DIAG
 inline bool diag_flag(const char* name) { return getenv(name) != nullptr; }

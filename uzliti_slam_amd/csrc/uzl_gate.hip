@@ -55,8 +55,6 @@ struct uzl_gate {
     bool dbg_on = false;
     int reg_slots = 2;               // open-list entries per lane gate_reg_kernel starts with (4 once a search of this handle outgrew 2)
     PinBuf<uint8_t> h_redo;
-    bool lane_kernel_only = false;   // A/B (diagnostic build, UZL_GATE_LANE=1): every search through gate_kernel, as in round 1
-    bool wave_kernel_only = false;   // A/B (UZL_GATE_WAVE=1): gate_wave_kernel (list in LDS, per-node state in HBM) instead of gate_reg_kernel
     int64_t n_wave = 0, n_lane = 0;  // searches run by either kernel (uzl_gate_search_counts)
     int64_t n_bound = 0;             // candidates the deciding search (gate_bound_kernel) settled without the reference's search
     PinBuf<uint8_t> h_pre, h_heur;
@@ -154,8 +152,6 @@ int uzl_gate_create(const uzl_gate_cfg* cfg, uzl_gate** out)
     uzl_gate* h = new (std::nothrow) uzl_gate();
     if (!h) return UZL_ERR_OOM;
     h->cfg = c;
-    h->lane_kernel_only = diag_flag("UZL_GATE_LANE");
-    h->wave_kernel_only = diag_flag("UZL_GATE_WAVE");
     h->dbg_on = diag_flag("UZL_GATE_DBG");
     if (hipSetDevice(c.device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
         delete h;
@@ -275,7 +271,7 @@ int uzl_gate_check(uzl_gate* h, int32_t nc, const uzl_gate_edge* cand, uint8_t* 
         UZL_HIP(hipMemcpyAsync(h->d_run.p + first, run.data() + first, (size_t)m, hipMemcpyHostToDevice, s));
         // ---- one wave per candidate, open list in LDS
         h->d_redo.reserve((size_t)nc); h->h_redo.reserve((size_t)nc);
-        const bool lds_path = !h->wave_kernel_only && gate_lds_bytes(n) <= kGateLdsMax;
+        const bool lds_path = gate_lds_bytes(n) <= kGateLdsMax;
         if (lds_path) h->d_gclosed.reserve((size_t)m * std::max(n, 1));                       // written before it is read: no clearing
         else {
             h->d_gst.reserve((size_t)m * std::max(n, 1));
@@ -294,7 +290,7 @@ int uzl_gate_check(uzl_gate* h, int32_t nc, const uzl_gate_edge* cand, uint8_t* 
         if (h->dbg_on) { h->d_dbg.reserve((size_t)m * 8); UZL_HIP(hipMemsetAsync(h->d_dbg.p, 0, sizeof(long long) * 8 * (size_t)m, s)); wa.dbg = h->d_dbg.p; }
         // Nobody asked for the path lengths: a search that only decides first (gate_bound_kernel).  What it cannot decide goes on to the
         // reference's search below, the rest keeps its verdict (keep_unrun).
-        if (wa.skip_decided && lds_path && !h->lane_kernel_only && launch_gate_bound(wa, s)) {
+        if (wa.skip_decided && lds_path && launch_gate_bound(wa, s)) {
             UZL_HIP(hipGetLastError());
             UZL_HIP(hipMemcpyAsync(h->h_redo.p + first, h->d_redo.p + first, (size_t)m, hipMemcpyDeviceToHost, s));
             UZL_HIP(hipStreamSynchronize(s));
@@ -309,7 +305,7 @@ int uzl_gate_check(uzl_gate* h, int32_t nc, const uzl_gate_edge* cand, uint8_t* 
             UZL_HIP(hipStreamSynchronize(s));
             wa.keep_unrun = 1; any_left = any;
         }
-        if (!h->lane_kernel_only && any_left) {
+        if (any_left) {
             bool reg_ok = lds_path && launch_gate_reg(wa, h->reg_slots, s);
             if (!reg_ok) {
                 if (lds_path) {                                                                // the attribute could not be raised: the HBM-state kernel
@@ -340,17 +336,17 @@ int uzl_gate_check(uzl_gate* h, int32_t nc, const uzl_gate_edge* cand, uint8_t* 
                 for (int32_t k = 0; k < m; k++) h->h_redo.p[first + k] = run4[k] ? redo4[k] : 0;
             }
         }
-        bool any_redo = h->lane_kernel_only;
+        bool any_redo = false;
         for (int32_t k = first; k < last && !any_redo; k++) any_redo = h->h_redo.p[k] != 0;
         for (int32_t k = first; k < last; k++) {
             if (!srch[k]) continue;
-            if (h->lane_kernel_only || h->h_redo.p[k]) h->n_lane++; else h->n_wave++;
+            if (h->h_redo.p[k]) h->n_lane++; else h->n_wave++;
         }
         if (any_redo) {
-            // candidates whose open list outgrew LDS (or all of them under the A/B switch): the lane kernel with its heap in HBM.
+            // candidates whose open list outgrew LDS: the lane kernel with its heap in HBM.
             // Its outputs overwrite pre_ok / heur_ok / dist of every candidate it runs for.
             std::vector<uint8_t> run2((size_t)m);
-            for (int32_t k = 0; k < m; k++) run2[k] = (srch[first + k] && (h->lane_kernel_only || h->h_redo.p[first + k])) ? 1 : 0;
+            for (int32_t k = 0; k < m; k++) run2[k] = (srch[first + k] && h->h_redo.p[first + k]) ? 1 : 0;
             UZL_HIP(hipMemcpyAsync(h->d_run.p + first, run2.data(), (size_t)m, hipMemcpyHostToDevice, s));
             UZL_HIP(hipStreamSynchronize(s));
         }
@@ -370,7 +366,6 @@ int uzl_gate_check(uzl_gate* h, int32_t nc, const uzl_gate_edge* cand, uint8_t* 
         a.ssf = h->cfg.scope_size_factor;
         a.skip_decided = astar_dist ? 0 : 1;
         a.pre_ok = h->d_pre.p + first; a.heur_ok = h->d_heur.p + first; a.dist = h->d_dist.p + first; a.overflow = h->d_over.p;
-        a.keep_unrun = h->lane_kernel_only ? 0 : 1;
         if (any_redo) launch_gate(a, s);
         UZL_HIP(hipGetLastError());
         UZL_HIP(hipMemcpyAsync(h->h_pre.p + first, h->d_pre.p + first, (size_t)m, hipMemcpyDeviceToHost, s));

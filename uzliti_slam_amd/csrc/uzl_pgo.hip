@@ -53,27 +53,19 @@ RcclApi& rccl()
 
 namespace uzl {
 const int kUpperNs = 4;                   // Newton-Schulz steps of the dense levels above the composite level (even: the result ends in Ydense[l])
-const bool kAlwaysRefresh = diag_flag("UZL_ML_ALWAYS_REFRESH");             // A/B switch
-const double kRefreshRel = diag_double("UZL_ML_REFRESH_REL", 1e-3);
-// ... and where the rebuild is synchronous (large loopy graphs: its GEMMs are 1.4 ms at 10k / 50k, 7 ms at 20k / 100k, in front of the
-// solve): the chi2 rule only while the problem still changes wholesale, the PCG-rate rule (kRateDrop, pgo_lm.hpp) from then on
-const double kRefreshRelSync = diag_double("UZL_ML_REFRESH_REL_SYNC", 3e-2);
-// ... and its rate rule: with the dense operator of that class a rebuild pays as soon as the rate has fallen to 0.75 of the fresh one
-// (0.6 elsewhere; tests/diag/r5_ratedrop.sh: -3 ... -8 % on eight of nine such shapes, the 30k / 150k graph - no dense operator - +14 %)
-const double kRateDropSyncDense = diag_double("UZL_ML_RATE_DROP_SYNC", 0.75);
+// the rate rule where the rebuild is synchronous: with the dense operator of that class a rebuild pays as soon as the rate has fallen to
+// 0.75 of the fresh one (0.6 elsewhere; -3 ... -8 % on eight of nine such shapes, the 30k / 150k graph - no dense operator - +14 %)
+constexpr double kRateDropSyncDense = 0.75;
 // Newton-Schulz steps of a synchronous set-up at LM iteration `it` for a structure that asks for `structure_steps` (4 on large loopy
-// graphs): 2 in the first kNsEarlyIts iterations (tests/diag/knob_sweep.sh "UZL_ML_NS_EARLY_ITS=0" against the default: -3.4 % over fourteen
-// large shapes at the same PCG iteration count; 4 iterations instead of 2 gain on the largest and lose at 10k, 8 lose everywhere; NO step at
-// all in those two - the cycle's operator as it comes, UZL_ML_NS_EARLY_STEPS=0 - another -2.5 %, not taken: that operator is what the
-// residual guard exists for)
+// graphs): 2 in the first kNsEarlyIts iterations (against the full count from the start: -3.4 % over fourteen large shapes at the same
+// PCG iteration count; 4 iterations instead of 2 gain on the largest and lose at 10k, 8 lose everywhere; NO step at all in those two - the
+// cycle's operator as it comes - another -2.5 %, not taken: that operator is what the residual guard exists for)
 int ml_ns_steps_at(int structure_steps, int it)
 {
-    static const int early_its = diag_int("UZL_ML_NS_EARLY_ITS", 2), early_steps = diag_int("UZL_ML_NS_EARLY_STEPS", 2);
-    return (structure_steps > 2 && it < early_its) ? early_steps : structure_steps;
+    constexpr int kNsEarlyIts = 2, kNsEarlySteps = 2;
+    return (structure_steps > 2 && it < kNsEarlyIts) ? kNsEarlySteps : structure_steps;
 }
 double ml_rate_drop(const uzl_pgo* h) { return (!ml_async_level(h) && h->ml_comp) ? kRateDropSyncDense : kRateDrop; }
-const double kLambdaRetake = diag_double("UZL_LAMBDA_RETAKE", 32.);         // lambda grown by this factor since the inverses were taken: take them again
-const int kGraphPairs = std::max(1, diag_int("UZL_GRAPH_PAIRS", 8));        // one graph replay = 2 x pairs PCG iterations
 int pgo_fail(uzl_pgo* h, int code, const char* msg)
 {
     h->last_error = msg;
@@ -83,8 +75,6 @@ int pgo_fail(uzl_pgo* h, int code, const char* msg)
 
 namespace {
 
-static const bool& always_refresh = kAlwaysRefresh;
-static const double& refresh_rel = kRefreshRel;
 inline int fail(uzl_pgo* h, int code, const char* msg) { return pgo_fail(h, code, msg); }
 
 struct Timed {
@@ -272,13 +262,11 @@ void build_ml(uzl_pgo* h, const std::vector<int32_t>& row_ptr0, const std::vecto
     // rebuild (Newton-Schulz GEMMs, n^3) outgrows what the exact level-1 solve saves in PCG iterations between 3000 and 4000 vertices on
     // loopy graphs (>= 3 edges per vertex: 3000/12000 20.6 -> 18.3 ms, 4000/16000 24.5 -> 26.3 ms) and later on sparse ones - the shape of a
     // Schur-reduced online graph (4000/6000 26.0 -> 17.2 ms; config 5's last solve 2328 -> 1288 PCG iterations).
-    static const int agg1_env = diag_int("UZL_ML_AGG1_MAX", 0);
-    const int agg1_max = agg1_env > 0 ? agg1_env : (nslots >= 6 * nb ? 3072 : 4096);
+    const int agg1_max = nslots >= 6 * nb ? 3072 : 4096;
     h->ml_agg = (nb <= agg1_max && !h->red.strong_blocks) ? 1 : 4;           // (strong aggregates in blocks of 4 x 8 rows are laid out for AGG = 4)
     int L = 0;
     h->ml_fan.assign(1, 1);
     // composite path: one aggregate per workgroup, at least two coarse levels, 6 n_1 <= 960 (<= 1280 free vertices)
-    static const bool comp_off = diag_flag("UZL_ML_NO_COMP");                // A/B switch
     // large graphs (AGG = 4, gather level 2): the same construction one level up - the hierarchy above level 2 as one dense
     // operator that ml_cg_kernel<4> applies instead of its LDS walk (measured 733 -> 332 ms at 20k / 100k, the rebuild's
     // Newton-Schulz GEMMs take 7 ms there).  6 n_2 <= 18432 - the cap was 4096 (21.8k vertices)
@@ -286,14 +274,13 @@ void build_ml(uzl_pgo* h, const std::vector<int32_t>& row_ptr0, const std::vecto
     // operator (1.8 k), 40k / 200k 5.13 -> 0.62 s, 50k / 250k 10.9 -> 1.56 s (tests/diag/big_graphs.py; at n = 7500 a GEMM is 10 ms, half of
     // that solve), 64k / 320k ~11 -> 2.3 s, 90k / 450k 29.3 -> 6.3 s.  The path ends where ml_cg's gather-level vector no longer fits the LDS
     // (95k vertices: 6 n_2 = 17.9k, 2.6 GB per matrix, a GEMM 136 ms); kMaxPartials ml_spmv workgroups admit 131k
-    static const bool comp4_off = diag_flag("UZL_ML_NO_COMP4");             // A/B switch
-    static const int comp4_max = diag_int("UZL_ML_COMP4_MAX", 18432);
-    static const int top_wide = diag_int("UZL_ML_TOP_WIDE", kMlTopWide);    // A/B switch (8 = the round-3 hierarchy)
+    static const bool comp4_off = diag_flag("UZL_ML_NO_COMP4");             // the walked hierarchy instead (tests/test_ab_paths_gpu.py)
+    constexpr int kComp4Max = 18432;
     // A level above the composite one may be the top with up to kMlTopWide aggregates: config 2 (1000 vertices: 125 / 16 / 2) loses its
     // 2-aggregate level and with it ten launches per rebuild (the cycle around it and four Newton-Schulz steps of the 96-row level)
     auto top_max = [&](int lvl) {
-        const bool comp_here = h->ml_agg == 1 ? (lvl >= 2 && 6 * h->ml_n[1] <= 3072) : (!comp4_off && lvl >= 3 && 6 * h->ml_n[2] <= comp4_max);
-        return (!comp_off && comp_here) ? std::min(std::max(top_wide, kMlTopMax), kMlTopWide) : kMlTopMax;
+        const bool comp_here = h->ml_agg == 1 ? (lvl >= 2 && 6 * h->ml_n[1] <= 3072) : (!comp4_off && lvl >= 3 && 6 * h->ml_n[2] <= kComp4Max);
+        return comp_here ? kMlTopWide : kMlTopMax;
     };
     while (h->ml_n.back() > top_max(L) && L < kMlMaxLevels) {
         const int fan = (L == 1 && h->ml_agg == 4) ? kMlFanout2 : kMlFanout;     // large graphs: level 2 = 4 level-1 aggregates
@@ -304,7 +291,7 @@ void build_ml(uzl_pgo* h, const std::vector<int32_t>& row_ptr0, const std::vecto
     // the PCG kernels' LDS: with the dense level-2 operator ml_cg stages nothing but the gather-level vector (ml_cg_variant); the walked
     // hierarchy needs every level above the gather level.  Beyond either limit (and beyond kMaxPartials ml_spmv workgroups = 131k
     // vertices): block-Jacobi
-    const bool comp4_here = !comp_off && !comp4_off && h->ml_agg == 4 && L >= 3 && 6 * h->ml_n[2] <= comp4_max;
+    const bool comp4_here = !comp4_off && h->ml_agg == 4 && L >= 3 && 6 * h->ml_n[2] <= kComp4Max;
     const bool fits = comp4_here ? ml_comp4_fits(nb, h->ml_n[2]) : ml_fits_lds(h->ml_n.data(), L, h->ml_agg);
     if (!fits) { h->ml_n.assign(1, nb); return; }
     h->ml_levels = L;
@@ -423,26 +410,23 @@ void build_ml(uzl_pgo* h, const std::vector<int32_t>& row_ptr0, const std::vecto
     std::vector<size_t> geo_sub((size_t)L + 1, 0);
     for (int l = 1; l <= L; l++) { geo_sub[l] = geo_blob_doubles; geo_blob_doubles += (size_t)std::max(h->ml_n[l], 1) * 3; }
     const size_t o_geo_blob = take(geo_blob_doubles * 8 + 64);     // ml_cg copies levels g..L-1 with one linear loop
-    const bool comp1 = !comp_off && h->ml_agg == 1 && L >= 2 && 6 * h->ml_n[1] <= 3072;     // ml_cg_comp_kernel<5> / <8> / <12> / <16>
+    const bool comp1 = h->ml_agg == 1 && L >= 2 && 6 * h->ml_n[1] <= 3072;     // ml_cg_comp_kernel<5> / <8> / <12> / <16>
     const bool comp4 = comp4_here;                  // (one predicate: the admission test above)
     h->ml_comp = comp1 || comp4;
     h->ml_cl = comp1 ? 1 : (comp4 ? 2 : 0);
     const int cl = h->ml_cl;
     std::vector<size_t> o_dense((size_t)L + 1, 0);
     if (h->ml_comp) for (int l = cl; l < L; l++) o_dense[l] = take((size_t)(6 * h->ml_n[l]) * (size_t)(6 * h->ml_n[l]) * 8);
-    static const bool mult_off = diag_flag("UZL_ML_ADDITIVE");                 // A/B switch
     // A handle whose graphs made the multiplicative operator break down (chain-like graphs: few loop closures per vertex, the
     // shape of an online run) keeps the additive operator for its later structures instead of failing once per add_graph.
-    h->ml_mult = h->ml_comp && !mult_off && !h->mult_banned;
+    h->ml_mult = h->ml_comp && !h->mult_banned;
     const size_t n12 = h->ml_mult ? (size_t)h->ml_n[cl] * h->ml_n[cl + 1] * 36 * 8 : 0;
     const size_t o_mQ = take(n12), o_mQY = take(n12);
     // Newton-Schulz steps of the composite operator per rebuild: 2; 4 on large loopy graphs (AGG = 4, >= 6 slots per row), where two
     // more GEMM pairs per rebuild buy a quarter of the PCG iterations (10k/50k 1882 -> 1455 per solve, 107.7 -> 94.1 ms; 5k/25k 68.6 ->
     // 62.3; 20k/100k 242 -> 224) - on chain-like graphs of that size they cost more than they save (20k/21.7k: 209 -> 261 ms), on
-    // small graphs the count barely moves (config 2: 538 -> 511 for +0.3 ms).  tests/diag/ns_sweep.sh
-    static const int ns_env = diag_int("UZL_ML_NS_STEPS", -1);
-    const int ns_auto = (h->ml_agg == 4 && nslots >= 6 * nb) ? 4 : 2;
-    h->ml_ns_steps = h->ml_mult ? std::max(0, std::min(ns_env >= 0 ? ns_env : ns_auto, 4)) : 0;
+    // small graphs the count barely moves (config 2: 538 -> 511 for +0.3 ms)
+    h->ml_ns_steps = h->ml_mult ? ((h->ml_agg == 4 && nslots >= 6 * nb) ? 4 : 2) : 0;
     const size_t nsq = h->ml_mult ? (size_t)(6 * h->ml_n[cl]) * (size_t)(6 * h->ml_n[cl]) * 8 : 0;     // also the scratch of the levels above cl
     const size_t o_nsT = take(nsq), o_nsX = take(nsq);
     const int c32_stride = h->ml_comp ? ((6 * h->ml_n[cl] + 3) & ~3) : 0;
@@ -555,12 +539,10 @@ void build_ml(uzl_pgo* h, const std::vector<int32_t>& row_ptr0, const std::vecto
 namespace uzl {
 // Asynchronous rebuild (second stream, second copy of the hierarchy) pays on the composite level-1 path, and for the reduced system of a
 // chain-like graph on the level-2 path: there a rebuild (0.8 ms) is as long as the LM iteration it would otherwise hold up.  (Other
-// level-2 graphs - config 4 - measured +9 % PCG iterations for no net gain: UZL_ML_ASYNC_LARGE.)
+// level-2 graphs - config 4 - measured +9 % PCG iterations for no net gain.)
 bool ml_async_level(const uzl_pgo* h)
 {
-    static const bool async_large = diag_flag("UZL_ML_ASYNC_LARGE");          // A/B switches
-    static const int async_strong = diag_int("UZL_ML_ASYNC_STRONG", 1);
-    return h->ml_cl == 1 || (h->ml_cl == 2 && (async_large || (h->red.on && h->red.strong && async_strong)));
+    return h->ml_cl == 1 || (h->ml_cl == 2 && h->red.on && h->red.strong);
 }
 void ml_setup_numeric(uzl_pgo* h, int bi, hipStream_t s, const PgoDev& D, bool timed)
 {
@@ -776,22 +758,20 @@ void build_structure(uzl_pgo* h)
     uzl_pgo::Reduced& Rd = h->red;
     Rd.on = false; Rd.n_int = 0; Rd.n_runs = 0; Rd.longest_run = 0; Rd.strong = false; Rd.strong_blocks = false; Rd.n_sep = 0;
     PgoDev& Dp = h->Dp;
-    static const int schur_diag = diag_int("UZL_SCHUR", 1);                  // A/B switches (diagnostic build)
     // longest run: 24.  (Twelve for small graphs paid 3 - 8 % while one wave walked a whole run; with a run eliminated from both ends the
     // chain is twelve steps anyway, and stars of 20-vertex arms keep being eliminated completely: tests/test_schur_gpu.py.)
-    static const int schur_cap = diag_int("UZL_SCHUR_CAP", 24);
-    static const int schur_min_pct = diag_int("UZL_SCHUR_MIN_PCT", 33);
+    constexpr int kSchurCap = 24;
+    constexpr int kSchurMinPct = 33;                                        // reduced when at least this share of the free vertices goes
     const bool may_shard = h->allreduce != nullptr || h->rccl_comm != nullptr;
     std::vector<int32_t> rrow_ptr, rcol;
-    if (h->cfg.schur_reduce >= 0 && schur_diag && nb > 0) {
+    if (h->cfg.schur_reduce >= 0 && nb > 0) {
         tick("block-CSR + uploads");
         // The reduced system of a large chain-like graph is numbered by strong aggregates (pgo_schur.hpp) and takes the AGG = 4 hierarchy: the
         // separators an aggregate holds then move (nearly) rigidly together, which is what its six coarse modes can represent.  In row order
         // "8 consecutive separators" put loop-closure partners into different aggregates and the two ends of a long soft run into the same
         // one: config 5's last re-optimisation took 70 - 140 PCG iterations per LM iteration (tests/diag/reduced_proto.py: 70 -> 23).
-        static const int strong_env = diag_int("UZL_SCHUR_STRONG_MIN", -1);     // A/B switch: separators from which on (0 = never)
-        static const int strong_theta_pct = diag_int("UZL_SCHUR_STRONG_THETA", 25);
-        int strong_min = (may_shard || h->cfg.preconditioner == 0) ? 0 : (strong_env >= 0 ? strong_env : kSchurStrongMin);
+        constexpr int kStrongThetaPct = 25;                                   // groups hang together by edges >= 0.25 x the stiffest at either end
+        int strong_min = (may_shard || h->cfg.preconditioner == 0) ? 0 : kSchurStrongMin;
         // Which numbering (uzl_pgo_cfg::reduced_numbering)?  Strong aggregates pay where loop closures are stiffer than the runs between
         // separators (config 5: 71 -> 31 PCG iterations per LM iteration); where the runs are the stiff part the matching follows the chain,
         // the groups are runs of consecutive separators anyway, and the row order with its level-1 path is better (tests/diag/strong_ab.py).
@@ -817,12 +797,11 @@ void build_structure(uzl_pgo* h)
             slot_w.resize((size_t)std::max(nslots, 1));
             for (int q = 0; q < nslots; q++) slot_w[q] = h->edge_w[slot_edge[q] >> 1];
         }
-        static const int one_level_max = diag_int("UZL_SCHUR_STRONG_ONE_MAX", kSchurStrongOneMax);
-        // (reduced when >= 64 rows and >= schur_min_pct of the rows go: the plan stops early otherwise)
-        const int min_int = std::max(64, (int)(((int64_t)schur_min_pct * nb + 99) / 100));
-        SchurPlan P = schur_plan(nb, row_ptr, col, schur_cap, slot_w.empty() ? nullptr : slot_w.data(), strong_min, 0.01 * strong_theta_pct, max_contig, one_level_max, min_int);
+        // (reduced when >= 64 rows and >= kSchurMinPct of the rows go: the plan stops early otherwise)
+        const int min_int = std::max(64, (int)(((int64_t)kSchurMinPct * nb + 99) / 100));
+        SchurPlan P = schur_plan(nb, row_ptr, col, kSchurCap, slot_w.empty() ? nullptr : slot_w.data(), strong_min, 0.01 * kStrongThetaPct, max_contig, kSchurStrongOneMax, min_int);
         tick("Schur plan");
-        if (P.n_int >= 64 && (int64_t)100 * P.n_int >= (int64_t)schur_min_pct * nb) {
+        if (P.n_int >= 64 && (int64_t)100 * P.n_int >= (int64_t)kSchurMinPct * nb) {
             Rd.on = true; Rd.n_int = P.n_int; Rd.n_runs = P.n_runs; Rd.longest_run = P.longest_run; Rd.strong = P.strong; Rd.strong_blocks = P.strong && P.n_strong2 > 0; Rd.n_sep = P.n_sep;
             const size_t nr = (size_t)std::max(P.nbr, 1), nsr = (size_t)std::max(P.nslots_r, 1), ni = (size_t)P.n_int, nru = (size_t)P.n_runs;
             auto up = [&](DevBuf<int32_t>& b, const std::vector<int32_t>& v, size_t min_n) {
@@ -1002,12 +981,12 @@ int pcg_solve(uzl_pgo* h, bool* converged)
     int launched = 0;
     // first batch sized from the previous solve (in steps of 2 x kShortPairs iterations), then two short ones, then long ones; the
     // kernels no-op once `done` is set
-    static const int first_pct = diag_int("UZL_FIRST_PCT", 95);
+    constexpr int kFirstPct = 95;                                           // the first batch: 95 % of the previous solve's count
     constexpr int kStep = 2 * kShortPairs;
     const int kLong = 2 * kGraphPairs;
     auto round_up = [](int v) { return ((v + kStep - 1) / kStep) * kStep; };
     // (+ 1: a solve that ends by the stop test after k iterations is declared done by the ml_spmv of iteration k + 1)
-    int want = h->prev_pcg_iters > 0 ? std::max(kStep, round_up((h->prev_pcg_iters * first_pct) / 100 + 1)) : kLong;
+    int want = h->prev_pcg_iters > 0 ? std::max(kStep, round_up((h->prev_pcg_iters * kFirstPct) / 100 + 1)) : kLong;
     for (int round = 0;; round++) {
         want = round_up(std::max(1, std::min(want, max_it - launched)));
         if (timed) enqueue_pcg_pairs(h, want / 2, h->timer.on);
@@ -1113,7 +1092,7 @@ int do_optimize_host(uzl_pgo* h, int32_t iterations, uzl_pgo_stats* st)
     // hierarchy while this iteration's PCG still uses the current one (any SPD preconditioner gives the same solution; one
     // that is one linearisation old costs a few iterations, a rebuild on the critical path costs ~0.4 ms).  The copy is
     // adopted at the start of the next iteration, which has to wait for it anyway before it overwrites H and the poses.
-    static const bool async_off = diag_flag("UZL_ML_SYNC_REBUILD");             // A/B switch
+    static const bool async_off = diag_flag("UZL_ML_SYNC_REBUILD");             // diagnostic build: every rebuild synchronous (tests/test_ab_paths_gpu.py)
     // (small graphs only: at 10k vertices the rebuild's Newton-Schulz GEMMs take more from the overlapped PCG than they give back:
     // 113.2 -> 115.1 ms; config 2: 11.09 -> 10.67 ms with 540 instead of 517 PCG iterations)
     const bool async_ok = !async_off && h->ml_levels > 0 && ml_async_level(h) && !h->sharded && !h->timer.on && h->stream2 != nullptr;
@@ -1161,7 +1140,7 @@ int do_optimize_host(uzl_pgo* h, int32_t iterations, uzl_pgo_stats* st)
         // previous iteration is as good as a fresh one (geometry + Galerkin + inverses are ~170 us per rebuild).
         // A rebuild is also forced when the iteration count has grown by a third since the last one.
         // (an asynchronous rebuild is for the NEXT iteration: none in the last one)
-        const bool refresh = lm_refresh(it, iterations, always_refresh, !async_ok, last_rel, ml_async_level(h) ? refresh_rel : kRefreshRelSync, rate_ref, rate_last, ml_rate_drop(h));
+        const bool refresh = lm_refresh(it, iterations, !async_ok, last_rel, ml_async_level(h) ? kRefreshRel : kRefreshRelSync, rate_ref, rate_last, ml_rate_drop(h));
         bool launch_async = false;
         bool fetched = false;
         if (red) {                                      // the hierarchy is built on the reduced system, which needs lambda: lambda_0 first
@@ -1395,7 +1374,7 @@ static int pgo_create_on(const uzl_pgo_cfg* cfg, hipStream_t shared, hipStream_t
         // had taken its streams as they came).  Streams go back to the pool with the handle: making a handle no longer costs two
         // hipStreamCreates (7 ms) once the pool holds a pair.
         h->stream = stream_lease(c.device, 0, {}, false);
-        h->stream2 = h->stream ? stream_lease(c.device, diag_int("UZL_S2_PRIO", -1), {h->stream}, false) : nullptr;
+        h->stream2 = h->stream ? stream_lease(c.device, -1, {h->stream}, false) : nullptr;
         ok = h->stream && h->stream2;
     }
     ok = ok && hipEventCreateWithFlags(&h->ev_lin, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&h->ev_setup, hipEventDisableTiming) == hipSuccess;
@@ -1423,7 +1402,7 @@ void uzl::own_streams(uzl_pgo* h, bool drain_borrowed)
         if (h->stream2) UZL_HIP(hipStreamSynchronize(h->stream2));
     }
     hipStream_t a = stream_lease(h->cfg.device, 0, {}, false);
-    hipStream_t b = a ? stream_lease(h->cfg.device, diag_int("UZL_S2_PRIO", -1), {a}, false) : nullptr;
+    hipStream_t b = a ? stream_lease(h->cfg.device, -1, {a}, false) : nullptr;
     if (!a || !b) { stream_release(h->cfg.device, a); throw HipError{hipErrorUnknown, "stream_lease", __FILE__, __LINE__}; }
     h->stream = a; h->stream2 = b; h->streams_borrowed = false;
 }
@@ -1792,9 +1771,6 @@ struct uzl_pgo_batch {
     // of eight graphs, not sixteen.  Only with four streams that do not stand in each other's way (uzl_pgo_batch_create).
     hipStream_t stream_b = nullptr, stream2_b = nullptr;
     uzl::LmRun* lm_b = nullptr;
-    // diagnostic build, UZL_BATCH_LANES=4: four sequences, one per compute pipe, each with its rebuilds on its own stream
-    hipStream_t stream_x[2] = {nullptr, nullptr};
-    uzl::LmRun* lm_x[2] = {nullptr, nullptr};
     KernelTimer timer;                    // profiling (uzl_pgo_batch_set_profiling): the two PCG kernels, launched eagerly with event pairs
 };
 
@@ -1833,35 +1809,31 @@ int batch_optimize(uzl_pgo_batch* b, int32_t iterations, uzl_pgo_stats* stats, i
         b->last_batched = 0;
         return rc_all;
     }
-    static const int lanes_env = diag_int("UZL_BATCH_LANES", 2);               // A/B switch (diagnostic build): 1 = one launch sequence
+    static const bool one_lane = diag_int("UZL_BATCH_LANES", 2) < 2;          // diagnostic build, UZL_BATCH_LANES=1: one launch sequence
     const bool eager = b->h[0]->no_graph, verbose = b->cfg.verbose != 0;
-    static const bool no_s2 = diag_flag("UZL_BATCH_NO_S2");                   // A/B switch: rebuilds on the sequence's own stream
-    hipStream_t s2a = no_s2 ? b->stream : b->stream2, s2b = no_s2 ? b->stream_b : b->stream2_b;
     auto one_sequence = [&]() {
-        const int done = batch_optimize_lm(b->lm, b->h, b->resident, b->stream, s2a, iterations, eager, verbose, &b->timer, stats, &rc_all);
+        const int done = batch_optimize_lm(b->lm, b->h, b->resident, b->stream, b->stream2, iterations, eager, verbose, &b->timer, stats, &rc_all);
         if (done < 0) { b->last_error = b->h[(size_t)(-1 - done)]->last_error; return rc_all; }
         b->last_batched = done;
         if (n_batched) *n_batched = done;
         return rc_all;
     };
-    static const int lane_min = diag_int("UZL_BATCH_LANE_MIN", kBatchLaneMin);      // A/B switch (diagnostic build)
-    if (B < lane_min || lanes_env < 2 || b->resident == 1 || b->timer.on || !b->stream_b || !b->stream2_b) return one_sequence();
+    if (B < kBatchLaneMin || one_lane || b->resident == 1 || b->timer.on || !b->stream_b || !b->stream2_b) return one_sequence();
     // ---- L launch sequences: the graphs in L runs, the first from this thread, the others from helper threads.  The sequences share
     //      nothing but the device (every graph has its handle, every sequence its streams, slot table and captured segments), and a graph's
     //      result does not depend on its neighbours in the batch, so the split changes no bit of any result.
-    const bool four = lanes_env >= 4 && b->stream_x[0] && b->stream_x[1] && B >= 4 * (lane_min / 2) && (b->resident == 0 || b->resident >= 4);
-    const int L = four ? 4 : 2;
+    constexpr int L = 2;
     struct Lane { uzl::LmRun** lm; hipStream_t s, s2; int first, count, resident, rc, done; std::exception_ptr ex; };
     std::vector<Lane> lanes((size_t)L);
     {
-        uzl::LmRun** lms[4] = {&b->lm, &b->lm_b, &b->lm_x[0], &b->lm_x[1]};
-        hipStream_t ss[4] = {b->stream, b->stream_b, b->stream_x[0], b->stream_x[1]};
-        hipStream_t s2s[4] = {s2a, s2b, b->stream_x[0], b->stream_x[1]};
+        uzl::LmRun** lms[L] = {&b->lm, &b->lm_b};
+        hipStream_t ss[L] = {b->stream, b->stream_b};
+        hipStream_t s2s[L] = {b->stream2, b->stream2_b};
         int first = 0, res_left = b->resident;
         for (int l = 0; l < L; l++) {
             const int count = (B - first + (L - l) - 1) / (L - l);
             const int res = b->resident > 0 ? (res_left + (L - l) - 1) / (L - l) : 0;
-            lanes[(size_t)l] = Lane{lms[l], ss[l], four ? ss[l] : s2s[l], first, count, res, UZL_OK, 0, nullptr};
+            lanes[(size_t)l] = Lane{lms[l], ss[l], s2s[l], first, count, res, UZL_OK, 0, nullptr};
             first += count; res_left -= res;
         }
     }
@@ -1923,23 +1895,17 @@ int uzl_pgo_batch_create(const uzl_pgo_cfg* cfg, int32_t n_graphs, uzl_pgo_batch
     // get a second launch sequence if four such streams can be had within the pool's budget - otherwise, and with UZL_STREAM_PROBE=0,
     // the batch runs as ONE launch sequence whatever streams it got; a rebuild stream that cannot be had apart from the solver's is
     // replaced by any stream (slower, not wrong).
-    static const int prio2 = diag_int("UZL_BATCH_S2_PRIO", 0);                     // A/B switches (diagnostic build)
-    static const bool two_on = diag_int("UZL_BATCH_LANES", 2) >= 2;
+    static const bool two_on = diag_int("UZL_BATCH_LANES", 2) >= 2;          // diagnostic build, UZL_BATCH_LANES=1: one launch sequence
     const int dev = c.device;
     b->stream = stream_lease(dev, 0, {}, false);
     bool ok = b->stream != nullptr;
-    if (ok && two_on && n_graphs >= diag_int("UZL_BATCH_LANE_MIN", kBatchLaneMin)) b->stream_b = stream_lease(dev, 0, {b->stream}, true);
-    if (ok && b->stream_b && diag_int("UZL_BATCH_LANES", 2) >= 4) {             // diagnostic build: two more solver streams, four pipes in all
-        b->stream_x[0] = stream_lease(dev, 0, {b->stream, b->stream_b}, true);
-        if (b->stream_x[0]) b->stream_x[1] = stream_lease(dev, 0, {b->stream, b->stream_b, b->stream_x[0]}, true);
-    }
-    const bool four = b->stream_x[1] != nullptr;                // (then the rebuild streams only serve batches too small for four sequences)
+    if (ok && two_on && n_graphs >= kBatchLaneMin) b->stream_b = stream_lease(dev, 0, {b->stream}, true);
     if (ok) {
-        b->stream2 = four ? stream_lease(dev, prio2, {b->stream}, false) : stream_lease(dev, prio2, {b->stream, b->stream_b}, false);
+        b->stream2 = stream_lease(dev, 0, {b->stream, b->stream_b}, false);
         ok = b->stream2 != nullptr;
     }
     if (ok && b->stream_b) {
-        b->stream2_b = four ? stream_lease(dev, prio2, {b->stream, b->stream_b}, true) : stream_lease(dev, prio2, {b->stream, b->stream_b, b->stream2}, true);
+        b->stream2_b = stream_lease(dev, 0, {b->stream, b->stream_b, b->stream2}, true);
         if (!b->stream2_b) { stream_release(dev, b->stream_b); b->stream_b = nullptr; }      // no fourth: one sequence
     }
     int rc_h = UZL_OK;
@@ -1951,7 +1917,7 @@ int uzl_pgo_batch_create(const uzl_pgo_cfg* cfg, int32_t n_graphs, uzl_pgo_batch
     }
     if (!ok) {
         for (uzl_pgo* x : b->h) uzl_pgo_destroy(x);
-        for (hipStream_t q : {b->stream, b->stream2, b->stream_b, b->stream2_b, b->stream_x[0], b->stream_x[1]}) stream_release(dev, q);
+        for (hipStream_t q : {b->stream, b->stream2, b->stream_b, b->stream2_b}) stream_release(dev, q);
         delete b;
         return rc_h != UZL_OK ? rc_h : UZL_ERR_HIP;
     }
@@ -1963,12 +1929,11 @@ void uzl_pgo_batch_destroy(uzl_pgo_batch* b)
 {
     if (!b) return;
     (void)hipSetDevice(b->cfg.device);
-    for (hipStream_t q : {b->stream2, b->stream, b->stream2_b, b->stream_b, b->stream_x[0], b->stream_x[1]}) if (q) (void)hipStreamSynchronize(q);
+    for (hipStream_t q : {b->stream2, b->stream, b->stream2_b, b->stream_b}) if (q) (void)hipStreamSynchronize(q);
     lm_run_destroy(b->lm); b->lm = nullptr;
     lm_run_destroy(b->lm_b); b->lm_b = nullptr;
-    for (uzl::LmRun*& r : b->lm_x) { lm_run_destroy(r); r = nullptr; }
     for (uzl_pgo* x : b->h) uzl_pgo_destroy(x);
-    for (hipStream_t q : {b->stream, b->stream2, b->stream_b, b->stream2_b, b->stream_x[0], b->stream_x[1]}) stream_release(b->cfg.device, q);      // back to the pool, verdicts kept
+    for (hipStream_t q : {b->stream, b->stream2, b->stream_b, b->stream2_b}) stream_release(b->cfg.device, q);      // back to the pool, verdicts kept
     delete b;
 }
 

@@ -64,9 +64,6 @@ void lm_run_destroy(LmRun* r)
 
 namespace {
 
-static const bool lm_host_forced = diag_flag("UZL_LM_HOST");              // A/B switch (diagnostic build): the host-driven loop everywhere
-static const bool lm_slot_ptr = diag_flag("UZL_LM_SLOT_PTR");             // A/B switch: PCG kernels read the slot through its pointer also for one graph
-
 LmRun* new_run()
 {
     LmRun* R = new LmRun();
@@ -104,7 +101,7 @@ void enq_setup(LmRun* R, int which, hipStream_t s)
     kl_ml_numeric(R->d_slots.p, R->shape, which, s);
     kl_ml_trial(R->d_slots.p, R->shape, which, s);
 }
-const LmSlot* by_value_slot(LmRun* R) { return (R->shape.nslots == 1 && !R->shape.batch_geometry && !lm_slot_ptr) ? R->slots.data() : nullptr; }
+const LmSlot* by_value_slot(LmRun* R) { return (R->shape.nslots == 1 && !R->shape.batch_geometry) ? R->slots.data() : nullptr; }
 void enq_init(LmRun* R, hipStream_t s) { UZL_HIP(kl_ml_init(R->d_slots.p, by_value_slot(R), R->shape, s)); }
 void enq_pcg(LmRun* R, int first, int n, hipStream_t s, hipEvent_t* ev = nullptr) { UZL_HIP(kl_ml_pcg_its(R->d_slots.p, by_value_slot(R), R->shape, first, n, s, ev)); }
 void enq_tail(LmRun* R, hipStream_t s)
@@ -197,7 +194,6 @@ LmDev initial_state(const uzl_pgo* h, int iterations)
     I.init_pass = I.schur_pass = I.numeric_pass = I.trial_pass = I.build_pass = -1;
     I.iterations = iterations;
     I.max_it = h->cfg.pcg_max_iter > 0 ? h->cfg.pcg_max_iter : 6 * std::max(h->Dp.nb, 1);
-    I.always_refresh = kAlwaysRefresh ? 1 : 0;
     // (do_optimize_host's async_ok: rebuilds run ahead for the small-graph class only - at 10k vertices the rebuild's GEMMs take more from
     //  the overlapped PCG than they give back)
     I.sync_rebuild = (h->ml_comp && ml_async_level(h)) ? 0 : 1;
@@ -218,7 +214,7 @@ LmDev idle_state()
 
 // Waits until lm_tail launch number `seq` (or a later one) of slot `sl` has published and copies the snapshot; returns its number.
 // lm_tail writes the fields and seq_begin (unordered among themselves), waits until they have been acknowledged, then seq
-// (publish_wait_own_stores, uzl_common.hpp).  What keeps a copy whole is the DRIVER'S ORDER: a slot's snapshot is copied here before the
+// (publish_wait_own_stores, pgo_device.hpp).  What keeps a copy whole is the DRIVER'S ORDER: a slot's snapshot is copied here before the
 // pass whose tail writes the next one is enqueued; seq_begin == seq around the copy cross-checks it.
 uint32_t wait_pub(hipStream_t s, LmRun* R, int sl, uint32_t seq, LmHost* out)
 {
@@ -343,14 +339,12 @@ int lm_drive(LmRun* R, std::vector<LmJob>& jobs, const LmDriveOpts& o)
     // (it works on the graphs the tail has left in phase kLmLin and is a no-op for the others), so the GPU builds the Hessian while the
     // host reads the snapshot, chooses the next pass and launches it - otherwise ~12 us of idle GPU per pass (tail -> hessian in the
     // kernel trace).  Not while a rebuild on the second stream still reads H, and a refill sends the linearisation again.
-    static const bool lin_ahead_on = diag_int("UZL_LM_LIN_AHEAD", 1) != 0;      // A/B switch
     bool lin_ahead = false;
     while (n_active > 0) {
         const auto tp0 = std::chrono::steady_clock::now();
         // ---- what this pass carries: predictions from the slots' last snapshots
         int pf = 0, want = 0;
         bool any_start = false;
-        std::vector<int> wants;
         for (int sl = 0; sl < nS; sl++) {
             if (slot_job[sl] < 0 || jobs[slot_job[sl]].finished) continue;      // (a finished graph waits in its slot for its cohort: every kernel no-ops on its state)
             const LmDev& v = snap[sl].lm;
@@ -365,7 +359,7 @@ int lm_drive(LmRun* R, std::vector<LmJob>& jobs, const LmDriveOpts& o)
                 any_start = true; solve_passes[sl] = 0;
                 if (v.phase == kLmNeedSetup) pf |= ((v.need & (kNeedNumeric | kNeedTrial)) ? kPassSetup : 0) | ((v.need & kNeedRebuild) ? kPassRebuild : 0);
                 else if (v.phase == kLmLin) {
-                    if (lm_refresh(v.it, v.iterations, kAlwaysRefresh, v.sync_rebuild != 0, v.last_rel, v.refresh_rel, v.rate_ref, v.rate_last, v.rate_drop))
+                    if (lm_refresh(v.it, v.iterations, v.sync_rebuild != 0, v.last_rel, v.refresh_rel, v.rate_ref, v.rate_last, v.rate_drop))
                         pf |= (v.it == 0 || v.sync_rebuild) ? kPassSetup : kPassRebuild;
                     if (v.it > 0 && v.lambda > kLambdaRetake * v.lambda_setup[v.ix ^ (v.pending ? 1 : 0)]) pf |= kPassSetup;
                 } else if (v.phase == kLmRetry) {
@@ -377,12 +371,10 @@ int lm_drive(LmRun* R, std::vector<LmJob>& jobs, const LmDriveOpts& o)
                 // one: a re-optimisation), a fresh run starts with two long replays.
                 // uzl_pgo_cfg::pass_history = 1: nothing an earlier optimize of this handle learned sizes a pass (the first solve starts with
                 // two long replays, every later one follows its predecessor in the same optimize)
-                static const bool no_history_env = diag_flag("UZL_LM_NO_HISTORY");           // A/B switch
-                const bool no_history = no_history_env || jobs[(size_t)slot_job[sl]].h->cfg.pass_history == 1;
+                const bool no_history = jobs[(size_t)slot_job[sl]].h->cfg.pass_history == 1;
                 // One graph: exactly count + 1 launches (odd or even; a continuation pass picks the parity up from the solve's own
                 // iteration count).  A batch keeps whole pairs: its graphs share the launches' parity.
-                static const bool odd_ok = diag_int("UZL_LM_ODD_K", 1) != 0;      // A/B switch
-                auto up = [&](int count) { return (nS == 1 && odd_ok) ? count + 1 : ((count + 2) & ~1); };
+                auto up = [&](int count) { return nS == 1 ? count + 1 : ((count + 2) & ~1); };
                 w = v.pcg_last > 0 ? up(v.pcg_last) : ((R->first_solve_its > 0 && !no_history) ? up(R->first_solve_its) : 2 * kLong);
                 // counts that RISE from trial to trial (lambda falls after accepted steps, the system gets harder: chain-like graphs climb by 2
                 // per trial for ten trials, each time one launch short of `last + 2`): extrapolate the last rise
@@ -394,10 +386,7 @@ int lm_drive(LmRun* R, std::vector<LmJob>& jobs, const LmDriveOpts& o)
                 w = std::min(w, ((v.max_it + 1) & ~1));
             }
             want = std::max(want, w);
-            wants.push_back(w);
         }
-        static const int k_pct = diag_int("UZL_BATCH_K_PCT", 100);      // A/B switch: the pass's PCG count as a percentile of the slots' predictions (100 = the longest)
-        if (k_pct < 100 && wants.size() > 1) { std::sort(wants.begin(), wants.end()); want = wants[std::min(wants.size() - 1, (wants.size() * (size_t)k_pct) / 100)]; }
         want = std::max(2, want);
         // iteration index of the pass's first PCG launch: a single graph's continuation goes on where its solve stands (its count may be
         // odd); in a batch every pass holds whole pairs, so every solve stands at an even count
@@ -440,7 +429,7 @@ int lm_drive(LmRun* R, std::vector<LmJob>& jobs, const LmDriveOpts& o)
         }
         mark(5);
         enq_tail(R, s);
-        if (lin_ahead_on && !R->join_pending && !(o.timer && o.timer->on)) { enq_linearize(R, s); lin_ahead = true; }
+        if (!R->join_pending && !(o.timer && o.timer->on)) { enq_linearize(R, s); lin_ahead = true; }
         mark(6);
         passes++;
         for (int sl = 0; sl < nS; sl++) sent[sl]++;
@@ -471,10 +460,9 @@ int lm_drive(LmRun* R, std::vector<LmJob>& jobs, const LmDriveOpts& o)
         if (o.timer && o.timer->on) { UZL_HIP(hipStreamSynchronize(s)); o.timer->resolve(); }
         // A queue longer than the slots is worked off in COHORTS: the slots are refilled when every resident graph is through, so that the
         // residents walk through their LM iterations together - their solves need similar numbers of PCG iterations, and a pass is as long
-        // as its longest solve.  Refilling slot by slot (UZL_BATCH_FREE_RUNNING=1, diagnostic build) mixes converged graphs (4 iterations
+        // as its longest solve.  Refilling slot by slot mixes converged graphs (4 iterations
         // per solve) with fresh ones (60): measured on 256 queued config-2 graphs through 16 / 64 slots 49 / 69 M edges/s against 60 / 74 M.
-        static const bool free_running = diag_flag("UZL_BATCH_FREE_RUNNING");
-        if (refill && (free_running || n_active == 0 || nS == 1)) {
+        if (refill && (n_active == 0 || nS == 1)) {
             // (a rebuild of the outgoing graphs may still read the slot table and their LM state)
             if (R->join_pending && next_job < Q) { UZL_HIP(hipStreamWaitEvent(s, R->ev_join, 0)); R->join_pending = false; }
             for (int sl = 0; sl < nS; sl++)
@@ -532,7 +520,7 @@ void finish_job(LmJob& J, uzl_pgo_stats* st, double wall_ms)
 // which solves take the device-resident loop
 bool lm_eligible(const uzl_pgo* h)
 {
-    return !lm_host_forced && h->cfg.lm_loop != 1 && h->ml_levels > 0 && !h->sharded && h->nb > 0 && h->e > 0 && h->Dp.nb > 0 && !h->timer.on &&
+    return h->cfg.lm_loop != 1 && h->ml_levels > 0 && !h->sharded && h->nb > 0 && h->e > 0 && h->Dp.nb > 0 && !h->timer.on &&
            h->stream2 != nullptr;
 }
 
@@ -560,8 +548,7 @@ int do_optimize_lm(uzl_pgo* h, int32_t iterations, uzl_pgo_stats* st)
     // them again ~0.7 ms, which a structure that is solved once - every re-optimisation of a growing graph - never earns back (config 5:
     // 16.2 -> 15.7 ms per solve, structure 1.9 -> 1.2 ms).  A structure that comes back (uzl_pgo_reset, a timer-driven re-optimisation of an
     // unchanged graph) replays captured segments from its second solve on.  Same kernels, same results either way.
-    static const bool capture_first = diag_flag("UZL_LM_CAPTURE_FIRST");       // A/B switch
-    o.s = s; o.s2 = h->stream2; o.iterations = iterations; o.eager = h->no_graph || (R->solves_of_gen == 0 && !capture_first); o.verbose = h->cfg.verbose != 0;
+    o.s = s; o.s2 = h->stream2; o.iterations = iterations; o.eager = h->no_graph || R->solves_of_gen == 0; o.verbose = h->cfg.verbose != 0;
     R->solves_of_gen++;
     lm_drive(R, jobs, o);
     LmJob& J = jobs[0];
@@ -582,7 +569,7 @@ int do_optimize_lm(uzl_pgo* h, int32_t iterations, uzl_pgo_stats* st)
 // chain-like graphs (graph_slam_node.cpp:578-663: an odometry chain plus a few loop closures) batch on their reduced systems.
 bool lm_batch_eligible(const std::vector<uzl_pgo*>& hs)
 {
-    if (lm_host_forced || hs.empty() || (int)hs.size() > kBatchMax) return false;
+    if (hs.empty() || (int)hs.size() > kBatchMax) return false;
     const uzl_pgo* a = hs[0];
     for (const uzl_pgo* h : hs) {
         if (!(h->cfg.lm_loop != 1 && h->ml_levels > 0 && h->ml_agg == 1 && h->ml_comp && h->ml_mult && h->ml_cl == 1 && 6 * h->ml_n[1] <= 1536 && !h->sharded && h->nb > 0 &&
