@@ -212,6 +212,85 @@ def pgo_lm(poses, fixed, ij, meas, info, robust, iterations=20, delta=1.0):
     return X.reshape(-1, 12), stats
 
 
+# ----------------------------------------------------------------------------- the linear system stage by stage (test_pgo_system_gpu.py)
+def bcsr_to_sparse(row_ptr, col, blk, diag=None, nrows=None):
+    """Block-CSR (6 x 6 blocks, one slot per incident edge) -> scipy CSR of size 6 nrows.  Slots that name the same column are SUMMED
+    (multi-edges); col = -1 (the neighbour is fixed) contributes nothing; diag [nrows,6,6], when given, is added on the block diagonal."""
+    row_ptr = np.asarray(row_ptr, np.int64); col = np.asarray(col, np.int64); blk = np.asarray(blk, np.float64).reshape(-1, 6, 6)
+    nr = len(row_ptr) - 1 if nrows is None else int(nrows)
+    rows = np.repeat(np.arange(len(row_ptr) - 1), np.diff(row_ptr))
+    keep = col >= 0
+    r, c, B = rows[keep], col[keep], blk[:len(col)][keep]
+    if diag is not None:
+        d = np.asarray(diag, np.float64).reshape(-1, 6, 6)
+        r = np.concatenate([r, np.arange(len(d))]); c = np.concatenate([c, np.arange(len(d))]); B = np.concatenate([B, d])
+    rr = 6 * r[:, None, None] + np.arange(6)[None, :, None] + np.zeros((1, 1, 6), np.int64)
+    cc = 6 * c[:, None, None] + np.arange(6)[None, None, :] + np.zeros((1, 6, 1), np.int64)
+    return sp.coo_matrix((B.ravel(), (rr.ravel(), cc.ravel())), shape=(6 * nr, 6 * nr)).tocsr()      # (tocsr sums duplicates)
+
+
+def block_index(blocks):
+    """Scalar indices of the 6-blocks `blocks`, in order."""
+    blocks = np.asarray(blocks, np.int64)
+    return (6 * blocks[:, None] + np.arange(6)[None, :]).reshape(-1)
+
+
+def schur_dense(A, b, keep):
+    """Dense Schur complement of the blocks not in `keep`: S = A_ss - A_si A_ii^-1 A_is, g = b_s - A_si A_ii^-1 b_i (s = keep, in the order
+    given; i = the other blocks, ascending)."""
+    A = np.asarray(A.toarray() if sp.issparse(A) else A, np.float64); b = np.asarray(b, np.float64)
+    nbk = A.shape[0] // 6
+    keep = np.asarray(keep, np.int64)
+    elim = np.setdiff1d(np.arange(nbk), keep)
+    s, i = block_index(keep), block_index(elim)
+    if len(i) == 0:
+        return A[np.ix_(s, s)].copy(), b[s].copy()
+    X = np.linalg.solve(A[np.ix_(i, i)], np.concatenate([A[np.ix_(i, s)], b[i][:, None]], axis=1))
+    return A[np.ix_(s, s)] - A[np.ix_(s, i)] @ X[:, :-1], b[s] - A[np.ix_(s, i)] @ X[:, -1]
+
+
+def step_error(dx, dx_ref):
+    """Largest error of a step per kind of component: (translation [m], quaternion vector) over all vertices, dx [n,6] = (t, q_xyz)."""
+    d = np.abs(np.asarray(dx, np.float64).reshape(-1, 6) - np.asarray(dx_ref, np.float64).reshape(-1, 6))
+    if d.size == 0:
+        return 0.0, 0.0
+    return float(d[:, :3].max()), float(d[:, 3:].max())
+
+
+def system_magnitudes(poses, fixed, ij, meas, info, robust, jac, delta=1.0):
+    """Per entry, the sum of the magnitudes of the terms behind H and b (as build_system adds them, with |J| + s, |Omega'|): the scale of
+    the round-off an evaluation of H and b in another order or at poses rounded once differently can show.  b's terms carry |e| + s,
+    s = 1 + |t_i| + |t_j| + |t_z|: the error of an edge is a difference of translations of that size, so it is only known to eps s
+    absolutely however small it is (at the LM fixed point, b itself is rounding noise).  Returns (|H| terms as CSR, |b| terms [6 n])."""
+    P = np.asarray(poses, np.float64).reshape(-1, 3, 4); Z = np.asarray(meas, np.float64).reshape(-1, 3, 4)
+    ij = np.asarray(ij).reshape(-1, 2)
+    e = edge_errors(poses, ij, meas)
+    Om = np.asarray(info).reshape(-1, 6, 6)
+    c = np.einsum("ki,kij,kj->k", e, Om, e)
+    _, r1 = huber(c, delta)
+    w = np.where(np.asarray(robust) != 0, r1, 1.0)
+    s = 1.0 + np.abs(P[ij[:, 0], :, 3]).max(1) + np.abs(P[ij[:, 1], :, 3]).max(1) + np.abs(Z[:, :, 3]).max(1)
+    # a Jacobian entry is built from rotations (|.| <= 1) and relative translations (|.| <= s): rounded once differently it moves by a few
+    # eps s whatever its own size (a coupling term 2 R [t_b]x of two nearby vertices far from the origin cancels): |J| + s bounds its terms
+    Ji, Jj = (np.abs(np.asarray(j)) + s[:, None, None] for j in jac)
+    Aw = np.abs(Om) * w[:, None, None]
+    Hii = np.swapaxes(Ji, 1, 2) @ Aw @ Ji; Hjj = np.swapaxes(Jj, 1, 2) @ Aw @ Jj; Hij = np.swapaxes(Ji, 1, 2) @ Aw @ Jj
+    ae = np.abs(e) + s[:, None]
+    bi = np.einsum("kji,kjl,kl->ki", Ji, Aw, ae); bj = np.einsum("kji,kjl,kl->ki", Jj, Aw, ae)
+    n = P.shape[0]
+    fi = np.asarray(fixed)[ij[:, 0]] == 0; fj = np.asarray(fixed)[ij[:, 1]] == 0
+    both = fi & fj
+    rows = np.concatenate([ij[fi, 0], ij[fj, 1], ij[both, 0], ij[both, 1]])
+    cols = np.concatenate([ij[fi, 0], ij[fj, 1], ij[both, 1], ij[both, 0]])
+    blocks = np.concatenate([Hii[fi], Hjj[fj], Hij[both], np.swapaxes(Hij[both], 1, 2)])
+    rr = 6 * rows[:, None, None] + np.arange(6)[None, :, None] + np.zeros((1, 1, 6), np.int64)
+    cc = 6 * cols[:, None, None] + np.arange(6)[None, None, :] + np.zeros((1, 6, 1), np.int64)
+    H = sp.coo_matrix((blocks.ravel(), (rr.ravel(), cc.ravel())), shape=(6 * n, 6 * n)).tocsr()
+    b = np.zeros((n, 6))
+    np.add.at(b, ij[fi, 0], bi[fi]); np.add.at(b, ij[fj, 1], bj[fj])
+    return H, b.reshape(-1)
+
+
 # ------------------------------------------------------------------------------------------------------------
 # Edge filter: a third, pure-Python statement of TransformationFilter / EdgeCluster
 # (transformation_estimation/src/transformation_filter.cpp:43-350) with the reference's object semantics

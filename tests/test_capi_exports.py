@@ -34,6 +34,19 @@ def test_nothing_but_the_header_is_exported(capi):
     assert not [n for n in exported if "debug" in n]
 
 
+def test_stage_hooks_live_in_the_diagnostic_library_only(capi):
+    """The stage-level hooks of the pose-graph linear system (test_pgo_system_gpu.py): exported by the diagnostic twin, absent from
+    the product library."""
+    import subprocess
+    hooks = {"uzl_debug_pgo_linearize", "uzl_debug_pgo_solve", "uzl_debug_pgo_reduced", "uzl_debug_pgo_apply"}
+
+    def exported(path):
+        out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+        return set(line.split()[-1] for line in out.splitlines() if line.strip())
+
+    assert hooks <= exported(capi.DIAG_LIB_PATH)
+    assert not [n for n in exported(capi.LIB_PATH) if n.startswith("uzl_debug_pgo")]
+
 def test_struct_layouts_match_header(capi):
     assert ctypes.sizeof(capi.EdgeResult) == capi.EDGE_RESULT_DTYPE.itemsize == 432
     assert ctypes.sizeof(capi.PairJob) == capi.PAIR_JOB_DTYPE.itemsize == 24

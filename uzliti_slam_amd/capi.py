@@ -266,7 +266,14 @@ def diag_lib():
     if _diag is None:
         if not os.path.exists(DIAG_LIB_PATH):
             raise UzlError(UZL_ERR_STATE, f"{DIAG_LIB_PATH} is missing: make -C {CSRC} diag")
-        _diag = C.CDLL(DIAG_LIB_PATH)
+        D = C.CDLL(DIAG_LIB_PATH)
+        D.uzl_status_string.restype = C.c_char_p
+        D.uzl_pgo_last_error.restype = C.c_char_p
+        D.uzl_pgo_last_error.argtypes = [C.c_void_p]
+        D.uzl_pgo_destroy.restype = None
+        D.uzl_pgo_destroy.argtypes = [C.c_void_p]
+        D.uzl_pgo_cfg_default.restype = None
+        _diag = D
     return _diag
 
 
@@ -464,8 +471,10 @@ class Match:
 class Pgo:
     """Thin object wrapper over the uzl_pgo_* C ABI."""
 
+    _lib = staticmethod(lambda: lib())
+
     def __init__(self, **cfg):
-        L = lib()
+        L = self._lib()
         c = PgoCfg()
         L.uzl_pgo_cfg_default(C.byref(c))
         for k, v in cfg.items():
@@ -480,20 +489,20 @@ class Pgo:
 
     def close(self):
         if getattr(self, "_h", None):
-            lib().uzl_pgo_destroy(self._h)
+            self._lib().uzl_pgo_destroy(self._h)
             self._h = None
 
     __del__ = close
 
     def _check(self, rc, allow=()):
         if rc != UZL_OK and rc not in allow:
-            raise UzlError(rc, lib().uzl_pgo_last_error(self._h).decode())
+            raise UzlError(rc, self._lib().uzl_pgo_last_error(self._h).decode())
         return rc
 
     def set_config(self, **cfg):
         for k, v in cfg.items():
             setattr(self.cfg, k, v)
-        self._check(lib().uzl_pgo_set_config(self._h, C.byref(self.cfg)))
+        self._check(self._lib().uzl_pgo_set_config(self._h, C.byref(self.cfg)))
 
     def add_graph(self, nodes_pose, nodes_fixed, edges, sensors=None):
         """Reference-shaped input (SlamNode / SlamEdge arrays, see synth.make_pose_graph)."""
@@ -508,7 +517,7 @@ class Pgo:
         if "diff_time" in edges:
             ea["diff_time"][:ne] = edges["diff_time"]
         S = np.ascontiguousarray(sensors, np.float64).reshape(-1, 12) if sensors is not None and len(sensors) else None
-        self._check(lib().uzl_pgo_add_graph(self._h, C.c_int32(n), _p(na, C.c_void_p), C.c_int32(ne), _p(ea, C.c_void_p),
+        self._check(self._lib().uzl_pgo_add_graph(self._h, C.c_int32(n), _p(na, C.c_void_p), C.c_int32(ne), _p(ea, C.c_void_p),
                                             C.c_int32(0 if S is None else S.shape[0]), _p(S, c_f64p)))
         self.n = n; self.e_in = ne
 
@@ -541,7 +550,7 @@ class Pgo:
         fi = np.ascontiguousarray(flag_index if flag_index is not None else [], np.int32)
         fv = np.ascontiguousarray(flag_valid if flag_valid is not None else [], np.uint8)
         assert fi.shape == fv.shape
-        self._check(lib().uzl_pgo_append_graph(self._h, C.c_int32(n), _p(na, C.c_void_p), C.c_int32(ne), _p(ea, C.c_void_p),
+        self._check(self._lib().uzl_pgo_append_graph(self._h, C.c_int32(n), _p(na, C.c_void_p), C.c_int32(ne), _p(ea, C.c_void_p),
                                                C.c_int32(len(fi)), _p(fi, c_i32p), _p(fv, c_u8p)))
         self.n += n; self.e_in += ne
 
@@ -550,13 +559,13 @@ class Pgo:
         ijc = np.ascontiguousarray(ij, np.int32).reshape(-1, 2)
         Z = np.ascontiguousarray(meas, np.float64).reshape(-1, 12)
         Om = np.ascontiguousarray(info, np.float64).reshape(-1, 36); rb = np.ascontiguousarray(robust, np.uint8)
-        self._check(lib().uzl_pgo_set_graph(self._h, C.c_int32(P.shape[0]), _p(P, c_f64p), _p(f, c_u8p),
+        self._check(self._lib().uzl_pgo_set_graph(self._h, C.c_int32(P.shape[0]), _p(P, c_f64p), _p(f, c_u8p),
                                             C.c_int32(ijc.shape[0]), _p(ijc, c_i32p), _p(Z, c_f64p), _p(Om, c_f64p),
                                             _p(rb, c_u8p)))
         self.n = P.shape[0]; self.e_in = ijc.shape[0]
 
     def reset(self):
-        self._check(lib().uzl_pgo_reset(self._h))
+        self._check(self._lib().uzl_pgo_reset(self._h))
 
     def set_shard(self, rank, world, allreduce=None):
         """Sharded single-graph solve (BASELINE config 4).  allreduce(dev_ptr:int, count:int, stream:int) -> int must sum
@@ -572,42 +581,107 @@ class Pgo:
                     traceback.print_exc()
                     return -1
             self._shard_cb = ALLREDUCE_FN(_cb)
-        self._check(lib().uzl_pgo_set_shard(self._h, C.c_int32(rank), C.c_int32(world), self._shard_cb, None))
+        self._check(self._lib().uzl_pgo_set_shard(self._h, C.c_int32(rank), C.c_int32(world), self._shard_cb, None))
 
     def set_shard_rccl(self, rank, world, unique_id):
         """Native exchange: the handle owns the RCCL communicator (collective call: every rank, same id from rccl_unique_id())."""
         buf = (C.c_char * RCCL_UNIQUE_ID_BYTES).from_buffer_copy(bytes(unique_id))
-        self._check(lib().uzl_pgo_set_shard_rccl(self._h, C.c_int32(rank), C.c_int32(world), buf, C.c_int32(RCCL_UNIQUE_ID_BYTES)))
+        self._check(self._lib().uzl_pgo_set_shard_rccl(self._h, C.c_int32(rank), C.c_int32(world), buf, C.c_int32(RCCL_UNIQUE_ID_BYTES)))
 
     def rccl_ranks(self):
         """ncclCommCount of the handle's communicator (0: none)."""
-        return int(lib().uzl_pgo_rccl_ranks(self._h))
+        return int(self._lib().uzl_pgo_rccl_ranks(self._h))
 
     def optimize(self, iterations=0):
         st = PgoStats()
-        rc = self._check(lib().uzl_pgo_optimize(self._h, C.c_int32(iterations), C.byref(st)),
+        rc = self._check(self._lib().uzl_pgo_optimize(self._h, C.c_int32(iterations), C.byref(st)),
                          allow=(UZL_ERR_NOT_CONVERGED,))
         d = st.as_dict(); d["status"] = rc
         return d
 
     def store(self):
         poses = np.empty((self.n, 12)); err = np.empty(max(self.e_in, 1)); used = np.empty(max(self.e_in, 1), np.uint8)
-        self._check(lib().uzl_pgo_store(self._h, _p(poses, c_f64p), _p(err, c_f64p), _p(used, c_u8p)))
+        self._check(self._lib().uzl_pgo_store(self._h, _p(poses, c_f64p), _p(err, c_f64p), _p(used, c_u8p)))
         return poses, err[:self.e_in], used[:self.e_in]
 
     def get_fixed(self):
         f = np.empty(self.n, np.uint8)
-        self._check(lib().uzl_pgo_get_fixed(self._h, _p(f, c_u8p)))
+        self._check(self._lib().uzl_pgo_get_fixed(self._h, _p(f, c_u8p)))
         return f
 
     def set_profiling(self, on):
-        self._check(lib().uzl_pgo_set_profiling(self._h, C.c_int32(1 if on else 0)))
+        self._check(self._lib().uzl_pgo_set_profiling(self._h, C.c_int32(1 if on else 0)))
 
     def kernel_times(self):
         cap = 64
         names = (C.c_char_p * cap)(); ms = (C.c_double * cap)(); ln = (C.c_int32 * cap)()
-        n = lib().uzl_pgo_kernel_times(self._h, C.c_int32(cap), names, ms, ln)
+        n = self._lib().uzl_pgo_kernel_times(self._h, C.c_int32(cap), names, ms, ln)
         return {names[i].decode(): dict(ms=ms[i], launches=ln[i]) for i in range(max(n, 0))}
+
+
+class DiagPgo(Pgo):
+    """A Pgo handle of the diagnostic library (diag_lib), with its stage-level hooks of the linear system (uzl_pgo.hip, UZL_DIAG): the
+    handle is created and fed by that library's own uzl_pgo_* - a handle of the product library must never reach a uzl_debug_* hook."""
+
+    _lib = staticmethod(lambda: diag_lib())
+
+    def linearize(self):
+        """One linearisation at the handle's current poses (after gauge + structure, as optimize): dict of v2b [n], row_ptr [nb+1],
+        col [nslots] (-1: fixed neighbour), blk [nslots,6,6] (H_{a,col} of row a, one slot per incident edge), haa [nb,6,6], b [nb,6],
+        chi2, diagmax, poses [n,12] (the linearisation point as store() writes it)."""
+        L = self._lib()
+        sz = np.zeros(4, np.int32)
+        self._check(L.uzl_debug_pgo_linearize(self._h, _p(sz, c_i32p), None, None, None, None, None, None, None, None))
+        n, nb, ns, _ = (int(v) for v in sz)
+        v2b = np.zeros(max(n, 1), np.int32); rp = np.zeros(nb + 1, np.int32); col = np.zeros(max(ns, 1), np.int32)
+        blk = np.zeros((max(ns, 1), 6, 6)); haa = np.zeros((max(nb, 1), 6, 6)); b = np.zeros((max(nb, 1), 6))
+        sc = np.zeros(2); P = np.zeros((max(n, 1), 12))
+        self._check(L.uzl_debug_pgo_linearize(self._h, _p(sz, c_i32p), _p(v2b, c_i32p), _p(rp, c_i32p), _p(col, c_i32p), _p(blk, c_f64p),
+                                              _p(haa, c_f64p), _p(b, c_f64p), _p(sc, c_f64p), _p(P, c_f64p)))
+        assert tuple(int(v) for v in sz[:3]) == (n, nb, ns), "the structure changed between the two calls"
+        return dict(v2b=v2b[:n], row_ptr=rp, col=col[:ns], blk=blk[:ns], haa=haa[:nb], b=b[:nb], chi2=float(sc[0]), diagmax=float(sc[1]),
+                    poses=P[:n])
+
+    def solve(self, lam=-1.0):
+        """One linear solve (H + lam I) dx = b at the current poses as an LM trial does it (lam < 0: lambda_init = 1e-5 max |H_jj|):
+        dict of dx [n,6] (zero rows for fixed vertices), its, converged, guard_trips, lam, res_ratio (|r|^2 / |b|^2), rz_end, rz_stop."""
+        n = self.n
+        dx = np.zeros((max(n, 1), 6)); info = np.zeros(8)
+        self._check(self._lib().uzl_debug_pgo_solve(self._h, C.c_double(lam), _p(dx, c_f64p), _p(info, c_f64p)))
+        return dict(dx=dx[:n], its=int(info[0]), converged=bool(info[1]), guard_trips=int(info[3]), lam=float(info[4]),
+                    res_ratio=float(info[5]), rz_end=float(info[6]), rz_stop=float(info[7]))
+
+    def reduced(self, lam=-1.0):
+        """The Schur-reduced system for lam (< 0: lambda_init), as the PCG sees it, or None when the structure has no reduction: dict of
+        sep_rows [nbr] (full-system row per reduced row, -1: empty row), row_ptr, col, blk [slots,6,6], hdiag [nbr,6,6] (without the
+        separators' lambda I, which the SpMV adds), b [nbr,6]."""
+        L = self._lib()
+        sz = np.zeros(3, np.int32)
+        self._check(L.uzl_debug_pgo_reduced(self._h, C.c_double(lam), _p(sz, c_i32p), None, None, None, None, None, None))
+        if not sz[2]:
+            return None
+        nr, ns = int(sz[0]), int(sz[1])
+        sep = np.zeros(max(nr, 1), np.int32); rp = np.zeros(nr + 1, np.int32); col = np.zeros(max(ns, 1), np.int32)
+        blk = np.zeros((max(ns, 1), 6, 6)); hd = np.zeros((max(nr, 1), 6, 6)); b = np.zeros((max(nr, 1), 6))
+        self._check(L.uzl_debug_pgo_reduced(self._h, C.c_double(lam), _p(sz, c_i32p), _p(sep, c_i32p), _p(rp, c_i32p), _p(col, c_i32p),
+                                            _p(blk, c_f64p), _p(hd, c_f64p), _p(b, c_f64p)))
+        assert (int(sz[0]), int(sz[1])) == (nr, ns), "the structure changed between the two calls"
+        return dict(sep_rows=sep[:nr], row_ptr=rp, col=col[:ns], blk=blk[:ns], hdiag=hd[:nr], b=b[:nr])
+
+    def apply_info(self):
+        """What the handle's PCG applies: dict(op = 0 block-Jacobi / 1 additive multilevel / 2 multiplicative, agg, cl, rows)."""
+        info = np.zeros(4)
+        self._check(self._lib().uzl_debug_pgo_apply(self._h, C.c_double(-1.0), C.c_int32(0), None, None, _p(info, c_f64p)))
+        return dict(op=int(info[0]), agg=int(info[1]), cl=int(info[2]), rows=int(info[3]))
+
+    def apply(self, op, x, lam=-1.0):
+        """op 0: (A + lam I) x with the PCG's own SpMV; op 1: M^-1 x with the preconditioner the PCG applies for lam (< 0: lambda_init).
+        x, result: [rows, 6] in the numbering of the system the PCG iterates on (reduced() when the structure has a reduction)."""
+        xx = np.ascontiguousarray(x, np.float64).reshape(-1, 6)
+        y = np.zeros_like(xx); info = np.zeros(4)
+        self._check(self._lib().uzl_debug_pgo_apply(self._h, C.c_double(lam), C.c_int32(op), _p(xx, c_f64p), _p(y, c_f64p), _p(info, c_f64p)))
+        assert int(info[3]) == xx.shape[0], "x has %d rows, the system %d" % (xx.shape[0], int(info[3]))
+        return y
 
 
 class _BorrowedPgo(Pgo):

@@ -1743,6 +1743,259 @@ int uzl_pgo_rccl_ranks(uzl_pgo* h)
 
 }  // extern "C"
 
+#ifdef UZL_DIAG
+// ---- stage-level test hooks of the pose-graph linear system (tests/test_pgo_system_gpu.py).  Diagnostic build only; every hook takes a
+//      handle made by THIS library's uzl_pgo_create / uzl_pgo_add_graph, runs the production kernels and host steps (no arithmetic of its
+//      own), and leaves the handle as usable as it found it: the poses are not touched and every buffer it writes is rewritten by the
+//      next optimize.  Array outputs: a call with null arrays returns the sizes only.
+namespace {
+// gauge + structure + slot records (as optimize), then one linearisation at the current poses: H in D.blk / D.hdiag, b, chi2, max diag
+void debug_linearize(uzl_pgo* h)
+{
+    if (h->sharded) throw HipError{hipErrorNotSupported, "stage hooks: not on a sharded handle", __FILE__, __LINE__};
+    UZL_HIP(hipSetDevice(h->cfg.device));
+    prepare_optimize(h);
+    PgoDev& D = h->D;
+    D.pose = h->cur; D.pose_trial = h->trial;
+    h->Dp.pose = h->cur; h->Dp.pose_trial = h->trial;
+    if (h->nb == 0 || h->e == 0) return;
+    int gl = 0, ga = 0;
+    UZL_HIP(k_hessian(D, h->cur, h->cfg.huber_delta, &gl, &ga, h->stream, true));
+    k_finalize(D, gl, 0, ga, 2, h->stream);
+}
+}  // namespace
+
+// sizes[4] = {n, nb, nslots, e}.  v2b [n]: vertex -> block row (-1: fixed); row_ptr [nb+1]; col [nslots] (-1: the neighbour is fixed, the
+// block is zero); blk [nslots][36]: H_{a, col} row-major for row a, one slot per incident edge (multi-edges give several slots of one
+// block); haa [nb][36] (no lambda); b [nb][6] = -J^T Omega' e; scal[2] = {chi2, max |H_jj|}; poses [n][12]: the poses linearised at, as
+// uzl_pgo_store writes them.  Structure (sizes) only when blk is null.
+extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_linearize(uzl_pgo* h, int32_t* sizes, int32_t* v2b, int32_t* row_ptr, int32_t* col,
+                                                       double* blk, double* haa, double* b, double* scal, double* poses)
+{
+    UZL_GUARD_BEGIN(h)
+    if (!h->have_graph) return fail(h, UZL_ERR_STATE, "linearize before add_graph/set_graph");
+    if (!sizes) return fail(h, UZL_ERR_BAD_ARG, "sizes is required");
+    own_streams(h, true);
+    hipStream_t s = h->stream;
+    if (!blk) {
+        UZL_HIP(hipSetDevice(h->cfg.device));
+        prepare_optimize(h);
+    } else {
+        debug_linearize(h);
+    }
+    sizes[0] = h->n; sizes[1] = h->nb; sizes[2] = h->nslots; sizes[3] = h->e;
+    if (!blk) { UZL_HIP(hipStreamSynchronize(s)); return UZL_OK; }
+    const size_t nb = (size_t)h->nb, ns = (size_t)h->nslots;
+    if (v2b && h->n) UZL_HIP(hipMemcpyAsync(v2b, h->d_v2b.p, sizeof(int32_t) * (size_t)h->n, hipMemcpyDeviceToHost, s));
+    if (row_ptr) UZL_HIP(hipMemcpyAsync(row_ptr, h->d_row_ptr.p, sizeof(int32_t) * (nb + 1), hipMemcpyDeviceToHost, s));
+    if (ns) {
+        if (col) UZL_HIP(hipMemcpyAsync(col, h->d_col.p, sizeof(int32_t) * ns, hipMemcpyDeviceToHost, s));
+        UZL_HIP(hipMemcpyAsync(blk, h->D.blk, sizeof(double) * 36 * ns, hipMemcpyDeviceToHost, s));
+    }
+    if (nb) {
+        if (haa) UZL_HIP(hipMemcpyAsync(haa, h->D.hdiag, sizeof(double) * 36 * nb, hipMemcpyDeviceToHost, s));
+        if (b) UZL_HIP(hipMemcpyAsync(b, h->D.b, sizeof(double) * 6 * nb, hipMemcpyDeviceToHost, s));
+    }
+    double sc[16] = {};
+    if (nb && h->e) UZL_HIP(hipMemcpyAsync(sc, h->D.scal, sizeof(sc), hipMemcpyDeviceToHost, s));
+    if (poses && h->n) {
+        h->d_out12.reserve((size_t)h->n * 12);
+        k_poses_out(h->cur, h->n, h->d_out12.p, s);
+        UZL_HIP(hipMemcpyAsync(poses, h->d_out12.p, sizeof(double) * 12 * (size_t)h->n, hipMemcpyDeviceToHost, s));
+    }
+    UZL_HIP(hipGetLastError());
+    UZL_HIP(hipStreamSynchronize(s));
+    if (scal) { scal[0] = sc[4]; scal[1] = sc[6]; }
+    return UZL_OK;
+    UZL_GUARD_END(h)
+}
+
+// One linear solve (H + lambda I) dx = b at the current poses, done as the first trial of an LM iteration of the host-driven loop does it
+// (do_optimize_host): linearise, Schur reduction for this lambda (when the structure has one), the preconditioner's set-up (numeric part
+// and lambda-dependent part; the multiplicative operator and its Newton-Schulz steps where the structure selected them), pcg_solve under the
+// handle's cfg (pcg_tol, pcg_stop, pcg_max_iter), back-substitution.  lambda < 0: g2o's lambda_init = 1e-5 max |H_jj|.  No fallback to the
+// additive operator: a residual-guard trip is reported (info[3]) and leaves converged = 0.
+// dx [n][6]: the step per vertex, zero rows for fixed vertices.  info[8] = {pcg iterations, converged, 0, guard trips, lambda used, |r|^2 / |b|^2 (scal[7]),
+// r.M^-1 r at the end (scal[0]), the stop threshold on it (scal[1])}.
+extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_solve(uzl_pgo* h, double lambda, double* dx, double* info)
+{
+    UZL_GUARD_BEGIN(h)
+    if (!h->have_graph) return fail(h, UZL_ERR_STATE, "solve before add_graph/set_graph");
+    if (!dx || !info) return fail(h, UZL_ERR_BAD_ARG, "dx and info are required");
+    own_streams(h, true);
+    debug_linearize(h);
+    hipStream_t s = h->stream;
+    const int n = h->n;
+    for (int i = 0; i < 8; i++) info[i] = 0.;
+    memset(dx, 0, sizeof(double) * 6 * (size_t)n);
+    if (h->nb == 0 || h->e == 0) { info[1] = 1.; return UZL_OK; }
+    PgoDev& D = h->D;
+    PgoDev& Dp = h->Dp;
+    if (lambda < 0.) {
+        double sc[16];
+        UZL_HIP(hipMemcpyAsync(sc, D.scal, sizeof(sc), hipMemcpyDeviceToHost, s));
+        UZL_HIP(hipStreamSynchronize(s));
+        lambda = 1e-5 * sc[6];
+    }
+    h->ml_ix = 0; h->ml_pending = false;
+    if (h->red.on) {
+        k_set_scalar(D.scal + 3, lambda, s);
+        k_schur_eliminate(D, h->red.S, s);
+        k_schur_assemble(D, Dp, h->red.S, s);
+    }
+    h->ml_ns_now = ml_ns_steps_at(h->ml_ns_steps, 0);
+    if (h->ml_levels > 0) { ml_setup_numeric(h, h->ml_ix, s, Dp, false); h->ml_trial_setup = true; }
+    set_lambda(h, lambda, tol_factor2(h->cfg));
+    h->prev_pcg_iters = 0;
+    const int trips0 = h->guard_trips;
+    bool conv = false;
+    const int its = pcg_solve(h, &conv);
+    h->ml_ns_now = -1;
+    h->prev_pcg_iters = 0;
+    if (h->red.on) k_schur_backsub(D, Dp, h->red.S, s);
+    const size_t nb = (size_t)h->nb;
+    std::vector<double> x(nb * 6);
+    std::vector<int32_t> v2b((size_t)n);
+    UZL_HIP(hipMemcpyAsync(x.data(), D.x, sizeof(double) * 6 * nb, hipMemcpyDeviceToHost, s));
+    UZL_HIP(hipMemcpyAsync(v2b.data(), h->d_v2b.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
+    UZL_HIP(hipGetLastError());
+    UZL_HIP(hipStreamSynchronize(s));
+    for (int v = 0; v < n; v++) {
+        const int32_t a = v2b[(size_t)v];
+        if (a < 0 || (size_t)a >= nb) continue;
+        for (int c = 0; c < 6; c++) dx[(size_t)v * 6 + c] = x[(size_t)a * 6 + c];
+    }
+    info[0] = its; info[1] = conv ? 1. : 0.; info[3] = h->guard_trips - trips0; info[4] = lambda;
+    info[5] = h->h_scal.p->scal[7]; info[6] = h->h_scal.p->scal[0]; info[7] = h->h_scal.p->scal[1];
+    h->guard_trips = trips0;
+    return UZL_OK;
+    UZL_GUARD_END(h)
+}
+
+namespace {
+double debug_lambda(uzl_pgo* h, double lambda)
+{
+    if (lambda >= 0.) return lambda;
+    double sc[16];
+    UZL_HIP(hipMemcpyAsync(sc, h->D.scal, sizeof(sc), hipMemcpyDeviceToHost, h->stream));
+    UZL_HIP(hipStreamSynchronize(h->stream));
+    return 1e-5 * sc[6];                                       // computeLambdaInit
+}
+// the Schur reduction for this lambda, as an LM trial makes it (do_optimize_host: schur_reduce)
+void debug_reduce(uzl_pgo* h, double lambda)
+{
+    if (!h->red.on) return;
+    k_set_scalar(h->D.scal + 3, lambda, h->stream);
+    k_schur_eliminate(h->D, h->red.S, h->stream);
+    k_schur_assemble(h->D, h->Dp, h->red.S, h->stream);
+}
+}  // namespace
+
+// The system the PCG sees when the structure Schur-eliminates chain interiors, for this lambda (< 0: lambda_init): linearisation, then
+// k_schur_eliminate / k_schur_assemble.  sizes[3] = {reduced rows nbr, reduced slots, 1 if the structure has a reduction (0: nothing
+// else is written)}.  sep_rows [nbr]: full-system block row of every reduced row (-1: an empty row of the strong-aggregate numbering);
+// row_ptr [nbr+1], col [slots] (-1: none), blk [slots][36]: off-diagonal blocks (kept and fill); hdiag [nbr][36] and b [nbr][6]: the
+// diagonal blocks and the right-hand side.  lambda is NOT in hdiag: the separators' own lambda I is added by the SpMV (as for the full
+// system), while the eliminated interiors' lambda is inside the Schur terms.  An empty row has hdiag = I, b = 0 and no slots.
+// Structure (sizes) only when blk is null.
+extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_reduced(uzl_pgo* h, double lambda, int32_t* sizes, int32_t* sep_rows, int32_t* row_ptr,
+                                                     int32_t* col, double* blk, double* hdiag, double* b)
+{
+    UZL_GUARD_BEGIN(h)
+    if (!h->have_graph) return fail(h, UZL_ERR_STATE, "reduced before add_graph/set_graph");
+    if (!sizes) return fail(h, UZL_ERR_BAD_ARG, "sizes is required");
+    own_streams(h, true);
+    hipStream_t s = h->stream;
+    if (!blk) { UZL_HIP(hipSetDevice(h->cfg.device)); prepare_optimize(h); }
+    else debug_linearize(h);
+    const bool on = h->red.on && h->nb > 0 && h->e > 0;
+    sizes[0] = on ? h->Dp.nb : 0; sizes[1] = on ? h->Dp.nslots : 0; sizes[2] = on ? 1 : 0;
+    if (!blk || !on) { UZL_HIP(hipStreamSynchronize(s)); return UZL_OK; }
+    debug_reduce(h, debug_lambda(h, lambda));
+    const PgoDev& R = h->Dp;
+    const size_t nr = (size_t)R.nb, ns = (size_t)R.nslots;
+    if (sep_rows && nr) UZL_HIP(hipMemcpyAsync(sep_rows, h->red.sep_rows.p, sizeof(int32_t) * nr, hipMemcpyDeviceToHost, s));
+    if (row_ptr) UZL_HIP(hipMemcpyAsync(row_ptr, R.row_ptr, sizeof(int32_t) * (nr + 1), hipMemcpyDeviceToHost, s));
+    if (ns) {
+        if (col) UZL_HIP(hipMemcpyAsync(col, R.col, sizeof(int32_t) * ns, hipMemcpyDeviceToHost, s));
+        UZL_HIP(hipMemcpyAsync(blk, R.blk, sizeof(double) * 36 * ns, hipMemcpyDeviceToHost, s));
+    }
+    if (nr) {
+        if (hdiag) UZL_HIP(hipMemcpyAsync(hdiag, R.hdiag, sizeof(double) * 36 * nr, hipMemcpyDeviceToHost, s));
+        if (b) UZL_HIP(hipMemcpyAsync(b, R.b, sizeof(double) * 6 * nr, hipMemcpyDeviceToHost, s));
+    }
+    UZL_HIP(hipGetLastError());
+    UZL_HIP(hipStreamSynchronize(s));
+    return UZL_OK;
+    UZL_GUARD_END(h)
+}
+
+// One application of the PCG's operators to x, on the system the PCG iterates on (the full one, or the reduced one in its numbering: x, y
+// [nb_sys][6]) for this lambda (< 0: lambda_init), after the set-up an LM trial makes (linearisation, Schur reduction, preconditioner
+// numeric and lambda-dependent parts, set_lambda).  The fused kernels are driven in a state where their fused part is exact:
+//   op 0, y = (A + lambda I) x: the PCG's init kernel (k_ml_init / k_precond + k_pcg_init: flags and iteration count cleared, so beta = 0),
+//         then x written into z and the iteration kernel run with the zero previous direction the init left: it forms p = z + 0 p_old = x
+//         and y = A p (ml_spmv / pcg_spmv, D.ap);
+//   op 1, y = M^-1 x: the right-hand side replaced by x (and restored afterwards), then the PCG's first step - k_ml_init + k_ml_cg with
+//         init = 1 (block-Jacobi: k_precond + k_pcg_init) - which forms z = M^-1 r0 = M^-1 x.
+// info[4] = {operator: 0 block-Jacobi, 1 additive multilevel, 2 multiplicative cycle / Newton-Schulz; aggregates per PCG workgroup (AGG);
+// level of the dense operator (0: none); rows of the system}.  x = null: info only (after the set-up).
+extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_apply(uzl_pgo* h, double lambda, int32_t op, const double* x, double* y, double* info)
+{
+    UZL_GUARD_BEGIN(h)
+    if (!h->have_graph) return fail(h, UZL_ERR_STATE, "apply before add_graph/set_graph");
+    if (!info || (op != 0 && op != 1) || (x && !y)) return fail(h, UZL_ERR_BAD_ARG, "apply: op 0 / 1, info, and y with x");
+    own_streams(h, true);
+    debug_linearize(h);
+    hipStream_t s = h->stream;
+    PgoDev& Dp = h->Dp;
+    const bool ml = h->ml_levels > 0;
+    info[0] = ml ? ((h->ml_mult || h->ml_ns_steps > 0) ? 2. : 1.) : 0.; info[1] = ml ? h->ml_agg : 0; info[2] = ml ? h->ml_cl : 0;
+    info[3] = (h->nb > 0 && h->e > 0) ? Dp.nb : 0;
+    if (!x || info[3] == 0) { UZL_HIP(hipStreamSynchronize(s)); return UZL_OK; }
+    const double lam = debug_lambda(h, lambda);
+    h->ml_ix = 0; h->ml_pending = false;
+    debug_reduce(h, lam);
+    set_lambda(h, lam, tol_factor2(h->cfg));                   // (before the lambda-dependent set-up, as in pcg_solve)
+    if (ml) {
+        h->ml_ns_now = ml_ns_steps_at(h->ml_ns_steps, 0);
+        ml_setup_numeric(h, 0, s, Dp, false);
+        ml_setup_trial(h, 0, s, Dp, false);
+        h->ml_ns_now = -1;
+        h->ml_trial_setup = true;                              // (the next solve takes its own inverses)
+    }
+    const size_t n6 = (size_t)Dp.nb * 6;
+    const double tol2 = h->cfg.pcg_tol * h->cfg.pcg_tol;
+    uzl_pgo::MlBuf& B = h->mlb[0];
+    DevBuf<double> saved;
+    if (op == 0) {
+        if (ml) k_ml_init(Dp, B.hot, h->ml_agg, h->pbuf[0], h->pbuf[1], B.rg[0], s);
+        else { k_precond(Dp, s); k_pcg_init(Dp, h->pbuf[0], h->pbuf[1], s); }
+        UZL_HIP(hipMemcpyAsync(Dp.z, x, sizeof(double) * n6, hipMemcpyHostToDevice, s));
+        if (ml) k_ml_spmv(Dp, B.hot, h->ml_agg, h->pbuf[0], h->pbuf[1], g_ml_rows(Dp.nb, h->ml_agg), tol2, s);
+        else k_pcg_spmv(Dp, h->pbuf[0], h->pbuf[1], g_pcg_update(Dp.nb), tol2, s);
+        UZL_HIP(hipMemcpyAsync(y, Dp.ap, sizeof(double) * n6, hipMemcpyDeviceToHost, s));
+    } else {
+        saved.reserve(n6);
+        UZL_HIP(hipMemcpyAsync(saved.p, Dp.b, sizeof(double) * n6, hipMemcpyDeviceToDevice, s));
+        UZL_HIP(hipMemcpyAsync(Dp.b, x, sizeof(double) * n6, hipMemcpyHostToDevice, s));
+        if (ml) {
+            k_ml_init(Dp, B.hot, h->ml_agg, h->pbuf[0], h->pbuf[1], B.rg[0], s);
+            UZL_HIP(k_ml_cg(Dp, B.hot, h->ml_agg, h->pbuf[0], B.rg[0], B.rg[1], 0, 1, h->ml_lds, s));
+        } else {
+            k_precond(Dp, s);
+            k_pcg_init(Dp, h->pbuf[0], h->pbuf[1], s);
+        }
+        UZL_HIP(hipMemcpyAsync(y, Dp.z, sizeof(double) * n6, hipMemcpyDeviceToHost, s));
+        UZL_HIP(hipMemcpyAsync(Dp.b, saved.p, sizeof(double) * n6, hipMemcpyDeviceToDevice, s));
+    }
+    UZL_HIP(hipGetLastError());
+    UZL_HIP(hipStreamSynchronize(s));
+    return UZL_OK;
+    UZL_GUARD_END(h)
+}
+#endif  // UZL_DIAG
+
 // =====================================================================================================================
 //  Batched solve: B independent graphs through ONE launch sequence (uzl_pgo_batch_*)
 //
