@@ -677,6 +677,81 @@ int  uzl_places_count(uzl_places* h);
 int  uzl_places_last_counts(uzl_places* h, int32_t cap, int32_t* counts);
 
 /* ======================================================================================
+ *  Appearance-based candidate pairs from one binary GIST descriptor per node
+ *
+ *  BinaryGistRecognizer (place_recognition/src/binary_gist_recognizer.cpp), the reference's
+ *  default place_recognition_method "gist" (graph_slam/src/graph_slam_node.cpp:102-105), behind
+ *  the filters of PlaceRecognizer (place_recognizer.cpp:71-180).  A node's descriptor is one ORB
+ *  descriptor of the whole downscaled image (feature_extraction_core.cpp:119-160, 32 bytes),
+ *  sent as SensorData.gist_descriptor (SENSOR_TYPE_BINARY_GIST, sensor_data.cpp:227-246).
+ *
+ *  Contract: the reference asks FLANN's LSH index (approximate, not reproducible) for the
+ *  k_nearest_neighbors nearest places under the Hamming distance; here the search is EXACT.
+ *  A search returns, in this order:
+ *    1. the k nearest live indexed places, ordered by (Hamming distance, place index) ascending
+ *       (knnSearch with nn = k, binary_gist_recognizer.cpp:50-53);
+ *    2. of those, the ones with distance <= T (inclusive; T is a double, so T = 10.5 acts as 10) (:54-60);
+ *    3. then PlaceRecognizer's filters: |stamp - query stamp| > min_time_gap, cut at k, and the
+ *       reported-once filter on (neighbour, query place) pairs (place_recognizer.cpp:87-114, 157-180).
+ *  The k cut of step 1 comes before the time gap of step 3, as in the reference: near-duplicate
+ *  frames of the last few seconds take k slots and are then dropped by the time filter, so a true
+ *  loop closure ranked k + 1 is NOT reported.  k_nearest_neighbors = 0 reports nothing.
+ *  search_and_add indexes the new place after its search (:63-76), add only indexes (:82-104),
+ *  search only searches.  A node without a GIST sensor (desc == NULL) still takes a place index
+ *  (place_count_++) and is never indexed.  Removal is by place index; the reference passes the place
+ *  index to flann removePoint (:136-140), which names the right point only while every place has a
+ *  GIST descriptor - here it always removes that place.  The descriptor length is fixed per handle
+ *  by the first indexed descriptor (1-256 bytes); a later call with another length returns
+ *  UZL_ERR_BAD_ARG and changes nothing.
+ *
+ *  Device side: descriptors in one store, row = place index, rows zero-padded to 16 bytes; one
+ *  workgroup per query, Hamming distance by xor + popcount, a distance histogram in LDS picks the
+ *  cutoff, a second pass emits the survivors in index order.  Integer only: results equal the
+ *  CPU restatement exactly.
+ * ====================================================================================== */
+typedef struct uzl_gist uzl_gist;
+typedef struct uzl_gist_cfg {
+    double  T;                    /* 10    PlaceRecognizer.cfg "T": max Hamming distance, inclusive      */
+    int32_t k_nearest_neighbors;  /* 10    PlaceRecognizer.cfg (0-100 there; 0-256 accepted here)       */
+    int32_t device;
+    double  min_time_gap;         /* 5.0   s, place_recognizer.cpp:90                                    */
+} uzl_gist_cfg;
+void uzl_gist_cfg_default(uzl_gist_cfg* cfg);
+/* UZL_ERR_BAD_ARG for T = NaN or k_nearest_neighbors outside 0-256; UZL_ERR_NO_DEVICE without a GPU (no CPU fallback) */
+int  uzl_gist_create(const uzl_gist_cfg* cfg, uzl_gist** out);
+void uzl_gist_destroy(uzl_gist* h);
+const char* uzl_gist_last_error(uzl_gist* h);
+/* PlaceRecognizer::searchAndAddPlace: desc = the node's `bytes` GIST bytes, or NULL for a node without a GIST sensor;
+ * stamp = node.stamps_.front().  neighbors (capacity cap) receives the place indices, *n_neighbors their number (at most
+ * k, all of them written when cap allows), *place_index the index given to this place. */
+int  uzl_gist_search_and_add(uzl_gist* h, const uint8_t* desc, int32_t bytes, int64_t stamp_ns, int32_t cap, int32_t* neighbors,
+                             int32_t* n_neighbors, int32_t* place_index);
+/* PlaceRecognizer::addPlace */
+int  uzl_gist_add(uzl_gist* h, const uint8_t* desc, int32_t bytes, int64_t stamp_ns, int32_t* place_index);
+/* PlaceRecognizer::searchPlace; query_place = the querying node's place index (for the reported-once filter), -1 if none */
+int  uzl_gist_search(uzl_gist* h, const uint8_t* desc, int32_t bytes, int64_t stamp_ns, int32_t query_place, int32_t cap,
+                     int32_t* neighbors, int32_t* n_neighbors);
+/* PlaceRecognizer::removePlace; UZL_ERR_NOT_FOUND for a place index never given or already removed */
+int  uzl_gist_remove(uzl_gist* h, int32_t place_index);
+/* places given an index so far (removed ones included) */
+int  uzl_gist_count(uzl_gist* h);
+/* Defined as n successive uzl_gist_search_and_add calls in the given order: node i searches the places that existed before the
+ * call plus nodes 0..i-1 of the batch.  desc = n x bytes (NULL: no node has a GIST sensor); has_gist = n flags (NULL: all have
+ * one; rows of nodes without are ignored); stamps_ns = n stamps.  Neighbours are concatenated in node order, count_per_node
+ * (may be NULL) receives each node's number; *n_total = total found (may exceed cap: then only the first cap are written);
+ * *first_place_index (may be NULL) = index given to node 0, node i gets first + i. */
+int  uzl_gist_search_and_add_batch(uzl_gist* h, int32_t n, const uint8_t* desc, const uint8_t* has_gist, int32_t bytes,
+                                   const int64_t* stamps_ns, int64_t cap, int32_t* neighbors, int32_t* count_per_node,
+                                   int64_t* n_total, int32_t* first_place_index);
+/* n successive uzl_gist_add calls: the global-scope reload of a stored graph (graph_slam_node.cpp:146-151) */
+int  uzl_gist_add_batch(uzl_gist* h, int32_t n, const uint8_t* desc, const uint8_t* has_gist, int32_t bytes,
+                        const int64_t* stamps_ns, int32_t* first_place_index);
+/* (place, distance) list of the last single search / search_and_add (for a batch: its last node) after steps 1-2 of the
+ * contract, before the time and reported-once filters (parity tests); returns its length, writes at most cap entries
+ * (place or dist may be NULL) */
+int  uzl_gist_last_knn(uzl_gist* h, int32_t cap, int32_t* place, int32_t* dist);
+
+/* ======================================================================================
  *  Wire and disk formats  
  *
  *  The data formats either side of the path: graph_slam_msgs/{Edge,Node,SensorData,Features,
@@ -794,6 +869,17 @@ int  uzl_wire_meta_encode(const uzl_wire_meta* m, const uzl_wire_sensor_transfor
 int  uzl_wire_meta_decode(const uint8_t* buf, uint64_t len, uzl_wire_meta* out, int32_t cap,
                           uzl_wire_sensor_transform* sensor_transforms, int32_t cap_initial,
                           uzl_wire_sensor_transform* sensor_transforms_initial, uint64_t* consumed);
+
+/* SensorData.gist_descriptor of a decoded sensor (any type; re-parsed from s->raw): byte i = (unsigned char) of float i as
+ * BinaryGistData::fromMsg (sensor_data.cpp:238-246) - the Feature unpack's rule: truncation, low 8 bits of the integer, 0 for NaN
+ * and values outside the int32 range.  *n = number of elements (always reported); at most cap bytes are written. */
+int  uzl_wire_sensor_gist(const uzl_wire_sensor* s, int32_t cap, uint8_t* gist, int32_t* n);
+/* A SENSOR_TYPE_BINARY_GIST SensorData as SensorData::toMsg + BinaryGistData::toMsg write it (sensor_data.cpp:40-49, 227-236):
+ * header (stamp, frame_id = sensor_frame), displacement (row-major 3x4), gist_descriptor = one float per byte; features,
+ * camera info, images and scan default-constructed.  The bytes can go into uzl_wire_sensor.raw of uzl_wire_node_encode. */
+uint64_t uzl_wire_gist_sensor_size(uzl_span sensor_frame, int32_t n);
+int  uzl_wire_gist_sensor_encode(uint32_t stamp_sec, uint32_t stamp_nsec, uzl_span sensor_frame, const double* displacement,
+                                 const uint8_t* gist, int32_t n, uint8_t* buf, uint64_t cap, uint64_t* written);
 
 /* bytes of n Feature records with desc_len descriptor elements each */
 uint64_t uzl_wire_features_size(int32_t n, int32_t desc_len);

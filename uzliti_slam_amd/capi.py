@@ -17,6 +17,7 @@ c_f64p = C.POINTER(C.c_double)
 c_i32p = C.POINTER(C.c_int32)
 c_u8p = C.POINTER(C.c_uint8)
 c_u64p = C.POINTER(C.c_uint64)
+c_i64p = C.POINTER(C.c_int64)
 
 UZL_OK = 0
 UZL_ERR_BAD_ARG = -1
@@ -183,6 +184,10 @@ class PlacesCfg(C.Structure):
                 ("device", C.c_int32), ("min_time_gap", C.c_double)]
 
 
+class GistCfg(C.Structure):
+    _fields_ = [("T", C.c_double), ("k_nearest_neighbors", C.c_int32), ("device", C.c_int32), ("min_time_gap", C.c_double)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
 
 _lib = None
@@ -223,6 +228,13 @@ def lib():
             L.uzl_places_destroy.argtypes = [C.c_void_p]
             L.uzl_places_cfg_default.restype = None
             L.uzl_places_count.argtypes = [C.c_void_p]
+        if hasattr(L, "uzl_gist_create"):
+            L.uzl_gist_last_error.restype = C.c_char_p
+            L.uzl_gist_last_error.argtypes = [C.c_void_p]
+            L.uzl_gist_destroy.restype = None
+            L.uzl_gist_destroy.argtypes = [C.c_void_p]
+            L.uzl_gist_cfg_default.restype = None
+            L.uzl_gist_count.argtypes = [C.c_void_p]
         if hasattr(L, "uzl_radius_create"):
             L.uzl_radius_last_error.restype = C.c_char_p
             L.uzl_radius_last_error.argtypes = [C.c_void_p]
@@ -1035,3 +1047,108 @@ class Places:
         out = np.zeros(max(n, 1), np.int32)
         self._check(lib().uzl_places_last_counts(self._h, C.c_int32(len(out)), _p(out, c_i32p)))
         return out[:n]
+
+
+class Gist:
+    """uzl_gist_* (BinaryGistRecognizer / PlaceRecognizer, place_recognition/src): exact k-NN under the Hamming distance over one
+    binary GIST descriptor per node.  desc=None stands for a node without a GIST sensor."""
+
+    def __init__(self, **cfg):
+        L = lib()
+        c = GistCfg()
+        L.uzl_gist_cfg_default(C.byref(c))
+        for k, v in cfg.items():
+            setattr(c, k, v)
+        self.cfg = c
+        self._h = C.c_void_p()
+        rc = L.uzl_gist_create(C.byref(c), C.byref(self._h))
+        if rc != UZL_OK:
+            raise UzlError(rc, L.uzl_status_string(rc).decode())
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().uzl_gist_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def _check(self, rc):
+        if rc < 0:
+            raise UzlError(rc, lib().uzl_gist_last_error(self._h).decode())
+        return rc
+
+    @staticmethod
+    def _d(desc):
+        if desc is None:
+            return None, None, 0
+        d = np.ascontiguousarray(desc, np.uint8).reshape(-1)
+        return d, _p(d, c_u8p), len(d)
+
+    def _cap(self, cap, n=1):
+        return n * max(self.cfg.k_nearest_neighbors, 1) if cap is None else cap
+
+    def search_and_add(self, desc, stamp_ns, cap=None):
+        d, dp, nb = self._d(desc)
+        cap = self._cap(cap)
+        out = np.zeros(max(cap, 1), np.int32); n = C.c_int32(); idx = C.c_int32()
+        self._check(lib().uzl_gist_search_and_add(self._h, dp, C.c_int32(nb), C.c_int64(int(stamp_ns)), C.c_int32(cap), _p(out, c_i32p),
+                                                  C.byref(n), C.byref(idx)))
+        return out[:min(n.value, cap)].copy(), idx.value
+
+    def add(self, desc, stamp_ns):
+        d, dp, nb = self._d(desc)
+        idx = C.c_int32()
+        self._check(lib().uzl_gist_add(self._h, dp, C.c_int32(nb), C.c_int64(int(stamp_ns)), C.byref(idx)))
+        return idx.value
+
+    def search(self, desc, stamp_ns, query_place=-1, cap=None):
+        d, dp, nb = self._d(desc)
+        cap = self._cap(cap)
+        out = np.zeros(max(cap, 1), np.int32); n = C.c_int32()
+        self._check(lib().uzl_gist_search(self._h, dp, C.c_int32(nb), C.c_int64(int(stamp_ns)), C.c_int32(query_place), C.c_int32(cap),
+                                          _p(out, c_i32p), C.byref(n)))
+        return out[:min(n.value, cap)].copy()
+
+    def remove(self, place):
+        self._check(lib().uzl_gist_remove(self._h, C.c_int32(place)))
+
+    def count(self):
+        return self._check(lib().uzl_gist_count(self._h))
+
+    @staticmethod
+    def _batch(desc, has_gist, n):
+        if desc is None:
+            return None, None, None, None, 0
+        d = np.ascontiguousarray(desc, np.uint8).reshape(n, -1)
+        hg = None if has_gist is None else np.ascontiguousarray(has_gist, np.uint8).reshape(n)
+        return d, _p(d, c_u8p), hg, _p(hg, c_u8p), d.shape[1]
+
+    def search_and_add_batch(self, desc, stamps_ns, has_gist=None, cap=None):
+        """n successive search_and_add calls; returns (neighbour lists per node, first place index, total found).  With a cap
+        below the total, the lists hold what was written (the first cap neighbours in node order)."""
+        st = np.ascontiguousarray(stamps_ns, np.int64).reshape(-1)
+        n = len(st)
+        d, dp, hg, hp, nb = self._batch(desc, has_gist, n)
+        cap = self._cap(cap, n)
+        out = np.zeros(max(cap, 1), np.int32); cnt = np.zeros(max(n, 1), np.int32)
+        total = C.c_int64(); first = C.c_int32()
+        self._check(lib().uzl_gist_search_and_add_batch(self._h, C.c_int32(n), dp, hp, C.c_int32(nb), _p(st, c_i64p), C.c_int64(cap),
+                                                        _p(out, c_i32p), _p(cnt, c_i32p), C.byref(total), C.byref(first)))
+        offs = np.concatenate([[0], np.cumsum(cnt[:n])]).astype(np.int64)
+        lists = [out[min(offs[i], cap):min(offs[i + 1], cap)].copy() for i in range(n)]
+        return lists, first.value, total.value
+
+    def add_batch(self, desc, stamps_ns, has_gist=None):
+        st = np.ascontiguousarray(stamps_ns, np.int64).reshape(-1)
+        n = len(st)
+        d, dp, hg, hp, nb = self._batch(desc, has_gist, n)
+        first = C.c_int32()
+        self._check(lib().uzl_gist_add_batch(self._h, C.c_int32(n), dp, hp, C.c_int32(nb), _p(st, c_i64p), C.byref(first)))
+        return first.value
+
+    def last_knn(self):
+        """(place, distance) of the last single search / search_and_add before the time and reported-once filters"""
+        n = self._check(lib().uzl_gist_last_knn(self._h, C.c_int32(0), None, None))
+        pl = np.zeros(max(n, 1), np.int32); di = np.zeros(max(n, 1), np.int32)
+        self._check(lib().uzl_gist_last_knn(self._h, C.c_int32(n), _p(pl, c_i32p), _p(di, c_i32p)))
+        return pl[:n], di[:n]

@@ -173,8 +173,9 @@ void put_default_laser_scan(Writer& w) { w.zeros(16 + 28 + 4 + 4); }
 
 constexpr uint64_t kFeatureFixed = 4 + 4 + 1 + 4 + 4 + 24;       // u, v, is_3d, keypoint_strength, descriptor count, keypoint_position
 
-// graph_slam_msgs/SensorData (SensorData.msg): fields in declaration order
-void get_sensor(Reader& r, uzl_wire_sensor* out)
+// graph_slam_msgs/SensorData (SensorData.msg): fields in declaration order; gist (may be NULL) receives the gist_descriptor
+// elements (4 bytes each)
+void get_sensor(Reader& r, uzl_wire_sensor* out, uzl_span* gist = nullptr)
 {
     uzl_wire_sensor s;
     memset(&s, 0, sizeof(s));
@@ -203,7 +204,9 @@ void get_sensor(Reader& r, uzl_wire_sensor* out)
     skip_camera_info(r);
     if (r.ok) { s.camera_info.p = reinterpret_cast<const char*>(r.b + cam0); s.camera_info.n = r.o - cam0; }
     skip_image(r); skip_image(r);                                                // DepthImage: depth, color
-    r.skip_array<float>();                                                       // gist_descriptor
+    const uint32_t ng = r.get<uint32_t>();                                       // gist_descriptor
+    const uzl_span g = r.bytes((uint64_t)ng * 4);
+    if (gist) *gist = g;
     skip_laser_scan(r);
     r.skip(24);                                                                  // scan_center
     if (r.ok) { s.raw.p = reinterpret_cast<const char*>(r.b + start); s.raw.n = r.o - start; }
@@ -227,6 +230,34 @@ void put_sensor(Writer& w, const uzl_wire_sensor& s)
     w.val<uint32_t>(0);
     put_default_laser_scan(w);
     w.zeros(24);
+}
+
+// SensorData::toMsg (sensor_data.cpp:40-49) + BinaryGistData::toMsg (:227-236): a SENSOR_TYPE_BINARY_GIST message, one float per
+// descriptor byte; features, images and scan default-constructed
+void put_gist_sensor(Writer& w, uint32_t sec, uint32_t nsec, const uzl_span& frame, const double displacement[12], const uint8_t* gist,
+                     int32_t n)
+{
+    put_header(w, sec, nsec, frame);
+    w.val<int32_t>(UZL_SENSOR_TYPE_BINARY_GIST);
+    put_pose(w, displacement);
+    w.str(frame);
+    put_header(w, 0, 0, uzl_span{nullptr, 0});                                   // features: header, descriptor_type, features[]
+    w.val<int32_t>(0);
+    w.val<uint32_t>(0);
+    put_default_camera_info(w);
+    put_default_image(w); put_default_image(w);
+    w.val<uint32_t>((uint32_t)n);
+    for (int32_t i = 0; i < n; i++) w.val<float>((float)gist[i]);
+    put_default_laser_scan(w);
+    w.zeros(24);
+}
+
+// `(unsigned char) msg.gist_descriptor[i]` of BinaryGistData::fromMsg (sensor_data.cpp:238-246), the rule of the Feature unpack
+// (wire_kernels.hip float_to_byte): truncation towards zero, low eight bits; NaN and values outside the int32 range give 0
+uint8_t float_to_byte(float f)
+{
+    if (!(std::fabs(f) < 2147483648.f)) return 0;
+    return (uint8_t)((uint32_t)(int32_t)f & 0xffu);
 }
 
 void put_edge(Writer& w, const uzl_wire_edge& e)       // Conversions::toMsg(SlamEdge) (conversions.cpp:255-274), Edge.msg order
@@ -606,6 +637,42 @@ int uzl_wire_node_encode(const uzl_wire_node* n, const int64_t* stamps_ns, const
     }
     Writer w(buf, cap);
     put_node(w, *n, stamps_ns, edge_ids, sensors);
+    if (written) *written = w.o;
+    return w.fits() ? UZL_OK : UZL_ERR_TRUNCATED;
+}
+
+int uzl_wire_sensor_gist(const uzl_wire_sensor* s, int32_t cap, uint8_t* gist, int32_t* n)
+{
+    if (!s || !s->raw.p || !n || cap < 0 || (cap > 0 && !gist)) return UZL_ERR_BAD_ARG;
+    Reader r(reinterpret_cast<const uint8_t*>(s->raw.p), s->raw.n);
+    uzl_span g{nullptr, 0};
+    get_sensor(r, nullptr, &g);
+    if (!r.ok) return UZL_ERR_TRUNCATED;
+    const int32_t c = (int32_t)(g.n / 4);
+    for (int32_t i = 0; i < c && i < cap; i++) {
+        float f;
+        memcpy(&f, g.p + 4 * (size_t)i, 4);
+        gist[i] = float_to_byte(f);
+    }
+    *n = c;
+    return UZL_OK;
+}
+
+uint64_t uzl_wire_gist_sensor_size(uzl_span sensor_frame, int32_t n)
+{
+    if (n < 0) return 0;
+    Writer w(nullptr, 0);
+    const double I[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    put_gist_sensor(w, 0, 0, sensor_frame, I, nullptr, 0);
+    return w.o + 4ull * (uint64_t)n;
+}
+
+int uzl_wire_gist_sensor_encode(uint32_t stamp_sec, uint32_t stamp_nsec, uzl_span sensor_frame, const double* displacement,
+                                const uint8_t* gist, int32_t n, uint8_t* buf, uint64_t cap, uint64_t* written)
+{
+    if (!displacement || n < 0 || (n > 0 && !gist) || !buf || (sensor_frame.n && !sensor_frame.p)) return UZL_ERR_BAD_ARG;
+    Writer w(buf, cap);
+    put_gist_sensor(w, stamp_sec, stamp_nsec, sensor_frame, displacement, gist, n);
     if (written) *written = w.o;
     return w.fits() ? UZL_OK : UZL_ERR_TRUNCATED;
 }

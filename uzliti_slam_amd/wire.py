@@ -15,6 +15,7 @@ from . import capi
 UZL_ERR_TRUNCATED = -9
 UZL_ERR_UNSUPPORTED = -10
 SENSOR_TYPE_FEATURE = 1
+SENSOR_TYPE_BINARY_GIST = 3
 
 
 class Span(C.Structure):
@@ -63,8 +64,12 @@ def _lib():
     global _proto_done
     L = capi.lib()
     if not _proto_done:
-        for f in ("uzl_wire_edge_size", "uzl_wire_node_size", "uzl_wire_meta_size", "uzl_wire_features_size", "uzl_bag_single_size"):
+        for f in ("uzl_wire_edge_size", "uzl_wire_node_size", "uzl_wire_meta_size", "uzl_wire_features_size", "uzl_bag_single_size",
+                  "uzl_wire_gist_sensor_size"):
             getattr(L, f).restype = C.c_uint64
+        L.uzl_wire_gist_sensor_size.argtypes = [Span, C.c_int32]
+        L.uzl_wire_gist_sensor_encode.argtypes = [C.c_uint32, C.c_uint32, Span, C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.c_int32,
+                                                  C.POINTER(C.c_uint8), C.c_uint64, C.POINTER(C.c_uint64)]
         _proto_done = True
     return L
 
@@ -248,6 +253,34 @@ def decode_node(b):
              stamps_ns=[stamps[i] for i in range(w.n_stamps)], edge_ids=[_bytes(eids[i]) for i in range(w.n_edge_ids)],
              sensors=[_sensor_out(sens[i]) for i in range(w.n_sensors)])
     return DecodedNode(f, src, sens, used.value)
+
+
+def sensor_gist(sensor_c):
+    """SensorData.gist_descriptor of a decoded sensor (a WireSensor of DecodedNode.sensors_c) as bytes, converted as
+    BinaryGistData::fromMsg does (sensor_data.cpp:238-246)."""
+    L = _lib()
+    n = C.c_int32(0)
+    _check(L.uzl_wire_sensor_gist(C.byref(sensor_c), 0, None, C.byref(n)), "sensor_gist")
+    out = (C.c_uint8 * max(n.value, 1))()
+    _check(L.uzl_wire_sensor_gist(C.byref(sensor_c), n.value, out, C.byref(n)), "sensor_gist")
+    return np.frombuffer(bytes(out), np.uint8)[:n.value].copy()
+
+
+def encode_gist_sensor(stamp_sec, stamp_nsec, sensor_frame, displacement, gist):
+    """A SENSOR_TYPE_BINARY_GIST graph_slam_msgs/SensorData (SensorData::toMsg + BinaryGistData::toMsg); the bytes go into a
+    sensor dict's `raw` for encode_node."""
+    L = _lib()
+    k = _Keep()
+    fr = k.span(sensor_frame)
+    g = np.ascontiguousarray(gist, np.uint8).reshape(-1)
+    disp = (C.c_double * 12)(*_arr(displacement, 12))
+    size = L.uzl_wire_gist_sensor_size(fr, len(g))
+    buf = (C.c_uint8 * max(size, 1))()
+    wr = C.c_uint64(0)
+    _check(L.uzl_wire_gist_sensor_encode(stamp_sec, stamp_nsec, fr, disp, g.ctypes.data_as(C.POINTER(C.c_uint8)), len(g), buf,
+                                         C.c_uint64(size), C.byref(wr)), "gist_sensor_encode")
+    assert wr.value == size
+    return bytes(buf)[:size]
 
 
 def features_size(n, desc_len):
