@@ -75,6 +75,10 @@ def test_no_gpu_means_loud_failure(capi):
     with pytest.raises(capi.UzlError) as e:
         capi.Pgo()
     assert e.value.status == capi.UZL_ERR_NO_DEVICE
+    for make in (lambda: capi.PgoBatch(2), capi.Filter, capi.Gate, capi.Radius, capi.Places, capi.Gist):
+        with pytest.raises(capi.UzlError) as e:
+            make()
+        assert e.value.status == capi.UZL_ERR_NO_DEVICE
 
 
 def test_product_does_not_reference_the_oracle():

@@ -208,55 +208,28 @@ def lib():
         if not os.path.exists(LIB_PATH):
             raise UzlError(UZL_ERR_STATE, f"{LIB_PATH} is missing: run __graft_entry__.build() / make -C {CSRC}; "
                                           "there is no CPU fallback")
-        L = C.CDLL(LIB_PATH)
-        L.uzl_status_string.restype = C.c_char_p
-        L.uzl_match_last_error.restype = C.c_char_p
-        L.uzl_match_last_error.argtypes = [C.c_void_p]
-        L.uzl_match_destroy.restype = None
-        L.uzl_match_destroy.argtypes = [C.c_void_p]
-        L.uzl_match_cfg_default.restype = None
-        if hasattr(L, "uzl_pgo_last_error"):
-            L.uzl_pgo_last_error.restype = C.c_char_p
-            L.uzl_pgo_last_error.argtypes = [C.c_void_p]
-            L.uzl_pgo_destroy.restype = None
-            L.uzl_pgo_destroy.argtypes = [C.c_void_p]
-            L.uzl_pgo_cfg_default.restype = None
-        if hasattr(L, "uzl_places_create"):
-            L.uzl_places_last_error.restype = C.c_char_p
-            L.uzl_places_last_error.argtypes = [C.c_void_p]
-            L.uzl_places_destroy.restype = None
-            L.uzl_places_destroy.argtypes = [C.c_void_p]
-            L.uzl_places_cfg_default.restype = None
-            L.uzl_places_count.argtypes = [C.c_void_p]
-        if hasattr(L, "uzl_gist_create"):
-            L.uzl_gist_last_error.restype = C.c_char_p
-            L.uzl_gist_last_error.argtypes = [C.c_void_p]
-            L.uzl_gist_destroy.restype = None
-            L.uzl_gist_destroy.argtypes = [C.c_void_p]
-            L.uzl_gist_cfg_default.restype = None
-            L.uzl_gist_count.argtypes = [C.c_void_p]
-        if hasattr(L, "uzl_radius_create"):
-            L.uzl_radius_last_error.restype = C.c_char_p
-            L.uzl_radius_last_error.argtypes = [C.c_void_p]
-            L.uzl_radius_destroy.restype = None
-            L.uzl_radius_destroy.argtypes = [C.c_void_p]
-            L.uzl_radius_cfg_default.restype = None
-        if hasattr(L, "uzl_gate_create"):
-            L.uzl_gate_last_error.restype = C.c_char_p
-            L.uzl_gate_last_error.argtypes = [C.c_void_p]
-            L.uzl_gate_destroy.restype = None
-            L.uzl_gate_destroy.argtypes = [C.c_void_p]
-            L.uzl_gate_cfg_default.restype = None
-            L.uzl_gate_edge_count.argtypes = [C.c_void_p]
-        if hasattr(L, "uzl_filter_create"):
-            L.uzl_filter_last_error.restype = C.c_char_p
-            L.uzl_filter_last_error.argtypes = [C.c_void_p]
-            L.uzl_filter_destroy.restype = None
-            L.uzl_filter_destroy.argtypes = [C.c_void_p]
-            L.uzl_filter_cfg_default.restype = None
-            L.uzl_filter_cluster_count.argtypes = [C.c_void_p]
-        _lib = L
+        _lib = _declare(C.CDLL(LIB_PATH))
     return _lib
+
+
+_HANDLES = ("uzl_match", "uzl_pgo", "uzl_pgo_batch", "uzl_filter", "uzl_gate", "uzl_radius", "uzl_places", "uzl_gist")
+
+
+def _declare(L):
+    """The prototypes ctypes cannot guess: every handle's last_error / destroy / cfg_default, and the calls that take only a handle."""
+    L.uzl_status_string.restype = C.c_char_p
+    for p in _HANDLES:
+        getattr(L, p + "_last_error").restype = C.c_char_p
+        getattr(L, p + "_last_error").argtypes = [C.c_void_p]
+        getattr(L, p + "_destroy").restype = None
+        getattr(L, p + "_destroy").argtypes = [C.c_void_p]
+        if hasattr(L, p + "_cfg_default"):          # (a batch takes uzl_pgo_cfg)
+            getattr(L, p + "_cfg_default").restype = None
+    for f in ("uzl_places_count", "uzl_gist_count", "uzl_gate_edge_count", "uzl_filter_cluster_count"):
+        getattr(L, f).argtypes = [C.c_void_p]
+    L.uzl_pgo_batch_graph.restype = C.c_void_p
+    L.uzl_pgo_batch_graph.argtypes = [C.c_void_p, C.c_int32]
+    return L
 
 
 def _p(a, t):
@@ -278,14 +251,7 @@ def diag_lib():
     if _diag is None:
         if not os.path.exists(DIAG_LIB_PATH):
             raise UzlError(UZL_ERR_STATE, f"{DIAG_LIB_PATH} is missing: make -C {CSRC} diag")
-        D = C.CDLL(DIAG_LIB_PATH)
-        D.uzl_status_string.restype = C.c_char_p
-        D.uzl_pgo_last_error.restype = C.c_char_p
-        D.uzl_pgo_last_error.argtypes = [C.c_void_p]
-        D.uzl_pgo_destroy.restype = None
-        D.uzl_pgo_destroy.argtypes = [C.c_void_p]
-        D.uzl_pgo_cfg_default.restype = None
-        _diag = D
+        _diag = _declare(C.CDLL(DIAG_LIB_PATH))
     return _diag
 
 
@@ -311,37 +277,54 @@ def rccl_unique_id():
     return bytes(buf.raw)
 
 
-# --------------------------------------------------------------------------------------- estimator
-class Match:
-    """Thin object wrapper over the uzl_match_* C ABI."""
+# --------------------------------------------------------------------------------------- handles
+class _Handle:
+    """One uzl_<name>_* handle: `cfg` is <prefix>_cfg_default's config with the keyword arguments set on it, `_h` the handle."""
 
-    def __init__(self, **cfg):
-        L = lib()
-        c = MatchCfg()
-        L.uzl_match_cfg_default(C.byref(c))
+    _prefix = None                  # "uzl_gist", ...
+    _cfg_type = None                # its config struct
+    _cfg_default = None             # the function that fills it, when not <prefix>_cfg_default
+    _lib = staticmethod(lambda: lib())
+
+    def __init__(self, *args, **cfg):
+        """args: what <prefix>_create takes between the config and the handle (a batch's n_graphs)."""
+        L = self._lib()
+        c = self._cfg_type()
+        getattr(L, self._cfg_default or self._prefix + "_cfg_default")(C.byref(c))
         for k, v in cfg.items():
             setattr(c, k, v)
         self.cfg = c
         self._h = C.c_void_p()
-        rc = L.uzl_match_create(C.byref(c), C.byref(self._h))
+        rc = getattr(L, self._prefix + "_create")(C.byref(c), *args, C.byref(self._h))
         if rc != UZL_OK:
             raise UzlError(rc, L.uzl_status_string(rc).decode())
 
     def close(self):
         if getattr(self, "_h", None):
-            lib().uzl_match_destroy(self._h)
+            getattr(self._lib(), self._prefix + "_destroy")(self._h)
             self._h = None
 
     __del__ = close
 
-    def _check(self, rc):
-        if rc != UZL_OK:
-            raise UzlError(rc, lib().uzl_match_last_error(self._h).decode())
+    def _check(self, rc, allow=()):
+        """Raises with the handle's last_error for a failure status (< 0) not in `allow`; returns rc (counts are >= 0)."""
+        if rc < 0 and rc not in allow:
+            raise UzlError(rc, getattr(self._lib(), self._prefix + "_last_error")(self._h).decode())
+        return rc
 
-    def set_config(self, **cfg):
+    def _set_config(self, **cfg):
+        """set_config of the handles with a <prefix>_set_config (match and pgo)"""
         for k, v in cfg.items():
             setattr(self.cfg, k, v)
-        self._check(lib().uzl_match_set_config(self._h, C.byref(self.cfg)))
+        self._check(getattr(self._lib(), self._prefix + "_set_config")(self._h, C.byref(self.cfg)))
+
+
+# --------------------------------------------------------------------------------------- estimator
+class Match(_Handle):
+    """Thin object wrapper over the uzl_match_* C ABI."""
+
+    _prefix, _cfg_type = "uzl_match", MatchCfg
+    set_config = _Handle._set_config
 
     def add_frame(self, desc, pos, valid, feature_type=2, sensor_frame=0):
         """desc (n,bytes) u8; pos (3,n) f64; valid (n) u8 -> frame id."""
@@ -480,41 +463,16 @@ class Match:
 
 
 # --------------------------------------------------------------------------------------- optimizer
-class Pgo:
+class Pgo(_Handle):
     """Thin object wrapper over the uzl_pgo_* C ABI."""
 
-    _lib = staticmethod(lambda: lib())
+    _prefix, _cfg_type = "uzl_pgo", PgoCfg
+    set_config = _Handle._set_config
 
     def __init__(self, **cfg):
-        L = self._lib()
-        c = PgoCfg()
-        L.uzl_pgo_cfg_default(C.byref(c))
-        for k, v in cfg.items():
-            setattr(c, k, v)
-        self.cfg = c
-        self._h = C.c_void_p()
-        rc = L.uzl_pgo_create(C.byref(c), C.byref(self._h))
-        if rc != UZL_OK:
-            raise UzlError(rc, L.uzl_status_string(rc).decode())
+        super().__init__(**cfg)
         self.n = 0
         self.e_in = 0
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib().uzl_pgo_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def _check(self, rc, allow=()):
-        if rc != UZL_OK and rc not in allow:
-            raise UzlError(rc, self._lib().uzl_pgo_last_error(self._h).decode())
-        return rc
-
-    def set_config(self, **cfg):
-        for k, v in cfg.items():
-            setattr(self.cfg, k, v)
-        self._check(self._lib().uzl_pgo_set_config(self._h, C.byref(self.cfg)))
 
     def add_graph(self, nodes_pose, nodes_fixed, edges, sensors=None):
         """Reference-shaped input (SlamNode / SlamEdge arrays, see synth.make_pose_graph)."""
@@ -705,40 +663,25 @@ class _BorrowedPgo(Pgo):
     __del__ = close
 
 
-class PgoBatch:
+class PgoBatch(_Handle):
     """uzl_pgo_batch_*: n independent graphs solved through shared launches.  `graphs[i]` is an ordinary Pgo over handle i
     (add_graph / set_graph / reset / store); optimize() solves them all and returns one stats dict per graph."""
 
+    _prefix, _cfg_type, _cfg_default = "uzl_pgo_batch", PgoCfg, "uzl_pgo_cfg_default"
+
     def __init__(self, n_graphs, **cfg):
-        L = lib()
-        c = PgoCfg()
-        L.uzl_pgo_cfg_default(C.byref(c))
-        for k, v in cfg.items():
-            setattr(c, k, v)
-        self.cfg = c
-        self._b = C.c_void_p()
-        L.uzl_pgo_batch_graph.restype = C.c_void_p
-        L.uzl_pgo_batch_graph.argtypes = [C.c_void_p, C.c_int32]
-        L.uzl_pgo_batch_last_error.restype = C.c_char_p
-        L.uzl_pgo_batch_last_error.argtypes = [C.c_void_p]
-        L.uzl_pgo_batch_destroy.restype = None
-        L.uzl_pgo_batch_destroy.argtypes = [C.c_void_p]
-        rc = L.uzl_pgo_batch_create(C.byref(c), C.c_int32(n_graphs), C.byref(self._b))
-        if rc != UZL_OK:
-            raise UzlError(rc, L.uzl_status_string(rc).decode())
+        super().__init__(C.c_int32(n_graphs), **cfg)
         self.graphs = []
         for i in range(n_graphs):
             p = _BorrowedPgo.__new__(_BorrowedPgo)
-            p.cfg = c; p._h = C.c_void_p(L.uzl_pgo_batch_graph(self._b, i)); p.n = 0; p.e_in = 0
+            p.cfg = self.cfg; p._h = C.c_void_p(lib().uzl_pgo_batch_graph(self._h, i)); p.n = 0; p.e_in = 0
             self.graphs.append(p)
         self.n_batched = 0
 
     def optimize(self, iterations=0):
         n = len(self.graphs)
         st = (PgoStats * n)(); nb = C.c_int32()
-        rc = lib().uzl_pgo_batch_optimize(self._b, C.c_int32(iterations), st, C.byref(nb))
-        if rc not in (UZL_OK, UZL_ERR_NOT_CONVERGED):
-            raise UzlError(rc, lib().uzl_pgo_batch_last_error(self._b).decode())
+        rc = self._check(lib().uzl_pgo_batch_optimize(self._h, C.c_int32(iterations), st, C.byref(nb)), allow=(UZL_ERR_NOT_CONVERGED,))
         self.n_batched = nb.value
         out = []
         for i in range(n):
@@ -748,56 +691,33 @@ class PgoBatch:
 
     def set_resident(self, n):
         """graphs solved at a time (0 = all); the rest of the batch waits in a queue and takes the slots of finished graphs"""
-        rc = lib().uzl_pgo_batch_set_resident(self._b, C.c_int32(n))
+        rc = lib().uzl_pgo_batch_set_resident(self._h, C.c_int32(n))
         if rc != UZL_OK:
             raise UzlError(rc, "uzl_pgo_batch_set_resident")
 
     def set_profiling(self, on):
-        lib().uzl_pgo_batch_set_profiling(self._b, C.c_int32(1 if on else 0))
+        lib().uzl_pgo_batch_set_profiling(self._h, C.c_int32(1 if on else 0))
 
     def kernel_times(self):
         cap = 16
         names = (C.c_char_p * cap)(); ms = (C.c_double * cap)(); ln = (C.c_int32 * cap)()
-        n = lib().uzl_pgo_batch_kernel_times(self._b, C.c_int32(cap), names, ms, ln)
+        n = lib().uzl_pgo_batch_kernel_times(self._h, C.c_int32(cap), names, ms, ln)
         return {names[i].decode(): dict(ms=ms[i], launches=ln[i]) for i in range(max(n, 0))}
 
     def close(self):
-        if getattr(self, "_b", None):
+        if getattr(self, "_h", None):
             for p in self.graphs:
                 p._h = None
-            lib().uzl_pgo_batch_destroy(self._b)
-            self._b = None
+        super().close()
 
     __del__ = close
 
 
 # --------------------------------------------------------------------------------------- edge filter
-class Filter:
+class Filter(_Handle):
     """uzl_filter_* (TransformationFilter / EdgeCluster, transformation_filter.cpp:43-350)."""
 
-    def __init__(self, **cfg):
-        L = lib()
-        c = FilterCfg()
-        L.uzl_filter_cfg_default(C.byref(c))
-        for k, v in cfg.items():
-            setattr(c, k, v)
-        self.cfg = c
-        self._h = C.c_void_p()
-        rc = L.uzl_filter_create(C.byref(c), C.byref(self._h))
-        if rc != UZL_OK:
-            raise UzlError(rc, L.uzl_status_string(rc).decode())
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().uzl_filter_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def _check(self, rc):
-        if rc < 0:
-            raise UzlError(rc, lib().uzl_filter_last_error(self._h).decode())
-        return rc
+    _prefix, _cfg_type = "uzl_filter", FilterCfg
 
     def set_sensors(self, sensors):
         s = np.ascontiguousarray(sensors, np.float64).reshape(-1, 12)
@@ -856,32 +776,10 @@ class Filter:
 
 
 # --------------------------------------------------------------------------------------- edge acceptance gate
-class Gate:
+class Gate(_Handle):
     """uzl_gate_* (GraphSlamNode::newEdgeCallback / checkEdgeHeuristic / SlamGraph::astar)."""
 
-    def __init__(self, **cfg):
-        L = lib()
-        c = GateCfg()
-        L.uzl_gate_cfg_default(C.byref(c))
-        for k, v in cfg.items():
-            setattr(c, k, v)
-        self.cfg = c
-        self._h = C.c_void_p()
-        rc = L.uzl_gate_create(C.byref(c), C.byref(self._h))
-        if rc != UZL_OK:
-            raise UzlError(rc, L.uzl_status_string(rc).decode())
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().uzl_gate_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def _check(self, rc):
-        if rc < 0:
-            raise UzlError(rc, lib().uzl_gate_last_error(self._h).decode())
-        return rc
+    _prefix, _cfg_type = "uzl_gate", GateCfg
 
     def set_graph(self, poses, edges, merged=None):
         """poses (n,12); edges: GATE_EDGE_DTYPE array (from, to, type, valid); merged (n) u8 or None."""
@@ -939,32 +837,10 @@ def schur_plan_strong(row_ptr, col, slot_w, cap=24, strong_min=1, theta=0.25, on
 
 
 # --------------------------------------------------------------------------------------- distance loop-closure candidates
-class Radius:
+class Radius(_Handle):
     """uzl_radius_* (SlamGraph::getNodesWithinRadius + the caller's filters, graph_slam_node.cpp:272-289)."""
 
-    def __init__(self, **cfg):
-        L = lib()
-        c = RadiusCfg()
-        L.uzl_radius_cfg_default(C.byref(c))
-        for k, v in cfg.items():
-            setattr(c, k, v)
-        self.cfg = c
-        self._h = C.c_void_p()
-        rc = L.uzl_radius_create(C.byref(c), C.byref(self._h))
-        if rc != UZL_OK:
-            raise UzlError(rc, L.uzl_status_string(rc).decode())
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().uzl_radius_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def _check(self, rc):
-        if rc < 0:
-            raise UzlError(rc, lib().uzl_radius_last_error(self._h).decode())
-        return rc
+    _prefix, _cfg_type = "uzl_radius", RadiusCfg
 
     def set_nodes(self, poses, stamps_front_ns):
         P = np.ascontiguousarray(poses, np.float64).reshape(-1, 12); st = np.ascontiguousarray(stamps_front_ns, np.int64)
@@ -983,32 +859,10 @@ class Radius:
 
 
 # --------------------------------------------------------------------------------------- appearance-based candidates
-class Places:
+class Places(_Handle):
     """uzl_places_* (FastLshSet / LshSetRecognizer / PlaceRecognizer, place_recognition/src)."""
 
-    def __init__(self, **cfg):
-        L = lib()
-        c = PlacesCfg()
-        L.uzl_places_cfg_default(C.byref(c))
-        for k, v in cfg.items():
-            setattr(c, k, v)
-        self.cfg = c
-        self._h = C.c_void_p()
-        rc = L.uzl_places_create(C.byref(c), C.byref(self._h))
-        if rc != UZL_OK:
-            raise UzlError(rc, L.uzl_status_string(rc).decode())
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().uzl_places_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def _check(self, rc):
-        if rc < 0:
-            raise UzlError(rc, lib().uzl_places_last_error(self._h).decode())
-        return rc
+    _prefix, _cfg_type = "uzl_places", PlacesCfg
 
     @staticmethod
     def _d(desc):
@@ -1049,33 +903,11 @@ class Places:
         return out[:n]
 
 
-class Gist:
+class Gist(_Handle):
     """uzl_gist_* (BinaryGistRecognizer / PlaceRecognizer, place_recognition/src): exact k-NN under the Hamming distance over one
     binary GIST descriptor per node.  desc=None stands for a node without a GIST sensor."""
 
-    def __init__(self, **cfg):
-        L = lib()
-        c = GistCfg()
-        L.uzl_gist_cfg_default(C.byref(c))
-        for k, v in cfg.items():
-            setattr(c, k, v)
-        self.cfg = c
-        self._h = C.c_void_p()
-        rc = L.uzl_gist_create(C.byref(c), C.byref(self._h))
-        if rc != UZL_OK:
-            raise UzlError(rc, L.uzl_status_string(rc).decode())
-
-    def close(self):
-        if getattr(self, "_h", None):
-            lib().uzl_gist_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def _check(self, rc):
-        if rc < 0:
-            raise UzlError(rc, lib().uzl_gist_last_error(self._h).decode())
-        return rc
+    _prefix, _cfg_type = "uzl_gist", GistCfg
 
     @staticmethod
     def _d(desc):

@@ -91,9 +91,7 @@ hipError_t kl_ml_pcg_its(const LmSlot* sl, const LmSlot* host_slot, const LmShap
 namespace uzl { struct LmRun; }
 using namespace uzl;      // (private header of the uzl_pgo_* translation units; the handle itself is the C ABI's global-namespace type)
 
-struct uzl_pgo {
-    std::mutex mu;
-    std::string last_error;
+struct uzl_pgo : uzl::HandleBase {
     uzl_pgo_cfg cfg;
     hipStream_t stream = nullptr;
     // ---- host-side structure of the current problem
@@ -210,7 +208,6 @@ inline double pgo_tol_f2(const uzl_pgo_cfg& c) { return c.pcg_stop == 1 ? 1. : k
 inline double pgo_eps_t(const uzl_pgo_cfg& c) { return c.pcg_stop == 1 ? 0. : kStepT * c.pcg_tol; }
 inline double pgo_eps_r(const uzl_pgo_cfg& c) { return c.pcg_stop == 1 ? 0. : kStepR * c.pcg_tol; }
 // ---- shared host-side pieces (uzl_pgo.hip)
-int pgo_fail(uzl_pgo* h, int code, const char* msg);
 int32_t gauge_fix(uzl_pgo* h);                        // G2: setFixedNodes (g2o_optimizer.cpp:301-349)
 void build_structure(uzl_pgo* h);                     // block-CSR, Schur plan, hierarchy; bumps structure_gen
 void destroy_pcg_graph(uzl_pgo* h);

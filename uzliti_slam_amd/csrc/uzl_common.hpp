@@ -7,6 +7,7 @@
 #include <cstring>
 #include <map>
 #include <mutex>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -65,6 +66,49 @@ inline int report(std::string& last_error, const HipError& e)
            : (e.code == hipErrorNoDevice || e.code == hipErrorInvalidDevice) ? UZL_ERR_NO_DEVICE
                                                                              : UZL_ERR_HIP;
 }
+
+// What every uzl_* handle holds besides its own state: the lock its C-ABI calls take and the message of its last failure.  The handle
+// structs derive from it; they are opaque to C, so the ABI does not see it.
+struct HandleBase {
+    std::mutex mu;
+    std::string last_error;
+};
+
+inline int fail(HandleBase* h, int code, const char* msg)
+{
+    h->last_error = msg;
+    return code;
+}
+
+inline const char* last_error_of(const HandleBase* h) { return h ? h->last_error.c_str() : "null handle"; }
+
+// UZL_OK if `device` is a visible HIP device, else UZL_ERR_NO_DEVICE (there is no CPU fallback).
+inline int check_device(int device)
+{
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0 || device < 0 || device >= n) return UZL_ERR_NO_DEVICE;
+    return UZL_OK;
+}
+
+// The status of the exception being handled, its message written to `last_error`; call it inside a catch block.  The guard's three
+// catch clauses as one call, for a create, which has the same cleaning up to do whatever was thrown.
+inline int caught_status(std::string& last_error)
+{
+    try { throw; }
+    catch (const HipError& e) { return report(last_error, e); }
+    catch (const std::bad_alloc&) { last_error = "host out of memory"; return UZL_ERR_OOM; }
+    catch (...) { last_error = "unexpected exception"; return UZL_ERR_HIP; }
+}
+
+// The body of every C-ABI call on a handle: null check, the handle's lock, and every exception turned into a status.
+#define UZL_GUARD_BEGIN(h)                       \
+    if (!(h)) return UZL_ERR_BAD_ARG;            \
+    std::lock_guard<std::mutex> lock_((h)->mu);  \
+    try {
+#define UZL_GUARD_END(h)                                                             \
+    } catch (const ::uzl::HipError& e) { return ::uzl::report((h)->last_error, e); } \
+    catch (const std::bad_alloc&) { (h)->last_error = "host out of memory"; return UZL_ERR_OOM; } \
+    catch (...) { (h)->last_error = "unexpected exception"; return UZL_ERR_HIP; }
 
 // Growable device buffer (never shrinks).  Plain hipMalloc: 288 GB of HBM, nothing is paged.
 template <typename T>

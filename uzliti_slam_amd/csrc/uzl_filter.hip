@@ -96,9 +96,7 @@ typedef std::shared_ptr<Cluster> ClusterPtr;
 
 }  // namespace
 
-struct uzl_filter {
-    std::mutex mu;
-    std::string last_error;
+struct uzl_filter : HandleBase {
     uzl_filter_cfg cfg;
     uzl_match* fte = nullptr;                                       // TransformationFilter::fte (transformation_filter.h:105)
     std::vector<ClusterPtr> clusters;                               // clusters_
@@ -116,12 +114,6 @@ struct uzl_filter {
 };
 
 namespace {
-
-int fail(uzl_filter* h, int code, const char* msg)
-{
-    h->last_error = msg;
-    return code;
-}
 
 EdgeRec make_rec(const uzl_filter_edge& e, int64_t tf, int64_t tt)
 {
@@ -201,15 +193,6 @@ void remove_one(uzl_filter* h, uint64_t key)
 
 }  // namespace
 
-#define UZL_GUARD_BEGIN(h)                       \
-    if (!(h)) return UZL_ERR_BAD_ARG;            \
-    std::lock_guard<std::mutex> lock_((h)->mu);  \
-    try {
-#define UZL_GUARD_END(h)                                                             \
-    } catch (const ::uzl::HipError& e) { return ::uzl::report((h)->last_error, e); } \
-    catch (const std::bad_alloc&) { (h)->last_error = "host out of memory"; return UZL_ERR_OOM; } \
-    catch (...) { (h)->last_error = "unexpected exception"; return UZL_ERR_HIP; }
-
 extern "C" {
 
 void uzl_filter_cfg_default(uzl_filter_cfg* c)
@@ -248,7 +231,7 @@ void uzl_filter_destroy(uzl_filter* h)
     delete h;
 }
 
-const char* uzl_filter_last_error(uzl_filter* h) { return h ? h->last_error.c_str() : "null handle"; }
+const char* uzl_filter_last_error(uzl_filter* h) { return last_error_of(h); }
 
 int uzl_filter_set_sensors(uzl_filter* h, int32_t n_sensors, const double* sensors)
 {

@@ -25,9 +25,7 @@ bool launch_gate_bound(const GateWaveArgs& a, hipStream_t s);
 }
 using namespace uzl;
 
-struct uzl_gate {
-    std::mutex mu;
-    std::string last_error;
+struct uzl_gate : HandleBase {
     uzl_gate_cfg cfg;
     hipStream_t stream = nullptr;
     int32_t n = 0;
@@ -63,12 +61,6 @@ struct uzl_gate {
 };
 
 namespace {
-
-int fail(uzl_gate* h, int code, const char* msg)
-{
-    h->last_error = msg;
-    return code;
-}
 
 // node indices are below 2^28 (a graph of that size does not fit the search's scratch anyway), edge types below 2^8
 inline uint64_t pair_key(int32_t from, int32_t to, int32_t type)
@@ -121,15 +113,6 @@ void build_adjacency(uzl_gate* h)
 
 }  // namespace
 
-#define UZL_GUARD_BEGIN(h)                       \
-    if (!(h)) return UZL_ERR_BAD_ARG;            \
-    std::lock_guard<std::mutex> lock_((h)->mu);  \
-    try {
-#define UZL_GUARD_END(h)                                                             \
-    } catch (const ::uzl::HipError& e) { return ::uzl::report((h)->last_error, e); } \
-    catch (const std::bad_alloc&) { (h)->last_error = "host out of memory"; return UZL_ERR_OOM; } \
-    catch (...) { (h)->last_error = "unexpected exception"; return UZL_ERR_HIP; }
-
 extern "C" {
 
 void uzl_gate_cfg_default(uzl_gate_cfg* c)
@@ -146,18 +129,19 @@ int uzl_gate_create(const uzl_gate_cfg* cfg, uzl_gate** out)
     *out = nullptr;
     uzl_gate_cfg c;
     if (cfg) c = *cfg; else uzl_gate_cfg_default(&c);
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return UZL_ERR_NO_DEVICE;     // no CPU fallback
-    if (c.device < 0 || c.device >= count) return UZL_ERR_NO_DEVICE;
+    if (check_device(c.device) != UZL_OK) return UZL_ERR_NO_DEVICE;
     uzl_gate* h = new (std::nothrow) uzl_gate();
     if (!h) return UZL_ERR_OOM;
     h->cfg = c;
     h->dbg_on = diag_flag("UZL_GATE_DBG");
-    if (hipSetDevice(c.device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
+    try {
+        open_handle_stream(c.device, false, &h->stream);
+    } catch (...) {
+        const int code = caught_status(h->last_error);
+        close_handle_stream(c.device, h->stream);
         delete h;
-        return UZL_ERR_HIP;
+        return code;
     }
-    stream_register(c.device, h->stream, false);
     *out = h;
     return UZL_OK;
 }
@@ -166,11 +150,11 @@ void uzl_gate_destroy(uzl_gate* h)
 {
     if (!h) return;
     (void)hipSetDevice(h->cfg.device);
-    if (h->stream) { (void)hipStreamSynchronize(h->stream); stream_unregister(h->cfg.device, h->stream); (void)hipStreamDestroy(h->stream); }
+    close_handle_stream(h->cfg.device, h->stream);
     delete h;
 }
 
-const char* uzl_gate_last_error(uzl_gate* h) { return h ? h->last_error.c_str() : "null handle"; }
+const char* uzl_gate_last_error(uzl_gate* h) { return last_error_of(h); }
 
 int uzl_gate_set_graph(uzl_gate* h, int32_t n_nodes, const double* poses, const uint8_t* merged, int32_t n_edges,
                        const uzl_gate_edge* edges)

@@ -24,9 +24,7 @@ constexpr int kGistSlice = 4096;      // queries per launch of a batch (bounds t
 
 using namespace uzl;
 
-struct uzl_gist {
-    std::mutex mu;
-    std::string last_error;
+struct uzl_gist : HandleBase {
     uzl_gist_cfg cfg;
     hipStream_t stream = nullptr;
     int32_t bytes = 0, stride = 0;                 // fixed by the first indexed descriptor
@@ -40,8 +38,6 @@ struct uzl_gist {
 };
 
 namespace {
-
-int fail(uzl_gist* h, int code, const char* msg) { h->last_error = msg; return code; }
 
 // descriptor length of a call that indexes or searches with `bytes`
 int check_bytes(uzl_gist* h, int32_t bytes)
@@ -179,15 +175,6 @@ void search_and_add_n(uzl_gist* h, int32_t n, const uint8_t* desc, const uint8_t
 
 }  // namespace
 
-#define UZL_GUARD_BEGIN(h)                       \
-    if (!(h)) return UZL_ERR_BAD_ARG;            \
-    std::lock_guard<std::mutex> lock_((h)->mu);  \
-    try {
-#define UZL_GUARD_END(h)                                                             \
-    } catch (const ::uzl::HipError& e) { return ::uzl::report((h)->last_error, e); } \
-    catch (const std::bad_alloc&) { (h)->last_error = "host out of memory"; return UZL_ERR_OOM; } \
-    catch (...) { (h)->last_error = "unexpected exception"; return UZL_ERR_HIP; }
-
 extern "C" {
 
 void uzl_gist_cfg_default(uzl_gist_cfg* c)
@@ -204,18 +191,19 @@ int uzl_gist_create(const uzl_gist_cfg* cfg, uzl_gist** out)
     uzl_gist_cfg c;
     if (cfg) c = *cfg; else uzl_gist_cfg_default(&c);
     if (std::isnan(c.T) || c.k_nearest_neighbors < 0 || c.k_nearest_neighbors > kGistMaxK) return UZL_ERR_BAD_ARG;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return UZL_ERR_NO_DEVICE;     // no CPU fallback
-    if (c.device < 0 || c.device >= count) return UZL_ERR_NO_DEVICE;
+    if (check_device(c.device) != UZL_OK) return UZL_ERR_NO_DEVICE;
     uzl_gist* h = new (std::nothrow) uzl_gist();
     if (!h) return UZL_ERR_OOM;
     h->cfg = c;
     try {
-        UZL_HIP(hipSetDevice(c.device));
-        UZL_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        stream_register(c.device, h->stream, false);
+        open_handle_stream(c.device, false, &h->stream);
         h->d_query.reserve(kGistMaxBytes);
-    } catch (...) { delete h; return UZL_ERR_HIP; }
+    } catch (...) {
+        const int code = caught_status(h->last_error);
+        close_handle_stream(c.device, h->stream);
+        delete h;
+        return code;
+    }
     *out = h;
     return UZL_OK;
 }
@@ -224,11 +212,11 @@ void uzl_gist_destroy(uzl_gist* h)
 {
     if (!h) return;
     (void)hipSetDevice(h->cfg.device);
-    if (h->stream) { (void)hipStreamSynchronize(h->stream); stream_unregister(h->cfg.device, h->stream); (void)hipStreamDestroy(h->stream); }
+    close_handle_stream(h->cfg.device, h->stream);
     delete h;
 }
 
-const char* uzl_gist_last_error(uzl_gist* h) { return h ? h->last_error.c_str() : "null handle"; }
+const char* uzl_gist_last_error(uzl_gist* h) { return last_error_of(h); }
 
 int uzl_gist_search_and_add(uzl_gist* h, const uint8_t* desc, int32_t bytes, int64_t stamp_ns, int32_t cap, int32_t* neighbors,
                             int32_t* n_neighbors, int32_t* place_index)

@@ -34,9 +34,7 @@ struct Extent { size_t off, size; };
 
 using namespace uzl;
 
-struct uzl_match {
-    std::mutex mu;
-    std::string last_error;
+struct uzl_match : HandleBase {
     uzl_match_cfg cfg;
     hipStream_t stream = nullptr;
     // frame arena: one HBM allocation, frames addressed by offset so it can grow
@@ -77,12 +75,6 @@ struct uzl_match {
 };
 
 namespace {
-
-int fail(uzl_match* h, int code, const char* msg)
-{
-    h->last_error = msg;
-    return code;
-}
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 constexpr size_t kUpHalf = 8u << 20;          // bytes per half of the add_frame staging buffer
@@ -351,15 +343,6 @@ int enqueue_ransac(uzl_match* h, int32_t n_problems, const int32_t* offsets, con
 
 }  // namespace
 
-#define UZL_GUARD_BEGIN(h)                       \
-    if (!(h)) return UZL_ERR_BAD_ARG;            \
-    std::lock_guard<std::mutex> lock_((h)->mu);  \
-    try {
-#define UZL_GUARD_END(h)                                                             \
-    } catch (const ::uzl::HipError& e) { return ::uzl::report((h)->last_error, e); } \
-    catch (const std::bad_alloc&) { (h)->last_error = "host out of memory"; return UZL_ERR_OOM; } \
-    catch (...) { (h)->last_error = "unexpected exception"; return UZL_ERR_HIP; }
-
 extern "C" {
 
 int uzl_abi_version(void) { return UZL_ABI_VERSION; }
@@ -409,21 +392,16 @@ int uzl_match_create(const uzl_match_cfg* cfg, uzl_match** out)
     *out = nullptr;
     uzl_match_cfg c;
     if (cfg) c = *cfg; else uzl_match_cfg_default(&c);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return UZL_ERR_NO_DEVICE;
-    if (c.device < 0 || c.device >= ndev) return UZL_ERR_NO_DEVICE;
+    if (check_device(c.device) != UZL_OK) return UZL_ERR_NO_DEVICE;
     uzl_match* h = new (std::nothrow) uzl_match();
     if (!h) return UZL_ERR_OOM;
     h->cfg = c;
     try {
-        UZL_HIP(hipSetDevice(c.device));
-        UZL_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        stream_register(c.device, h->stream, true);               // (its launch sequences run beside a solve: config 5)
+        open_handle_stream(c.device, true, &h->stream);              // (its launch sequences run beside a solve: config 5)
         h->arena.reserve((size_t)64 << 20);
-    } catch (const HipError& e) {
-        std::string msg;
-        int code = report(msg, e);
-        if (h->stream) { stream_unregister(c.device, h->stream); (void)hipStreamDestroy(h->stream); }
+    } catch (...) {
+        const int code = caught_status(h->last_error);
+        close_handle_stream(c.device, h->stream);
         delete h;
         return code;
     }
@@ -435,7 +413,7 @@ void uzl_match_destroy(uzl_match* h)
 {
     if (!h) return;
     (void)hipSetDevice(h->cfg.device);
-    if (h->stream) { (void)hipStreamSynchronize(h->stream); stream_unregister(h->cfg.device, h->stream); (void)hipStreamDestroy(h->stream); }
+    close_handle_stream(h->cfg.device, h->stream);
     for (auto& e : h->up_ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : h->bulk_ev) if (e) (void)hipEventDestroy(e);
     delete h;
@@ -452,7 +430,7 @@ int uzl_match_set_config(uzl_match* h, const uzl_match_cfg* cfg)
     return UZL_OK;
 }
 
-const char* uzl_match_last_error(uzl_match* h) { return h ? h->last_error.c_str() : "null handle"; }
+const char* uzl_match_last_error(uzl_match* h) { return last_error_of(h); }
 
 int uzl_match_add_frame(uzl_match* h, const uzl_frame* f, int32_t* frame_id)
 {

@@ -66,16 +66,9 @@ int ml_ns_steps_at(int structure_steps, int it)
     return (structure_steps > 2 && it < kNsEarlyIts) ? kNsEarlySteps : structure_steps;
 }
 double ml_rate_drop(const uzl_pgo* h) { return (!ml_async_level(h) && h->ml_comp) ? kRateDropSyncDense : kRateDrop; }
-int pgo_fail(uzl_pgo* h, int code, const char* msg)
-{
-    h->last_error = msg;
-    return code;
-}
 }  // namespace uzl
 
 namespace {
-
-inline int fail(uzl_pgo* h, int code, const char* msg) { return pgo_fail(h, code, msg); }
 
 struct Timed {
     uzl_pgo* h;
@@ -1035,7 +1028,7 @@ void prepare_optimize(uzl_pgo* h)
 }
 int do_optimize(uzl_pgo* h, int32_t iterations, uzl_pgo_stats* st)
 {
-    if (!h->have_graph) return pgo_fail(h, UZL_ERR_STATE, "optimize before add_graph/set_graph");
+    if (!h->have_graph) return fail(h, UZL_ERR_STATE, "optimize before add_graph/set_graph");
     UZL_HIP(hipSetDevice(h->cfg.device));
     if (iterations <= 0) iterations = h->cfg.iterations;
     prepare_optimize(h);
@@ -1337,15 +1330,6 @@ static void keep_or_drop_numbering_history(uzl_pgo* h, const StructureKey& k)
     if (!grown) { h->num_its[0] = h->num_its[1] = -1.; h->num_last = -1; }
 }
 
-#define UZL_GUARD_BEGIN(h)                       \
-    if (!(h)) return UZL_ERR_BAD_ARG;            \
-    std::lock_guard<std::mutex> lock_((h)->mu);  \
-    try {
-#define UZL_GUARD_END(h)                                                             \
-    } catch (const ::uzl::HipError& e) { return ::uzl::report((h)->last_error, e); } \
-    catch (const std::bad_alloc&) { (h)->last_error = "host out of memory"; return UZL_ERR_OOM; } \
-    catch (...) { (h)->last_error = "unexpected exception"; return UZL_ERR_HIP; }
-
 // A handle with a stream pair of its own from the device's pool (uzl_pgo_create), or - the graphs of a batch - on the batch's streams: a
 // stream costs the runtime ~3.5 ms to make and ~2 ms to destroy (round 4's uzl_pgo_create 6.9 ms, measured: tests/diag/create_cost.py),
 // which a batch of 64 graphs paid 128 times over although its solves never use its handles' streams.  A batch's handle takes a pair
@@ -1356,9 +1340,7 @@ static int pgo_create_on(const uzl_pgo_cfg* cfg, hipStream_t shared, hipStream_t
     *out = nullptr;
     uzl_pgo_cfg c;
     if (cfg) c = *cfg; else uzl_pgo_cfg_default(&c);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return UZL_ERR_NO_DEVICE;
-    if (c.device < 0 || c.device >= ndev) return UZL_ERR_NO_DEVICE;
+    if (check_device(c.device) != UZL_OK) return UZL_ERR_NO_DEVICE;
     uzl_pgo* h = new (std::nothrow) uzl_pgo();
     if (!h) return UZL_ERR_OOM;
     h->cfg = c;
@@ -1463,7 +1445,7 @@ int uzl_pgo_set_config(uzl_pgo* h, const uzl_pgo_cfg* cfg)
     return UZL_OK;
 }
 
-const char* uzl_pgo_last_error(uzl_pgo* h) { return h ? h->last_error.c_str() : "null handle"; }
+const char* uzl_pgo_last_error(uzl_pgo* h) { return last_error_of(h); }
 
 int uzl_pgo_add_graph(uzl_pgo* h, int32_t n_nodes, const uzl_node* nodes, int32_t n_edges, const uzl_edge* edges,
                       int32_t n_sensors, const double* sensors)
@@ -2009,9 +1991,7 @@ extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_apply(uzl_pgo* h, double lambda, in
 //  Schur-reduced: chain-like graphs batch on their reduced systems; anything else - and any graph that meets an anomaly (PCG not
 //  converged, breakdown) - is solved by the single-graph path, so results never depend on whether a graph was batched.
 // =====================================================================================================================
-struct uzl_pgo_batch {
-    std::mutex mu;
-    std::string last_error;
+struct uzl_pgo_batch : HandleBase {
     uzl_pgo_cfg cfg;
     std::vector<uzl_pgo*> h;
     hipStream_t stream = nullptr;
@@ -2029,13 +2009,11 @@ struct uzl_pgo_batch {
 
 namespace {
 
-int bfail(uzl_pgo_batch* b, int code, const char* msg) { b->last_error = msg; return code; }
-
 int batch_optimize(uzl_pgo_batch* b, int32_t iterations, uzl_pgo_stats* stats, int32_t* n_batched)
 {
     const int B = (int)b->h.size();
     if (n_batched) *n_batched = 0;
-    for (uzl_pgo* h : b->h) if (!h->have_graph) return bfail(b, UZL_ERR_STATE, "optimize before every graph of the batch has been set");
+    for (uzl_pgo* h : b->h) if (!h->have_graph) return fail(b, UZL_ERR_STATE, "optimize before every graph of the batch has been set");
     UZL_HIP(hipSetDevice(b->cfg.device));
     // per graph: optimizeImpl's initializeOptimization + setFixedNodes (:139-146), structure
     for (int g = 0; g < B; g++) {
@@ -2119,15 +2097,6 @@ int batch_optimize(uzl_pgo_batch* b, int32_t iterations, uzl_pgo_stats* stats, i
 
 }  // namespace
 
-#define UZL_BGUARD_BEGIN(b)                      \
-    if (!(b)) return UZL_ERR_BAD_ARG;            \
-    std::lock_guard<std::mutex> lock_((b)->mu);  \
-    try {
-#define UZL_BGUARD_END(b)                                                            \
-    } catch (const ::uzl::HipError& e) { return ::uzl::report((b)->last_error, e); } \
-    catch (const std::bad_alloc&) { (b)->last_error = "host out of memory"; return UZL_ERR_OOM; } \
-    catch (...) { (b)->last_error = "unexpected exception"; return UZL_ERR_HIP; }
-
 extern "C" {
 
 int uzl_pgo_batch_create(const uzl_pgo_cfg* cfg, int32_t n_graphs, uzl_pgo_batch** out)
@@ -2136,10 +2105,7 @@ int uzl_pgo_batch_create(const uzl_pgo_cfg* cfg, int32_t n_graphs, uzl_pgo_batch
     *out = nullptr;
     uzl_pgo_cfg c;
     if (cfg) c = *cfg; else uzl_pgo_cfg_default(&c);
-    {
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || c.device < 0 || c.device >= ndev) return UZL_ERR_NO_DEVICE;
-    }
+    if (check_device(c.device) != UZL_OK) return UZL_ERR_NO_DEVICE;
     uzl_pgo_batch* b = new (std::nothrow) uzl_pgo_batch();
     if (!b) return UZL_ERR_OOM;
     b->cfg = c;
@@ -2190,7 +2156,7 @@ void uzl_pgo_batch_destroy(uzl_pgo_batch* b)
     delete b;
 }
 
-const char* uzl_pgo_batch_last_error(uzl_pgo_batch* b) { return b ? b->last_error.c_str() : "null handle"; }
+const char* uzl_pgo_batch_last_error(uzl_pgo_batch* b) { return last_error_of(b); }
 int uzl_pgo_batch_size(uzl_pgo_batch* b) { return b ? (int)b->h.size() : UZL_ERR_BAD_ARG; }
 uzl_pgo* uzl_pgo_batch_graph(uzl_pgo_batch* b, int32_t i) { return (b && i >= 0 && i < (int32_t)b->h.size()) ? b->h[(size_t)i] : nullptr; }
 
@@ -2219,9 +2185,9 @@ int uzl_pgo_batch_kernel_times(uzl_pgo_batch* b, int32_t cap, const char** names
 
 int uzl_pgo_batch_optimize(uzl_pgo_batch* b, int32_t iterations, uzl_pgo_stats* stats, int32_t* n_batched)
 {
-    UZL_BGUARD_BEGIN(b)
+    UZL_GUARD_BEGIN(b)
     return batch_optimize(b, iterations, stats, n_batched);
-    UZL_BGUARD_END(b)
+    UZL_GUARD_END(b)
 }
 
 }  // extern "C"

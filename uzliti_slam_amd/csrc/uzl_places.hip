@@ -143,9 +143,7 @@ __global__ __launch_bounds__(kPlBlk) void places_rehash_kernel(PlTable from, PlT
 
 using namespace uzl;
 
-struct uzl_places {
-    std::mutex mu;
-    std::string last_error;
+struct uzl_places : HandleBase {
     uzl_places_cfg cfg;
     hipStream_t stream = nullptr;
     int nt = 0;
@@ -161,8 +159,6 @@ struct uzl_places {
 };
 
 namespace {
-
-int fail(uzl_places* h, int code, const char* msg) { h->last_error = msg; return code; }
 
 void alloc_table(uzl_places* h, uzl_places::Tab& T, uint32_t cap)
 {
@@ -273,15 +269,6 @@ int check_desc(uzl_places* h, const uint8_t* desc, int32_t rows, int32_t bytes)
 
 }  // namespace
 
-#define UZL_GUARD_BEGIN(h)                       \
-    if (!(h)) return UZL_ERR_BAD_ARG;            \
-    std::lock_guard<std::mutex> lock_((h)->mu);  \
-    try {
-#define UZL_GUARD_END(h)                                                             \
-    } catch (const ::uzl::HipError& e) { return ::uzl::report((h)->last_error, e); } \
-    catch (const std::bad_alloc&) { (h)->last_error = "host out of memory"; return UZL_ERR_OOM; } \
-    catch (...) { (h)->last_error = "unexpected exception"; return UZL_ERR_HIP; }
-
 extern "C" {
 
 void uzl_places_cfg_default(uzl_places_cfg* c)
@@ -298,25 +285,26 @@ int uzl_places_create(const uzl_places_cfg* cfg, uzl_places** out)
     uzl_places_cfg c;
     if (cfg) c = *cfg; else uzl_places_cfg_default(&c);
     if (c.key_width < 1 || c.key_width > 8) return UZL_ERR_BAD_ARG;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return UZL_ERR_NO_DEVICE;     // no CPU fallback
-    if (c.device < 0 || c.device >= count) return UZL_ERR_NO_DEVICE;
+    if (check_device(c.device) != UZL_OK) return UZL_ERR_NO_DEVICE;
     uzl_places* h = new (std::nothrow) uzl_places();
     if (!h) return UZL_ERR_OOM;
     h->cfg = c;
     for (int i = 0; i < 32 - c.key_width + 1; i += c.key_width) h->nt++;                     // FastLshSet::clear :258-263
     if (h->nt > 8) h->nt = 8;
     try {
-        UZL_HIP(hipSetDevice(c.device));
-        UZL_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        stream_register(c.device, h->stream, false);
+        open_handle_stream(c.device, false, &h->stream);
         for (int t = 0; t < h->nt; t++) alloc_table(h, h->tab[t], 1u << 16);
         h->d_n_entries.reserve(1); h->d_used.reserve(8); h->h_small.reserve(16);
         UZL_HIP(hipMemsetAsync(h->d_n_entries.p, 0, 4, h->stream));
         UZL_HIP(hipMemsetAsync(h->d_used.p, 0, 32, h->stream));
         h->entries.reserve(1 << 16); h->entry_cap = 1 << 16;
         UZL_HIP(hipStreamSynchronize(h->stream));
-    } catch (...) { delete h; return UZL_ERR_HIP; }
+    } catch (...) {
+        const int code = caught_status(h->last_error);
+        close_handle_stream(c.device, h->stream);
+        delete h;
+        return code;
+    }
     *out = h;
     return UZL_OK;
 }
@@ -325,11 +313,11 @@ void uzl_places_destroy(uzl_places* h)
 {
     if (!h) return;
     (void)hipSetDevice(h->cfg.device);
-    if (h->stream) { (void)hipStreamSynchronize(h->stream); stream_unregister(h->cfg.device, h->stream); (void)hipStreamDestroy(h->stream); }
+    close_handle_stream(h->cfg.device, h->stream);
     delete h;
 }
 
-const char* uzl_places_last_error(uzl_places* h) { return h ? h->last_error.c_str() : "null handle"; }
+const char* uzl_places_last_error(uzl_places* h) { return last_error_of(h); }
 
 int uzl_places_search_and_add(uzl_places* h, const uint8_t* desc, int32_t rows, int32_t bytes, int64_t stamp_ns, int32_t cap,
                               int32_t* neighbors, int32_t* n_neighbors, int32_t* place_index)

@@ -124,9 +124,7 @@ __global__ __launch_bounds__(kRadBlk) void radius_kernel(RadiusArgs a)
 
 using namespace uzl;
 
-struct uzl_radius {
-    std::mutex mu;
-    std::string last_error;
+struct uzl_radius : HandleBase {
     uzl_radius_cfg cfg;
     hipStream_t stream = nullptr;
     int32_t n = 0;
@@ -136,19 +134,6 @@ struct uzl_radius {
     PinBuf<int32_t> h_count, h_from, h_to;
     PinBuf<int64_t> h_off;
 };
-
-namespace {
-int fail(uzl_radius* h, int code, const char* msg) { h->last_error = msg; return code; }
-}
-
-#define UZL_GUARD_BEGIN(h)                       \
-    if (!(h)) return UZL_ERR_BAD_ARG;            \
-    std::lock_guard<std::mutex> lock_((h)->mu);  \
-    try {
-#define UZL_GUARD_END(h)                                                             \
-    } catch (const ::uzl::HipError& e) { return ::uzl::report((h)->last_error, e); } \
-    catch (const std::bad_alloc&) { (h)->last_error = "host out of memory"; return UZL_ERR_OOM; } \
-    catch (...) { (h)->last_error = "unexpected exception"; return UZL_ERR_HIP; }
 
 extern "C" {
 
@@ -165,14 +150,18 @@ int uzl_radius_create(const uzl_radius_cfg* cfg, uzl_radius** out)
     *out = nullptr;
     uzl_radius_cfg c;
     if (cfg) c = *cfg; else uzl_radius_cfg_default(&c);
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return UZL_ERR_NO_DEVICE;     // no CPU fallback
-    if (c.device < 0 || c.device >= count) return UZL_ERR_NO_DEVICE;
+    if (check_device(c.device) != UZL_OK) return UZL_ERR_NO_DEVICE;
     uzl_radius* h = new (std::nothrow) uzl_radius();
     if (!h) return UZL_ERR_OOM;
     h->cfg = c;
-    if (hipSetDevice(c.device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; return UZL_ERR_HIP; }
-    stream_register(c.device, h->stream, false);
+    try {
+        open_handle_stream(c.device, false, &h->stream);
+    } catch (...) {
+        const int code = caught_status(h->last_error);
+        close_handle_stream(c.device, h->stream);
+        delete h;
+        return code;
+    }
     *out = h;
     return UZL_OK;
 }
@@ -181,11 +170,11 @@ void uzl_radius_destroy(uzl_radius* h)
 {
     if (!h) return;
     (void)hipSetDevice(h->cfg.device);
-    if (h->stream) { (void)hipStreamSynchronize(h->stream); stream_unregister(h->cfg.device, h->stream); (void)hipStreamDestroy(h->stream); }
+    close_handle_stream(h->cfg.device, h->stream);
     delete h;
 }
 
-const char* uzl_radius_last_error(uzl_radius* h) { return h ? h->last_error.c_str() : "null handle"; }
+const char* uzl_radius_last_error(uzl_radius* h) { return last_error_of(h); }
 
 int uzl_radius_set_nodes(uzl_radius* h, int32_t n, const double* poses, const int64_t* stamps)
 {

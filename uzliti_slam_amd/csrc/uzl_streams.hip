@@ -314,22 +314,28 @@ void stream_release(int device, hipStream_t s)
     P.pooled[at].leased = false;
 }
 
-void stream_register(int device, hipStream_t s, bool beside_solver)
+void open_handle_stream(int device, bool beside_solver, hipStream_t* s)
 {
-    if (!s) return;
+    UZL_HIP(hipSetDevice(device));
+    UZL_HIP(hipStreamCreateWithFlags(s, hipStreamNonBlocking));
     Pool& P = pool_of(device);
     std::lock_guard<std::mutex> lock(P.mu);
-    P.registered.push_back({s, beside_solver});
+    P.registered.push_back({*s, beside_solver});
 }
 
-void stream_unregister(int device, hipStream_t s)
+void close_handle_stream(int device, hipStream_t& s)
 {
     if (!s) return;
-    Pool& P = pool_of(device);
-    std::lock_guard<std::mutex> lock(P.mu);
-    for (size_t i = 0; i < P.registered.size(); i++)
-        if (P.registered[i].s == s) { P.registered.erase(P.registered.begin() + (long)i); break; }
-    P.forget(s);                                                // (the runtime may hand the address to another stream)
+    (void)hipStreamSynchronize(s);
+    {
+        Pool& P = pool_of(device);
+        std::lock_guard<std::mutex> lock(P.mu);
+        for (size_t i = 0; i < P.registered.size(); i++)
+            if (P.registered[i].s == s) { P.registered.erase(P.registered.begin() + (long)i); break; }
+        P.forget(s);                                            // (the runtime may hand the address to another stream)
+    }
+    (void)hipStreamDestroy(s);
+    s = nullptr;
 }
 
 StreamPoolStats stream_pool_stats(int device)

@@ -11,11 +11,13 @@ namespace uzl {
 hipStream_t stream_lease(int device, int priority, const std::vector<hipStream_t>& apart_from, bool required);
 void stream_release(int device, hipStream_t s);
 
-// Streams the other handles make for themselves (estimator, gate, places, radius) are entered so that the pool knows every
+// Streams the other handles make for themselves (estimator, gate, places, radius, gist) are entered so that the pool knows every
 // long-lived stream of the library; `beside_solver`: long launch sequences run on it while a solve is in flight (the estimator's), so
 // leases prefer streams that are independent of it too when that costs nothing.
-void stream_register(int device, hipStream_t s, bool beside_solver);
-void stream_unregister(int device, hipStream_t s);
+// open_handle_stream sets the device, creates a non-blocking stream into *s and registers it (throws HipError); close_handle_stream
+// synchronises, unregisters, destroys and nulls it, and is a no-op on a null stream.
+void open_handle_stream(int device, bool beside_solver, hipStream_t* s);
+void close_handle_stream(int device, hipStream_t& s);
 
 struct StreamPoolStats { int32_t pooled = 0, leased = 0, registered = 0, pairs_measured = 0, pairs_independent = 0, fallbacks = 0; double probe_ms = 0.; };
 StreamPoolStats stream_pool_stats(int device);
