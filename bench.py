@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the MI355X back end (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Primary metric   : SE(3) edges optimised / s   on BASELINE config 2 (1k nodes / 5k edges, 20 LM iterations)
+A plain run measures that alone: it sets up, warms up, times the K steps, dumps their outputs if asked and prints the record.  With
+--full the run goes on, after the timed steps, to every block below and `sharded_c4` (N > 1), to the primary's CPU baseline and parity against the oracle
+(`cpu_baseline`, `parity`), its profiled solve (`roofline`, `rooflines`, `kernels_ms_per_solve`), `lm_overhead`, `first_solve`,
+`repeat_identical`, `continued_from_solution` and `xy_only`; the --no-* switches leave blocks of it out.
 `secondary`      : node pairs matched / s      on BASELINE config 3 (512 pairs x 1000 ORB-256, 500 hypotheses)
 `batched`        : 16 independent config-2 graphs per GPU in one batch call (uzl_pgo_batch_*: shared launches, two launch sequences from 12 graphs on)
 `c4_1gpu`        : the north-star line: 10k nodes / 50k edges on ONE GPU against the CPU path (1 thread and all cores)   [N = 1]
@@ -58,6 +62,8 @@ def parse():
     ap.add_argument("--pairs", type=int, default=512)
     ap.add_argument("--keypoints", type=int, default=1000)
     ap.add_argument("--hypotheses", type=int, default=500)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps, run every other block, CPU baseline, parity check and roofline (off: the headline alone)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true")
     ap.add_argument("--no-formats", action="store_true")
@@ -785,18 +791,53 @@ def main():
     from uzliti_slam_amd import dist as ud
     capi.lib()
     dev = dist.local_rank
-    is_c2 = (a.nodes, a.edges) == (1000, 5000)
-    parity_fail = []
 
     # ------------------------------------------------------------------ primary: pose-graph solve, one independent graph per rank
-    B = pgo_block(capi, synth, dist, dev, a, a.nodes, a.edges, a.steps, a.warmup, ud.replica_seed(12345, dist.rank))
-    pgo, g, st, t_pgo = B["pgo"], B["g"], B["st"], B["t"]
+    B = pgo_block(capi, synth, dist, dev, a, a.nodes, a.edges, a.steps, a.warmup, ud.replica_seed(12345, dist.rank), repeat=a.full)
+    pgo, st, t_pgo = B["pgo"], B["st"], B["t"]
     value = dist.sum(float(B["edges"])) / t_pgo
+    cfg_name = {(1000, 5000): "BASELINE config 2", (10000, 50000): "BASELINE config 4 size on one GPU", (100, 300): "BASELINE config 1"}.get((a.nodes, a.edges), "custom size")
+    more, parity_fail = full_record(capi, synth, ud, dist, dev, a, B, value) if a.full else ({}, [])
+
+    if dist.rank == 0:
+        out = dict(
+            metric="SE(3) edges optimized/sec (node-pairs matched/sec in `secondary`)",
+            value=round(value, 1), unit="edges/s", n_gpus=dist.world, steps=a.steps, warmup=a.warmup,
+            ms_per_step=round(1e3 * t_pgo / a.steps, 4), higher_is_better=True, scaling="weak", vs_baseline=None,
+            dtype="f64", data="synthetic" if not dist.rehearsal else "synthetic (REHEARSAL over gloo, ranks sharing devices: not a measurement)",
+            config=dict(workload="%s: %d-node / %d-edge SE(3) pose graph, %d LM iterations, Huber(1) on loop closures; "
+                                 "one independent graph per GPU" % (cfg_name, a.nodes, a.edges, a.lm_iters),
+                        system_edges=st["n_edges"], lm_iterations_done=st["iterations_done"], lm_trials_per_solve=st["lm_trials"],
+                        pcg_iterations_per_solve=st["pcg_iterations"], preconditioner_builds_per_solve=st["precond_builds"], pcg_tol=pgo.cfg.pcg_tol,
+                        preconditioner=("multilevel, 8-vertex rigid-body aggregates (small graphs: dense level-1 operator, multiplicative cycle + 2 Newton-Schulz steps on the f64 matrix cores; "
+                                        "the PCG kernels apply an f32 COPY of that dense coarse operator (ml_cmat32_kernel) with f64 accumulation - preconditioner only: x, r, p, A p and every "
+                                        "reduction are f64, the converged solution does not depend on it)" if pgo.cfg.preconditioner else "block-Jacobi"),
+                        chi2_initial=st["chi2_initial"], chi2_final=st["chi2_final"]),
+            h2d_ms=round(B["h2d_ms"], 3), d2h_ms=round(B["d2h_ms"], 3),
+            timing="uzl_pgo_cfg::pass_history = 1: no pass of the LM loop is sized from an earlier optimize of the same graph")
+        out.update(more)
+        if a.dump_outputs:
+            out["dumped_outputs"] = dump_outputs(a.dump_outputs, pgo_outputs(B["stored"], st))
+        emit(out)
+    pgo.close()
+    dist.close()
+    if parity_fail:
+        print("[bench] PARITY MISS: %s" % json.dumps(parity_fail), file=sys.stderr)
+        sys.exit(3)
+
+
+def full_record(capi, synth, ud, dist, dev, a, B, value):
+    """`--full`: everything the bench measures and checks besides the headline, after the headline's timed steps (which it leaves as
+    they are): the primary's profiled solve and rooflines, LM overhead, first solves and xy-only point; the secondary and its deployed
+    point; formats; the batched, 10k / 50k, config 5 and sharded blocks; the CPU baselines and every parity check against the oracle.
+    Returns (the record's further keys - on rank 0, {} elsewhere -, parity misses)."""
+    pgo, g, st, t_pgo = B["pgo"], B["g"], B["st"], B["t"]
+    is_c2 = (a.nodes, a.edges) == (1000, 5000)
+    parity_fail = []
     st_prof, kt = pgo_profile(pgo, a)
     rooflines = pgo_rooflines(pgo, st, st_prof, kt, a.nodes, a.edges, is_c2)
     roofline = dict(rooflines[0]); roofline["traffic_source"] = traffic_source()
     kernels_ms = {k: round(v["ms"], 4) for k, v in sorted(kt.items(), key=lambda x: -x[1]["ms"])}
-    cfg_name = {(1000, 5000): "BASELINE config 2", (10000, 50000): "BASELINE config 4 size on one GPU", (100, 300): "BASELINE config 1"}.get((a.nodes, a.edges), "custom size")
     # What a solve costs besides its PCG iterations: the same graph solved so loosely that every solve stops at its first look; the slope
     # between the two is the cost of a PCG iteration, the rest - linearise, set-up / rebuild of the hierarchy, evaluation, the host's look
     # at the loop's state - is the LM overhead (VERDICT r3 next#1; tests/diag/lm_overhead.py is the same measurement for any size)
@@ -1282,42 +1323,22 @@ def main():
                                              sample="%d node pairs drawn cyclically from the same %d, %.1f s; gcc -O3 -march=native on this host" % (n1, len(pairs), dtm),
                                              all_cores=dict(value=round(n_all / dta, 2), cores=ncpu, sample="%d pairs over %d OpenMP threads (one estimator per core), %.1f s" % (n_all, ncpu, dta)))
 
-    if dist.rank == 0:
-        out = dict(
-            metric="SE(3) edges optimized/sec (node-pairs matched/sec in `secondary`)",
-            value=round(value, 1), unit="edges/s", n_gpus=dist.world, steps=a.steps, warmup=a.warmup,
-            ms_per_step=round(1e3 * t_pgo / a.steps, 4), higher_is_better=True, scaling="weak", vs_baseline=None,
-            dtype="f64", data="synthetic" if not dist.rehearsal else "synthetic (REHEARSAL over gloo, ranks sharing devices: not a measurement)",
-            config=dict(workload="%s: %d-node / %d-edge SE(3) pose graph, %d LM iterations, Huber(1) on loop closures; "
-                                 "one independent graph per GPU" % (cfg_name, a.nodes, a.edges, a.lm_iters),
-                        system_edges=st["n_edges"], lm_iterations_done=st["iterations_done"], lm_trials_per_solve=st["lm_trials"],
-                        pcg_iterations_per_solve=st["pcg_iterations"], preconditioner_builds_per_solve=st["precond_builds"], pcg_tol=pgo.cfg.pcg_tol,
-                        preconditioner=("multilevel, 8-vertex rigid-body aggregates (small graphs: dense level-1 operator, multiplicative cycle + 2 Newton-Schulz steps on the f64 matrix cores; "
-                                        "the PCG kernels apply an f32 COPY of that dense coarse operator (ml_cmat32_kernel) with f64 accumulation - preconditioner only: x, r, p, A p and every "
-                                        "reduction are f64, the converged solution does not depend on it)" if pgo.cfg.preconditioner else "block-Jacobi"),
-                        chi2_initial=st["chi2_initial"], chi2_final=st["chi2_final"]),
-            h2d_ms=round(B["h2d_ms"], 3), d2h_ms=round(B["d2h_ms"], 3),
-            timing="uzl_pgo_cfg::pass_history = 1: no pass of the LM loop is sized from an earlier optimize of the same graph",
-            first_solve_ms=first_warm["first_solve_ms"], first_solve=first_warm, repeat_identical=B.get("repeat"), continued_from_solution=B.get("continued"),
-            streams=capi.stream_stats(dev),
-            roofline=roofline, rooflines=rooflines, traffic_source=traffic_source() + " (rocprofv3 --pmc passes of profiles/collect.sh on the default workloads; not measured in this run)",
-            kernels_ms_per_solve=kernels_ms, kernels_ms_note="profiled solve: eager launches of the by-value instantiations of the kernel bodies (host-driven loop); "
-                                                            "the timed solves run the same bodies as slot twins (ml_spmv_lm_kernel, ...) under the device-resident loop",
-            lm_overhead_ms=(lm_overhead or {}).get("lm_overhead_ms"), lm_overhead=lm_overhead,
-            cpu_baseline=cpu, parity=parity, xy_only=xy_only, secondary=secondary)
-        for k, v in (("batched", batched), ("formats", formats), ("c4_1gpu", c4), ("online_c5", online_c5), ("sharded_c4", sharded_c4)):
-            if v is not None:
-                out[k] = v
-        if a.dump_outputs:
-            out["dumped_outputs"] = dump_outputs(a.dump_outputs, pgo_outputs(B["stored"], st))
-        emit(out)
-    pgo.close()
     if matcher is not None:
         matcher.close()
-    dist.close()
-    if parity_fail:
-        print("[bench] PARITY MISS: %s" % json.dumps(parity_fail), file=sys.stderr)
-        sys.exit(3)
+    if dist.rank != 0:
+        return {}, parity_fail
+    out = dict(
+        first_solve_ms=first_warm["first_solve_ms"], first_solve=first_warm, repeat_identical=B.get("repeat"), continued_from_solution=B.get("continued"),
+        streams=capi.stream_stats(dev),
+        roofline=roofline, rooflines=rooflines, traffic_source=traffic_source() + " (rocprofv3 --pmc passes of profiles/collect.sh on the default workloads; not measured in this run)",
+        kernels_ms_per_solve=kernels_ms, kernels_ms_note="profiled solve: eager launches of the by-value instantiations of the kernel bodies (host-driven loop); "
+                                                        "the timed solves run the same bodies as slot twins (ml_spmv_lm_kernel, ...) under the device-resident loop",
+        lm_overhead_ms=(lm_overhead or {}).get("lm_overhead_ms"), lm_overhead=lm_overhead,
+        cpu_baseline=cpu, parity=parity, xy_only=xy_only, secondary=secondary)
+    for k, v in (("batched", batched), ("formats", formats), ("c4_1gpu", c4), ("online_c5", online_c5), ("sharded_c4", sharded_c4)):
+        if v is not None:
+            out[k] = v
+    return out, parity_fail
 
 
 if __name__ == "__main__":

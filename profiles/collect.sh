@@ -12,17 +12,17 @@ rm -rf $OUT
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp UZL_NO_GRAPH=1
 # config 2 (primary) + config 3 (secondary) + formats; the 10k/50k block, the batched block and the online block have their own runs below
-ARGS="--steps 2 --warmup 1 --no-cpu-baseline --no-c4 --no-online --no-batched"
+ARGS="--full --steps 2 --warmup 1 --no-cpu-baseline --no-c4 --no-online --no-batched"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $OLDPWD/bench.py $ARGS > $OUT/trace.json 2> $OUT/trace.err
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $c --output-format csv -d $OUT/$c -- python3 $OLDPWD/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-c4 --no-online --no-batched > $OUT/$c.json 2> $OUT/$c.err
+  rocprofv3 --pmc $c --output-format csv -d $OUT/$c -- python3 $OLDPWD/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-c4 --no-online --no-batched > $OUT/$c.json 2> $OUT/$c.err
 done
 # 10k / 50k on one GPU: kernel stats + the same two counters (linearize and ml_spmv_kernel<4> of this size go into traffic.json
 # under their own keys only when config 2 did not provide them)
-C4="--nodes 10000 --edges 50000 --steps 2 --warmup 1 --no-cpu-baseline --no-secondary --no-c4 --no-online --no-batched"
+C4="--full --nodes 10000 --edges 50000 --steps 2 --warmup 1 --no-cpu-baseline --no-secondary --no-c4 --no-online --no-batched"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/c4_trace -- python3 $OLDPWD/bench.py $C4 > $OUT/c4_trace.json 2> $OUT/c4_trace.err
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $c --output-format csv -d $OUT/c4_$c -- python3 $OLDPWD/bench.py --nodes 10000 --edges 50000 --steps 1 --warmup 0 --no-cpu-baseline --no-secondary --no-c4 --no-online --no-batched > $OUT/c4_$c.json 2> $OUT/c4_$c.err
+  rocprofv3 --pmc $c --output-format csv -d $OUT/c4_$c -- python3 $OLDPWD/bench.py --full --nodes 10000 --edges 50000 --steps 1 --warmup 0 --no-cpu-baseline --no-secondary --no-c4 --no-online --no-batched > $OUT/c4_$c.json 2> $OUT/c4_$c.err
 done
 # the batched block (16 config-2 graphs) and the online block (config 5), kernel stats only
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/batch_trace -- python3 $OLDPWD/tests/diag/batch_scaling.py 16 > $OUT/batch_trace.log 2> $OUT/batch_trace.err

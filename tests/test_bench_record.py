@@ -128,3 +128,89 @@ def test_dumped_pgo_outputs_are_finite():
     assert np.array_equal(o["edge_error"], [0.5, 0.25, 1.0]) and np.array_equal(o["edge_used"], used)
     assert np.array_equal(o["chi2"], [4.0, 1.5]) and np.array_equal(o["poses"], poses)
     assert all(np.isfinite(np.asarray(v, np.float64)).all() for v in o.values())
+
+
+class _FakePgo:
+    """Stands in for capi.Pgo in the CPU tests of bench.main(): counts the solves, returns fixed stats."""
+    made = []
+
+    def __init__(self, device=0, **cfg):
+        import types
+        self.cfg = types.SimpleNamespace(pcg_tol=1e-5, preconditioner=1, **cfg)
+        self.solves = 0
+        _FakePgo.made.append(self)
+
+    def add_graph(self, poses, fixed, edges):
+        self.n = len(poses); self.m = len(edges["from"])
+
+    def reset(self):
+        pass
+
+    def set_config(self, **cfg):
+        pass
+
+    def optimize(self, iterations):
+        import time
+        time.sleep(0.002)
+        self.solves += 1
+        return dict(n_edges=self.m, iterations_done=iterations, lm_trials=iterations, pcg_iterations=300, precond_builds=1, chi2_initial=2.0,
+                    chi2_final=1.0, structure_ms=0.5, lm_passes=1)
+
+    def store(self):
+        import numpy as np
+        return np.zeros((self.n, 12)), np.full(self.m, 0.5), np.ones(self.m, np.uint8)
+
+    def close(self):
+        pass
+
+
+def _run_main(monkeypatch, tmp_path, argv):
+    import types
+    import bench
+    import uzliti_slam_amd
+    from uzliti_slam_amd import synth
+    fake = types.SimpleNamespace(lib=lambda: None, Pgo=_FakePgo)
+    monkeypatch.setattr(uzliti_slam_amd, "capi", fake, raising=False)
+    monkeypatch.setitem(sys.modules, "uzliti_slam_amd.capi", fake)
+    monkeypatch.setattr(synth, "make_pose_graph", lambda n, m, seed=0: dict(nodes_pose=[0] * n, nodes_fixed=[0] * n, edges={"from": [0] * m}))
+    monkeypatch.setattr(bench, "ROOT", str(tmp_path))
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+    _FakePgo.made = []
+    bench.main()
+
+
+FULL_ONLY = ("roofline", "rooflines", "cpu_baseline", "parity", "first_solve_ms", "repeat_identical", "continued_from_solution", "lm_overhead_ms",
+             "streams", "xy_only", "secondary", "batched", "formats", "c4_1gpu", "online_c5", "sharded_c4")
+
+
+def test_plain_run_solves_only_the_headline_steps(capsys, tmp_path, monkeypatch):
+    """Without --full the bench makes one handle and solves 1 (first) + W + N times: no other block, baseline or profiled solve."""
+    import numpy as np
+    import bench
+    monkeypatch.setattr(bench, "full_record", lambda *x: (_ for _ in ()).throw(AssertionError("--full block ran in a plain run")))
+    _run_main(monkeypatch, tmp_path, ["--steps", "5", "--warmup", "2", "--dump-outputs", str(tmp_path / "d")])
+    assert len(_FakePgo.made) == 1 and _FakePgo.made[0].solves == 1 + 2 + 5
+    lines = [l for l in capsys.readouterr().out.splitlines() if l.strip()]
+    assert len(lines) == 1
+    c = _strict(lines[0])
+    assert c["metric"] == "SE(3) edges optimized/sec (node-pairs matched/sec in `secondary`)" and c["unit"] == "edges/s"
+    assert c["higher_is_better"] is True and c["dtype"] == "f64" and c["steps"] == 5 and c["warmup"] == 2
+    assert c["value"] > 0 and c["ms_per_step"] > 0 and abs(c["value"] * c["ms_per_step"] * 1e-3 - 5000 * 20) < 1e-3 * 5000 * 20
+    assert c["config"]["workload"].startswith("BASELINE config 2")
+    assert not [k for k in FULL_ONLY if c.get(k)]                            # null: not measured in this run
+    assert sorted(f.name for f in (tmp_path / "d").iterdir()) == ["chi2.npy", "edge_error.npy", "edge_used.npy", "poses.npy"]
+    assert np.load(tmp_path / "d" / "poses.npy").shape == (1000, 12)
+
+
+def test_full_run_adds_the_other_blocks_after_the_headline(capsys, tmp_path, monkeypatch):
+    import bench
+    seen = {}
+
+    def full(capi, synth, ud, dist, dev, a, B, value):
+        seen["value"] = value
+        return dict(roofline=dict(kernel="k"), cpu_baseline=dict(value=1.0)), []
+    monkeypatch.setattr(bench, "full_record", full)
+    _run_main(monkeypatch, tmp_path, ["--steps", "3", "--warmup", "1", "--full"])
+    c = _strict(capsys.readouterr().out.splitlines()[-1])
+    assert c["value"] == round(seen["value"], 1) and c["steps"] == 3
+    assert c["roofline"]["kernel"] == "k" and c["cpu_baseline"]["value"] == 1.0
