@@ -752,6 +752,128 @@ int  uzl_gist_add_batch(uzl_gist* h, int32_t n, const uint8_t* desc, const uint8
 int  uzl_gist_last_knn(uzl_gist* h, int32_t cap, int32_t* place, int32_t* dist);
 
 /* ======================================================================================
+ *  Occupancy-grid map from the stored laser scans at the solved poses
+ *
+ *  GraphGridMapper::convertLaserScans2Map (map_projection/src/graph_grid_mapper.cpp:295-400), which
+ *  OccupancyGridProjector runs after every optimisation (graph_slam/src/graph_slam_node.cpp:1277):
+ *  every node's LaserscanData (SENSOR_TYPE_LASERSCAN, sensor_data.cpp:251-277) is projected at
+ *  pose * displacement and ray-traced into a nav_msgs/OccupancyGrid.  The reference hands the
+ *  arithmetic to occupancy_grid_utils (OverlayClouds) and laser_geometry::projectLaser, which are not
+ *  part of it; the contract below is this back end's own reading of them, stated exactly.  Every
+ *  step is IEEE-754 double unless it says f32, evaluated in the order written, with no fused
+ *  multiply-add; the results equal a NumPy restatement (tests/grid_reference.py) bit for bit.
+ *
+ *  A scan: node (an index into the poses of a build), displacement (LaserscanData::displacement_,
+ *  3x4 row-major), angle_min, angle_increment, range_min and ranges (f32, from the LaserScan).  The
+ *  scan's range_max is replaced by the config's (:356) and projectLaser walks ranges.size(), so the
+ *  message's range_max and angle_max are not inputs.  `present` (NULL = all) masks nodes; scans of
+ *  absent nodes and of node >= n_nodes are skipped.
+ *
+ *  1. Geometry (full build only; getMapOrigin, :535-572, and :311-316): minx/maxx/miny/maxy over the
+ *     translations of the present nodes; origin = (minx - 5 range_max, miny - 5 range_max);
+ *     width = (uint32)((maxx - minx + 10 range_max) / resolution), height likewise (truncation as
+ *     :316).  No present node, or width * height > max_cells: UZL_ERR_BAD_ARG.  Cell of a point:
+ *     cx = floor((x - origin_x) / resolution), cy likewise; index cy * width + cx.
+ *  2. Known free (addKnownFreePoint(..., node position, 0.5), :334), for each node the call adds,
+ *     before any scan: k = (int)(known_free_radius / resolution); every in-bounds cell within
+ *     Chebyshev distance k of the node's cell gets passes = max(passes, min_pass_through) (nothing
+ *     for k < 0 or min_pass_through <= 0); hits are untouched.
+ *  3. Beams (projectLaser): beam i is valid iff range_min <= r < range_max (drops NaN and +-inf);
+ *     theta_i = (double)angle_min + (double)i * (double)angle_increment; c_i = cos theta_i and
+ *     s_i = sin theta_i from the HOST's libm, once per distinct (angle_min, increment, n) and
+ *     uploaded as a table - the device evaluates no trigonometry; sensor-frame point
+ *     p = ((float)(r c_i), (float)(r s_i)) (laser_geometry writes Point32).
+ *  4. Sensor pose and map point: S = P_node * D on the host, each 3-term sum as
+ *     (a0 b0 + a1 b1) + a2 b2 and P.t added last for the translation; q_a = (S.R[a][0] px +
+ *     S.R[a][1] py) + S.t[a] for a = x, y; sensor position o = S.t.  r <= max_distance: the end
+ *     point is e = q and the ray scores a hit; otherwise e = o + (max_distance / r) (q - o) and no
+ *     hit (only when range_max > max_distance).
+ *  5. Ray: integer Bresenham from cell(o) to cell(e), both ends inclusive, in exactly this form:
+ *       dx = |x1-x0|, dy = -|y1-y0|, sx, sy = signs, err = dx + dy
+ *       loop: visit(x, y); if (x == x1 && y == y1) break; e2 = 2 err;
+ *             if (e2 >= dy) { err += dy; x += sx; }  if (e2 <= dx) { err += dx; y += sy; }
+ *     every visited in-bounds cell gets passes += 1, the end cell of a hit (if in bounds) also
+ *     hits += 1; out-of-bounds cells are skipped and the walk goes on.  Counts are uint32.
+ *  6. Classify (getGrid, :398), int8 row-major, nav_msgs/OccupancyGrid values:
+ *     passes < min_pass_through -> -1; else hits > occupancy_threshold * passes -> 100; else 0.
+ *
+ *  The max rule of step 2 and Bresenham as the ray rule are this project's reading of
+ *  occupancy_grid_utils.  Two divergences from the reference, both deliberate:
+ *   (a) every scan counts.  The reference never adds the first cloud after a reset
+ *       (clouds_.size() > 1, :373), and which cloud that is depends on the std::map order of node ids.
+ *   (b) the extent uses the real-valued maxx - minx.  The bare abs() of a double at :566-567 binds
+ *       to int abs on some toolchains.
+ *  The choice between a full and an incremental build (the 0.5 m / 5 deg test on map -> odom,
+ *  :305) stays with the caller, as it sits in the ROS node.
+ *
+ *  Device side: ranges of every scan in one append-only arena; a build bins the scans to the
+ *  128 x 128-cell tiles their range square touches (count + prefix sum, no atomic decides a
+ *  position), one workgroup per non-empty tile counts its rays in LDS (each ray enters at its first
+ *  step inside the tile - Bresenham's state after k steps has a closed form) and writes the tile's
+ *  counts and classified cells.  Integer counts: the result does not depend on the order.
+ * ====================================================================================== */
+typedef struct uzl_grid uzl_grid;
+typedef struct uzl_grid_cfg {
+    double  resolution;           /* 0.1   OccupancyGridProjector.cfg "resolution" [m]                        */
+    double  range_max;            /* 5.0   OccupancyGridProjector.cfg "range_max" [m]                         */
+    double  occupancy_threshold;  /* 0.1   createCloudOverlay(..., 0.1, 10, 1), graph_grid_mapper.cpp:320     */
+    double  max_distance;         /* 10.0  ditto [m]                                                          */
+    double  known_free_radius;    /* 0.5   addKnownFreePoint(..., 0.5), :334 [m]                              */
+    int32_t min_pass_through;     /* 1     createCloudOverlay, :320                                           */
+    int32_t device;
+    int64_t max_cells;            /* 2^28  size guard: counts + grid take 9 bytes per cell (2.4 GB here)      */
+} uzl_grid_cfg;
+/* One stored laser scan (LaserscanData): node = index into the poses of a build; ranges = n_ranges f32 (borrowed). */
+typedef struct uzl_grid_scan {
+    int32_t      node;
+    int32_t      n_ranges;
+    double       displacement[12];    /* LaserscanData::displacement_, row-major 3x4                          */
+    float        angle_min, angle_increment, range_min;
+    const float* ranges;
+} uzl_grid_scan;
+/* The grid after a build / extend (nav_msgs/MapMetaData) and what that call projected. */
+typedef struct uzl_grid_info {
+    double   origin_x, origin_y, resolution;
+    uint32_t width, height;
+    int64_t  valid_beams;         /* valid beams (step 3) of the scans the call projected                     */
+    int64_t  hits;                /* hits the call added to the grid (hit beams with an in-bounds end cell)   */
+    int32_t  scans;               /* scans the call projected                                                 */
+    int32_t  off_grid;            /* extend: 1 iff an added node lies within range_max of the border (:336-342) */
+} uzl_grid_info;
+void uzl_grid_cfg_default(uzl_grid_cfg* cfg);
+/* UZL_ERR_BAD_ARG for resolution <= 0, range_max < 0, max_distance < 0, any NaN, known_free_radius / resolution >= 2^30
+ * or max_cells < 1; UZL_ERR_NO_DEVICE without a GPU (no CPU fallback) */
+int  uzl_grid_create(const uzl_grid_cfg* cfg, uzl_grid** out);
+void uzl_grid_destroy(uzl_grid* h);
+const char* uzl_grid_last_error(uzl_grid* h);
+/* Same checks as create; the new config takes effect at the next full build (extend keeps the config of the last one). */
+int  uzl_grid_set_config(uzl_grid* h, const uzl_grid_cfg* cfg);
+/* Append n scans (LaserscanData of the nodes, :350-360) to the device store; *first_scan (may be NULL) = index of scans[0].
+ * UZL_ERR_BAD_ARG (nothing stored) for n < 0, a NULL array, node < 0, n_ranges < 0, ranges NULL with n_ranges > 0,
+ * a non-finite angle_min / angle_increment / displacement entry, or range_min < 0 or NaN. */
+int  uzl_grid_add_scans(uzl_grid* h, int32_t n, const uzl_grid_scan* scans, int32_t* first_scan);
+/* scans stored so far */
+int  uzl_grid_scan_count(uzl_grid* h);
+/* Full rebuild, steps 1-6 over every stored scan: the reset branch of convertLaserScans2Map (:308-324).  poses = n_nodes x 12
+ * (row-major 3x4 SlamNode::pose_), present = n_nodes flags or NULL.  UZL_ERR_BAD_ARG (handle unchanged) for n_nodes < 0, NULL
+ * poses, a non-finite pose entry of a present node, no present node, width * height > max_cells, or a scan whose pose scales
+ * its rays beyond 2^24 cells.  info may be NULL. */
+int  uzl_grid_build(uzl_grid* h, int32_t n_nodes, const double* poses, const uint8_t* present, uzl_grid_info* info);
+/* The incremental branch (:305-307, getNodesAfter): keeps the geometry and counts of the last build, applies steps 2-5 for the
+ * present nodes >= first_node and their scans, then step 6.  info->off_grid = 1 iff one of those nodes lies within range_max of
+ * the border (the force-clear test of :336-342; the caller then does a full build).  UZL_ERR_STATE before any build;
+ * UZL_ERR_BAD_ARG as build, and for first_node < 0. */
+int  uzl_grid_extend(uzl_grid* h, int32_t n_nodes, const double* poses, const uint8_t* present, int32_t first_node,
+                     uzl_grid_info* info);
+/* info of the last build / extend; UZL_ERR_STATE before any build */
+int  uzl_grid_get_info(uzl_grid* h, uzl_grid_info* info);
+/* The classified grid (OccupancyGrid.data, width * height int8, row-major); UZL_ERR_TRUNCATED when cap < width * height,
+ * UZL_ERR_STATE before any build. */
+int  uzl_grid_read(uzl_grid* h, int64_t cap, int8_t* data);
+/* The counts behind it (hits, passes: width * height uint32 each, either may be NULL); errors as uzl_grid_read. */
+int  uzl_grid_counts(uzl_grid* h, int64_t cap, uint32_t* hits, uint32_t* passes);
+
+/* ======================================================================================
  *  Wire and disk formats  
  *
  *  The data formats either side of the path: graph_slam_msgs/{Edge,Node,SensorData,Features,
@@ -880,6 +1002,25 @@ int  uzl_wire_sensor_gist(const uzl_wire_sensor* s, int32_t cap, uint8_t* gist, 
 uint64_t uzl_wire_gist_sensor_size(uzl_span sensor_frame, int32_t n);
 int  uzl_wire_gist_sensor_encode(uint32_t stamp_sec, uint32_t stamp_nsec, uzl_span sensor_frame, const double* displacement,
                                  const uint8_t* gist, int32_t n, uint8_t* buf, uint64_t cap, uint64_t* written);
+
+/* SensorData.scan (sensor_msgs/LaserScan) and scan_center: what LaserscanData::toMsg writes and fromMsg reads
+ * (sensor_data.cpp:261-277).  ranges / intensities are the arrays' raw little-endian f32 bytes (unaligned, 4 n bytes). */
+typedef struct uzl_wire_scan {
+    uint32_t seq, stamp_sec, stamp_nsec;  /* scan.header                                                   */
+    uzl_span frame_id;
+    float    angle_min, angle_max, angle_increment, time_increment, scan_time, range_min, range_max;
+    int32_t  n_ranges, n_intensities;
+    uzl_span ranges, intensities;
+    double   scan_center[3];
+} uzl_wire_scan;
+/* The scan of a decoded sensor (any type; re-parsed from s->raw; spans point into s->raw). */
+int  uzl_wire_sensor_scan(const uzl_wire_sensor* s, uzl_wire_scan* out);
+/* A SENSOR_TYPE_LASERSCAN SensorData as SensorData::toMsg + LaserscanData::toMsg write it (sensor_data.cpp:40-49, 261-269):
+ * header (stamp, frame_id = sensor_frame), displacement, the scan and scan_center; features, camera info and images
+ * default-constructed, gist_descriptor empty.  scan->ranges / intensities must hold 4 n_ranges / 4 n_intensities bytes. */
+uint64_t uzl_wire_scan_sensor_size(uzl_span sensor_frame, const uzl_wire_scan* scan);
+int  uzl_wire_scan_sensor_encode(uint32_t stamp_sec, uint32_t stamp_nsec, uzl_span sensor_frame, const double* displacement,
+                                 const uzl_wire_scan* scan, uint8_t* buf, uint64_t cap, uint64_t* written);
 
 /* bytes of n Feature records with desc_len descriptor elements each */
 uint64_t uzl_wire_features_size(int32_t n, int32_t desc_len);

@@ -188,6 +188,24 @@ class GistCfg(C.Structure):
     _fields_ = [("T", C.c_double), ("k_nearest_neighbors", C.c_int32), ("device", C.c_int32), ("min_time_gap", C.c_double)]
 
 
+class GridCfg(C.Structure):
+    _fields_ = [("resolution", C.c_double), ("range_max", C.c_double), ("occupancy_threshold", C.c_double), ("max_distance", C.c_double),
+                ("known_free_radius", C.c_double), ("min_pass_through", C.c_int32), ("device", C.c_int32), ("max_cells", C.c_int64)]
+
+
+class GridScan(C.Structure):
+    _fields_ = [("node", C.c_int32), ("n_ranges", C.c_int32), ("displacement", C.c_double * 12), ("angle_min", C.c_float),
+                ("angle_increment", C.c_float), ("range_min", C.c_float), ("ranges", C.POINTER(C.c_float))]
+
+
+class GridInfo(C.Structure):
+    _fields_ = [("origin_x", C.c_double), ("origin_y", C.c_double), ("resolution", C.c_double), ("width", C.c_uint32),
+                ("height", C.c_uint32), ("valid_beams", C.c_int64), ("hits", C.c_int64), ("scans", C.c_int32), ("off_grid", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
 
 _lib = None
@@ -213,19 +231,20 @@ def lib():
 
 
 _HANDLES = ("uzl_match", "uzl_pgo", "uzl_pgo_batch", "uzl_filter", "uzl_gate", "uzl_radius", "uzl_places", "uzl_gist")
+_MORE_HANDLES = ("uzl_grid",)       # declared like _HANDLES; kept apart because tests pin _HANDLES to the first eight
 
 
 def _declare(L):
     """The prototypes ctypes cannot guess: every handle's last_error / destroy / cfg_default, and the calls that take only a handle."""
     L.uzl_status_string.restype = C.c_char_p
-    for p in _HANDLES:
+    for p in _HANDLES + _MORE_HANDLES:
         getattr(L, p + "_last_error").restype = C.c_char_p
         getattr(L, p + "_last_error").argtypes = [C.c_void_p]
         getattr(L, p + "_destroy").restype = None
         getattr(L, p + "_destroy").argtypes = [C.c_void_p]
         if hasattr(L, p + "_cfg_default"):          # (a batch takes uzl_pgo_cfg)
             getattr(L, p + "_cfg_default").restype = None
-    for f in ("uzl_places_count", "uzl_gist_count", "uzl_gate_edge_count", "uzl_filter_cluster_count"):
+    for f in ("uzl_places_count", "uzl_gist_count", "uzl_grid_scan_count", "uzl_gate_edge_count", "uzl_filter_cluster_count"):
         getattr(L, f).argtypes = [C.c_void_p]
     L.uzl_pgo_batch_graph.restype = C.c_void_p
     L.uzl_pgo_batch_graph.argtypes = [C.c_void_p, C.c_int32]
@@ -984,3 +1003,76 @@ class Gist(_Handle):
         pl = np.zeros(max(n, 1), np.int32); di = np.zeros(max(n, 1), np.int32)
         self._check(lib().uzl_gist_last_knn(self._h, C.c_int32(n), _p(pl, c_i32p), _p(di, c_i32p)))
         return pl[:n], di[:n]
+
+
+class Grid(_Handle):
+    """uzl_grid_* (GraphGridMapper::convertLaserScans2Map, map_projection/src/graph_grid_mapper.cpp:295-400): stored laser scans
+    ray-traced into an occupancy grid at caller-given poses, fully (build) or for the nodes after the last map (extend)."""
+
+    _prefix, _cfg_type = "uzl_grid", GridCfg
+    set_config = _Handle._set_config
+
+    @staticmethod
+    def pack_scans(scans):
+        """scans: dicts with node, ranges (f32), angle_min, angle_increment, range_min and optionally displacement (12 or 3x4,
+        default identity) -> (GridScan array, the ranges it points into)"""
+        arr = (GridScan * max(len(scans), 1))()
+        keep = []
+        for i, s in enumerate(scans):
+            r = np.ascontiguousarray(s["ranges"], np.float32).reshape(-1)
+            keep.append(r)
+            g = arr[i]
+            g.node = int(s["node"]); g.n_ranges = len(r)
+            g.displacement[:] = np.asarray(s.get("displacement", np.eye(3, 4)), np.float64).reshape(12).tolist()
+            g.angle_min = float(s["angle_min"]); g.angle_increment = float(s["angle_increment"]); g.range_min = float(s["range_min"])
+            g.ranges = r.ctypes.data_as(C.POINTER(C.c_float)) if len(r) else None
+        return arr, keep
+
+    def add_scans(self, scans):
+        """-> index of the first scan added"""
+        arr, keep = self.pack_scans(scans)
+        first = C.c_int32(-1)
+        self._check(lib().uzl_grid_add_scans(self._h, C.c_int32(len(scans)), arr, C.byref(first)))
+        return first.value
+
+    def scan_count(self):
+        return self._check(lib().uzl_grid_scan_count(self._h))
+
+    @staticmethod
+    def _poses(poses, present):
+        P = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
+        pr = None if present is None else np.ascontiguousarray(present, np.uint8).reshape(len(P))
+        return P, pr
+
+    def build(self, poses, present=None):
+        P, pr = self._poses(poses, present)
+        info = GridInfo()
+        self._check(lib().uzl_grid_build(self._h, C.c_int32(len(P)), _p(P, c_f64p), _p(pr, c_u8p), C.byref(info)))
+        return info.as_dict()
+
+    def extend(self, poses, first_node, present=None):
+        P, pr = self._poses(poses, present)
+        info = GridInfo()
+        self._check(lib().uzl_grid_extend(self._h, C.c_int32(len(P)), _p(P, c_f64p), _p(pr, c_u8p), C.c_int32(first_node), C.byref(info)))
+        return info.as_dict()
+
+    def info(self):
+        info = GridInfo()
+        self._check(lib().uzl_grid_get_info(self._h, C.byref(info)))
+        return info.as_dict()
+
+    def read(self):
+        """OccupancyGrid.data as an int8 (height, width) array"""
+        i = self.info()
+        out = np.zeros(i["width"] * i["height"], np.int8)
+        self._check(lib().uzl_grid_read(self._h, C.c_int64(out.size), out.ctypes.data_as(C.POINTER(C.c_int8))))
+        return out.reshape(i["height"], i["width"])
+
+    def counts(self):
+        """(hits, passes), uint32 (height, width) each"""
+        i = self.info()
+        n = i["width"] * i["height"]
+        hits = np.zeros(n, np.uint32); passes = np.zeros(n, np.uint32)
+        u32p = C.POINTER(C.c_uint32)
+        self._check(lib().uzl_grid_counts(self._h, C.c_int64(n), hits.ctypes.data_as(u32p), passes.ctypes.data_as(u32p)))
+        return hits.reshape(i["height"], i["width"]), passes.reshape(i["height"], i["width"])

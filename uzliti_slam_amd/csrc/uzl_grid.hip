@@ -1,0 +1,517 @@
+// uzl_grid.hip — occupancy-grid map from stored laser scans (host + C ABI uzl_grid_*).
+//
+// Mirrors GraphGridMapper::convertLaserScans2Map (map_projection/src/graph_grid_mapper.cpp:295-400); include/uzl_mi355x.h states
+// the contract.  HBM layout: one append-only arena of ranges (f32, scan after scan), one of (cos, sin) tables shared by scans of
+// the same (angle_min, angle_increment, n), and the grid's hits / passes (uint32) and classified cells (int8), row-major.
+// Host work per build: geometry, S = P * D per scan, each scan's conservative cell box, and the bins (scans and known-free squares
+// per tile, by count + prefix sum), uploaded in one copy; the device does every beam (grid_kernels.hip).
+#include "grid_types.hpp"
+#include "uzl_common.hpp"
+#include "uzl_streams.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <map>
+#include <new>
+#include <tuple>
+
+namespace uzl {
+
+constexpr double kGridMaxRayCells = 16777216.0;   // 2^24: a scan's rays must stay within this many cells of its sensor
+
+struct GridScanHost {
+    int32_t node, n;
+    double D[12];
+    float range_min;
+    int64_t ranges_off, trig_off;
+};
+
+struct GridGeom {
+    double origin_x = 0, origin_y = 0;
+    uint32_t width = 0, height = 0;
+};
+
+}  // namespace uzl
+
+using namespace uzl;
+
+struct uzl_grid : HandleBase {
+    uzl_grid_cfg cfg;            // as set
+    uzl_grid_cfg gcfg;           // of the last full build (extend keeps it)
+    hipStream_t stream = nullptr;
+    bool built = false;
+    GridGeom geom;
+    uzl_grid_info info{};
+    std::vector<GridScanHost> scans;
+    int64_t n_ranges = 0, n_trig = 0;
+    std::map<std::tuple<uint32_t, uint32_t, int32_t>, int64_t> tables;   // (angle_min bits, increment bits, n) -> trig_off
+    DevBuf<float> d_ranges;
+    DevBuf<double2> d_trig;
+    DevBuf<uint32_t> d_hits, d_passes;
+    DevBuf<int8_t> d_grid;
+    DevBuf<uint8_t> d_work;
+    DevBuf<unsigned long long> d_totals;
+    PinBuf<uint8_t> h_work;
+    PinBuf<unsigned long long> h_totals;
+};
+
+namespace {
+
+int check_cfg(const uzl_grid_cfg& c)
+{
+    if (std::isnan(c.resolution) || std::isnan(c.range_max) || std::isnan(c.occupancy_threshold) || std::isnan(c.max_distance) ||
+        std::isnan(c.known_free_radius))
+        return UZL_ERR_BAD_ARG;
+    if (!(c.resolution > 0.) || c.range_max < 0. || c.max_distance < 0. || c.max_cells < 1) return UZL_ERR_BAD_ARG;
+    if (std::fabs(c.known_free_radius / c.resolution) >= 1073741824.0) return UZL_ERR_BAD_ARG;
+    return UZL_OK;
+}
+
+inline int32_t cell_of(double v, double origin, double res) { return (int32_t)std::floor((v - origin) / res); }
+
+// S = P * D, row-major 3x4: each 3-term sum as (a0 b0 + a1 b1) + a2 b2, P.t added last
+void compose(const double* P, const double* D, double* S)
+{
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) S[4 * i + j] = (P[4 * i] * D[j] + P[4 * i + 1] * D[4 + j]) + P[4 * i + 2] * D[8 + j];
+        S[4 * i + 3] = ((P[4 * i] * D[3] + P[4 * i + 1] * D[7]) + P[4 * i + 2] * D[11]) + P[4 * i + 3];
+    }
+}
+
+bool finite12(const double* v)
+{
+    for (int i = 0; i < 12; i++) if (!std::isfinite(v[i])) return false;
+    return true;
+}
+
+// the nodes a call adds: present, < n_nodes, >= first
+bool adds(const uint8_t* present, int32_t i, int32_t first) { return i >= first && (!present || present[i]); }
+
+int check_poses(uzl_grid* h, int32_t n_nodes, const double* poses, const uint8_t* present)
+{
+    if (n_nodes < 0 || (n_nodes > 0 && !poses)) return fail(h, UZL_ERR_BAD_ARG, "bad node count or null poses");
+    for (int32_t i = 0; i < n_nodes; i++)
+        if ((!present || present[i]) && !finite12(poses + 12 * (size_t)i)) return fail(h, UZL_ERR_BAD_ARG, "non-finite pose of a present node");
+    return UZL_OK;
+}
+
+// steps 1: origin and size over the present nodes (getMapOrigin, graph_grid_mapper.cpp:535-572)
+int geometry(uzl_grid* h, const uzl_grid_cfg& c, int32_t n_nodes, const double* poses, const uint8_t* present, GridGeom* g)
+{
+    bool any = false;
+    double minx = 0, maxx = 0, miny = 0, maxy = 0;
+    for (int32_t i = 0; i < n_nodes; i++) {
+        if (present && !present[i]) continue;
+        const double x = poses[12 * (size_t)i + 3], y = poses[12 * (size_t)i + 7];
+        if (!any) { minx = maxx = x; miny = maxy = y; any = true; continue; }
+        minx = std::min(minx, x); maxx = std::max(maxx, x); miny = std::min(miny, y); maxy = std::max(maxy, y);
+    }
+    if (!any) return fail(h, UZL_ERR_BAD_ARG, "no present node");
+    g->origin_x = minx - 5 * c.range_max;
+    g->origin_y = miny - 5 * c.range_max;
+    const double w = (maxx - minx + 10 * c.range_max) / c.resolution, hh = (maxy - miny + 10 * c.range_max) / c.resolution;
+    if (!(w < 4294967296.0) || !(hh < 4294967296.0)) return fail(h, UZL_ERR_BAD_ARG, "grid larger than max_cells");
+    g->width = (uint32_t)w;
+    g->height = (uint32_t)hh;
+    if ((double)g->width * (double)g->height > (double)c.max_cells) return fail(h, UZL_ERR_BAD_ARG, "grid larger than max_cells");
+    return UZL_OK;
+}
+
+// One build's bins, packed for a single upload.
+struct Plan {
+    std::vector<GridScanRec> recs;             // every projected scan (the stats kernel counts their valid beams)
+    std::vector<int32_t> tiles, ent_start, ent_scan, kf_start;
+    std::vector<int64_t> ent_beam;
+    std::vector<int4> kf_rect;
+};
+
+// Steps 2-5 of the nodes >= first: the scans' records and cell boxes, the known-free rectangles, and their tiles.
+int plan(uzl_grid* h, const uzl_grid_cfg& c, const GridGeom& g, int32_t n_nodes, const double* poses, const uint8_t* present,
+         int32_t first, Plan& p)
+{
+    const int32_t W = (int32_t)g.width, H = (int32_t)g.height;
+    const int32_t tiles_x = (W + kGridTile - 1) / kGridTile, tiles_y = (H + kGridTile - 1) / kGridTile;
+    const int64_t n_tiles = (int64_t)tiles_x * tiles_y;
+    const double res = c.resolution;
+    // rays reach at most R_eff = min(range_max, max_distance) from o, scaled by the rotation rows (range_min >= 0: every valid r >= 0)
+    const double reff = std::max(0., std::min(c.range_max, c.max_distance));
+    struct Box { int32_t x0, y0, x1, y1; };
+    std::vector<Box> sbox;                     // per record: tile box (x0 > x1: off the grid)
+    for (const GridScanHost& s : h->scans) {
+        if (s.node >= n_nodes || !adds(present, s.node, first)) continue;
+        double S[12];
+        compose(poses + 12 * (size_t)s.node, s.D, S);
+        GridScanRec r;
+        r.r00 = S[0]; r.r01 = S[1]; r.r10 = S[4]; r.r11 = S[5]; r.tx = S[3]; r.ty = S[7];
+        r.ranges_off = s.ranges_off; r.trig_off = s.trig_off; r.n = s.n; r.range_min = s.range_min;
+        const double bx = std::sqrt(S[0] * S[0] + S[1] * S[1]) * reff, by = std::sqrt(S[4] * S[4] + S[5] * S[5]) * reff;
+        if (!std::isfinite(bx) || !std::isfinite(by) || bx / res > kGridMaxRayCells || by / res > kGridMaxRayCells)
+            return fail(h, UZL_ERR_BAD_ARG, "a scan's pose scales its rays beyond 2^24 cells");
+        // conservative world box (relative slack for the roundings of p, q, e), one cell of margin for the floor
+        const double sx = bx * (1 + 1e-6) + 1e-9 * (std::fabs(r.tx) + 1.), sy = by * (1 + 1e-6) + 1e-9 * (std::fabs(r.ty) + 1.);
+        const double cx0 = std::floor((r.tx - sx - g.origin_x) / res) - 1, cx1 = std::floor((r.tx + sx - g.origin_x) / res) + 1;
+        const double cy0 = std::floor((r.ty - sy - g.origin_y) / res) - 1, cy1 = std::floor((r.ty + sy - g.origin_y) / res) + 1;
+        Box b{1, 1, 0, 0};
+        if (n_tiles > 0 && cx1 >= 0 && cy1 >= 0 && cx0 <= W - 1 && cy0 <= H - 1 && s.n > 0) {
+            b.x0 = (int32_t)std::max(cx0, 0.) / kGridTile; b.x1 = (int32_t)std::min(cx1, (double)(W - 1)) / kGridTile;
+            b.y0 = (int32_t)std::max(cy0, 0.) / kGridTile; b.y1 = (int32_t)std::min(cy1, (double)(H - 1)) / kGridTile;
+            r.ocx = cell_of(r.tx, g.origin_x, res); r.ocy = cell_of(r.ty, g.origin_y, res);   // within 2^24 + 2 cells of the grid
+        } else {
+            r.ocx = r.ocy = 0;
+        }
+        p.recs.push_back(r);
+        sbox.push_back(b);
+    }
+    // known-free rectangles (step 2), clipped to the grid
+    std::vector<int4> rects;
+    const double kd = c.known_free_radius / res;
+    const int64_t k = (int64_t)kd;                                              // (int), truncation
+    if (k >= 0 && c.min_pass_through > 0 && n_tiles > 0) {
+        for (int32_t i = 0; i < n_nodes; i++) {
+            if (!adds(present, i, first)) continue;
+            const double fx = std::floor((poses[12 * (size_t)i + 3] - g.origin_x) / res), fy = std::floor((poses[12 * (size_t)i + 7] - g.origin_y) / res);
+            const double x0 = std::max(fx - (double)k, 0.), x1 = std::min(fx + (double)k, (double)(W - 1));
+            const double y0 = std::max(fy - (double)k, 0.), y1 = std::min(fy + (double)k, (double)(H - 1));
+            if (x0 > x1 || y0 > y1) continue;
+            rects.push_back(make_int4((int)x0, (int)y0, (int)x1, (int)y1));
+        }
+    }
+    // bins: count, prefix sum, fill in scan / node order
+    std::vector<int32_t> n_ent((size_t)n_tiles, 0), n_kf((size_t)n_tiles, 0);
+    for (const Box& b : sbox)
+        for (int32_t ty = b.y0; ty <= b.y1; ty++)
+            for (int32_t tx = b.x0; tx <= b.x1; tx++) n_ent[(size_t)ty * tiles_x + tx]++;
+    for (const int4& q : rects)
+        for (int32_t ty = q.y / kGridTile; ty <= q.w / kGridTile; ty++)
+            for (int32_t tx = q.x / kGridTile; tx <= q.z / kGridTile; tx++) n_kf[(size_t)ty * tiles_x + tx]++;
+    std::vector<int32_t> slot((size_t)n_tiles, -1);
+    p.ent_start.push_back(0); p.kf_start.push_back(0);
+    for (int64_t t = 0; t < n_tiles; t++) {
+        if (!n_ent[t] && !n_kf[t]) continue;
+        slot[t] = (int32_t)p.tiles.size();
+        p.tiles.push_back((int32_t)t);
+        p.ent_start.push_back(p.ent_start.back() + n_ent[t]);
+        p.kf_start.push_back(p.kf_start.back() + n_kf[t]);
+    }
+    p.ent_scan.resize(p.ent_start.back());
+    p.ent_beam.resize(p.ent_start.back());
+    p.kf_rect.resize(p.kf_start.back());
+    std::vector<int32_t> fill_e(p.tiles.size()), fill_k(p.tiles.size());
+    std::vector<int64_t> beams(p.tiles.size(), 0);
+    for (size_t j = 0; j < p.tiles.size(); j++) { fill_e[j] = p.ent_start[j]; fill_k[j] = p.kf_start[j]; }
+    for (size_t si = 0; si < sbox.size(); si++) {
+        const Box& b = sbox[si];
+        for (int32_t ty = b.y0; ty <= b.y1; ty++)
+            for (int32_t tx = b.x0; tx <= b.x1; tx++) {
+                const int32_t j = slot[(size_t)ty * tiles_x + tx];
+                p.ent_scan[fill_e[j]] = (int32_t)si;
+                p.ent_beam[fill_e[j]++] = beams[j];
+                beams[j] += p.recs[si].n;
+            }
+    }
+    for (const int4& q : rects)
+        for (int32_t ty = q.y / kGridTile; ty <= q.w / kGridTile; ty++)
+            for (int32_t tx = q.x / kGridTile; tx <= q.z / kGridTile; tx++) p.kf_rect[fill_k[slot[(size_t)ty * tiles_x + tx]]++] = q;
+    return UZL_OK;
+}
+
+size_t align256(size_t v) { return (v + 255) / 256 * 256; }
+
+// Upload the plan in one copy and run it; fills the call's totals into h->info.
+void run(uzl_grid* h, const Plan& p, bool fresh)
+{
+    hipStream_t s = h->stream;
+    const uzl_grid_cfg& c = h->gcfg;
+    const GridGeom& g = h->geom;
+    const size_t cells = (size_t)g.width * g.height;
+    if (fresh) {
+        h->d_hits.reserve(std::max<size_t>(cells, 1)); h->d_passes.reserve(std::max<size_t>(cells, 1));
+        h->d_grid.reserve(std::max<size_t>(cells, 1));
+        const int8_t empty = 0 < c.min_pass_through ? (int8_t)-1 : (int8_t)0;    // step 6 of zero counts
+        if (cells) {
+            UZL_HIP(hipMemsetAsync(h->d_hits.p, 0, cells * 4, s));
+            UZL_HIP(hipMemsetAsync(h->d_passes.p, 0, cells * 4, s));
+            UZL_HIP(hipMemsetAsync(h->d_grid.p, (int)(uint8_t)empty, cells, s));
+        }
+    }
+    // one staging area: recs | tiles | ent_start | ent_scan | ent_beam | kf_start | kf_rect
+    size_t off[8];
+    off[0] = 0;
+    off[1] = off[0] + align256(p.recs.size() * sizeof(GridScanRec));
+    off[2] = off[1] + align256(p.tiles.size() * 4);
+    off[3] = off[2] + align256(p.ent_start.size() * 4);
+    off[4] = off[3] + align256(p.ent_scan.size() * 4);
+    off[5] = off[4] + align256(p.ent_beam.size() * 8);
+    off[6] = off[5] + align256(p.kf_start.size() * 4);
+    off[7] = off[6] + align256(p.kf_rect.size() * sizeof(int4));
+    h->h_work.reserve(std::max<size_t>(off[7], 256));
+    h->d_work.reserve(std::max<size_t>(off[7], 256));
+    uint8_t* w = h->h_work.p;
+    auto put = [&](int i, const void* src, size_t n) { if (n) memcpy(w + off[i], src, n); };
+    put(0, p.recs.data(), p.recs.size() * sizeof(GridScanRec));
+    put(1, p.tiles.data(), p.tiles.size() * 4);
+    put(2, p.ent_start.data(), p.ent_start.size() * 4);
+    put(3, p.ent_scan.data(), p.ent_scan.size() * 4);
+    put(4, p.ent_beam.data(), p.ent_beam.size() * 8);
+    put(5, p.kf_start.data(), p.kf_start.size() * 4);
+    put(6, p.kf_rect.data(), p.kf_rect.size() * sizeof(int4));
+    UZL_HIP(hipMemcpyAsync(h->d_work.p, w, off[7], hipMemcpyHostToDevice, s));
+    h->d_totals.reserve(2);
+    UZL_HIP(hipMemsetAsync(h->d_totals.p, 0, 2 * sizeof(unsigned long long), s));
+    uint8_t* d = h->d_work.p;
+    const GridScanRec* recs = reinterpret_cast<const GridScanRec*>(d + off[0]);
+
+    GridStatsArgs sa;
+    sa.ranges = h->d_ranges.p; sa.scans = recs; sa.range_max = c.range_max; sa.valid_total = h->d_totals.p;
+    launch_grid_stats(sa, (int)p.recs.size(), s);
+    UZL_HIP(hipGetLastError());
+
+    GridTileArgs a;
+    a.ranges = h->d_ranges.p; a.trig = h->d_trig.p; a.scans = recs;
+    a.tiles = reinterpret_cast<const int32_t*>(d + off[1]);
+    a.ent_start = reinterpret_cast<const int32_t*>(d + off[2]);
+    a.ent_scan = reinterpret_cast<const int32_t*>(d + off[3]);
+    a.ent_beam = reinterpret_cast<const int64_t*>(d + off[4]);
+    a.kf_start = reinterpret_cast<const int32_t*>(d + off[5]);
+    a.kf_rect = reinterpret_cast<const int4*>(d + off[6]);
+    a.hits = h->d_hits.p; a.passes = h->d_passes.p; a.grid = h->d_grid.p; a.hit_total = h->d_totals.p + 1;
+    a.origin_x = g.origin_x; a.origin_y = g.origin_y; a.resolution = c.resolution; a.range_max = c.range_max;
+    a.max_distance = c.max_distance; a.occupancy_threshold = c.occupancy_threshold;
+    a.width = (int32_t)g.width; a.height = (int32_t)g.height; a.tiles_x = ((int32_t)g.width + kGridTile - 1) / kGridTile;
+    a.min_pass_through = c.min_pass_through; a.fresh = fresh ? 1 : 0;
+    launch_grid_tiles(a, (int)p.tiles.size(), s);
+    UZL_HIP(hipGetLastError());
+
+    h->h_totals.reserve(2);
+    UZL_HIP(hipMemcpyAsync(h->h_totals.p, h->d_totals.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    UZL_HIP(hipStreamSynchronize(s));
+    h->info.origin_x = g.origin_x; h->info.origin_y = g.origin_y; h->info.resolution = c.resolution;
+    h->info.width = g.width; h->info.height = g.height;
+    h->info.valid_beams = (int64_t)h->h_totals.p[0];
+    h->info.hits = (int64_t)h->h_totals.p[1];
+    h->info.scans = (int32_t)p.recs.size();
+}
+
+// the force-clear test of graph_grid_mapper.cpp:336-342 over the nodes a call adds
+int32_t off_grid(const uzl_grid_cfg& c, const GridGeom& g, int32_t n_nodes, const double* poses, const uint8_t* present, int32_t first)
+{
+    for (int32_t i = 0; i < n_nodes; i++) {
+        if (!adds(present, i, first)) continue;
+        const double x = poses[12 * (size_t)i + 3], y = poses[12 * (size_t)i + 7];
+        if (x < g.origin_x + c.range_max || y < g.origin_y + c.range_max ||
+            x > (g.origin_x + (double)g.width * c.resolution) - c.range_max || y > (g.origin_y + (double)g.height * c.resolution) - c.range_max)
+            return 1;
+    }
+    return 0;
+}
+
+int check_out(uzl_grid* h, int64_t cap)
+{
+    if (!h->built) return fail(h, UZL_ERR_STATE, "no grid built yet");
+    if (cap < 0) return fail(h, UZL_ERR_BAD_ARG, "negative capacity");
+    if ((uint64_t)cap < (uint64_t)h->geom.width * h->geom.height) return fail(h, UZL_ERR_TRUNCATED, "capacity below width * height");
+    return UZL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void uzl_grid_cfg_default(uzl_grid_cfg* c)
+{
+    if (!c) return;
+    memset(c, 0, sizeof(*c));
+    c->resolution = 0.1; c->range_max = 5.0; c->occupancy_threshold = 0.1; c->max_distance = 10.0; c->known_free_radius = 0.5;
+    c->min_pass_through = 1; c->device = 0; c->max_cells = (int64_t)1 << 28;
+}
+
+int uzl_grid_create(const uzl_grid_cfg* cfg, uzl_grid** out)
+{
+    if (!out) return UZL_ERR_BAD_ARG;
+    *out = nullptr;
+    uzl_grid_cfg c;
+    if (cfg) c = *cfg; else uzl_grid_cfg_default(&c);
+    if (check_cfg(c) != UZL_OK) return UZL_ERR_BAD_ARG;
+    if (check_device(c.device) != UZL_OK) return UZL_ERR_NO_DEVICE;
+    uzl_grid* h = new (std::nothrow) uzl_grid();
+    if (!h) return UZL_ERR_OOM;
+    h->cfg = h->gcfg = c;
+    try {
+        open_handle_stream(c.device, false, &h->stream);
+    } catch (...) {
+        const int code = caught_status(h->last_error);
+        close_handle_stream(c.device, h->stream);
+        delete h;
+        return code;
+    }
+    *out = h;
+    return UZL_OK;
+}
+
+void uzl_grid_destroy(uzl_grid* h)
+{
+    if (!h) return;
+    (void)hipSetDevice(h->cfg.device);
+    close_handle_stream(h->cfg.device, h->stream);
+    delete h;
+}
+
+const char* uzl_grid_last_error(uzl_grid* h) { return last_error_of(h); }
+
+int uzl_grid_set_config(uzl_grid* h, const uzl_grid_cfg* cfg)
+{
+    UZL_GUARD_BEGIN(h)
+    if (!cfg || check_cfg(*cfg) != UZL_OK) return fail(h, UZL_ERR_BAD_ARG, "bad config");
+    if (cfg->device != h->cfg.device) return fail(h, UZL_ERR_BAD_ARG, "the device of a handle cannot change");
+    h->cfg = *cfg;
+    return UZL_OK;
+    UZL_GUARD_END(h)
+}
+
+int uzl_grid_add_scans(uzl_grid* h, int32_t n, const uzl_grid_scan* scans, int32_t* first_scan)
+{
+    UZL_GUARD_BEGIN(h)
+    if (n < 0 || (n > 0 && !scans)) return fail(h, UZL_ERR_BAD_ARG, "bad scan count or null scans");
+    int64_t total = 0;
+    for (int32_t i = 0; i < n; i++) {
+        const uzl_grid_scan& s = scans[i];
+        if (s.node < 0 || s.n_ranges < 0 || (s.n_ranges > 0 && !s.ranges)) return fail(h, UZL_ERR_BAD_ARG, "bad scan node / ranges");
+        if (!std::isfinite(s.angle_min) || !std::isfinite(s.angle_increment) || !finite12(s.displacement))
+            return fail(h, UZL_ERR_BAD_ARG, "non-finite scan angle or displacement");
+        if (!(s.range_min >= 0.f)) return fail(h, UZL_ERR_BAD_ARG, "range_min negative or NaN");
+        total += s.n_ranges;
+    }
+    if (h->n_ranges + total >= ((int64_t)1 << 40)) return fail(h, UZL_ERR_BAD_ARG, "too many ranges");
+    UZL_HIP(hipSetDevice(h->cfg.device));
+    hipStream_t st = h->stream;
+    // new (cos, sin) tables, host libm (contract step 3)
+    std::vector<double2> trig;
+    std::vector<int64_t> toff(n);
+    auto tables = h->tables;
+    int64_t n_trig = h->n_trig;
+    for (int32_t i = 0; i < n; i++) {
+        const uzl_grid_scan& s = scans[i];
+        uint32_t ka, ki;
+        memcpy(&ka, &s.angle_min, 4); memcpy(&ki, &s.angle_increment, 4);
+        const auto key = std::make_tuple(ka, ki, s.n_ranges);
+        auto it = tables.find(key);
+        if (it == tables.end()) {
+            it = tables.emplace(key, n_trig).first;
+            for (int32_t b = 0; b < s.n_ranges; b++) {
+                const double th = (double)s.angle_min + (double)b * (double)s.angle_increment;
+                trig.push_back(make_double2(std::cos(th), std::sin(th)));
+            }
+            n_trig += s.n_ranges;
+        }
+        toff[i] = it->second;
+    }
+    h->d_ranges.reserve((size_t)std::max<int64_t>(h->n_ranges + total, 1), true, st);
+    h->d_trig.reserve((size_t)std::max<int64_t>(n_trig, 1), true, st);
+    if (!trig.empty())
+        UZL_HIP(hipMemcpyAsync(h->d_trig.p + h->n_trig, trig.data(), trig.size() * sizeof(double2), hipMemcpyHostToDevice, st));
+    if (total) {
+        h->h_work.reserve((size_t)total * 4);
+        float* w = reinterpret_cast<float*>(h->h_work.p);
+        int64_t o = 0;
+        for (int32_t i = 0; i < n; i++) { memcpy(w + o, scans[i].ranges, (size_t)scans[i].n_ranges * 4); o += scans[i].n_ranges; }
+        UZL_HIP(hipMemcpyAsync(h->d_ranges.p + h->n_ranges, w, (size_t)total * 4, hipMemcpyHostToDevice, st));
+    }
+    UZL_HIP(hipStreamSynchronize(st));
+    if (first_scan) *first_scan = (int32_t)h->scans.size();
+    int64_t o = h->n_ranges;
+    for (int32_t i = 0; i < n; i++) {
+        GridScanHost g;
+        g.node = scans[i].node; g.n = scans[i].n_ranges; memcpy(g.D, scans[i].displacement, sizeof(g.D));
+        g.range_min = scans[i].range_min; g.ranges_off = o; g.trig_off = toff[i];
+        o += g.n;
+        h->scans.push_back(g);
+    }
+    h->n_ranges = o;
+    h->tables.swap(tables);
+    h->n_trig = n_trig;
+    return UZL_OK;
+    UZL_GUARD_END(h)
+}
+
+int uzl_grid_scan_count(uzl_grid* h)
+{
+    if (!h) return UZL_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    return (int)h->scans.size();
+}
+
+int uzl_grid_build(uzl_grid* h, int32_t n_nodes, const double* poses, const uint8_t* present, uzl_grid_info* info)
+{
+    UZL_GUARD_BEGIN(h)
+    if (int rc = check_poses(h, n_nodes, poses, present)) return rc;
+    const uzl_grid_cfg c = h->cfg;
+    GridGeom g;
+    if (int rc = geometry(h, c, n_nodes, poses, present, &g)) return rc;
+    Plan p;
+    if (int rc = plan(h, c, g, n_nodes, poses, present, 0, p)) return rc;
+    UZL_HIP(hipSetDevice(h->cfg.device));
+    h->built = false;                        // a failure below leaves no half-built grid behind
+    h->gcfg = c;
+    h->geom = g;
+    h->info = uzl_grid_info{};
+    run(h, p, true);
+    h->built = true;
+    if (info) *info = h->info;
+    return UZL_OK;
+    UZL_GUARD_END(h)
+}
+
+int uzl_grid_extend(uzl_grid* h, int32_t n_nodes, const double* poses, const uint8_t* present, int32_t first_node, uzl_grid_info* info)
+{
+    UZL_GUARD_BEGIN(h)
+    if (!h->built) return fail(h, UZL_ERR_STATE, "extend before any build");
+    if (first_node < 0) return fail(h, UZL_ERR_BAD_ARG, "negative first_node");
+    if (int rc = check_poses(h, n_nodes, poses, present)) return rc;
+    Plan p;
+    if (int rc = plan(h, h->gcfg, h->geom, n_nodes, poses, present, first_node, p)) return rc;
+    UZL_HIP(hipSetDevice(h->cfg.device));
+    const int32_t og = off_grid(h->gcfg, h->geom, n_nodes, poses, present, first_node);
+    run(h, p, false);
+    h->info.off_grid = og;
+    if (info) *info = h->info;
+    return UZL_OK;
+    UZL_GUARD_END(h)
+}
+
+int uzl_grid_get_info(uzl_grid* h, uzl_grid_info* info)
+{
+    UZL_GUARD_BEGIN(h)
+    if (!info) return fail(h, UZL_ERR_BAD_ARG, "null info");
+    if (!h->built) return fail(h, UZL_ERR_STATE, "no grid built yet");
+    *info = h->info;
+    return UZL_OK;
+    UZL_GUARD_END(h)
+}
+
+int uzl_grid_read(uzl_grid* h, int64_t cap, int8_t* data)
+{
+    UZL_GUARD_BEGIN(h)
+    if (int rc = check_out(h, cap)) return rc;
+    const size_t cells = (size_t)h->geom.width * h->geom.height;
+    if (cells && !data) return fail(h, UZL_ERR_BAD_ARG, "null output");
+    UZL_HIP(hipSetDevice(h->cfg.device));
+    if (cells) UZL_HIP(hipMemcpyAsync(data, h->d_grid.p, cells, hipMemcpyDeviceToHost, h->stream));
+    UZL_HIP(hipStreamSynchronize(h->stream));
+    return UZL_OK;
+    UZL_GUARD_END(h)
+}
+
+int uzl_grid_counts(uzl_grid* h, int64_t cap, uint32_t* hits, uint32_t* passes)
+{
+    UZL_GUARD_BEGIN(h)
+    if (int rc = check_out(h, cap)) return rc;
+    const size_t cells = (size_t)h->geom.width * h->geom.height;
+    UZL_HIP(hipSetDevice(h->cfg.device));
+    if (cells && hits) UZL_HIP(hipMemcpyAsync(hits, h->d_hits.p, cells * 4, hipMemcpyDeviceToHost, h->stream));
+    if (cells && passes) UZL_HIP(hipMemcpyAsync(passes, h->d_passes.p, cells * 4, hipMemcpyDeviceToHost, h->stream));
+    UZL_HIP(hipStreamSynchronize(h->stream));
+    return UZL_OK;
+    UZL_GUARD_END(h)
+}
+
+}  // extern "C"

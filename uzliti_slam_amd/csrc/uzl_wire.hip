@@ -170,12 +170,31 @@ void skip_laser_scan(Reader& r)       // sensor_msgs/LaserScan
     r.skip_array<float>();
 }
 void put_default_laser_scan(Writer& w) { w.zeros(16 + 28 + 4 + 4); }
+void get_laser_scan(Reader& r, uzl_wire_scan* out)     // sensor_msgs/LaserScan, field for field
+{
+    const Header h = get_header(r);
+    out->seq = h.seq; out->stamp_sec = h.sec; out->stamp_nsec = h.nsec; out->frame_id = h.frame_id;
+    out->angle_min = r.get<float>(); out->angle_max = r.get<float>(); out->angle_increment = r.get<float>();
+    out->time_increment = r.get<float>(); out->scan_time = r.get<float>(); out->range_min = r.get<float>(); out->range_max = r.get<float>();
+    const uint32_t nr = r.get<uint32_t>();
+    out->ranges = r.bytes((uint64_t)nr * 4); out->n_ranges = (int32_t)nr;
+    const uint32_t ni = r.get<uint32_t>();
+    out->intensities = r.bytes((uint64_t)ni * 4); out->n_intensities = (int32_t)ni;
+}
+void put_laser_scan(Writer& w, const uzl_wire_scan& s)
+{
+    w.val<uint32_t>(s.seq); w.val(s.stamp_sec); w.val(s.stamp_nsec); w.str(s.frame_id);
+    w.val(s.angle_min); w.val(s.angle_max); w.val(s.angle_increment); w.val(s.time_increment); w.val(s.scan_time);
+    w.val(s.range_min); w.val(s.range_max);
+    w.val<uint32_t>((uint32_t)s.n_ranges); w.put(s.ranges.p, 4 * (uint64_t)s.n_ranges);
+    w.val<uint32_t>((uint32_t)s.n_intensities); w.put(s.intensities.p, 4 * (uint64_t)s.n_intensities);
+}
 
 constexpr uint64_t kFeatureFixed = 4 + 4 + 1 + 4 + 4 + 24;       // u, v, is_3d, keypoint_strength, descriptor count, keypoint_position
 
 // graph_slam_msgs/SensorData (SensorData.msg): fields in declaration order; gist (may be NULL) receives the gist_descriptor
 // elements (4 bytes each)
-void get_sensor(Reader& r, uzl_wire_sensor* out, uzl_span* gist = nullptr)
+void get_sensor(Reader& r, uzl_wire_sensor* out, uzl_span* gist = nullptr, uzl_wire_scan* scan = nullptr)
 {
     uzl_wire_sensor s;
     memset(&s, 0, sizeof(s));
@@ -207,8 +226,13 @@ void get_sensor(Reader& r, uzl_wire_sensor* out, uzl_span* gist = nullptr)
     const uint32_t ng = r.get<uint32_t>();                                       // gist_descriptor
     const uzl_span g = r.bytes((uint64_t)ng * 4);
     if (gist) *gist = g;
-    skip_laser_scan(r);
-    r.skip(24);                                                                  // scan_center
+    if (scan) {
+        get_laser_scan(r, scan);
+        for (int i = 0; i < 3; i++) scan->scan_center[i] = r.get<double>();
+    } else {
+        skip_laser_scan(r);
+        r.skip(24);                                                              // scan_center
+    }
     if (r.ok) { s.raw.p = reinterpret_cast<const char*>(r.b + start); s.raw.n = r.o - start; }
     if (out) *out = s;
 }
@@ -250,6 +274,24 @@ void put_gist_sensor(Writer& w, uint32_t sec, uint32_t nsec, const uzl_span& fra
     for (int32_t i = 0; i < n; i++) w.val<float>((float)gist[i]);
     put_default_laser_scan(w);
     w.zeros(24);
+}
+
+// SensorData::toMsg (sensor_data.cpp:40-49) + LaserscanData::toMsg (:261-269): a SENSOR_TYPE_LASERSCAN message; features and images
+// default-constructed, gist_descriptor empty
+void put_scan_sensor(Writer& w, uint32_t sec, uint32_t nsec, const uzl_span& frame, const double displacement[12], const uzl_wire_scan& scan)
+{
+    put_header(w, sec, nsec, frame);
+    w.val<int32_t>(UZL_SENSOR_TYPE_LASERSCAN);
+    put_pose(w, displacement);
+    w.str(frame);
+    put_header(w, 0, 0, uzl_span{nullptr, 0});
+    w.val<int32_t>(0);
+    w.val<uint32_t>(0);
+    put_default_camera_info(w);
+    put_default_image(w); put_default_image(w);
+    w.val<uint32_t>(0);
+    put_laser_scan(w, scan);
+    for (int i = 0; i < 3; i++) w.val(scan.scan_center[i]);
 }
 
 // `(unsigned char) msg.gist_descriptor[i]` of BinaryGistData::fromMsg (sensor_data.cpp:238-246), the rule of the Feature unpack
@@ -474,6 +516,14 @@ void put_bag(Writer& w, const uzl_bag_msg& m)
     w.val(conn); w.val(one);
 }
 
+// the spans of an encoder's scan hold what its counts say
+bool scan_ok(const uzl_wire_scan* s)
+{
+    return s && s->n_ranges >= 0 && s->n_intensities >= 0 && (s->frame_id.n == 0 || s->frame_id.p) &&
+           (s->n_ranges == 0 || (s->ranges.p && s->ranges.n == 4 * (uint64_t)s->n_ranges)) &&
+           (s->n_intensities == 0 || (s->intensities.p && s->intensities.n == 4 * (uint64_t)s->n_intensities));
+}
+
 }  // namespace
 
 extern "C" {
@@ -673,6 +723,35 @@ int uzl_wire_gist_sensor_encode(uint32_t stamp_sec, uint32_t stamp_nsec, uzl_spa
     if (!displacement || n < 0 || (n > 0 && !gist) || !buf || (sensor_frame.n && !sensor_frame.p)) return UZL_ERR_BAD_ARG;
     Writer w(buf, cap);
     put_gist_sensor(w, stamp_sec, stamp_nsec, sensor_frame, displacement, gist, n);
+    if (written) *written = w.o;
+    return w.fits() ? UZL_OK : UZL_ERR_TRUNCATED;
+}
+
+int uzl_wire_sensor_scan(const uzl_wire_sensor* s, uzl_wire_scan* out)
+{
+    if (!s || !s->raw.p || !out) return UZL_ERR_BAD_ARG;
+    Reader r(reinterpret_cast<const uint8_t*>(s->raw.p), s->raw.n);
+    uzl_wire_scan sc;
+    memset(&sc, 0, sizeof(sc));
+    get_sensor(r, nullptr, nullptr, &sc);
+    if (!r.ok) return UZL_ERR_TRUNCATED;
+    *out = sc;
+    return UZL_OK;
+}
+uint64_t uzl_wire_scan_sensor_size(uzl_span sensor_frame, const uzl_wire_scan* scan)
+{
+    if (!scan_ok(scan)) return 0;
+    Writer w(nullptr, 0);
+    const double I[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    put_scan_sensor(w, 0, 0, sensor_frame, I, *scan);
+    return w.o;
+}
+int uzl_wire_scan_sensor_encode(uint32_t stamp_sec, uint32_t stamp_nsec, uzl_span sensor_frame, const double* displacement,
+                                const uzl_wire_scan* scan, uint8_t* buf, uint64_t cap, uint64_t* written)
+{
+    if (!displacement || !scan_ok(scan) || !buf || (sensor_frame.n && !sensor_frame.p)) return UZL_ERR_BAD_ARG;
+    Writer w(buf, cap);
+    put_scan_sensor(w, stamp_sec, stamp_nsec, sensor_frame, displacement, *scan);
     if (written) *written = w.o;
     return w.fits() ? UZL_OK : UZL_ERR_TRUNCATED;
 }

@@ -16,6 +16,7 @@ UZL_ERR_TRUNCATED = -9
 UZL_ERR_UNSUPPORTED = -10
 SENSOR_TYPE_FEATURE = 1
 SENSOR_TYPE_BINARY_GIST = 3
+SENSOR_TYPE_LASERSCAN = 4
 
 
 class Span(C.Structure):
@@ -35,6 +36,16 @@ class WireSensor(C.Structure):
                 ("sensor_frame", Span), ("displacement", C.c_double * 12), ("descriptor_type", C.c_int32),
                 ("n_features", C.c_int32), ("desc_len", C.c_int32), ("uniform", C.c_int32), ("records", Span),
                 ("camera_info", Span)]
+
+
+class WireScan(C.Structure):
+    _fields_ = [("seq", C.c_uint32), ("stamp_sec", C.c_uint32), ("stamp_nsec", C.c_uint32), ("frame_id", Span),
+                ("angle_min", C.c_float), ("angle_max", C.c_float), ("angle_increment", C.c_float), ("time_increment", C.c_float),
+                ("scan_time", C.c_float), ("range_min", C.c_float), ("range_max", C.c_float), ("n_ranges", C.c_int32),
+                ("n_intensities", C.c_int32), ("ranges", Span), ("intensities", Span), ("scan_center", C.c_double * 3)]
+
+
+_SCAN_F32 = ("angle_min", "angle_max", "angle_increment", "time_increment", "scan_time", "range_min", "range_max")
 
 
 class WireNode(C.Structure):
@@ -65,8 +76,11 @@ def _lib():
     L = capi.lib()
     if not _proto_done:
         for f in ("uzl_wire_edge_size", "uzl_wire_node_size", "uzl_wire_meta_size", "uzl_wire_features_size", "uzl_bag_single_size",
-                  "uzl_wire_gist_sensor_size"):
+                  "uzl_wire_gist_sensor_size", "uzl_wire_scan_sensor_size"):
             getattr(L, f).restype = C.c_uint64
+        L.uzl_wire_scan_sensor_size.argtypes = [Span, C.c_void_p]
+        L.uzl_wire_scan_sensor_encode.argtypes = [C.c_uint32, C.c_uint32, Span, C.POINTER(C.c_double), C.c_void_p, C.POINTER(C.c_uint8),
+                                                  C.c_uint64, C.POINTER(C.c_uint64)]
         L.uzl_wire_gist_sensor_size.argtypes = [Span, C.c_int32]
         L.uzl_wire_gist_sensor_encode.argtypes = [C.c_uint32, C.c_uint32, Span, C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.c_int32,
                                                   C.POINTER(C.c_uint8), C.c_uint64, C.POINTER(C.c_uint64)]
@@ -279,6 +293,46 @@ def encode_gist_sensor(stamp_sec, stamp_nsec, sensor_frame, displacement, gist):
     wr = C.c_uint64(0)
     _check(L.uzl_wire_gist_sensor_encode(stamp_sec, stamp_nsec, fr, disp, g.ctypes.data_as(C.POINTER(C.c_uint8)), len(g), buf,
                                          C.c_uint64(size), C.byref(wr)), "gist_sensor_encode")
+    assert wr.value == size
+    return bytes(buf)[:size]
+
+
+def sensor_scan(sensor_c):
+    """SensorData.scan and scan_center of a decoded sensor (a WireSensor of DecodedNode.sensors_c), as LaserscanData::fromMsg reads
+    them (sensor_data.cpp:271-277): a dict of the LaserScan fields with numpy f32 `ranges` / `intensities`."""
+    L = _lib()
+    w = WireScan()
+    _check(L.uzl_wire_sensor_scan(C.byref(sensor_c), C.byref(w)), "sensor_scan")
+    d = dict(seq=w.seq, stamp_sec=w.stamp_sec, stamp_nsec=w.stamp_nsec, frame_id=_bytes(w.frame_id),
+             ranges=np.frombuffer(_bytes(w.ranges), "<f4").copy(), intensities=np.frombuffer(_bytes(w.intensities), "<f4").copy(),
+             scan_center=np.array(w.scan_center[:]))
+    d.update({k: getattr(w, k) for k in _SCAN_F32})
+    return d
+
+
+def encode_scan_sensor(stamp_sec, stamp_nsec, sensor_frame, displacement, scan):
+    """A SENSOR_TYPE_LASERSCAN graph_slam_msgs/SensorData (SensorData::toMsg + LaserscanData::toMsg); scan = dict as sensor_scan
+    returns (missing fields default to 0 / empty).  The bytes go into a sensor dict's `raw` for encode_node."""
+    L = _lib()
+    k = _Keep()
+    w = WireScan()
+    w.seq = int(scan.get("seq", 0)); w.stamp_sec = int(scan.get("stamp_sec", 0)); w.stamp_nsec = int(scan.get("stamp_nsec", 0))
+    w.frame_id = k.span(scan.get("frame_id"))
+    for f in _SCAN_F32:
+        setattr(w, f, float(scan.get(f, 0.0)))
+    r = np.ascontiguousarray(scan.get("ranges", []), "<f4").reshape(-1)
+    it = np.ascontiguousarray(scan.get("intensities", []), "<f4").reshape(-1)
+    w.n_ranges, w.n_intensities = len(r), len(it)
+    w.ranges = k.span(r.tobytes()) if len(r) else Span(None, 0)
+    w.intensities = k.span(it.tobytes()) if len(it) else Span(None, 0)
+    w.scan_center[:] = np.asarray(scan.get("scan_center", [0.0, 0.0, 0.0]), np.float64).reshape(3).tolist()
+    fr = k.span(sensor_frame)
+    disp = (C.c_double * 12)(*_arr(displacement, 12))
+    size = L.uzl_wire_scan_sensor_size(fr, C.byref(w))
+    buf = (C.c_uint8 * max(size, 1))()
+    wr = C.c_uint64(0)
+    _check(L.uzl_wire_scan_sensor_encode(stamp_sec, stamp_nsec, fr, disp, C.byref(w), buf, C.c_uint64(size), C.byref(wr)),
+           "scan_sensor_encode")
     assert wr.value == size
     return bytes(buf)[:size]
 
