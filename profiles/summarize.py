@@ -38,7 +38,7 @@ for k, d in pmc.items():
     f = d.get("FETCH_SIZE", {}).get("mean_kb", 0.0)
     w = d.get("WRITE_SIZE", {}).get("mean_kb", 0.0)
     d["hbm_bytes_per_launch"] = (2.0 * f + w) * 1024.0
-# the 10k/50k run: its own kernel stats; its counters only add kernels config 2 does not launch (ml_spmv_kernel<4>) or are kept
+# the 10k/50k run: its own kernel stats; its counters only add kernels config 2 does not launch (ml_spmv_lm_kernel<4, ...>) or are kept
 # under a c4_ prefix
 for tag in ("c4_trace", "batch_trace", "online_trace"):
     ks2 = sorted(glob.glob(f"{src}/{tag}/*/*kernel_stats.csv") + glob.glob(f"{src}/{tag}/*kernel_stats.csv"), key=os.path.getmtime, reverse=True)
@@ -101,14 +101,14 @@ def stats_avg_us(path, prefixes):
 
 
 rp = {}
-for key, path, prefixes in (("pcg_spmv", out + "_kernel_stats.csv", ("uzl::ml_spmv_kernel<1>",)),
+for key, path, prefixes in (("pcg_spmv", out + "_kernel_stats.csv", ("uzl::ml_spmv_lm_kernel<1, 1, 8,",)),
                             ("hessian", out + "_kernel_stats.csv", ("uzl::hessian_kernel",)),
                             ("ns_gemm32", out + "_kernel_stats.csv", ("uzl::ml_ns_gemm32_kernel",)),
                             ("knn2", out + "_kernel_stats.csv", ("uzl::knn2_mfma_kernel<8, 2",)),
                             ("estimate", out + "_kernel_stats.csv", ("uzl::estimate_kernel",)),
                             ("wire_unpack", out + "_kernel_stats.csv", ("uzl::wire_unpack_kernel",)),
-                            ("pcg_spmv4", out + "_c4_kernel_stats.csv", ("uzl::ml_spmv_kernel<4>",)),
-                            ("pcg_cg4", out + "_c4_kernel_stats.csv", ("uzl::ml_cg_kernel<4",)),
+                            ("pcg_spmv4", out + "_c4_kernel_stats.csv", ("uzl::ml_spmv_lm_kernel<4,",)),
+                            ("pcg_cg4", out + "_c4_kernel_stats.csv", ("uzl::ml_cg_lm_kernel<4,",)),
                             ("c4_hessian", out + "_c4_kernel_stats.csv", ("uzl::hessian_kernel",)),
                             ("c4_ns_gemm", out + "_c4_kernel_stats.csv", ("uzl::ml_ns_gemm_kernel",))):
     v = stats_avg_us(path, prefixes)

@@ -70,7 +70,7 @@ def test_without_schur_and_with_block_hierarchy_variants(capi):
     g = synth.make_pose_graph(1500, 1530, seed=3)
     _same(capi, g, 8, schur_reduce=-1)
     _same(capi, synth.make_pose_graph(6000, 30000, seed=5), 6)          # AGG = 4 with the six operator rows in registers
-    _same(capi, synth.make_pose_graph(14000, 60000, seed=6), 4)         # ... streamed, alpha prepared by ml_alpha_kernel
+    _same(capi, synth.make_pose_graph(14000, 60000, seed=6), 4)         # ... streamed, alpha prepared by ml_alpha_lm_kernel
 
 
 def test_rejected_trials_and_termination(capi):

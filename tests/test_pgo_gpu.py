@@ -184,7 +184,7 @@ def test_block_jacobi_and_multilevel_agree(capi, oracle):
 @pytest.mark.parametrize("n,e", [(9, 20), (17, 40), (64, 200), (65, 200), (513, 2000), (1281, 5000), (1800, 7000), (2049, 8000)])
 def test_multilevel_hierarchy_edge_sizes(capi, oracle, n, e):
     """aggregate boundaries: 8^k and 8^k + 1 vertices, partially filled last aggregates; 1281 / 1800: the level-1 dense operator
-    beyond 960 columns (ml_cg_comp_kernel<8>); 2049: the first size on the four-aggregates-per-workgroup path."""
+    beyond 960 columns (ml_cg_comp_lm_kernel<8, ...>); 2049: the first size on the four-aggregates-per-workgroup path."""
     g = synth.make_pose_graph(n, e, seed=n)
     p = capi.Pgo()
     p.add_graph(g["nodes_pose"], g["nodes_fixed"], g["edges"])
@@ -453,9 +453,9 @@ def test_chain_like_graphs(capi, oracle, n, e, its):
 @pytest.mark.parametrize("n,e", [(10000, 10800), (12600, 13600), (20000, 21700), (23000, 24600)])
 def test_large_sparse_graphs_on_every_kernel_path_against_oracle(capi, oracle, n, e):
     """The large-graph PCG kernels against the oracle's direct solve at sizes the oracle still finishes in a second (few loop closures:
-    little fill): 10k = six rows of the level-2 operator in registers (ml_cg_kernel<4, true, true>), 12.6k and 20k = ml_alpha_kernel +
-    streamed rows (ml_cg_kernel<4, true, false, true>; 6 n_2 = 2364 / 3750), 23k = no dense level-2 operator (6 n_2 > 4096:
-    ml_cg_kernel<4>, restrict / top solve / prolong through LDS); ml_spmv_kernel<4> in half-aggregate workgroups throughout."""
+    little fill): 10k = six rows of the level-2 operator in registers (ml_cg_lm_kernel<4, true, true, ...>), 12.6k and 20k = ml_alpha_lm_kernel +
+    streamed rows (ml_cg_lm_kernel<4, true, false, true, ...>; 6 n_2 = 2364 / 3750), 23k = no dense level-2 operator (6 n_2 > 4096:
+    ml_cg_lm_kernel<4, false, ...>, restrict / top solve / prolong through LDS); ml_spmv_lm_kernel<4, ...> in half-aggregate workgroups throughout."""
     p = capi.Pgo()
     try:
         st, so = _check(p, oracle, synth.make_pose_graph(n, e, seed=n), iterations=6)

@@ -40,7 +40,7 @@ class InProcessAllReduce:
 
 
 @pytest.mark.parametrize("n,e,world", [(300, 1200, 2), (1000, 5000, 2), (600, 2500, 3), (3000, 12000, 2), (10000, 50000, 2),   # BASELINE config 4 at its size
-                                       (13000, 16000, 2),        # the ml_alpha_kernel path (12k .. 21.8k vertices)
+                                       (13000, 16000, 2),        # the ml_alpha_lm_kernel path (12k .. 21.8k vertices)
                                        (2000, 2040, 2), (20000, 21800, 2), (5000, 5400, 3)])      # chain-like: chain interiors Schur-eliminated by every rank
 def test_sharded_equals_unsharded(capi, oracle, n, e, world):
     g = synth.make_pose_graph(n, e, seed=n + world)

@@ -53,15 +53,10 @@ int g_ml_spmv(int nb, int agg);
 size_t ml_cg_lds_bytes(const int* n, int levels, int agg);
 bool ml_fits_lds(const int* n_per_level, int levels, int agg);
 // The ONE statement of the PCG kernels' LDS budget and of what ml_cg stages when the dense level-2 operator is present (the gather-level
-// vector and nothing else): build_ml's admission test, k_ml_cg, ml_cg_variant and ml_fits_lds all read these (tests/test_ml_admission.py
+// vector and nothing else): build_ml's admission test, ml_cg_variant and ml_fits_lds all read these (tests/test_ml_admission.py
 // holds the boundaries through uzl_debug_ml_admission)
 // (kMlLdsLimit, ml_comp4_lds: pgo_types.hpp)
 bool ml_comp4_fits(int nb, int n2);          // LDS of the comp4 variant and ml_spmv's partial count
-void k_ml_init(const PgoDev& D, const MlHot& ml, int agg, double* p0, double* p1, double* rg, hipStream_t s);
-void k_ml_spmv(const PgoDev& D, const MlHot& ml, int agg, const double* p_old, double* p_new, int n_part, double tol2, hipStream_t s,
-               hipEvent_t ev_a = nullptr, hipEvent_t ev_b = nullptr);
-hipError_t k_ml_cg(const PgoDev& D, const MlHot& ml, int agg, const double* p, const double* rg_old, double* rg_new, int n_part,
-                   int init, size_t lds, hipStream_t s, hipEvent_t ev_a = nullptr, hipEvent_t ev_b = nullptr);
 int k_oplus(const PgoDev& D, const double* pose_in, double* pose_out, hipStream_t s);
 int g_edges_for(int e);
 void k_slot_records(const double* zinv, const double* info, int e, const int32_t* slot_edge, int nslots, double* srec, hipStream_t s);
@@ -82,8 +77,12 @@ void kl_schur_backsub(const LmSlot* sl, int nslots, int max_grid, hipStream_t s)
 void kl_ml_numeric(const LmSlot* sl, const LmShape& sh, int which, hipStream_t s);
 void kl_ml_trial(const LmSlot* sl, const LmShape& sh, int which, hipStream_t s);
 void ml_cg_variant(const MlHot& ml, int agg, size_t lds_full, int32_t* variant, int32_t* comp_u, uint64_t* lds);
-hipError_t kl_ml_init(const LmSlot* sl, const LmSlot* host_slot, const LmShape& sh, hipStream_t s);
-hipError_t kl_ml_pcg_its(const LmSlot* sl, const LmSlot* host_slot, const LmShape& sh, int first, int n, hipStream_t s, hipEvent_t* ev = nullptr);
+hipError_t kl_ml_init(const LmSlot* sl, const LmSlot* by_value, const LmShape& sh, hipStream_t s);
+hipError_t kl_ml_pcg_its(const LmSlot* sl, const LmSlot* by_value, const LmShape& sh, int first, int n, hipStream_t s, hipEvent_t* ev = nullptr);
+// the same PCG kernels for the host-driven loop (pgo_types.hpp: HostSlot): init, and the two launches of iteration `parity` one by one
+void kl_ml_pcg_init(const HostSlot& hs, const LmShape& sh, hipStream_t s);
+void kl_ml_spmv(const HostSlot& hs, const LmShape& sh, int parity, hipStream_t s, hipEvent_t ev_a = nullptr, hipEvent_t ev_b = nullptr);
+hipError_t kl_ml_cg(const HostSlot& hs, const LmShape& sh, int parity, int init, hipStream_t s, hipEvent_t ev_a = nullptr, hipEvent_t ev_b = nullptr);
 }  // namespace uzl
 
 
@@ -197,6 +196,10 @@ struct uzl_pgo : uzl::HandleBase {
     bool mult_banned = false;        // the multiplicative operator broke down on a graph of this handle: later structures start additive
     KernelTimer timer;
     uzl::LmRun* lm = nullptr;        // the device-resident LM loop's slot table and captured passes (uzl_pgo_lm.hip)
+    // the host-driven loop's slot and launch geometry of the multilevel PCG kernels, for structure generation ml_slot_gen (uzl_pgo.hip: host_slot)
+    LmSlot ml_slot{};
+    LmShape ml_shape{};
+    uint64_t ml_slot_gen = ~0ull;
     bool last_structure_reused = false;
     std::chrono::steady_clock::time_point t_start;      // start of the running uzl_pgo_optimize (solve_ms)
 };
@@ -226,6 +229,8 @@ void lm_run_destroy(LmRun* r);
 bool lm_eligible(const uzl_pgo* h);
 int do_optimize_lm(uzl_pgo* h, int32_t iterations, uzl_pgo_stats* st);
 bool lm_batch_eligible(const std::vector<uzl_pgo*>& hs);
+LmSlot make_slot(const uzl_pgo* h, LmDev* d_lm, LmHost* d_pub);
+LmShape make_shape(const std::vector<uzl_pgo*>& hs, int nslots, bool batch_geometry);
 int batch_optimize_lm(LmRun*& R, const std::vector<uzl_pgo*>& hs, int resident, hipStream_t s, hipStream_t s2, int32_t iterations, bool eager, bool verbose, KernelTimer* timer,
                       uzl_pgo_stats* stats, int* rc_all);
 constexpr int kSchurStrongOneMax = 256;                // strong aggregates: up to this many groups as ONE level (level-1 path), beyond in blocks of 4 (pgo_schur.hpp)

@@ -1410,11 +1410,6 @@ __device__ __forceinline__ void ml_init_kernel_body(PgoDev D, MlHot H, double* _
     }
     if (blockIdx.x == 0 && tid == 0) { D.flags[0] = 0; D.flags[1] = 0; D.flags[2] = 0; D.flags[3] = 0; D.scal[2] = 1.; }
 }
-template <int AGG>
-__global__ __launch_bounds__(kCgBlk) void ml_init_kernel(PgoDev D, MlHot H, double* __restrict__ p0, double* __restrict__ p1, double* __restrict__ rg)
-{
-    ml_init_kernel_body<AGG>(D, H, p0, p1, rg);
-}
 
 // This file is compiled with -ffp-contract=off (two geometries of one kernel body must give the same bits): the products that matter
 // for speed say fma() themselves.
@@ -1779,13 +1774,6 @@ __device__ __forceinline__ void ml_spmv_kernel_body(PgoDev D, MlHot H, const dou
     if (blockIdx.x == 0 && tid == 0) atomicAdd(&g_stamps[47], 1ull);
 #endif
 }
-// AGG = 1: 4 waves per SIMD = two 512-lane workgroups per CU (<= 128 VGPRs; the body needs 98).  AGG = 4: 140 VGPRs, 3 waves per SIMD =
-// three 256-lane workgroups per CU (held at 128 it spilled 44 B per lane and was slower: 18.5 vs 17.3 us at 10k vertices)
-template <int AGG>
-__global__ __launch_bounds__(AGG == 1 ? 512 : 64 * kSpmvWaves4) __attribute__((amdgpu_waves_per_eu(AGG == 1 ? 4 : 3))) void ml_spmv_kernel(PgoDev D, MlHot H, const double* __restrict__ p_old, double* __restrict__ p_new, int n_part, double tol2)
-{
-    ml_spmv_kernel_body<AGG>(D, H, p_old, p_new, n_part, tol2);
-}
 constexpr int kSpmvBatchRpw = 4, kSpmvBatchWaves = 2;      // ml_spmv_batch_kernel: 8 rows = one level-1 aggregate in 128 lanes
 
 // init = 1: first application (r = b stored, exact rg in rg_old): only the preconditioner part runs.
@@ -1798,7 +1786,7 @@ constexpr int kSpmvBatchRpw = 4, kSpmvBatchWaves = 2;      // ml_spmv_batch_kern
 // memory round trip per launch instead of two (10k/50k: 12.7 -> ~9 us).  ~220 VGPRs: two workgroups per CU, enough for the <= 375
 // workgroups of such a graph.
 // VPRE (COMP, larger graphs: 12k .. 21.8k vertices): alpha and the gather-level residual estimate v = rg - alpha Sg come from
-// ml_alpha_kernel, launched in front.  Without it every one of the 400 - 680 workgroups reduces the same partials and stages the same
+// ml_alpha_lm_kernel, launched in front.  Without it every one of the 400 - 680 workgroups reduces the same partials and stages the same
 // two (with the half-aggregate parts: three) 30-KB vectors through its registers - at 20k vertices that, not the product with Y_2,
 // was most of the kernel (33 us per launch).
 constexpr int kYU = 18;
@@ -2195,15 +2183,8 @@ __device__ __forceinline__ void ml_cg_kernel_body(PgoDev D, MlHot H, const doubl
     if (blockIdx.x == 0 && tid == 0) atomicAdd(&g_stamps[31], 1ull);
 #endif
 }
-template <int AGG, bool COMP = false, bool YPRE = false, bool VPRE = false>
-__global__ __launch_bounds__(kCgBlk) __attribute__((amdgpu_waves_per_eu(COMP ? (YPRE ? 2 : 3) : 1))) void ml_cg_kernel(PgoDev D, MlHot H, const double* __restrict__ p,
-                                                      const double* __restrict__ rg_old, double* __restrict__ rg_new,
-                                                      int n_part, int init)
-{
-    ml_cg_kernel_body<AGG, COMP, YPRE, VPRE>(D, H, p, rg_old, rg_new, n_part, init);
-}
 
-// alpha = r.z / p.Ap and v = rg - alpha Sg for ml_cg_kernel<4, true, false, true>: every workgroup sums the p.Ap partials (same order,
+// alpha = r.z / p.Ap and v = rg - alpha Sg for ml_cg's VPRE variant: every workgroup sums the p.Ap partials (same order,
 // same alpha), each writes 256 entries of v; workgroup 0 leaves alpha and the breakdown flag in scal[9], scal[10].
 __device__ __forceinline__ void ml_alpha_kernel_body(PgoDev D, MlHot H, const double* __restrict__ rg_old, int n_part)
 {
@@ -2222,14 +2203,13 @@ __device__ __forceinline__ void ml_alpha_kernel_body(PgoDev D, MlHot H, const do
     if (t < n6) H.Vg[t] = rgv - alpha * sgv;
     if (blockIdx.x == 0 && tid == 0) { D.scal[9] = alpha; D.scal[10] = bad ? 1. : 0.; }
 }
-__global__ __launch_bounds__(256) void ml_alpha_kernel(PgoDev D, MlHot H, const double* __restrict__ rg_old, int n_part) { ml_alpha_kernel_body(D, H, rg_old, n_part); }
 
 // ------------------------------------------------------------------------------------------------
 // ml_cg for small graphs (<= 1280 free vertices, one level-1 aggregate per workgroup): the hierarchy above level 1
 // has been folded into the dense operator Y_1 (ml_dense_level_kernel), so the coarse correction of the own aggregate
 // is  y1 = Y_1[rows 6A..6A+5] (rg_old - alpha Sg): every operand is loaded at entry (one memory latency), the
 // restrict / top-solve / prolong walk through LDS and its barriers are gone.  Same preconditioner, same results up to
-// rounding as ml_cg_kernel<1>.
+// rounding as the walked AGG = 1 variant of ml_cg.
 // ------------------------------------------------------------------------------------------------
 // kCompU gather-level values per lane: 5 covers 6 n_1 <= 960 (<= 1280 free vertices), 8 covers 6 n_1 <= 1536 (<= 2048), 12 <= 2304 (3072), 16 <= 3072 (4096)
 template <int kCompU, bool kLds = false>
@@ -2360,11 +2340,6 @@ __device__ __forceinline__ void ml_cg_comp_kernel_body(PgoDev D, MlHot H, const 
         }
     }
 }
-template <int kCompU>
-__global__ __launch_bounds__(kCgBlk) void ml_cg_comp_kernel(PgoDev D, MlHot H, const double* __restrict__ p, const double* __restrict__ rg_old, double* __restrict__ rg_new, int n_part, int init)
-{
-    ml_cg_comp_kernel_body<kCompU>(D, H, p, rg_old, rg_new, n_part, init);
-}
 
 // ------------------------------------------------------------------------------------------------
 // launchers
@@ -2418,7 +2393,7 @@ void k_ml_sibling(const PgoDev& D, const MlDev* ml, int total_aggs, hipStream_t 
 int g_ml_rows(int nb, int agg) { return (nb + kMlFanout * agg - 1) / (kMlFanout * agg); }
 // workgroups of ml_spmv (= p.Ap partials ml_cg sums): AGG = 4 runs two half workgroups per level-2 aggregate
 int g_ml_spmv(int nb, int agg) { return agg == 1 ? g_ml_rows(nb, 1) : g_ml_rows(nb, agg) * (8 / kSpmvWaves4); }
-// dynamic LDS of ml_cg_kernel for a hierarchy (n[0..levels]) and workgroup geometry agg
+// dynamic LDS of ml_cg for a hierarchy (n[0..levels]) and workgroup geometry agg
 size_t ml_cg_lds_bytes(const int* n, int levels, int agg)
 {
     const int g = (agg == 1 || levels < 2) ? 1 : 2;
@@ -2435,89 +2410,6 @@ bool ml_fits_lds(const int* n_per_level, int levels, int agg)
     return ml_cg_lds_bytes(n_per_level, levels, agg) <= kMlLdsLimit && g_ml_spmv(n_per_level[0], agg) <= kMaxPartials;
 }
 bool ml_comp4_fits(int nb, int n2) { return ml_comp4_lds(n2) <= kMlLdsLimit && g_ml_spmv(nb, 4) <= kMaxPartials; }
-void k_ml_init(const PgoDev& D, const MlHot& ml, int agg, double* p0, double* p1, double* rg, hipStream_t s)
-{
-    if (agg == 1) hipLaunchKernelGGL(ml_init_kernel<1>, dim3(g_ml_rows(D.nb, 1)), dim3(kCgBlk), 0, s, D, ml, p0, p1, rg);
-    else hipLaunchKernelGGL(ml_init_kernel<4>, dim3(g_ml_rows(D.nb, 4)), dim3(kCgBlk), 0, s, D, ml, p0, p1, rg);
-}
-// ev_a / ev_b (profiling only): the dispatch's own start / stop timestamps
-void k_ml_spmv(const PgoDev& D, const MlHot& ml, int agg, const double* p_old, double* p_new, int n_part, double tol2, hipStream_t s,
-               hipEvent_t ev_a, hipEvent_t ev_b)
-{
-    if (ev_a) {
-        if (agg == 1) hipExtLaunchKernelGGL(ml_spmv_kernel<1>, dim3(g_ml_rows(D.nb, 1)), dim3(512), 0, s, ev_a, ev_b, 0, D, ml, p_old, p_new, n_part, tol2);
-        else hipExtLaunchKernelGGL(ml_spmv_kernel<4>, dim3(g_ml_spmv(D.nb, 4)), dim3(64 * kSpmvWaves4), 0, s, ev_a, ev_b, 0, D, ml, p_old, p_new, n_part, tol2);
-        return;
-    }
-    if (agg == 1) hipLaunchKernelGGL(ml_spmv_kernel<1>, dim3(g_ml_rows(D.nb, 1)), dim3(512), 0, s, D, ml, p_old, p_new, n_part, tol2);
-    else hipLaunchKernelGGL(ml_spmv_kernel<4>, dim3(g_ml_spmv(D.nb, 4)), dim3(64 * kSpmvWaves4), 0, s, D, ml, p_old, p_new, n_part, tol2);
-}
-hipError_t k_ml_cg(const PgoDev& D, const MlHot& ml, int agg, const double* p, const double* rg_old, double* rg_new, int n_part,
-                   int init, size_t lds, hipStream_t s, hipEvent_t ev_a, hipEvent_t ev_b)
-{
-    // largest dynamic-LDS size each kernel variant has been raised to, PER DEVICE (a function attribute is per device), under a lock
-    // (handles of several threads / devices share this table)
-    constexpr int kMaxDev = 16;
-    static size_t configured_tab[kMaxDev][5] = {};
-    static std::mutex configured_mu;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) dev = 0;
-    const bool comp4 = agg != 1 && ml.Cmat != nullptr;
-    const bool ypre = comp4 && ml.levels >= 2 && 6 * ml.n[2] <= 4 * 32 * kYU;       // the six rows of Y_2 fit the registers
-    const bool vpre = comp4 && !ypre && !init && ml.Vg != nullptr;                  // alpha and rg - alpha Sg prepared once, by ml_alpha_kernel
-    // COMP stages nothing but the gather-level vector: asking for the LDS of the full restrict / top / chain walk (52 KB at 20k
-    // vertices) held the kernel at two workgroups per CU - 625 workgroups ran in two rounds
-    if (comp4) lds = ml_comp4_lds(ml.n[2]);
-    if (lds > kMlLdsLimit) return hipErrorInvalidValue;                             // (build_ml admits no such hierarchy)
-    const int ci = agg == 1 ? 0 : (comp4 ? (ypre ? 3 : (vpre ? 4 : 2)) : 1);
-    std::unique_lock<std::mutex> cfg_lock(configured_mu);
-    size_t* configured = configured_tab[dev];
-    if (lds > configured[ci]) {
-        const void* fn = agg == 1 ? reinterpret_cast<const void*>(&ml_cg_kernel<1>)
-                                  : (comp4 ? (ypre ? reinterpret_cast<const void*>(&ml_cg_kernel<4, true, true>)
-                                                   : (vpre ? reinterpret_cast<const void*>(&ml_cg_kernel<4, true, false, true>) : reinterpret_cast<const void*>(&ml_cg_kernel<4, true>)))
-                                           : reinterpret_cast<const void*>(&ml_cg_kernel<4>));
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        configured[ci] = lds;
-    }
-    cfg_lock.unlock();
-    if (agg == 1 && ml.Cmat) {           // small graphs: composite coarse operator
-        // columns of the dense level-1 operator a lane holds: 5 (6 n_1 <= 960), 8 (<= 1536), 12 (<= 2304), 16 (<= 3072: 4096 free vertices)
-        const int cols = 6 * ml.n[1];
-        const dim3 g(g_ml_rows(D.nb, 1)), t(kCgBlk);
-#define UZL_COMP_LAUNCH(U)                                                                                                              \
-        do { if (ev_a) hipExtLaunchKernelGGL(ml_cg_comp_kernel<U>, g, t, 0, s, ev_a, ev_b, 0, D, ml, p, rg_old, rg_new, n_part, init);  \
-             else hipLaunchKernelGGL(ml_cg_comp_kernel<U>, g, t, 0, s, D, ml, p, rg_old, rg_new, n_part, init); } while (0)
-        if (cols <= 5 * kCgBlk) UZL_COMP_LAUNCH(5);
-        else if (cols <= 8 * kCgBlk) UZL_COMP_LAUNCH(8);
-        else if (cols <= 12 * kCgBlk) UZL_COMP_LAUNCH(12);
-        else UZL_COMP_LAUNCH(16);
-#undef UZL_COMP_LAUNCH
-        return hipSuccess;
-    }
-    if (ev_a) {
-        if (agg == 1) hipExtLaunchKernelGGL(ml_cg_kernel<1>, dim3(g_ml_rows(D.nb, 1)), dim3(kCgBlk), lds, s, ev_a, ev_b, 0, D, ml, p, rg_old, rg_new, n_part, init);
-        else if (ypre) hipExtLaunchKernelGGL((ml_cg_kernel<4, true, true>), dim3(g_ml_rows(D.nb, 4)), dim3(kCgBlk), lds, s, ev_a, ev_b, 0, D, ml, p, rg_old, rg_new, n_part, init);
-        else if (vpre) {
-            hipLaunchKernelGGL(ml_alpha_kernel, dim3((6 * ml.n[2] + 255) / 256), dim3(256), 0, s, D, ml, rg_old, n_part);
-            hipExtLaunchKernelGGL((ml_cg_kernel<4, true, false, true>), dim3(g_ml_rows(D.nb, 4)), dim3(kCgBlk), lds, s, ev_a, ev_b, 0, D, ml, p, rg_old, rg_new, n_part, init);
-        }
-        else if (comp4) hipExtLaunchKernelGGL((ml_cg_kernel<4, true>), dim3(g_ml_rows(D.nb, 4)), dim3(kCgBlk), lds, s, ev_a, ev_b, 0, D, ml, p, rg_old, rg_new, n_part, init);
-        else hipExtLaunchKernelGGL(ml_cg_kernel<4>, dim3(g_ml_rows(D.nb, 4)), dim3(kCgBlk), lds, s, ev_a, ev_b, 0, D, ml, p, rg_old, rg_new, n_part, init);
-        return hipSuccess;
-    }
-    if (agg == 1) hipLaunchKernelGGL(ml_cg_kernel<1>, dim3(g_ml_rows(D.nb, 1)), dim3(kCgBlk), lds, s, D, ml, p, rg_old, rg_new, n_part, init);
-    else if (ypre) hipLaunchKernelGGL((ml_cg_kernel<4, true, true>), dim3(g_ml_rows(D.nb, 4)), dim3(kCgBlk), lds, s, D, ml, p, rg_old, rg_new, n_part, init);
-    else if (vpre) {
-        hipLaunchKernelGGL(ml_alpha_kernel, dim3((6 * ml.n[2] + 255) / 256), dim3(256), 0, s, D, ml, rg_old, n_part);
-        hipLaunchKernelGGL((ml_cg_kernel<4, true, false, true>), dim3(g_ml_rows(D.nb, 4)), dim3(kCgBlk), lds, s, D, ml, p, rg_old, rg_new, n_part, init);
-    }
-    else if (comp4) hipLaunchKernelGGL((ml_cg_kernel<4, true>), dim3(g_ml_rows(D.nb, 4)), dim3(kCgBlk), lds, s, D, ml, p, rg_old, rg_new, n_part, init);
-    else hipLaunchKernelGGL(ml_cg_kernel<4>, dim3(g_ml_rows(D.nb, 4)), dim3(kCgBlk), lds, s, D, ml, p, rg_old, rg_new, n_part, init);
-    return hipSuccess;
-}
-
 
 // ------------------------------------------------------------------------------------------------
 // slot twins of the device-resident LM loop (pgo_types.hpp: LmSlot / LmDev; uzl_pgo_lm.hip): graph = blockIdx.z, arguments from its
@@ -2657,11 +2549,18 @@ void kl_ml_trial(const LmSlot* sl, const LmShape& sh, int which, hipStream_t s)
     if (sh.ns_steps == 0) hipLaunchKernelGGL(ml_cmat32_lm_kernel, dim3((unsigned)((work32 + kBlk - 1) / kBlk), 1, B), dim3(kBlk), 0, s, sl, which, cl);
 }
 
-// ---- PCG: init + the two iteration kernels.  SLOT = `const LmSlot*` (blockIdx.z picks the graph) or `LmSlot` BY VALUE for a pass of
-// one graph - the slot then sits in the kernel-argument segment like the by-value kernels' arguments: no pointer hop in front of the
-// first loads of kernels that are a chain of round trips.
+// ---- PCG: init + the two iteration kernels, for both LM loops.  SLOT = `const LmSlot*` (blockIdx.z picks the graph), `LmSlot` BY VALUE
+// for a pass of one graph, or `HostSlot` (by value) for a solve of the host-driven loop - a slot by value sits in the kernel-argument
+// segment: no pointer hop in front of the first loads of kernels that are a chain of round trips.
 __device__ __forceinline__ const LmSlot& slot_of(const LmSlot* __restrict__ slots) { return slots[blockIdx.z]; }
 __device__ __forceinline__ const LmSlot& slot_of(const LmSlot& slot) { return slot; }
+__device__ __forceinline__ const LmSlot& slot_of(const HostSlot& hs) { return hs.S; }
+// what these kernels read of the graph's LM state, through `lm`: the hierarchy copy the PCG applies (ix), pcg_tol^2 (tol2), and whether
+// its solve starts in this pass (init_due).  A HostSlot has no LM state behind it: it carries ix and tol2 itself, and its init always runs
+template <class SLOT> __device__ __forceinline__ const LmDev* state_of(const LmSlot& S, const SLOT&) { return S.lm; }
+__device__ __forceinline__ const HostSlot* state_of(const LmSlot&, const HostSlot& hs) { return &hs; }
+__device__ __forceinline__ bool init_due(const LmDev* lm) { return lm->phase == kLmSolve && lm->init_pass == lm->pass; }
+__device__ __forceinline__ bool init_due(const HostSlot*) { return true; }
 
 // The hot subset of hierarchy copy `ix`.  Both copies sit in one arena, `copy_stride` bytes apart, and share every size: copy 0's
 // struct with its arena pointers moved - an add behind the ix load, where indexing hot[] with ix would be a second, dependent load of the slot
@@ -2684,16 +2583,19 @@ template <int AGG, class SLOT>
 __global__ __launch_bounds__(kCgBlk) void ml_init_lm_kernel(const SLOT slots)
 {
     const LmSlot& S = slot_of(slots);
-    const LmDev* lm = S.lm;
-    if (lm->phase != kLmSolve || lm->init_pass != lm->pass || (int)blockIdx.x >= S.g_rows) return;
+    const auto* lm = state_of(S, slots);
+    if (!init_due(lm) || (int)blockIdx.x >= S.g_rows) return;
     ml_init_kernel_body<AGG>(S.Dp, hot_of(S, lm->ix), S.pbuf[0], S.pbuf[1], rg_of(S, lm->ix, 0));
 }
-// PCG iteration i of a replay (parity = i & 1): p_old = pbuf[parity], p_new = pbuf[parity ^ 1]; a no-op once flags[0] is set
+// PCG iteration i of a replay (parity = i & 1): p_old = pbuf[parity], p_new = pbuf[parity ^ 1]; a no-op once flags[0] is set.
+// 8 waves (AGG = 1; AGG = 4 up to two workgroups per CU): 4 waves per SIMD = two 512-lane workgroups per CU (<= 128 VGPRs; the AGG = 1
+// body needs 98).  AGG = 4 on 4 waves: 140 VGPRs, 3 waves per SIMD = three 256-lane workgroups per CU (held at 128 it spilled 44 B per
+// lane and was slower: 18.5 vs 17.3 us at 10k vertices)
 template <int AGG, int RPW, int WAVES, class SLOT>
 __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(WAVES == 8 ? 4 : 3))) void ml_spmv_lm_kernel(const SLOT slots, int parity)
 {
     const LmSlot& S = slot_of(slots);
-    const LmDev* lm = S.lm;
+    const auto* lm = state_of(S, slots);
     ml_spmv_kernel_body<AGG, RPW, WAVES>(S.Dp, hot_of(S, lm->ix), S.pbuf[parity], S.pbuf[parity ^ 1], S.g_rows, lm->tol2);
 }
 // init = 1: the first application of the preconditioner (r = b), in the pass that starts the solve
@@ -2702,10 +2604,10 @@ __global__ __launch_bounds__(kCgBlk) void ml_cg_comp_lm_kernel(const SLOT slots,
 {
     const LmSlot& S = slot_of(slots);
     if ((int)blockIdx.x >= S.g_rows) return;                 // (a batch launches the largest graph's grid)
-    const LmDev* lm = S.lm;
+    const auto* lm = state_of(S, slots);
     const int ix = lm->ix;
     if (init) {
-        if (lm->phase != kLmSolve || lm->init_pass != lm->pass) return;
+        if (!init_due(lm)) return;
         ml_cg_comp_kernel_body<kCompU, kLds>(S.Dp, hot_of(S, ix), S.pbuf[0], rg_of(S, ix, 0), rg_of(S, ix, 1), 0, 1);
     } else ml_cg_comp_kernel_body<kCompU, kLds>(S.Dp, hot_of(S, ix), S.pbuf[parity ^ 1], rg_of(S, ix, parity ^ 1), rg_of(S, ix, parity), S.g_spmv, 0);
 }
@@ -2714,10 +2616,10 @@ __global__ __launch_bounds__(kCgBlk) __attribute__((amdgpu_waves_per_eu(COMP ? (
 {
     const LmSlot& S = slot_of(slots);
     if ((int)blockIdx.x >= S.g_rows) return;
-    const LmDev* lm = S.lm;
+    const auto* lm = state_of(S, slots);
     const int ix = lm->ix;
     if (init) {
-        if (lm->phase != kLmSolve || lm->init_pass != lm->pass) return;
+        if (!init_due(lm)) return;
         ml_cg_kernel_body<AGG, COMP, YPRE, false>(S.Dp, hot_of(S, ix), S.pbuf[0], rg_of(S, ix, 0), rg_of(S, ix, 1), 0, 1);
     } else ml_cg_kernel_body<AGG, COMP, YPRE, VPRE>(S.Dp, hot_of(S, ix), S.pbuf[parity ^ 1], rg_of(S, ix, parity ^ 1), rg_of(S, ix, parity), S.g_spmv, 0);
 }
@@ -2725,14 +2627,14 @@ template <class SLOT>
 __global__ __launch_bounds__(256) void ml_alpha_lm_kernel(const SLOT slots, int parity)
 {
     const LmSlot& S = slot_of(slots);
-    const LmDev* lm = S.lm;
+    const auto* lm = state_of(S, slots);
     ml_alpha_kernel_body(S.Dp, hot_of(S, lm->ix), rg_of(S, lm->ix, parity ^ 1), S.g_spmv);
 }
 
 // raises the dynamic-LDS limit of an ml_cg variant once per device (a function attribute is per device)
 static hipError_t lm_cg_lds(const void* fn, int variant_ix, size_t lds)
 {
-    constexpr int kMaxDev = 16, kVar = 16;
+    constexpr int kMaxDev = 16, kVar = 24;
     static size_t configured_tab[kMaxDev][kVar] = {};
     static std::mutex mu;
     int dev = 0;
@@ -2745,64 +2647,54 @@ static hipError_t lm_cg_lds(const void* fn, int variant_ix, size_t lds)
     }
     return hipSuccess;
 }
+// a launch that takes the dispatch's own start / stop timestamps when ev_a / ev_b are given (profiling only)
+template <class K, class... A>
+static void launch(K kernel, dim3 g, dim3 t, size_t lds, hipStream_t s, hipEvent_t ev_a, hipEvent_t ev_b, A... args)
+{
+    if (ev_a) hipExtLaunchKernelGGL(kernel, g, t, (uint32_t)lds, s, ev_a, ev_b, 0, args...);
+    else hipLaunchKernelGGL(kernel, g, t, lds, s, args...);
+}
 
 // the ml_cg launch of iteration parity `parity` (init = 1: first application) for the shape's variant; SLOT as above
-// (ev_a / ev_b, profiling only: the dispatch's own start / stop timestamps - the throughput-geometry variants a batch runs)
 template <class SLOT>
 static hipError_t kl_ml_cg_t(SLOT sl, const LmShape& sh, int parity, int init, hipStream_t s, hipEvent_t ev_a = nullptr, hipEvent_t ev_b = nullptr)
 {
-    constexpr bool kPtr = std::is_pointer<SLOT>::value;
+    constexpr int kSlotKind = std::is_pointer<SLOT>::value ? 0 : (std::is_same<SLOT, LmSlot>::value ? 1 : 2);
     const dim3 g(sh.g_rows, 1, sh.nslots), t(kCgBlk);
-    size_t lds = (size_t)sh.cg_lds;
+    const size_t lds = (size_t)sh.cg_lds;
+    if (lds > kMlLdsLimit) return hipErrorInvalidValue;                             // (build_ml admits no such hierarchy)
+    auto cg = [&](auto kernel) {
+        const hipError_t e = lm_cg_lds(reinterpret_cast<const void*>(kernel), 8 * kSlotKind + sh.cg_variant, lds);
+        if (e == hipSuccess) launch(kernel, g, t, lds, s, ev_a, ev_b, sl, parity, init);
+        return e;
+    };
     switch (sh.cg_variant) {
-    case kCgComp1:
-#define UZL_LM_COMP(U, LDS) do { if (ev_a) hipExtLaunchKernelGGL((ml_cg_comp_lm_kernel<U, LDS, SLOT>), g, t, 0, s, ev_a, ev_b, 0, sl, parity, init); \
-                                 else hipLaunchKernelGGL((ml_cg_comp_lm_kernel<U, LDS, SLOT>), g, t, 0, s, sl, parity, init); } while (0)
-        if (sh.batch_geometry) { if (sh.comp_u <= 5) UZL_LM_COMP(5, true); else UZL_LM_COMP(8, true); }
-        else if (sh.comp_u <= 5) UZL_LM_COMP(5, false);
-        else if (sh.comp_u <= 8) UZL_LM_COMP(8, false);
-        else if (sh.comp_u <= 12) UZL_LM_COMP(12, false);
-        else UZL_LM_COMP(16, false);
-#undef UZL_LM_COMP
-        return hipSuccess;
-    case kCgPlain1: {
-        const hipError_t e = lm_cg_lds(reinterpret_cast<const void*>(&ml_cg_lm_kernel<1, false, false, false, SLOT>), kPtr ? 0 : 8, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((ml_cg_lm_kernel<1, false, false, false, SLOT>), g, t, lds, s, sl, parity, init);
+    case kCgComp1: {                                                                  // (no dynamic LDS)
+        const int u = sh.comp_u;
+        auto kernel = sh.batch_geometry ? (u <= 5 ? ml_cg_comp_lm_kernel<5, true, SLOT> : ml_cg_comp_lm_kernel<8, true, SLOT>)
+                    : u <= 5 ? ml_cg_comp_lm_kernel<5, false, SLOT> : u <= 8 ? ml_cg_comp_lm_kernel<8, false, SLOT>
+                    : u <= 12 ? ml_cg_comp_lm_kernel<12, false, SLOT> : ml_cg_comp_lm_kernel<16, false, SLOT>;
+        launch(kernel, g, t, 0, s, ev_a, ev_b, sl, parity, init);
         return hipSuccess; }
-    case kCgPlain4: {
-        const hipError_t e = lm_cg_lds(reinterpret_cast<const void*>(&ml_cg_lm_kernel<4, false, false, false, SLOT>), kPtr ? 1 : 9, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((ml_cg_lm_kernel<4, false, false, false, SLOT>), g, t, lds, s, sl, parity, init);
-        return hipSuccess; }
-    case kCgComp4: {
-        const hipError_t e = lm_cg_lds(reinterpret_cast<const void*>(&ml_cg_lm_kernel<4, true, false, false, SLOT>), kPtr ? 2 : 10, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((ml_cg_lm_kernel<4, true, false, false, SLOT>), g, t, lds, s, sl, parity, init);
-        return hipSuccess; }
-    case kCgComp4Ypre: {
-        const hipError_t e = lm_cg_lds(reinterpret_cast<const void*>(&ml_cg_lm_kernel<4, true, true, false, SLOT>), kPtr ? 3 : 11, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((ml_cg_lm_kernel<4, true, true, false, SLOT>), g, t, lds, s, sl, parity, init);
-        return hipSuccess; }
-    case kCgComp4Vpre: {
-        const hipError_t e = lm_cg_lds(reinterpret_cast<const void*>(&ml_cg_lm_kernel<4, true, false, true, SLOT>), kPtr ? 4 : 12, lds);
-        if (e != hipSuccess) return e;
-        // alpha and rg - alpha Sg prepared once by ml_alpha_kernel (not with r = b: the init application takes the plain COMP path)
+    case kCgPlain1: return cg(ml_cg_lm_kernel<1, false, false, false, SLOT>);
+    case kCgPlain4: return cg(ml_cg_lm_kernel<4, false, false, false, SLOT>);
+    case kCgComp4: return cg(ml_cg_lm_kernel<4, true, false, false, SLOT>);
+    case kCgComp4Ypre: return cg(ml_cg_lm_kernel<4, true, true, false, SLOT>);
+    case kCgComp4Vpre:
+        // alpha and rg - alpha Sg prepared once by ml_alpha_lm_kernel (not with r = b: the init application takes the plain COMP path)
         if (!init) hipLaunchKernelGGL((ml_alpha_lm_kernel<SLOT>), dim3((6 * sh.n_lv[2] + 255) / 256, 1, sh.nslots), dim3(256), 0, s, sl, parity);
-        hipLaunchKernelGGL((ml_cg_lm_kernel<4, true, false, true, SLOT>), g, t, lds, s, sl, parity, init);
-        return hipSuccess; }
+        return cg(ml_cg_lm_kernel<4, true, false, true, SLOT>);
     }
     return hipErrorInvalidValue;
 }
 template <class SLOT>
 static void kl_ml_spmv_t(SLOT sl, const LmShape& sh, int parity, hipStream_t s, hipEvent_t ev_a = nullptr, hipEvent_t ev_b = nullptr)
 {
-    if (sh.batch_geometry && ev_a) hipExtLaunchKernelGGL((ml_spmv_lm_kernel<1, kSpmvBatchRpw, kSpmvBatchWaves, SLOT>), dim3(sh.g_spmv, 1, sh.nslots), dim3(64 * kSpmvBatchWaves), 0, s, ev_a, ev_b, 0, sl, parity);
-    else if (sh.batch_geometry) hipLaunchKernelGGL((ml_spmv_lm_kernel<1, kSpmvBatchRpw, kSpmvBatchWaves, SLOT>), dim3(sh.g_spmv, 1, sh.nslots), dim3(64 * kSpmvBatchWaves), 0, s, sl, parity);
+    const dim3 g(sh.g_spmv, 1, sh.nslots);
+    if (sh.batch_geometry) launch(ml_spmv_lm_kernel<1, kSpmvBatchRpw, kSpmvBatchWaves, SLOT>, g, dim3(64 * kSpmvBatchWaves), 0, s, ev_a, ev_b, sl, parity);
     else if (sh.agg == 1) {
         // one row per wave, 8 waves (two rows per wave on 4 waves: the same bits, config 2 5.68 -> 6.06 ms)
-        hipLaunchKernelGGL((ml_spmv_lm_kernel<1, 1, 8, SLOT>), dim3(sh.g_spmv, 1, sh.nslots), dim3(512), 0, s, sl, parity);
+        launch(ml_spmv_lm_kernel<1, 1, 8, SLOT>, g, dim3(512), 0, s, ev_a, ev_b, sl, parity);
     }
     else {
         // rows per wave of the AGG = 4 geometry (16 rows per workgroup; the same bits either way).  Up to two such workgroups per CU the
@@ -2810,18 +2702,17 @@ static void kl_ml_spmv_t(SLOT sl, const LmShape& sh, int parity, hipStream_t s, 
         // 35.8 -> 34.2); beyond, four rows per wave keep three workgroups on a CU (10k / 50k: 626 workgroups in one round; 47.0 -> 49.2 ms
         // at two rows per wave)
         static const int two_per_cu = [] { int dev = 0, cu = 256; if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev); return 2 * cu; }();
-        if (sh.g_spmv <= two_per_cu) hipLaunchKernelGGL((ml_spmv_lm_kernel<4, 2, 8, SLOT>), dim3(sh.g_spmv, 1, sh.nslots), dim3(512), 0, s, sl, parity);
-        else hipLaunchKernelGGL((ml_spmv_lm_kernel<4, 4, kSpmvWaves4, SLOT>), dim3(sh.g_spmv, 1, sh.nslots), dim3(64 * kSpmvWaves4), 0, s, sl, parity);
+        if (sh.g_spmv <= two_per_cu) launch(ml_spmv_lm_kernel<4, 2, 8, SLOT>, g, dim3(512), 0, s, ev_a, ev_b, sl, parity);
+        else launch(ml_spmv_lm_kernel<4, 4, kSpmvWaves4, SLOT>, g, dim3(64 * kSpmvWaves4), 0, s, ev_a, ev_b, sl, parity);
     }
 }
+// x = 0, r = b, flags and iteration count cleared (the first application of the preconditioner is kl_ml_cg_t with init = 1)
 template <class SLOT>
-static hipError_t kl_ml_init_t(SLOT sl, const LmShape& sh, hipStream_t s)
+static void kl_ml_init_t(SLOT sl, const LmShape& sh, hipStream_t s, hipEvent_t ev_a = nullptr, hipEvent_t ev_b = nullptr)
 {
-    if (sh.agg == 1) hipLaunchKernelGGL((ml_init_lm_kernel<1, SLOT>), dim3(sh.g_rows, 1, sh.nslots), dim3(kCgBlk), 0, s, sl);
-    else hipLaunchKernelGGL((ml_init_lm_kernel<4, SLOT>), dim3(sh.g_rows, 1, sh.nslots), dim3(kCgBlk), 0, s, sl);
-    return kl_ml_cg_t<SLOT>(sl, sh, 0, 1, s);
+    launch(sh.agg == 1 ? ml_init_lm_kernel<1, SLOT> : ml_init_lm_kernel<4, SLOT>, dim3(sh.g_rows, 1, sh.nslots), dim3(kCgBlk), 0, s, ev_a, ev_b, sl);
 }
-// which ml_cg kernel serves a hierarchy (the choice k_ml_cg makes per launch), and its dynamic LDS
+// which ml_cg kernel serves a hierarchy, and its dynamic LDS: the one place the variant is chosen
 void ml_cg_variant(const MlHot& ml, int agg, size_t lds_full, int32_t* variant, int32_t* comp_u, uint64_t* lds)
 {
     *comp_u = 0; *lds = lds_full;
@@ -2838,26 +2729,35 @@ void ml_cg_variant(const MlHot& ml, int agg, size_t lds_full, int32_t* variant, 
     *variant = ypre ? kCgComp4Ypre : (ml.Vg != nullptr ? kCgComp4Vpre : kCgComp4);
 }
 // x = 0, r = b, first application of the preconditioner - for the graphs whose solve starts in this pass.  by_value: the pass has one
-// graph and `host_slot` is its slot (the device table `sl` is what every other twin reads)
-hipError_t kl_ml_init(const LmSlot* sl, const LmSlot* host_slot, const LmShape& sh, hipStream_t s)
+// graph and `by_value` is its slot (the device table `sl` is what every other twin reads)
+hipError_t kl_ml_init(const LmSlot* sl, const LmSlot* by_value, const LmShape& sh, hipStream_t s)
 {
-    if (host_slot && sh.nslots == 1) return kl_ml_init_t<LmSlot>(*host_slot, sh, s);
-    return kl_ml_init_t<const LmSlot*>(sl, sh, s);
+    if (by_value && sh.nslots == 1) { kl_ml_init_t<LmSlot>(*by_value, sh, s); return kl_ml_cg_t<LmSlot>(*by_value, sh, 0, 1, s); }
+    kl_ml_init_t<const LmSlot*>(sl, sh, s);
+    return kl_ml_cg_t<const LmSlot*>(sl, sh, 0, 1, s);
 }
 // PCG iterations first .. first + n - 1 of a solve (iteration i: p_old = pbuf[i & 1], p_new = pbuf[(i & 1) ^ 1]).  ev (profiling only, may
 // be null): 4 events per iteration - spmv start / stop, cg start / stop (dispatch timestamps; the batch's kernels)
-hipError_t kl_ml_pcg_its(const LmSlot* sl, const LmSlot* host_slot, const LmShape& sh, int first, int n, hipStream_t s, hipEvent_t* ev)
+hipError_t kl_ml_pcg_its(const LmSlot* sl, const LmSlot* by_value, const LmShape& sh, int first, int n, hipStream_t s, hipEvent_t* ev)
 {
-    const bool by_value = host_slot && sh.nslots == 1 && !ev;
+    const bool one = by_value && sh.nslots == 1 && !ev;
     for (int q = 0; q < n; q++) {
         const int par = (first + q) & 1;
         hipError_t e;
         if (ev) { kl_ml_spmv_t<const LmSlot*>(sl, sh, par, s, ev[4 * q], ev[4 * q + 1]); e = kl_ml_cg_t<const LmSlot*>(sl, sh, par, 0, s, ev[4 * q + 2], ev[4 * q + 3]); }
-        else if (by_value) { kl_ml_spmv_t<LmSlot>(*host_slot, sh, par, s); e = kl_ml_cg_t<LmSlot>(*host_slot, sh, par, 0, s); }
+        else if (one) { kl_ml_spmv_t<LmSlot>(*by_value, sh, par, s); e = kl_ml_cg_t<LmSlot>(*by_value, sh, par, 0, s); }
         else { kl_ml_spmv_t<const LmSlot*>(sl, sh, par, s); e = kl_ml_cg_t<const LmSlot*>(sl, sh, par, 0, s); }
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+// the host-driven loop (uzl_pgo.hip): the init kernel, and the two launches of a PCG iteration one by one - a sharded solve all-reduces
+// A p between them, a profiled one times each
+void kl_ml_pcg_init(const HostSlot& hs, const LmShape& sh, hipStream_t s) { kl_ml_init_t<HostSlot>(hs, sh, s); }
+void kl_ml_spmv(const HostSlot& hs, const LmShape& sh, int parity, hipStream_t s, hipEvent_t ev_a, hipEvent_t ev_b) { kl_ml_spmv_t<HostSlot>(hs, sh, parity, s, ev_a, ev_b); }
+hipError_t kl_ml_cg(const HostSlot& hs, const LmShape& sh, int parity, int init, hipStream_t s, hipEvent_t ev_a, hipEvent_t ev_b)
+{
+    return kl_ml_cg_t<HostSlot>(hs, sh, parity, init, s, ev_a, ev_b);
 }
 
 }  // namespace uzl

@@ -59,7 +59,7 @@ struct PgoDev {
     double* part_c;          // [kMaxPartials] block partials (max |H_jj|)
     double* scal;            // [16]: 0 rz, 1 rz threshold, 2 rz_prev, 3 lambda, 4 chi2, 5 scale, 6 diagmax, 7 |r|^2 / |b|^2 after PCG,
                              //       8 factor on pcg_tol^2 for this LM iteration's solves (host: do_optimize), 9 alpha and 10 breakdown of the current PCG
-                             //       iteration (ml_alpha_kernel -> ml_cg_kernel); 11 r.z at the last progress check (first: of r_0), 12 / 13 the
+                             //       iteration (ml_alpha_lm_kernel -> ml_cg_lm_kernel); 11 r.z at the last progress check (first: of r_0), 12 / 13 the
                              //       step accuracy asked for [m] / [rad], 14 |b|^2 and 15 the movement of x over the last look's window in units of 12 / 13 (multilevel path; block-Jacobi path: 14 / 15 the estimates in m / rad);
                              //       0..7 go back to the host
     int32_t* flags;          // [4]: 0 done, 1 iterations, 2 breakdown, 3 this iteration's ml_cg leaves the stop test's partials (set by ml_spmv)
@@ -141,7 +141,7 @@ struct MlHot {
     int32_t c32_stride;                    // workgroup A; stride = 6 n_cl rounded up to 4, pad = 0).  A preconditioner needs no more, the
     int32_t c32_pad;                       // operator is still one fixed linear map per solve, and it is the kernels' largest stream.
     double* Sg;                            // [n_g][6] restriction of A p at the gather level g = min(2, levels) (gather level 2: [n_2][6][2], see sg_at)
-    double* Vg;                            // [6 n_2] gather-level residual estimate rg - alpha Sg prepared by ml_alpha_kernel (graphs of 12k .. 21.8k vertices)
+    double* Vg;                            // [6 n_2] gather-level residual estimate rg - alpha Sg prepared by ml_alpha_lm_kernel (graphs of 12k .. 21.8k vertices)
 };
 
 constexpr int kBatchMax = 256;      // graphs per uzl_pgo_batch
@@ -234,6 +234,14 @@ struct LmSlot {
     double* pose[2];
     int32_t g_edges, g_asm, g_oplus, g_rows, g_spmv, red, pad0, pad1;      // grids (= partial counts) of this graph's launches; red: Schur-reduced
     int64_t copy_stride;                       // bytes from an array of hierarchy copy 0 to the same array of copy 1 (one arena, two halves)
+};
+// the slot of a solve of the host-driven loop (uzl_pgo.hip), BY VALUE to the PCG slot twins: there is no LmDev behind it (S.lm is null,
+// S.D / S.Dp carry the handle's own flags), so what those kernels read from one comes along - the hierarchy copy the PCG applies and
+// pcg_tol^2 - and the init kernel always runs
+struct HostSlot {
+    LmSlot S;
+    int32_t ix, pad0;
+    double tol2;
 };
 
 // launch geometry of a pass: what the host needs besides the slot table (one structure, or the common shape of a batch)

@@ -251,7 +251,7 @@ void build_ml(uzl_pgo* h, const std::vector<int32_t>& row_ptr0, const std::vecto
 {
     h->ml_levels = 0; h->ml_n.assign(1, nb); h->ml_nslots.assign(1, nslots); h->ml_chunks.assign(1, 0); h->ml_inner_aggs = 0;
     if (h->cfg.preconditioner == 0 || nb <= kMlTopMax) return;
-    // Up to here the level-1 dense operator applies (6 n_1 <= 3072: ml_cg_comp_kernel<16>); above, AGG = 4 with the level-2 one.  Its
+    // Up to here the level-1 dense operator applies (6 n_1 <= 3072: ml_cg_comp_lm_kernel<16, ...>); above, AGG = 4 with the level-2 one.  Its
     // rebuild (Newton-Schulz GEMMs, n^3) outgrows what the exact level-1 solve saves in PCG iterations between 3000 and 4000 vertices on
     // loopy graphs (>= 3 edges per vertex: 3000/12000 20.6 -> 18.3 ms, 4000/16000 24.5 -> 26.3 ms) and later on sparse ones - the shape of a
     // Schur-reduced online graph (4000/6000 26.0 -> 17.2 ms; config 5's last solve 2328 -> 1288 PCG iterations).
@@ -261,7 +261,7 @@ void build_ml(uzl_pgo* h, const std::vector<int32_t>& row_ptr0, const std::vecto
     h->ml_fan.assign(1, 1);
     // composite path: one aggregate per workgroup, at least two coarse levels, 6 n_1 <= 960 (<= 1280 free vertices)
     // large graphs (AGG = 4, gather level 2): the same construction one level up - the hierarchy above level 2 as one dense
-    // operator that ml_cg_kernel<4> applies instead of its LDS walk (measured 733 -> 332 ms at 20k / 100k, the rebuild's
+    // operator that ml_cg_lm_kernel<4, true, ...> applies instead of its LDS walk (measured 733 -> 332 ms at 20k / 100k, the rebuild's
     // Newton-Schulz GEMMs take 7 ms there).  6 n_2 <= 18432 - the cap was 4096 (21.8k vertices)
     // until round 5, and a 30k / 150k graph took 2.39 s (11.9 k PCG iterations on the walked hierarchy) where it takes 0.32 s with the
     // operator (1.8 k), 40k / 200k 5.13 -> 0.62 s, 50k / 250k 10.9 -> 1.56 s (tests/diag/big_graphs.py; at n = 7500 a GEMM is 10 ms, half of
@@ -403,7 +403,7 @@ void build_ml(uzl_pgo* h, const std::vector<int32_t>& row_ptr0, const std::vecto
     std::vector<size_t> geo_sub((size_t)L + 1, 0);
     for (int l = 1; l <= L; l++) { geo_sub[l] = geo_blob_doubles; geo_blob_doubles += (size_t)std::max(h->ml_n[l], 1) * 3; }
     const size_t o_geo_blob = take(geo_blob_doubles * 8 + 64);     // ml_cg copies levels g..L-1 with one linear loop
-    const bool comp1 = h->ml_agg == 1 && L >= 2 && 6 * h->ml_n[1] <= 3072;     // ml_cg_comp_kernel<5> / <8> / <12> / <16>
+    const bool comp1 = h->ml_agg == 1 && L >= 2 && 6 * h->ml_n[1] <= 3072;     // ml_cg_comp_lm_kernel<5> / <8> / <12> / <16>
     const bool comp4 = comp4_here;                  // (one predicate: the admission test above)
     h->ml_comp = comp1 || comp4;
     h->ml_cl = comp1 ? 1 : (comp4 ? 2 : 0);
@@ -423,7 +423,7 @@ void build_ml(uzl_pgo* h, const std::vector<int32_t>& row_ptr0, const std::vecto
     const size_t nsq = h->ml_mult ? (size_t)(6 * h->ml_n[cl]) * (size_t)(6 * h->ml_n[cl]) * 8 : 0;     // also the scratch of the levels above cl
     const size_t o_nsT = take(nsq), o_nsX = take(nsq);
     const int c32_stride = h->ml_comp ? ((6 * h->ml_n[cl] + 3) & ~3) : 0;
-    const size_t o_c32 = take(h->ml_comp ? (size_t)(6 * h->ml_n[cl]) * c32_stride * 4 + 16384 : 0);      // f32 copy of Y_cl: what the PCG kernels read (+ slack: ml_cg_kernel<4, true, true> prefetches 18 x 512 B per row unconditionally)
+    const size_t o_c32 = take(h->ml_comp ? (size_t)(6 * h->ml_n[cl]) * c32_stride * 4 + 16384 : 0);      // f32 copy of Y_cl: what the PCG kernels read (+ slack: ml_cg_lm_kernel<4, true, true, ...> prefetches 18 x 512 B per row unconditionally)
     // slot ranges by parent aggregate, for every level the multiplicative cycle is built at (cl .. L-1): [n_l*n_{l+1}] begin | end
     std::vector<std::vector<int32_t>> grp((size_t)L + 1);
     std::vector<size_t> o_grp((size_t)L + 1, 0);
@@ -871,6 +871,20 @@ void build_structure(uzl_pgo* h)
 }  // namespace uzl
 namespace {
 
+// the multilevel PCG kernels' slot for this handle: its slot (the handle's own flags; rebuilt with the structure - the additive fallback
+// bumps structure_gen when it swaps hot.Cmat), the hierarchy copy in use and pcg_tol^2.  Launch geometry: h->ml_shape
+HostSlot host_slot(uzl_pgo* h)
+{
+    if (h->ml_slot_gen != h->structure_gen) {
+        h->ml_slot = make_slot(h, nullptr, nullptr);
+        h->ml_shape = make_shape({h}, 1, false);
+        h->ml_slot_gen = h->structure_gen;
+    }
+    HostSlot hs;
+    hs.S = h->ml_slot; hs.ix = h->ml_ix; hs.pad0 = 0; hs.tol2 = h->cfg.pcg_tol * h->cfg.pcg_tol;
+    return hs;
+}
+
 // enqueue `pairs` x 2 PCG iterations (p0 -> p1 -> p0); kernels no-op once the device `done` flag is set
 void enqueue_pcg_pairs(uzl_pgo* h, int pairs, bool timed)
 {
@@ -878,7 +892,8 @@ void enqueue_pcg_pairs(uzl_pgo* h, int pairs, bool timed)
     const PgoDev& D = h->Dp;
     const double tol2 = h->cfg.pcg_tol * h->cfg.pcg_tol;
     const bool ml = h->ml_levels > 0;
-    const int ga = ml ? g_ml_spmv(D.nb, h->ml_agg) : g_pcg_spmv(D.nb), gu = ml ? g_ml_rows(D.nb, h->ml_agg) : g_pcg_update(D.nb);   // partials written by spmv / by cg
+    const HostSlot hs = ml ? host_slot(h) : HostSlot{};
+    const int ga = g_pcg_spmv(D.nb), gu = g_pcg_update(D.nb);                     // block-Jacobi: partials written by spmv / by update
     double* pb[2] = {h->pbuf[0], h->pbuf[1]};
     auto progress = [&]() {                                                         // how far is x from settled: the stop test (pgo_kernels.hip)
         if (timed) h->timer.begin("pcg_progress", s);
@@ -892,11 +907,11 @@ void enqueue_pcg_pairs(uzl_pgo* h, int pairs, bool timed)
         hipEvent_t ea = nullptr, eb = nullptr;
         if (ml) {
             if (timed) h->timer.pair("pcg_spmv", &ea, &eb);                      // dispatch timestamps: agree with rocprofv3
-            k_ml_spmv(D, h->mlb[h->ml_ix].hot, h->ml_agg, po, pn, gu, tol2, s, ea, eb);
+            kl_ml_spmv(hs, h->ml_shape, i & 1, s, ea, eb);
             shard_allreduce(h, D.ap, h->iter_span);                              // the one exchange per PCG iteration
             ea = eb = nullptr;
             if (timed) h->timer.pair("ml_cg", &ea, &eb);
-            UZL_HIP(k_ml_cg(D, h->mlb[h->ml_ix].hot, h->ml_agg, pn, h->mlb[h->ml_ix].rg[(i & 1) ^ 1], h->mlb[h->ml_ix].rg[i & 1], ga, 0, h->ml_lds, s, ea, eb));
+            UZL_HIP(kl_ml_cg(hs, h->ml_shape, i & 1, 0, s, ea, eb));
         } else {
             if (timed) h->timer.begin("pcg_spmv", s);
             k_pcg_spmv(D, po, pn, gu, tol2, s);
@@ -963,9 +978,9 @@ int pcg_solve(uzl_pgo* h, bool* converged)
             h->ml_trial_setup = false;
             h->mlb[h->ml_ix].lambda_setup = h->lambda_now;
         }
-        uzl_pgo::MlBuf& B = h->mlb[h->ml_ix];
-        { Timed t(h, "pcg_init"); k_ml_init(D, B.hot, h->ml_agg, h->pbuf[0], h->pbuf[1], B.rg[0], s); }
-        { Timed t(h, "ml_cg"); UZL_HIP(k_ml_cg(D, B.hot, h->ml_agg, h->pbuf[0], B.rg[0], B.rg[1], 0, 1, h->ml_lds, s)); }
+        const HostSlot hs = host_slot(h);
+        { Timed t(h, "pcg_init"); kl_ml_pcg_init(hs, h->ml_shape, s); }
+        { Timed t(h, "ml_cg"); UZL_HIP(kl_ml_cg(hs, h->ml_shape, 0, 1, s)); }
     } else {
         { Timed t(h, "precond"); k_precond(D, s); }
         Timed t(h, "pcg_init"); k_pcg_init(D, h->pbuf[0], h->pbuf[1], s);
@@ -1915,10 +1930,10 @@ extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_reduced(uzl_pgo* h, double lambda, 
 // One application of the PCG's operators to x, on the system the PCG iterates on (the full one, or the reduced one in its numbering: x, y
 // [nb_sys][6]) for this lambda (< 0: lambda_init), after the set-up an LM trial makes (linearisation, Schur reduction, preconditioner
 // numeric and lambda-dependent parts, set_lambda).  The fused kernels are driven in a state where their fused part is exact:
-//   op 0, y = (A + lambda I) x: the PCG's init kernel (k_ml_init / k_precond + k_pcg_init: flags and iteration count cleared, so beta = 0),
+//   op 0, y = (A + lambda I) x: the PCG's init kernel (kl_ml_pcg_init / k_precond + k_pcg_init: flags and iteration count cleared, so beta = 0),
 //         then x written into z and the iteration kernel run with the zero previous direction the init left: it forms p = z + 0 p_old = x
 //         and y = A p (ml_spmv / pcg_spmv, D.ap);
-//   op 1, y = M^-1 x: the right-hand side replaced by x (and restored afterwards), then the PCG's first step - k_ml_init + k_ml_cg with
+//   op 1, y = M^-1 x: the right-hand side replaced by x (and restored afterwards), then the PCG's first step - kl_ml_pcg_init + kl_ml_cg with
 //         init = 1 (block-Jacobi: k_precond + k_pcg_init) - which forms z = M^-1 r0 = M^-1 x.
 // info[4] = {operator: 0 block-Jacobi, 1 additive multilevel, 2 multiplicative cycle / Newton-Schulz; aggregates per PCG workgroup (AGG);
 // level of the dense operator (0: none); rows of the system}.  x = null: info only (after the set-up).
@@ -1948,13 +1963,13 @@ extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_apply(uzl_pgo* h, double lambda, in
     }
     const size_t n6 = (size_t)Dp.nb * 6;
     const double tol2 = h->cfg.pcg_tol * h->cfg.pcg_tol;
-    uzl_pgo::MlBuf& B = h->mlb[0];
+    const HostSlot hs = ml ? host_slot(h) : HostSlot{};
     DevBuf<double> saved;
     if (op == 0) {
-        if (ml) k_ml_init(Dp, B.hot, h->ml_agg, h->pbuf[0], h->pbuf[1], B.rg[0], s);
+        if (ml) kl_ml_pcg_init(hs, h->ml_shape, s);
         else { k_precond(Dp, s); k_pcg_init(Dp, h->pbuf[0], h->pbuf[1], s); }
         UZL_HIP(hipMemcpyAsync(Dp.z, x, sizeof(double) * n6, hipMemcpyHostToDevice, s));
-        if (ml) k_ml_spmv(Dp, B.hot, h->ml_agg, h->pbuf[0], h->pbuf[1], g_ml_rows(Dp.nb, h->ml_agg), tol2, s);
+        if (ml) kl_ml_spmv(hs, h->ml_shape, 0, s);
         else k_pcg_spmv(Dp, h->pbuf[0], h->pbuf[1], g_pcg_update(Dp.nb), tol2, s);
         UZL_HIP(hipMemcpyAsync(y, Dp.ap, sizeof(double) * n6, hipMemcpyDeviceToHost, s));
     } else {
@@ -1962,8 +1977,8 @@ extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_apply(uzl_pgo* h, double lambda, in
         UZL_HIP(hipMemcpyAsync(saved.p, Dp.b, sizeof(double) * n6, hipMemcpyDeviceToDevice, s));
         UZL_HIP(hipMemcpyAsync(Dp.b, x, sizeof(double) * n6, hipMemcpyHostToDevice, s));
         if (ml) {
-            k_ml_init(Dp, B.hot, h->ml_agg, h->pbuf[0], h->pbuf[1], B.rg[0], s);
-            UZL_HIP(k_ml_cg(Dp, B.hot, h->ml_agg, h->pbuf[0], B.rg[0], B.rg[1], 0, 1, h->ml_lds, s));
+            kl_ml_pcg_init(hs, h->ml_shape, s);
+            UZL_HIP(kl_ml_cg(hs, h->ml_shape, 0, 1, s));
         } else {
             k_precond(Dp, s);
             k_pcg_init(Dp, h->pbuf[0], h->pbuf[1], s);

@@ -133,13 +133,15 @@ void run_seg(LmRun::Seg& q, bool eager, hipStream_t s, F&& enqueue)
     UZL_HIP(hipGraphLaunch(q.x, s));
 }
 
-// the slot of a handle's current structure, its LM state in lm / snapshot in pub
+}  // namespace
+
+// the slot of a handle's current structure, its LM state in lm / snapshot in pub (both null: a solve of the host-driven loop - HostSlot)
 LmSlot make_slot(const uzl_pgo* h, LmDev* d_lm, LmHost* d_pub)
 {
     LmSlot S;
     memset(&S, 0, sizeof(S));
     S.D = h->D; S.Dp = h->Dp;
-    S.D.flags = d_lm->flags; S.Dp.flags = d_lm->flags;          // the PCG kernels' done / iterations / breakdown words live in the LM state
+    if (d_lm) { S.D.flags = d_lm->flags; S.Dp.flags = d_lm->flags; }      // the PCG kernels' done / iterations / breakdown words live in the LM state
     S.D.pose = nullptr; S.D.pose_trial = nullptr; S.Dp.pose = nullptr; S.Dp.pose_trial = nullptr;
     S.SD = h->red.S; S.red = h->red.on ? 1 : 0;
     S.lm = d_lm; S.pub = d_pub;
@@ -183,6 +185,8 @@ LmShape make_shape(const std::vector<uzl_pgo*>& hs, int nslots, bool batch_geome
     }
     return sh;
 }
+
+namespace {
 
 // the state a graph starts its loop in
 LmDev initial_state(const uzl_pgo* h, int iterations)
