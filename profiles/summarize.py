@@ -86,8 +86,8 @@ for key, names in (("pcg_spmv_bytes_per_launch", ("uzl::ml_spmv_lm_kernel<1, 1, 
         if hit:
             t[key] = pmc[hit[0]]["hbm_bytes_per_launch"]
             break
-# the same kernels' average dispatch duration in the rocprofv3 --kernel-trace --stats summaries of this collection (the by-value
-# instantiations the profiled solve of bench.py launches): bench.py prints them beside its own event-timed figures
+# the same kernels' average dispatch duration in the rocprofv3 --kernel-trace --stats summaries of this collection (the instantiations the
+# profiled solve of bench.py launches): bench.py prints them beside its own event-timed figures
 def stats_avg_us(path, prefixes):
     try:
         rows = list(csv.DictReader(open(path)))
@@ -103,14 +103,14 @@ def stats_avg_us(path, prefixes):
 rp = {}
 for key, path, prefixes in (("pcg_spmv", out + "_kernel_stats.csv", ("uzl::ml_spmv_lm_kernel<1, 1, 8,",)),
                             ("hessian", out + "_kernel_stats.csv", ("uzl::hessian_kernel",)),
-                            ("ns_gemm32", out + "_kernel_stats.csv", ("uzl::ml_ns_gemm32_kernel",)),
+                            ("ns_gemm32", out + "_kernel_stats.csv", ("uzl::ml_ns_gemm32_lm_kernel<uzl::HostSlot>",)),
                             ("knn2", out + "_kernel_stats.csv", ("uzl::knn2_mfma_kernel<8, 2",)),
                             ("estimate", out + "_kernel_stats.csv", ("uzl::estimate_kernel",)),
                             ("wire_unpack", out + "_kernel_stats.csv", ("uzl::wire_unpack_kernel",)),
                             ("pcg_spmv4", out + "_c4_kernel_stats.csv", ("uzl::ml_spmv_lm_kernel<4,",)),
                             ("pcg_cg4", out + "_c4_kernel_stats.csv", ("uzl::ml_cg_lm_kernel<4,",)),
                             ("c4_hessian", out + "_c4_kernel_stats.csv", ("uzl::hessian_kernel",)),
-                            ("c4_ns_gemm", out + "_c4_kernel_stats.csv", ("uzl::ml_ns_gemm_kernel",))):
+                            ("c4_ns_gemm", out + "_c4_kernel_stats.csv", ("uzl::ml_ns_gemm_lm_kernel<uzl::HostSlot>",))):
     v = stats_avg_us(path, prefixes)
     if v is not None:
         rp[key + "_rocprof_avg_us"] = v

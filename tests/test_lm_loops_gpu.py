@@ -124,3 +124,22 @@ def test_pass_history_changes_passes_not_results(capi, n, e):
     assert out[0][0][0]["lm_passes"] > 0 and out[1][2][0]["lm_passes"] >= out[0][2][0]["lm_passes"]
     for k in (1, 2):                                          # every repetition of a handle solves the same problem to the same bits
         assert np.array_equal(out[1][0][1], out[1][k][1])
+
+
+@pytest.mark.parametrize("n,e,seed,reduced", [(1000, 5000, 12345, False), (1500, 1530, 3, True)])
+def test_profiled_solve_kernel_times(capi, n, e, seed, reduced):
+    """A profiled solve (set_profiling: the host-driven loop, every rebuild synchronous, each stage timed - what bench.py reads back):
+    config 2's graph, whose dense operator takes Newton-Schulz steps, and a chain-like graph with its interiors Schur-eliminated."""
+    g = synth.make_pose_graph(n, e, seed=seed)
+    p = capi.Pgo()
+    p.add_graph(g["nodes_pose"], g["nodes_fixed"], g["edges"])
+    p.set_profiling(True)
+    st = p.optimize(20)
+    kt = p.kernel_times()
+    p.close()
+    assert st["status"] == 0 and st["lm_passes"] == 0 and (st["n_eliminated"] > 0) == reduced, st
+    for k in ("linearize", "pcg_spmv") + (("schur_eliminate",) if reduced else ("ml_ns_gemm",)):
+        assert k in kt and kt[k]["launches"] > 0, (k, kt)
+    geo, gal = kt["ml_geometry"]["launches"], kt["ml_galerkin"]["launches"]
+    assert geo == st["precond_builds"] > 0, (kt, st)
+    assert gal > 0 and gal % geo == 0, (kt, st)

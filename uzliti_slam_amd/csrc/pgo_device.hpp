@@ -422,4 +422,13 @@ __device__ __forceinline__ double progress_unit(const double* __restrict__ scal,
     return eps > 0. ? 1. / eps : 1e300;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Slot twins serve both LM loops.  SLOT = `const LmSlot*` (the device-resident loop's table: blockIdx.z picks the graph), `LmSlot` BY VALUE
+// (a pass of one graph), or `HostSlot` (by value: the host-driven loop) - a slot by value sits in the kernel-argument segment: no pointer
+// hop in front of the first loads.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ const LmSlot& slot_of(const LmSlot* __restrict__ slots) { return slots[blockIdx.z]; }
+__device__ __forceinline__ const LmSlot& slot_of(const LmSlot& slot) { return slot; }
+__device__ __forceinline__ const LmSlot& slot_of(const HostSlot& hs) { return hs.S; }
+
 }  // namespace uzl

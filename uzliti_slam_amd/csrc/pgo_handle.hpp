@@ -11,6 +11,7 @@
 #include <chrono>
 #include <cstdlib>
 #include <cmath>
+#include <functional>
 #include <limits>
 #include <new>
 #include <numeric>
@@ -39,15 +40,6 @@ int k_pcg_spmv(const PgoDev& D, const double* p_old, double* p_new, int n_part, 
 int k_pcg_update(const PgoDev& D, const double* p, int n_part, hipStream_t s);
 int g_pcg_spmv(int nb);
 int g_pcg_update(int nb);
-constexpr int kGeoAllMaxHost = 1024;                  // (= kGeoAllMax of pgo_ml_kernels.hip)
-void k_ml_geometry(const PgoDev& D, const MlDev* ml, const double* pose, int l, int n_l, hipStream_t s);
-void k_ml_galerkin(const PgoDev& D, const MlDev* ml, int f, int n_chunks, hipStream_t s);
-void k_ml_sibling(const PgoDev& D, const MlDev* ml, int total_aggs, hipStream_t s);
-void k_ml_dense_level(const MlDev* ml, int l, int n_l, hipStream_t s);
-void k_ml_mult_level(const PgoDev& D, const MlDev* ml, int lev, int n1, int n2, hipStream_t s);
-void k_ml_cmat32(const MlHot& hot, int n6, hipStream_t s);
-void k_ml_ns_step(const PgoDev& D, const MlDev* ml, int lev, int n1, const double* X, double* T, double* Xn, hipStream_t s,
-                  hipEvent_t ev_a = nullptr, hipEvent_t ev_b = nullptr, float* c32 = nullptr, int c32_stride = 0);
 int g_ml_rows(int nb, int agg);
 int g_ml_spmv(int nb, int agg);
 size_t ml_cg_lds_bytes(const int* n, int levels, int agg);
@@ -64,18 +56,22 @@ int g_oplus_for(int n);
 void k_edge_error(const PgoDev& D, const double* pose, double* err, hipStream_t s);
 void k_poses_out(const double* pose, int n, double* out12, hipStream_t s);
 void k_schur_gather(const PgoDev& D, const SchurDev& S, hipStream_t s);
-void k_schur_eliminate(const PgoDev& D, const SchurDev& S, hipStream_t s);
-void k_schur_assemble(const PgoDev& D, const PgoDev& R, const SchurDev& S, hipStream_t s);
-void k_schur_backsub(const PgoDev& D, const PgoDev& R, const SchurDev& S, hipStream_t s);
 // slot twins of the device-resident LM loop (pgo_types.hpp: LmSlot / LmDev / LmShape)
 void k_lm_head(const LmSlot* slots, int nslots, int pass_flags, hipStream_t s);
 void k_lm_tail(const LmSlot* slots, int nslots, hipStream_t s);
 hipError_t kl_linearize(const LmSlot* sl, int nslots, int g_edges, int g_asm, hipStream_t s);
 void kl_eval(const LmSlot* sl, int nslots, int g_edges, int g_oplus, hipStream_t s);
-void kl_schur_reduce(const LmSlot* sl, int nslots, int max_runs, long max_items, hipStream_t s);
-void kl_schur_backsub(const LmSlot* sl, int nslots, int max_grid, hipStream_t s);
+// The Schur reduction and the hierarchy set-up, for both loops: a slot table (`which`: the segment of a pass, pgo_ml_kernels.hip) or the
+// host-driven loop's HostSlot (timer, may be null: the profiled solve's records).  ns_steps: Newton-Schulz steps of the composite level.
+// level1_done (may be empty) runs once level 1's Galerkin product is enqueued: a sharded solve all-reduces it there.
+void kl_schur_reduce(const LmSlot* sl, const LmShape& sh, hipStream_t s);
+void kl_schur_backsub(const LmSlot* sl, const LmShape& sh, hipStream_t s);
+void kl_schur_reduce(const HostSlot& hs, const LmShape& sh, hipStream_t s, KernelTimer* timer);
+void kl_schur_backsub(const HostSlot& hs, const LmShape& sh, hipStream_t s, KernelTimer* timer);
 void kl_ml_numeric(const LmSlot* sl, const LmShape& sh, int which, hipStream_t s);
-void kl_ml_trial(const LmSlot* sl, const LmShape& sh, int which, hipStream_t s);
+void kl_ml_trial(const LmSlot* sl, const LmShape& sh, int which, int ns_steps, hipStream_t s);
+void kl_ml_numeric(const HostSlot& hs, const LmShape& sh, hipStream_t s, KernelTimer* timer, const std::function<void()>& level1_done);
+void kl_ml_trial(const HostSlot& hs, const LmShape& sh, int ns_steps, hipStream_t s, KernelTimer* timer);
 void ml_cg_variant(const MlHot& ml, int agg, size_t lds_full, int32_t* variant, int32_t* comp_u, uint64_t* lds);
 hipError_t kl_ml_init(const LmSlot* sl, const LmSlot* by_value, const LmShape& sh, hipStream_t s);
 hipError_t kl_ml_pcg_its(const LmSlot* sl, const LmSlot* by_value, const LmShape& sh, int first, int n, hipStream_t s, hipEvent_t* ev = nullptr);
@@ -115,7 +111,6 @@ struct uzl_pgo : uzl::HandleBase {
     DevBuf<int32_t> d_slot_edge, d_rb_ptr;
     DevBuf<double> d_srec;                     // slot records (pgo_kernels.hip: slot_records_kernel): values of the edges in the order of the structure's slots
     DevBuf<int4> d_smeta;
-    int ml_ns_now = -1;                        // Newton-Schulz steps of the set-up in progress (-1: ml_ns_steps; host-driven loop)
     bool srec_stale = true;                    // edges' values or the structure changed since d_srec was written
     DevBuf<double> d_zinv, d_info, d_blk, d_hdiag, d_minv, d_b, d_x, d_xs, d_r, d_z, d_p, d_p2, d_ap;
     DevBuf<double> d_part_a, d_part_b, d_part_c, d_scal, d_err, d_out12, d_stage;
@@ -217,8 +212,6 @@ void destroy_pcg_graph(uzl_pgo* h);
 bool ml_async_level(const uzl_pgo* h);
 double ml_rate_drop(const uzl_pgo* h);
 int ml_ns_steps_at(int structure_steps, int lm_iteration);
-void ml_setup_numeric(uzl_pgo* h, int bi, hipStream_t s, const PgoDev& D, bool timed);
-void ml_setup_trial(uzl_pgo* h, int bi, hipStream_t s, const PgoDev& D, bool timed);
 void prepare_optimize(uzl_pgo* h);                    // optimizeImpl's front part: gauge + structure (cached), t_start
 void own_streams(uzl_pgo* h, bool drain_borrowed);               // a batch's handle takes streams of its own (uzl_pgo.hip)
 int do_optimize_host(uzl_pgo* h, int32_t iterations, uzl_pgo_stats* st);      // the host-driven loop (sharded / block-Jacobi / profiled solves, anomaly fallback)

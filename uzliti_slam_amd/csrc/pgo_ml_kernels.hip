@@ -11,6 +11,7 @@
 // Per LM trial      : D_l(lambda)^-1 = (G_l + lambda M_l)^-1, dense inverse of the <= 48-dof top level
 // Per PCG iteration : ml_spmv (p, A p, restricted A p) -> ml_cg (alpha, coarse chain in LDS, x, r, z)
 #include <hip/hip_ext.h>
+#include <functional>
 #include <mutex>
 #include <type_traits>
 
@@ -203,10 +204,6 @@ __device__ __forceinline__ void ml_geometry_kernel_body(PgoDev D, const MlDev* _
         __syncthreads();
     }
 }
-__global__ __launch_bounds__(kBlk) void ml_geometry_kernel(PgoDev D, const MlDev* __restrict__ mlp, const double* __restrict__ pose, int l)
-{
-    ml_geometry_kernel_body(D, mlp, pose, l);
-}
 
 // ---- the same Galerkin product as ONE kernel per level: a GATHER.  The host cuts the coarse level's output blocks into chunks of
 //      consecutive blocks with <= kGalItems contributions (MlLevel::chunk / cslot, build_ml); a workgroup transforms its chunk's
@@ -319,10 +316,6 @@ __device__ __forceinline__ void ml_galerkin_kernel_body(PgoDev D, const MlDev* _
         C.G[(size_t)o0 * 36 + tid] = acc;
         C.M[(size_t)o0 * 36 + tid] = m;
     }
-}
-__global__ __launch_bounds__(kBlk) void ml_galerkin_kernel(PgoDev D, const MlDev* __restrict__ mlp, int f)
-{
-    ml_galerkin_kernel_body(D, mlp, f);
 }
 
 // ---- per LM trial: the sibling-block smoothers and the top level: dense SPD inverses of 24 .. 96 rows.
@@ -510,7 +503,6 @@ __device__ __forceinline__ void ml_dense_level_kernel_body(const MlDev* __restri
 #pragma unroll
     for (int i = 0; i < 36; i++) Y[(size_t)(6 * B + i / 6) * n6 + 6 * Bp + i % 6] = out[i];
 }
-__global__ __launch_bounds__(kBlk) void ml_dense_level_kernel(const MlDev* __restrict__ mlp, int l) { ml_dense_level_kernel_body(mlp, l); }
 
 // ---- composite path, level 1: MULTIPLICATIVE coupling of the level-1 smoother with the levels above,
 //          Y_1 = 2 S - S A S + Q Y_2 Q^T,   Q = P - S A P                     (S = blockdiag of the sibling inverses W_1^-1,
@@ -545,10 +537,6 @@ __device__ __forceinline__ void ml_mult_qy_kernel_body(const MlDev* __restrict__
     double* o = ml.mQY + (size_t)t * 36 + r * 6;
 #pragma unroll
     for (int c = 0; c < 6; c++) o[c] = acc[c];
-}
-__global__ __launch_bounds__(kBlk) void ml_mult_qy_kernel(const MlDev* __restrict__ mlp, int cl)
-{
-    ml_mult_qy_kernel_body(mlp, cl);
 }
 
 // ---- the cycle's operands per PAIR of sibling groups, in one launch (round 4; was A P | A S, then Q | 2 S - S (A S): two launches of
@@ -677,10 +665,6 @@ __device__ __forceinline__ void ml_mult_pair_kernel_body(PgoDev D, const MlDev* 
         ml.mQ[((size_t)i * np + p) * 36 + (r % 6) * 6 + c] = ((g == p) ? sPp[r * 6 + c] : 0.) - t;
     }
 }
-__global__ __launch_bounds__(kBlk) void ml_mult_pair_kernel(PgoDev D, const MlDev* __restrict__ mlp, int cl)
-{
-    ml_mult_pair_kernel_body(D, mlp, cl);
-}
 
 // ---- composite path: Newton-Schulz refinement  X <- 2 X - X A_1 X  of the dense level-1 operator (X = Y_1 is already a
 //      good approximate inverse of A_1: one step squares the error of the cycle, two make it exact to PCG's eyes).
@@ -745,10 +729,6 @@ __device__ __forceinline__ void ml_ns_ax_kernel_body(PgoDev D, const MlDev* __re
 #pragma unroll
         for (int r = 0; r < 6; r++) T[(size_t)(6 * i + r) * n6 + c] = acc[r];
     }
-}
-__global__ __launch_bounds__(kBlk) void ml_ns_ax_kernel(PgoDev D, const MlDev* __restrict__ mlp, int cl, const double* __restrict__ X, double* __restrict__ T)
-{
-    ml_ns_ax_kernel_body(D, mlp, cl, X, T);
 }
 
 constexpr int kGemmTile = 64, kGemmK = 64;
@@ -951,11 +931,6 @@ __device__ __forceinline__ void ml_ns_gemm_kernel_body(int n, const double* __re
     else if ((tj + 1) * kGemmTile <= n) ml_ns_gemm_tile<0>(n, ti, tj, X, T, Xn, c32, c32_stride, sA, sB);      // (ti <= tj: the rows are inside too)
     else ml_ns_gemm_tile<1>(n, ti, tj, X, T, Xn, c32, c32_stride, sA, sB);
 }
-__global__ __launch_bounds__(256) void ml_ns_gemm_kernel(int n, const double* __restrict__ X, const double* __restrict__ T, double* __restrict__ Xn,
-                                                        float* __restrict__ c32, int c32_stride)
-{
-    ml_ns_gemm_kernel_body(n, X, T, Xn, c32, c32_stride);
-}
 
 // The same product for ONE small graph (n <= kGemm32Max): 78 tiles of 64 x 64 leave two thirds of the chip idle at n = 750 and every
 // workgroup walks all of K alone (53 us = 0.11 of the f64 matrix-core peak).  Here a workgroup owns a 32 x 32 tile and its four waves a
@@ -1095,11 +1070,6 @@ __device__ __forceinline__ void ml_ns_gemm32_kernel_body(int n, const double* __
     if ((tj + 1) * 32 <= n) ml_ns_gemm32_tile<false>(n, ti, tj, X, T, Xn, c32, c32_stride, sP);       // (ti <= tj: the rows are inside too)
     else ml_ns_gemm32_tile<true>(n, ti, tj, X, T, Xn, c32, c32_stride, sP);
 }
-__global__ __launch_bounds__(256) void ml_ns_gemm32_kernel(int n, const double* __restrict__ X, const double* __restrict__ T, double* __restrict__ Xn,
-                                                          float* __restrict__ c32, int c32_stride)
-{
-    ml_ns_gemm32_kernel_body(n, X, T, Xn, c32, c32_stride);
-}
 
 // Y_cl += QY Q^T on the f64 matrix cores - the last term of the multiplicative cycle, 2 (6 n_cl)^2 (6 n_{cl+1}) flops (13 GFLOP at 20k
 // vertices, where one lane per 6 x 6 block took 1.3 ms per rebuild).  Same tiling as ml_ns_gemm_kernel: 64 x 64 tiles on and above the
@@ -1182,10 +1152,6 @@ __device__ __forceinline__ void ml_mult_qyqt_kernel_body(const MlDev* __restrict
                 }
             }
 }
-__global__ __launch_bounds__(256) void ml_mult_qyqt_kernel(const MlDev* __restrict__ mlp, int cl)
-{
-    ml_mult_qyqt_kernel_body(mlp, cl);
-}
 
 // ---- per LM trial: dense inverse of the top level A_L(lambda) (<= 96 x 96: kMlTopWide aggregates), one workgroup of 16 x 16 lanes,
 //      one 6 x 6 tile per lane (gj_tiles above); the last workgroup of ml_inverses_kernel
@@ -1220,10 +1186,6 @@ __device__ __forceinline__ void ml_top_tiles(PgoDev D, const MlDev* __restrict__
         for (int k = 0; k < 36; k++) out[(k / 6) * n + k % 6] = a[k];
     }
 }
-__global__ __launch_bounds__(kBlk) void ml_inverses_kernel(PgoDev D, const MlDev* __restrict__ mlp)
-{
-    ml_inverses_kernel_body(D, mlp);
-}
 // The dense operator the PCG kernels apply, rounded to f32 once per rebuild (MlHot::Cmat32).  It is the largest stream of an
 // iteration (config 2: 4.5 of 10 MB; 20k vertices: 112 MB); a preconditioner does not need the last 29 bits, and being rounded once,
 // outside the iteration, it is still one fixed linear operator for the whole solve.  Four columns per lane; pad columns are zero.
@@ -1240,10 +1202,6 @@ __device__ __forceinline__ void ml_cmat32_body(const double* __restrict__ src, f
     o.z = (c + 2 < n6) ? (float)sr[2] : 0.f;
     o.w = (c + 3 < n6) ? (float)sr[3] : 0.f;
     *reinterpret_cast<float4*>(dst + (size_t)row * stride + c) = o;
-}
-__global__ __launch_bounds__(kBlk) void ml_cmat32_kernel(const double* __restrict__ src, float* __restrict__ dst, int n6, int stride)
-{
-    ml_cmat32_body(src, dst, n6, stride);
 }
 
 
@@ -2342,54 +2300,8 @@ __device__ __forceinline__ void ml_cg_comp_kernel_body(PgoDev D, MlHot H, const 
 }
 
 // ------------------------------------------------------------------------------------------------
-// launchers
+// launch geometry
 // ------------------------------------------------------------------------------------------------
-void k_ml_geometry(const PgoDev& D, const MlDev* ml, const double* pose, int l, int n_l, hipStream_t s)
-{
-    hipLaunchKernelGGL(ml_geometry_kernel, dim3(l == 0 ? 1 : (n_l + kBlk - 1) / kBlk), dim3(kBlk), 0, s, D, ml, pose, l);
-}
-void k_ml_galerkin(const PgoDev& D, const MlDev* ml, int f, int n_chunks, hipStream_t s)
-{
-    if (n_chunks > 0) hipLaunchKernelGGL(ml_galerkin_kernel, dim3(n_chunks), dim3(kBlk), 0, s, D, ml, f);
-}
-void k_ml_dense_level(const MlDev* ml, int l, int n_l, hipStream_t s)
-{
-    hipLaunchKernelGGL(ml_dense_level_kernel, dim3((n_l * n_l + kBlk - 1) / kBlk), dim3(kBlk), 0, s, ml, l);
-}
-void k_ml_mult_level(const PgoDev& D, const MlDev* ml, int lev, int n1, int n2, hipStream_t s)
-{
-    hipLaunchKernelGGL(ml_mult_pair_kernel, dim3(n2 * n2), dim3(kBlk), 0, s, D, ml, lev);
-    const int g12r = (n1 * n2 * 6 + kBlk - 1) / kBlk;
-    hipLaunchKernelGGL(ml_mult_qy_kernel, dim3(g12r), dim3(kBlk), 0, s, ml, lev);
-    const int gt = (6 * n1 + kGemmTile - 1) / kGemmTile;
-    hipLaunchKernelGGL(ml_mult_qyqt_kernel, dim3(gt * (gt + 1) / 2), dim3(256), 0, s, ml, lev);
-}
-// one Newton-Schulz step at level `lev`: Xn = 2 X - X (A_lev X); T is scratch
-void k_ml_ns_step(const PgoDev& D, const MlDev* ml, int lev, int n1, const double* X, double* T, double* Xn, hipStream_t s,
-                  hipEvent_t ev_a, hipEvent_t ev_b, float* c32, int c32_stride)
-{
-    const int n6 = 6 * n1;
-    hipLaunchKernelGGL(ml_ns_ax_kernel, dim3(kXcds * n1 * ax_parts(n6)), dim3(kBlk), 0, s, D, ml, lev, X, T);
-    const int g = (n6 + kGemmTile - 1) / kGemmTile, gtri = g * (g + 1) / 2;     // tiles on and above the diagonal
-    if (n6 <= kGemm32Max) {                                                       // one small graph: 32 x 32 tiles, K split over the waves (same bits)
-        const int g32 = gemm32_grid((n6 + 31) / 32);
-        if (ev_a) hipExtLaunchKernelGGL(ml_ns_gemm32_kernel, dim3(g32), dim3(256), 0, s, ev_a, ev_b, 0, n6, X, T, Xn, c32, c32_stride);
-        else hipLaunchKernelGGL(ml_ns_gemm32_kernel, dim3(g32), dim3(256), 0, s, n6, X, T, Xn, c32, c32_stride);
-        return;
-    }
-    if (ev_a) hipExtLaunchKernelGGL(ml_ns_gemm_kernel, dim3(gtri), dim3(256), 0, s, ev_a, ev_b, 0, n6, X, T, Xn, c32, c32_stride);     // dispatch timestamps of the GEMM alone
-    else hipLaunchKernelGGL(ml_ns_gemm_kernel, dim3(gtri), dim3(256), 0, s, n6, X, T, Xn, c32, c32_stride);
-}
-void k_ml_cmat32(const MlHot& hot, int n6, hipStream_t s)
-{
-    if (!hot.Cmat || !hot.Cmat32) return;
-    const long work = (long)n6 * (hot.c32_stride >> 2);
-    hipLaunchKernelGGL(ml_cmat32_kernel, dim3((unsigned)((work + kBlk - 1) / kBlk)), dim3(kBlk), 0, s, hot.Cmat, const_cast<float*>(hot.Cmat32), n6, hot.c32_stride);
-}
-void k_ml_sibling(const PgoDev& D, const MlDev* ml, int total_aggs, hipStream_t s)
-{
-    hipLaunchKernelGGL(ml_inverses_kernel, dim3((total_aggs + kSibPerBlk - 1) / kSibPerBlk + 1), dim3(kBlk), 0, s, D, ml);
-}
 int g_ml_rows(int nb, int agg) { return (nb + kMlFanout * agg - 1) / (kMlFanout * agg); }
 // workgroups of ml_spmv (= p.Ap partials ml_cg sums): AGG = 4 runs two half workgroups per level-2 aggregate
 int g_ml_spmv(int nb, int agg) { return agg == 1 ? g_ml_rows(nb, 1) : g_ml_rows(nb, agg) * (8 / kSpmvWaves4); }
@@ -2412,151 +2324,201 @@ bool ml_fits_lds(const int* n_per_level, int levels, int agg)
 bool ml_comp4_fits(int nb, int n2) { return ml_comp4_lds(n2) <= kMlLdsLimit && g_ml_spmv(nb, 4) <= kMaxPartials; }
 
 // ------------------------------------------------------------------------------------------------
-// slot twins of the device-resident LM loop (pgo_types.hpp: LmSlot / LmDev; uzl_pgo_lm.hip): graph = blockIdx.z, arguments from its
-// slot, every kernel predicated on the graph's LM state.  Same bodies as the by-value kernels above: same arithmetic, same bits.
+// slot twins (pgo_device.hpp: SLOT), the one form of every set-up and PCG kernel for both LM loops: arguments from the graph's slot,
+// every kernel predicated on the graph's LM state (uzl_pgo_lm.hip) - or, for a HostSlot, run whenever the host-driven loop launches it.
 // ------------------------------------------------------------------------------------------------
-// Set-up kernels serve two segments of a pass (`which`):
+// A set-up kernel's body runs as body(S, c, D, pose) when the kernel is due: S the graph's slot, c the hierarchy copy it builds, D the
+// system it reads (scal: the lambda of its segment), pose() the poses of the linearisation.  In a slot table a set-up kernel serves one
+// of two segments of a pass (`which`):
 //   0 = rebuild of copy LmDev::build_ix AHEAD of the trial loop (second stream): numeric + trial part, lambda from LmDev::scal2, poses
 //       of buffer build_cur - all three snapshots lm_head_kernel took, because the main stream moves cur / ix on while this runs;
 //   1 = set-up of the copy in use: numeric part in the pass stamped numeric_pass, trial part in the pass stamped trial_pass.
-#define UZL_LM_SETUP(NUMERIC)                                                                             \
-    const LmSlot& S = slots[blockIdx.z];                                                                  \
-    const LmDev* lm = S.lm;                                                                               \
-    if ((which == 0 ? lm->build_pass : ((NUMERIC) ? lm->numeric_pass : lm->trial_pass)) != lm->pass) return;      \
-    const int c = which == 0 ? lm->build_ix : lm->ix;                                                     \
-    PgoDev D = S.Dp;                                                                                      \
+// A HostSlot builds copy hs.ix from poses hs.cur with the scalars of hs.S.Dp (for a rebuild ahead of the trial loop the host hands over a
+// copy whose Dp.scal is the lambda slot of that rebuild); `which` is not read.
+template <bool NUMERIC, class F>
+__device__ __forceinline__ void setup_of(const LmSlot* __restrict__ slots, int which, F&& body)
+{
+    const LmSlot& S = slots[blockIdx.z];
+    const LmDev* lm = S.lm;
+    if ((which == 0 ? lm->build_pass : (NUMERIC ? lm->numeric_pass : lm->trial_pass)) != lm->pass) return;
+    const int c = which == 0 ? lm->build_ix : lm->ix;
+    PgoDev D = S.Dp;
     if (which == 0) D.scal = const_cast<double*>(lm->scal2);
+    body(S, c, D, [&] { return S.pose[which == 0 ? lm->build_cur : lm->cur]; });
+}
+template <bool NUMERIC, class F>
+__device__ __forceinline__ void setup_of(const HostSlot& hs, int, F&& body) { body(hs.S, hs.ix, hs.S.Dp, [&] { return hs.S.pose[hs.cur]; }); }
 
-__global__ __launch_bounds__(kBlk) void ml_geometry_lm_kernel(const LmSlot* __restrict__ slots, int which, int l)
+template <class SLOT>
+__global__ __launch_bounds__(kBlk) void ml_geometry_lm_kernel(const SLOT slots, int which, int l)
 {
-    UZL_LM_SETUP(true)
-    ml_geometry_kernel_body(D, S.dml[c], S.pose[which == 0 ? lm->build_cur : lm->cur], l);
+    setup_of<true>(slots, which, [&](const LmSlot& S, int c, const PgoDev& D, auto pose) { ml_geometry_kernel_body(D, S.dml[c], pose(), l); });
 }
-__global__ __launch_bounds__(kBlk) void ml_galerkin_lm_kernel(const LmSlot* __restrict__ slots, int which, int f)
+template <class SLOT>
+__global__ __launch_bounds__(kBlk) void ml_galerkin_lm_kernel(const SLOT slots, int which, int f)
 {
-    UZL_LM_SETUP(true)
-    ml_galerkin_kernel_body(D, S.dml[c], f);
+    setup_of<true>(slots, which, [&](const LmSlot& S, int c, const PgoDev& D, auto) { ml_galerkin_kernel_body(D, S.dml[c], f); });
 }
-__global__ __launch_bounds__(kBlk) void ml_inverses_lm_kernel(const LmSlot* __restrict__ slots, int which)
+template <class SLOT>
+__global__ __launch_bounds__(kBlk) void ml_inverses_lm_kernel(const SLOT slots, int which)
 {
-    UZL_LM_SETUP(false)
-    ml_inverses_kernel_body(D, S.dml[c]);
+    setup_of<false>(slots, which, [&](const LmSlot& S, int c, const PgoDev& D, auto) { ml_inverses_kernel_body(D, S.dml[c]); });
 }
-__global__ __launch_bounds__(kBlk) void ml_dense_level_lm_kernel(const LmSlot* __restrict__ slots, int which, int l)
+template <class SLOT>
+__global__ __launch_bounds__(kBlk) void ml_dense_level_lm_kernel(const SLOT slots, int which, int l)
 {
-    UZL_LM_SETUP(false)
-    (void)D;
-    ml_dense_level_kernel_body(S.dml[c], l);
+    setup_of<false>(slots, which, [&](const LmSlot& S, int c, const PgoDev&, auto) { ml_dense_level_kernel_body(S.dml[c], l); });
 }
-__global__ __launch_bounds__(kBlk) void ml_mult_pair_lm_kernel(const LmSlot* __restrict__ slots, int which, int lev)
+template <class SLOT>
+__global__ __launch_bounds__(kBlk) void ml_mult_pair_lm_kernel(const SLOT slots, int which, int lev)
 {
-    UZL_LM_SETUP(false)
-    ml_mult_pair_kernel_body(D, S.dml[c], lev);
+    setup_of<false>(slots, which, [&](const LmSlot& S, int c, const PgoDev& D, auto) { ml_mult_pair_kernel_body(D, S.dml[c], lev); });
 }
-__global__ __launch_bounds__(kBlk) void ml_mult_qy_lm_kernel(const LmSlot* __restrict__ slots, int which, int lev)
+template <class SLOT>
+__global__ __launch_bounds__(kBlk) void ml_mult_qy_lm_kernel(const SLOT slots, int which, int lev)
 {
-    UZL_LM_SETUP(false)
-    (void)D;
-    ml_mult_qy_kernel_body(S.dml[c], lev);
+    setup_of<false>(slots, which, [&](const LmSlot& S, int c, const PgoDev&, auto) { ml_mult_qy_kernel_body(S.dml[c], lev); });
 }
-__global__ __launch_bounds__(256) void ml_mult_qyqt_lm_kernel(const LmSlot* __restrict__ slots, int which, int lev)
+template <class SLOT>
+__global__ __launch_bounds__(256) void ml_mult_qyqt_lm_kernel(const SLOT slots, int which, int lev)
 {
-    UZL_LM_SETUP(false)
-    (void)D;
-    { const int gt = (6 * S.hot[0].n[lev] + kGemmTile - 1) / kGemmTile; if ((int)blockIdx.x >= gt * (gt + 1) / 2) return; }      // (a batch launches the largest graph's grid)
-    ml_mult_qyqt_kernel_body(S.dml[c], lev);
+    setup_of<false>(slots, which, [&](const LmSlot& S, int c, const PgoDev&, auto) {
+        { const int gt = (6 * S.hot[0].n[lev] + kGemmTile - 1) / kGemmTile; if ((int)blockIdx.x >= gt * (gt + 1) / 2) return; }      // (a batch launches the largest graph's grid)
+        ml_mult_qyqt_kernel_body(S.dml[c], lev);
+    });
 }
 // Newton-Schulz step k at level lev: X ping-pongs between Ydense[lev] and nsX, starting in Ydense[lev]
-__global__ __launch_bounds__(kBlk) void ml_ns_ax_lm_kernel(const LmSlot* __restrict__ slots, int which, int lev, int k)
+template <class SLOT>
+__global__ __launch_bounds__(kBlk) void ml_ns_ax_lm_kernel(const SLOT slots, int which, int lev, int k)
 {
-    UZL_LM_SETUP(false)
-    const bool by_xcd = gridDim.z == 1;
-    if (by_xcd && (int)blockIdx.x >= kXcds * S.hot[0].n[lev] * ax_parts(6 * S.hot[0].n[lev])) return;
-    const double* X = (k & 1) ? S.nsX[c] : S.dense[c][lev];
-    ml_ns_ax_kernel_body(D, S.dml[c], lev, X, S.nsT[c], by_xcd);
+    setup_of<false>(slots, which, [&](const LmSlot& S, int c, const PgoDev& D, auto) {
+        const bool by_xcd = gridDim.z == 1;
+        if (by_xcd && (int)blockIdx.x >= kXcds * S.hot[0].n[lev] * ax_parts(6 * S.hot[0].n[lev])) return;
+        const double* X = (k & 1) ? S.nsX[c] : S.dense[c][lev];
+        ml_ns_ax_kernel_body(D, S.dml[c], lev, X, S.nsT[c], by_xcd);
+    });
 }
-__global__ __launch_bounds__(256) void ml_ns_gemm_lm_kernel(const LmSlot* __restrict__ slots, int which, int lev, int k, int last)
+template <class SLOT>
+__global__ __launch_bounds__(256) void ml_ns_gemm_lm_kernel(const SLOT slots, int which, int lev, int k, int last)
 {
-    UZL_LM_SETUP(false)
-    (void)D;
-    const int n6 = 6 * S.hot[0].n[lev];
-    { const int gt = (n6 + kGemmTile - 1) / kGemmTile; if ((int)blockIdx.x >= gt * (gt + 1) / 2) return; }
-    const double* X = (k & 1) ? S.nsX[c] : S.dense[c][lev];
-    double* Xn = (k & 1) ? S.dense[c][lev] : S.nsX[c];
-    const MlHot& H = S.hot[c];
-    ml_ns_gemm_kernel_body(n6, X, S.nsT[c], Xn, last ? const_cast<float*>(H.Cmat32) : nullptr, H.c32_stride);      // (last step: Xn = H.Cmat)
+    setup_of<false>(slots, which, [&](const LmSlot& S, int c, const PgoDev&, auto) {
+        const int n6 = 6 * S.hot[0].n[lev];
+        { const int gt = (n6 + kGemmTile - 1) / kGemmTile; if ((int)blockIdx.x >= gt * (gt + 1) / 2) return; }
+        const double* X = (k & 1) ? S.nsX[c] : S.dense[c][lev];
+        double* Xn = (k & 1) ? S.dense[c][lev] : S.nsX[c];
+        const MlHot& H = S.hot[c];
+        ml_ns_gemm_kernel_body(n6, X, S.nsT[c], Xn, last ? const_cast<float*>(H.Cmat32) : nullptr, H.c32_stride);      // (last step: Xn = H.Cmat)
+    });
 }
-__global__ __launch_bounds__(256) void ml_ns_gemm32_lm_kernel(const LmSlot* __restrict__ slots, int which, int lev, int k, int last)
+template <class SLOT>
+__global__ __launch_bounds__(256) void ml_ns_gemm32_lm_kernel(const SLOT slots, int which, int lev, int k, int last)
 {
-    UZL_LM_SETUP(false)
-    (void)D;
-    const int n6 = 6 * S.hot[0].n[lev];
-    const double* X = (k & 1) ? S.nsX[c] : S.dense[c][lev];
-    double* Xn = (k & 1) ? S.dense[c][lev] : S.nsX[c];
-    const MlHot& H = S.hot[c];
-    ml_ns_gemm32_kernel_body(n6, X, S.nsT[c], Xn, last ? const_cast<float*>(H.Cmat32) : nullptr, H.c32_stride);
+    setup_of<false>(slots, which, [&](const LmSlot& S, int c, const PgoDev&, auto) {
+        const int n6 = 6 * S.hot[0].n[lev];
+        const double* X = (k & 1) ? S.nsX[c] : S.dense[c][lev];
+        double* Xn = (k & 1) ? S.dense[c][lev] : S.nsX[c];
+        const MlHot& H = S.hot[c];
+        ml_ns_gemm32_kernel_body(n6, X, S.nsT[c], Xn, last ? const_cast<float*>(H.Cmat32) : nullptr, H.c32_stride);
+    });
 }
-__global__ __launch_bounds__(kBlk) void ml_cmat32_lm_kernel(const LmSlot* __restrict__ slots, int which, int cl)
+template <class SLOT>
+__global__ __launch_bounds__(kBlk) void ml_cmat32_lm_kernel(const SLOT slots, int which, int cl)
 {
-    UZL_LM_SETUP(false)
-    (void)D;
-    const MlHot& H = S.hot[c];
-    if (!H.Cmat || !H.Cmat32) return;
-    const int n6 = 6 * H.n[cl];
-    ml_cmat32_body(H.Cmat, const_cast<float*>(H.Cmat32), n6, H.c32_stride);
+    setup_of<false>(slots, which, [&](const LmSlot& S, int c, const PgoDev&, auto) {
+        const MlHot& H = S.hot[c];
+        if (!H.Cmat || !H.Cmat32) return;
+        const int n6 = 6 * H.n[cl];
+        ml_cmat32_body(H.Cmat, const_cast<float*>(H.Cmat32), n6, H.c32_stride);
+    });
 }
 
-// numeric part (geometry, Galerkin products level by level): the launch sequence of ml_setup_numeric (uzl_pgo.hip)
-void kl_ml_numeric(const LmSlot* sl, const LmShape& sh, int which, hipStream_t s)
+// a launch that takes the dispatch's own start / stop timestamps when ev_a / ev_b are given (profiling only)
+template <class K, class... A>
+static void launch(K kernel, dim3 g, dim3 t, size_t lds, hipStream_t s, hipEvent_t ev_a, hipEvent_t ev_b, A... args)
+{
+    if (ev_a) hipExtLaunchKernelGGL(kernel, g, t, (uint32_t)lds, s, ev_a, ev_b, 0, args...);
+    else hipLaunchKernelGGL(kernel, g, t, lds, s, args...);
+}
+
+// The set-up of a hierarchy copy, the one statement of its launch sequences: SLOT as above, `which` the segment of a slot table's pass.
+// timer (may be null): the profiled solve's records.
+// Numeric part: geometry, Galerkin products level by level.  level1_done (may be empty) runs once level 1 is enqueued: a sharded solve
+// all-reduces it there, and the levels above need no exchange.
+template <class SLOT>
+static void kl_ml_numeric_t(SLOT sl, const LmShape& sh, int which, hipStream_t s, KernelTimer* timer, const std::function<void()>& level1_done)
 {
     const int B = sh.nslots;
-    if (sh.n_lv[1] <= kGeoAllMax) hipLaunchKernelGGL(ml_geometry_lm_kernel, dim3(1, 1, B), dim3(kBlk), 0, s, sl, which, 0);     // all levels, one workgroup per graph
+    if (timer) timer->begin("ml_geometry", s);
+    if (sh.n_lv[1] <= kGeoAllMax) hipLaunchKernelGGL(ml_geometry_lm_kernel<SLOT>, dim3(1, 1, B), dim3(kBlk), 0, s, sl, which, 0);     // all levels, one workgroup per graph
     else
         for (int l = 1; l <= sh.levels; l++)
-            hipLaunchKernelGGL(ml_geometry_lm_kernel, dim3((sh.n_lv[l] + kBlk - 1) / kBlk, 1, B), dim3(kBlk), 0, s, sl, which, l);
-    for (int f = 0; f < sh.levels; f++)
-        if (sh.chunks[f + 1] > 0) hipLaunchKernelGGL(ml_galerkin_lm_kernel, dim3(sh.chunks[f + 1], 1, B), dim3(kBlk), 0, s, sl, which, f);
+            hipLaunchKernelGGL(ml_geometry_lm_kernel<SLOT>, dim3((sh.n_lv[l] + kBlk - 1) / kBlk, 1, B), dim3(kBlk), 0, s, sl, which, l);
+    if (timer) timer->end(s);
+    for (int f = 0; f < sh.levels; f++) {
+        if (timer) timer->begin("ml_galerkin", s);
+        if (sh.chunks[f + 1] > 0) hipLaunchKernelGGL(ml_galerkin_lm_kernel<SLOT>, dim3(sh.chunks[f + 1], 1, B), dim3(kBlk), 0, s, sl, which, f);
+        if (timer) timer->end(s);
+        if (f == 0 && level1_done) level1_done();
+    }
 }
-// lambda-dependent part: the launch sequence of ml_setup_trial (uzl_pgo.hip)
-void kl_ml_trial(const LmSlot* sl, const LmShape& sh, int which, hipStream_t s)
+// Lambda-dependent part: inverse sibling blocks and top level, then the dense operator - additive, or the multiplicative cycle refined by
+// ns_steps Newton-Schulz steps on the composite level.  The profiled solve's ml_dense record ends in front of those steps, whose GEMMs it
+// times one by one.
+template <class SLOT>
+static void kl_ml_trial_t(SLOT sl, const LmShape& sh, int which, int ns_steps, hipStream_t s, KernelTimer* timer)
 {
     const int B = sh.nslots, L = sh.levels, cl = sh.cl;
-    hipLaunchKernelGGL(ml_inverses_lm_kernel, dim3((sh.inner_aggs + kSibPerBlk - 1) / kSibPerBlk + 1, 1, B), dim3(kBlk), 0, s, sl, which);
+    if (timer) timer->begin("ml_sibling", s);
+    hipLaunchKernelGGL(ml_inverses_lm_kernel<SLOT>, dim3((sh.inner_aggs + kSibPerBlk - 1) / kSibPerBlk + 1, 1, B), dim3(kBlk), 0, s, sl, which);
+    if (timer) timer->end(s);
     if (cl == 0) return;                                                       // no dense operator
     const int n6c = 6 * sh.n_lv[cl];
     const long work32 = (long)n6c * (((n6c + 3) & ~3) >> 2);
+    if (timer) timer->begin("ml_dense", s);
     if (!sh.mult) {                                                            // additive operator: Y_l = blockdiag(W_l^-1) + P Y_{l+1} P^T
         for (int l = L - 1; l >= cl; l--)
-            hipLaunchKernelGGL(ml_dense_level_lm_kernel, dim3((sh.n_lv[l] * sh.n_lv[l] + kBlk - 1) / kBlk, 1, B), dim3(kBlk), 0, s, sl, which, l);
-        hipLaunchKernelGGL(ml_cmat32_lm_kernel, dim3((unsigned)((work32 + kBlk - 1) / kBlk), 1, B), dim3(kBlk), 0, s, sl, which, cl);
+            hipLaunchKernelGGL(ml_dense_level_lm_kernel<SLOT>, dim3((sh.n_lv[l] * sh.n_lv[l] + kBlk - 1) / kBlk, 1, B), dim3(kBlk), 0, s, sl, which, l);
+        hipLaunchKernelGGL(ml_cmat32_lm_kernel<SLOT>, dim3((unsigned)((work32 + kBlk - 1) / kBlk), 1, B), dim3(kBlk), 0, s, sl, which, cl);
+        if (timer) timer->end(s);
         return;
     }
-    for (int l = L - 1; l >= cl; l--) {                                        // multiplicative cycle + Newton-Schulz, from the top down
+    // Multiplicative operator.  The cycle X0 = 2S - S A S + Q Y Q^T has eig(X0 A) in (0, 1] - and Newton-Schulz then converges
+    // monotonically - only if its coarse operator Y does not OVER-correct (eig(Y A_c) <= 2).  The additive operator of the levels above
+    // does (eig up to ~3 on chain-like graphs: tests/diag/cycle_spectrum.py), so those levels are built the same way from the top down:
+    // cycle around the (numerically) exact level above, then upper_ns Newton-Schulz steps.  They are small ((6 n_l)^2 with n_l <= n_cl / 8):
+    // a few launches per level.
+    for (int l = L - 1; l >= cl; l--) {
         const int n1 = sh.n_lv[l], n2 = sh.n_lv[l + 1];
-        hipLaunchKernelGGL(ml_mult_pair_lm_kernel, dim3(n2 * n2, 1, B), dim3(kBlk), 0, s, sl, which, l);
+        hipLaunchKernelGGL(ml_mult_pair_lm_kernel<SLOT>, dim3(n2 * n2, 1, B), dim3(kBlk), 0, s, sl, which, l);
         const int g12r = (n1 * n2 * 6 + kBlk - 1) / kBlk;
-        hipLaunchKernelGGL(ml_mult_qy_lm_kernel, dim3(g12r, 1, B), dim3(kBlk), 0, s, sl, which, l);
+        hipLaunchKernelGGL(ml_mult_qy_lm_kernel<SLOT>, dim3(g12r, 1, B), dim3(kBlk), 0, s, sl, which, l);
         const int n6 = 6 * n1, gt = (n6 + kGemmTile - 1) / kGemmTile;
-        hipLaunchKernelGGL(ml_mult_qyqt_lm_kernel, dim3(gt * (gt + 1) / 2, 1, B), dim3(256), 0, s, sl, which, l);
-        const int steps = l > cl ? sh.upper_ns : sh.ns_steps;
+        hipLaunchKernelGGL(ml_mult_qyqt_lm_kernel<SLOT>, dim3(gt * (gt + 1) / 2, 1, B), dim3(256), 0, s, sl, which, l);
+        if (l == cl && timer) timer->end(s);
+        const int steps = l > cl ? sh.upper_ns : ns_steps;
         for (int k = 0; k < steps; k++) {
-            hipLaunchKernelGGL(ml_ns_ax_lm_kernel, dim3(B == 1 ? kXcds * n1 * ax_parts(n6) : n1 * ((n6 + kBlk - 1) / kBlk), 1, B), dim3(kBlk), 0, s, sl, which, l, k);
-            const int last = (l == cl && k == steps - 1) ? 1 : 0;
-            if (B == 1 && n6 <= kGemm32Max) hipLaunchKernelGGL(ml_ns_gemm32_lm_kernel, dim3(gemm32_grid((n6 + 31) / 32), 1, 1), dim3(256), 0, s, sl, which, l, k, last);
-            else hipLaunchKernelGGL(ml_ns_gemm_lm_kernel, dim3(gt * (gt + 1) / 2, 1, B), dim3(256), 0, s, sl, which, l, k, last);
+            hipLaunchKernelGGL(ml_ns_ax_lm_kernel<SLOT>, dim3(B == 1 ? kXcds * n1 * ax_parts(n6) : n1 * ((n6 + kBlk - 1) / kBlk), 1, B), dim3(kBlk), 0, s, sl, which, l, k);
+            const int last = (l == cl && k == steps - 1) ? 1 : 0;             // its epilogue also writes the f32 copy the PCG kernels read
+            hipEvent_t ea = nullptr, eb = nullptr;
+            if (l == cl && timer) timer->pair("ml_ns_gemm", &ea, &eb);         // the f64 matrix-core GEMM of the refinement, on its own
+            if (B == 1 && n6 <= kGemm32Max) launch(ml_ns_gemm32_lm_kernel<SLOT>, dim3(gemm32_grid((n6 + 31) / 32), 1, 1), dim3(256), 0, s, ea, eb, sl, which, l, k, last);
+            else launch(ml_ns_gemm_lm_kernel<SLOT>, dim3(gt * (gt + 1) / 2, 1, B), dim3(256), 0, s, ea, eb, sl, which, l, k, last);
         }
     }
-    if (sh.ns_steps == 0) hipLaunchKernelGGL(ml_cmat32_lm_kernel, dim3((unsigned)((work32 + kBlk - 1) / kBlk), 1, B), dim3(kBlk), 0, s, sl, which, cl);
+    if (ns_steps == 0) hipLaunchKernelGGL(ml_cmat32_lm_kernel<SLOT>, dim3((unsigned)((work32 + kBlk - 1) / kBlk), 1, B), dim3(kBlk), 0, s, sl, which, cl);
 }
+void kl_ml_numeric(const LmSlot* sl, const LmShape& sh, int which, hipStream_t s) { kl_ml_numeric_t(sl, sh, which, s, nullptr, {}); }
+void kl_ml_trial(const LmSlot* sl, const LmShape& sh, int which, int ns_steps, hipStream_t s) { kl_ml_trial_t(sl, sh, which, ns_steps, s, nullptr); }
+void kl_ml_numeric(const HostSlot& hs, const LmShape& sh, hipStream_t s, KernelTimer* timer, const std::function<void()>& level1_done)
+{
+    kl_ml_numeric_t(hs, sh, 0, s, timer, level1_done);
+}
+void kl_ml_trial(const HostSlot& hs, const LmShape& sh, int ns_steps, hipStream_t s, KernelTimer* timer) { kl_ml_trial_t(hs, sh, 0, ns_steps, s, timer); }
 
-// ---- PCG: init + the two iteration kernels, for both LM loops.  SLOT = `const LmSlot*` (blockIdx.z picks the graph), `LmSlot` BY VALUE
-// for a pass of one graph, or `HostSlot` (by value) for a solve of the host-driven loop - a slot by value sits in the kernel-argument
-// segment: no pointer hop in front of the first loads of kernels that are a chain of round trips.
-__device__ __forceinline__ const LmSlot& slot_of(const LmSlot* __restrict__ slots) { return slots[blockIdx.z]; }
-__device__ __forceinline__ const LmSlot& slot_of(const LmSlot& slot) { return slot; }
-__device__ __forceinline__ const LmSlot& slot_of(const HostSlot& hs) { return hs.S; }
-// what these kernels read of the graph's LM state, through `lm`: the hierarchy copy the PCG applies (ix), pcg_tol^2 (tol2), and whether
-// its solve starts in this pass (init_due).  A HostSlot has no LM state behind it: it carries ix and tol2 itself, and its init always runs
+// ---- PCG: init + the two iteration kernels, for both LM loops (SLOT as above; by value, a slot spares kernels that are a chain of
+// round trips the pointer hop).  What they read of the graph's LM state, through `lm`: the hierarchy copy the PCG applies (ix),
+// pcg_tol^2 (tol2), and whether its solve starts in this pass (init_due).  A HostSlot has no LM state behind it: it carries ix and tol2
+// itself, and its init always runs
 template <class SLOT> __device__ __forceinline__ const LmDev* state_of(const LmSlot& S, const SLOT&) { return S.lm; }
 __device__ __forceinline__ const HostSlot* state_of(const LmSlot&, const HostSlot& hs) { return &hs; }
 __device__ __forceinline__ bool init_due(const LmDev* lm) { return lm->phase == kLmSolve && lm->init_pass == lm->pass; }
@@ -2646,13 +2608,6 @@ static hipError_t lm_cg_lds(const void* fn, int variant_ix, size_t lds)
         configured_tab[dev][variant_ix] = lds;
     }
     return hipSuccess;
-}
-// a launch that takes the dispatch's own start / stop timestamps when ev_a / ev_b are given (profiling only)
-template <class K, class... A>
-static void launch(K kernel, dim3 g, dim3 t, size_t lds, hipStream_t s, hipEvent_t ev_a, hipEvent_t ev_b, A... args)
-{
-    if (ev_a) hipExtLaunchKernelGGL(kernel, g, t, (uint32_t)lds, s, ev_a, ev_b, 0, args...);
-    else hipLaunchKernelGGL(kernel, g, t, lds, s, args...);
 }
 
 // the ml_cg launch of iteration parity `parity` (init = 1: first application) for the shape's variant; SLOT as above
@@ -2771,8 +2726,21 @@ extern "C" UZL_DIAG_EXPORT int uzl_debug_read_stamps(unsigned long long* out, in
 }
 #endif
 
-// test hooks of the diagnostic build (not part of include/uzl_mi355x.h): out = 2 X - X T for host matrices, through ml_ns_gemm_kernel
+// test hooks of the diagnostic build (not part of include/uzl_mi355x.h): out = 2 X - X T for host matrices of any n, through the bodies of
+// the two Newton-Schulz GEMMs (their slot twins read n from a hierarchy: 6 n_l)
 #ifdef UZL_DIAG
+namespace uzl {
+__global__ __launch_bounds__(256) void ml_ns_gemm_kernel(int n, const double* __restrict__ X, const double* __restrict__ T, double* __restrict__ Xn,
+                                                        float* __restrict__ c32, int c32_stride)
+{
+    ml_ns_gemm_kernel_body(n, X, T, Xn, c32, c32_stride);
+}
+__global__ __launch_bounds__(256) void ml_ns_gemm32_kernel(int n, const double* __restrict__ X, const double* __restrict__ T, double* __restrict__ Xn,
+                                                          float* __restrict__ c32, int c32_stride)
+{
+    ml_ns_gemm32_kernel_body(n, X, T, Xn, c32, c32_stride);
+}
+}  // namespace uzl
 extern "C" UZL_DIAG_EXPORT int uzl_debug_ns_gemm32(int n, const double* X, const double* T, double* out)
 {
     if (n <= 0 || n > uzl::kGemm32Max || !X || !T || !out) return -1;

@@ -12,6 +12,7 @@
 // in practice: a run is a chain of <= cap dependent 6x6 steps.
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
 
 #include "uzl_common.hpp"
 #include "pgo_device.hpp"
@@ -546,29 +547,36 @@ __global__ __launch_bounds__(kBlk) void schur_gather_kernel(PgoDev D, SchurDev S
     else { const int run = (int)(item - S.n_int); slot = S.endL[run] >= 0 ? S.slotP[S.run_ptr[run]] : -1; }
     S.runblk[item * 36 + k] = slot >= 0 ? D.blk[(size_t)slot * 36 + k] : 0.;
 }
-__global__ __launch_bounds__(128) void schur_eliminate_kernel(PgoDev D, SchurDev S) { schur_eliminate_kernel_body(D, S); }
-__global__ __launch_bounds__(kBlk) void schur_assemble_kernel(PgoDev D, PgoDev R, SchurDev S) { schur_assemble_kernel_body(D, R, S); }
-__global__ __launch_bounds__(128) void schur_backsub_kernel(PgoDev D, PgoDev R, SchurDev S) { schur_backsub_kernel_body(D, R, S); }
-
-// slot twins of the device-resident LM loop (pgo_types.hpp): graph = blockIdx.z; the reduction runs in the pass lm_head_kernel stamped
-// (a new lambda), the back-substitution with the evaluation of a trial
-__global__ __launch_bounds__(128) void schur_eliminate_lm_kernel(const LmSlot* __restrict__ slots)
+// slot twins, for both LM loops (pgo_device.hpp: SLOT).  In a slot table the reduction runs in the pass lm_head_kernel stamped (a new
+// lambda), the back-substitution with the evaluation of a trial; a HostSlot's kernels run whenever the host-driven loop launches them
+template <class SLOT>
+__global__ __launch_bounds__(128) void schur_eliminate_lm_kernel(const SLOT slots)
 {
-    const LmSlot& S = slots[blockIdx.z];
-    if (!S.red || S.lm->schur_pass != S.lm->pass) return;
+    const LmSlot& S = slot_of(slots);
+    if constexpr (std::is_pointer<SLOT>::value) {
+        const LmDev* lm = S.lm;
+        if (!S.red || lm->schur_pass != lm->pass) return;
+    }
     schur_eliminate_kernel_body(S.D, S.SD);
 }
-__global__ __launch_bounds__(kBlk) void schur_assemble_lm_kernel(const LmSlot* __restrict__ slots)
+template <class SLOT>
+__global__ __launch_bounds__(kBlk) void schur_assemble_lm_kernel(const SLOT slots)
 {
-    const LmSlot& S = slots[blockIdx.z];
-    if (!S.red || S.lm->schur_pass != S.lm->pass) return;
+    const LmSlot& S = slot_of(slots);
+    if constexpr (std::is_pointer<SLOT>::value) {
+        const LmDev* lm = S.lm;
+        if (!S.red || lm->schur_pass != lm->pass) return;
+    }
     schur_assemble_kernel_body(S.D, S.Dp, S.SD);
 }
-__global__ __launch_bounds__(128) void schur_backsub_lm_kernel(const LmSlot* __restrict__ slots)
+template <class SLOT>
+__global__ __launch_bounds__(128) void schur_backsub_lm_kernel(const SLOT slots)
 {
-    const LmSlot& S = slots[blockIdx.z];
-    const LmDev* lm = S.lm;
-    if (!S.red || !(lm->phase == kLmSolve && lm->flags[0] != 0 && lm->flags[2] == 0)) return;
+    const LmSlot& S = slot_of(slots);
+    if constexpr (std::is_pointer<SLOT>::value) {
+        const LmDev* lm = S.lm;
+        if (!S.red || !(lm->phase == kLmSolve && lm->flags[0] != 0 && lm->flags[2] == 0)) return;
+    }
     if ((int)blockIdx.x >= S.SD.n_runs + (S.SD.nbr * 6 + 63) / 64) return;
     schur_backsub_kernel_body(S.D, S.Dp, S.SD);
 }
@@ -626,29 +634,28 @@ void k_schur_gather(const PgoDev& D, const SchurDev& S, hipStream_t s)
     const long items = (long)(S.n_int + S.n_runs) * 36;
     if (items > 0 && S.runblk) hipLaunchKernelGGL(schur_gather_kernel, dim3((unsigned)((items + kBlk - 1) / kBlk)), dim3(kBlk), 0, s, D, S);
 }
-void k_schur_eliminate(const PgoDev& D, const SchurDev& S, hipStream_t s)
+// grids: the largest over the slots of a pass (a twin leaves at once past its own graph's extent - the bodies check run / item counts).
+// timer (may be null): the profiled solve's records
+template <class SLOT>
+static void kl_schur_reduce_t(SLOT sl, const LmShape& sh, hipStream_t s, KernelTimer* timer)
 {
-    if (S.n_runs > 0) hipLaunchKernelGGL(schur_eliminate_kernel, dim3(S.n_runs), dim3(128), 0, s, D, S);
+    const long items = (long)sh.schur_items;
+    if (timer) timer->begin("schur_eliminate", s);
+    if (sh.schur_runs > 0) hipLaunchKernelGGL(schur_eliminate_lm_kernel<SLOT>, dim3(sh.schur_runs, 1, sh.nslots), dim3(128), 0, s, sl);
+    if (timer) { timer->end(s); timer->begin("schur_assemble", s); }
+    if (items > 0) hipLaunchKernelGGL(schur_assemble_lm_kernel<SLOT>, dim3((unsigned)((items + kBlk - 1) / kBlk), 1, sh.nslots), dim3(kBlk), 0, s, sl);
+    if (timer) timer->end(s);
 }
-void k_schur_assemble(const PgoDev& D, const PgoDev& R, const SchurDev& S, hipStream_t s)
+template <class SLOT>
+static void kl_schur_backsub_t(SLOT sl, const LmShape& sh, hipStream_t s, KernelTimer* timer)
 {
-    const long items = (long)(S.nslots_r + S.nbr) * 36;
-    if (items > 0) hipLaunchKernelGGL(schur_assemble_kernel, dim3((unsigned)((items + kBlk - 1) / kBlk)), dim3(kBlk), 0, s, D, R, S);
+    if (timer) timer->begin("schur_backsub", s);
+    if (sh.schur_backsub_grid > 0) hipLaunchKernelGGL(schur_backsub_lm_kernel<SLOT>, dim3(sh.schur_backsub_grid, 1, sh.nslots), dim3(128), 0, s, sl);
+    if (timer) timer->end(s);
 }
-void k_schur_backsub(const PgoDev& D, const PgoDev& R, const SchurDev& S, hipStream_t s)
-{
-    const int g = S.n_runs + (S.nbr * 6 + 63) / 64;
-    if (g > 0) hipLaunchKernelGGL(schur_backsub_kernel, dim3(g), dim3(128), 0, s, D, R, S);
-}
-// grids: the largest over the slots of a pass (a twin leaves at once past its own graph's extent - the bodies check run / item counts)
-void kl_schur_reduce(const LmSlot* sl, int nslots, int max_runs, long max_items, hipStream_t s)
-{
-    if (max_runs > 0) hipLaunchKernelGGL(schur_eliminate_lm_kernel, dim3(max_runs, 1, nslots), dim3(128), 0, s, sl);
-    if (max_items > 0) hipLaunchKernelGGL(schur_assemble_lm_kernel, dim3((unsigned)((max_items + kBlk - 1) / kBlk), 1, nslots), dim3(kBlk), 0, s, sl);
-}
-void kl_schur_backsub(const LmSlot* sl, int nslots, int max_grid, hipStream_t s)
-{
-    if (max_grid > 0) hipLaunchKernelGGL(schur_backsub_lm_kernel, dim3(max_grid, 1, nslots), dim3(128), 0, s, sl);
-}
+void kl_schur_reduce(const LmSlot* sl, const LmShape& sh, hipStream_t s) { kl_schur_reduce_t(sl, sh, s, nullptr); }
+void kl_schur_backsub(const LmSlot* sl, const LmShape& sh, hipStream_t s) { kl_schur_backsub_t(sl, sh, s, nullptr); }
+void kl_schur_reduce(const HostSlot& hs, const LmShape& sh, hipStream_t s, KernelTimer* timer) { kl_schur_reduce_t(hs, sh, s, timer); }
+void kl_schur_backsub(const HostSlot& hs, const LmShape& sh, hipStream_t s, KernelTimer* timer) { kl_schur_backsub_t(hs, sh, s, timer); }
 
 }  // namespace uzl

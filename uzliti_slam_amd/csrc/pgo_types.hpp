@@ -235,12 +235,12 @@ struct LmSlot {
     int32_t g_edges, g_asm, g_oplus, g_rows, g_spmv, red, pad0, pad1;      // grids (= partial counts) of this graph's launches; red: Schur-reduced
     int64_t copy_stride;                       // bytes from an array of hierarchy copy 0 to the same array of copy 1 (one arena, two halves)
 };
-// the slot of a solve of the host-driven loop (uzl_pgo.hip), BY VALUE to the PCG slot twins: there is no LmDev behind it (S.lm is null,
-// S.D / S.Dp carry the handle's own flags), so what those kernels read from one comes along - the hierarchy copy the PCG applies and
-// pcg_tol^2 - and the init kernel always runs
+// the slot of the host-driven loop (uzl_pgo.hip), BY VALUE to the slot twins: there is no LmDev behind it (S.lm is null, S.D / S.Dp
+// carry the handle's own flags), so what those kernels read from one comes along - the hierarchy copy the PCG applies or the set-up
+// builds (ix), the pose buffer of the current estimate (cur) and pcg_tol^2 - and every kernel runs whenever it is launched
 struct HostSlot {
     LmSlot S;
-    int32_t ix, pad0;
+    int32_t ix, cur;
     double tol2;
 };
 

@@ -526,8 +526,6 @@ void build_ml(uzl_pgo* h, const std::vector<int32_t>& row_ptr0, const std::vecto
     UZL_HIP(hipMemcpyAsync(h->d_ml.p, Mh, sizeof(Mh), hipMemcpyHostToDevice, s));
     UZL_HIP(hipStreamSynchronize(s));      // stage / Mh are locals
 }
-
-// numeric part, once per linearisation: geometry, then A_{l+1} = P^T A_l P level by level
 }  // namespace
 namespace uzl {
 // Asynchronous rebuild (second stream, second copy of the hierarchy) pays on the composite level-1 path, and for the reduced system of a
@@ -536,67 +534,6 @@ namespace uzl {
 bool ml_async_level(const uzl_pgo* h)
 {
     return h->ml_cl == 1 || (h->ml_cl == 2 && h->red.on && h->red.strong);
-}
-void ml_setup_numeric(uzl_pgo* h, int bi, hipStream_t s, const PgoDev& D, bool timed)
-{
-    if (h->ml_levels == 0) return;
-    const int L = h->ml_levels;
-    MlDev* dml = h->mlb[bi].dml;
-    if (timed) h->timer.begin("ml_geometry", s);
-    if (h->ml_n[1] <= kGeoAllMaxHost) k_ml_geometry(D, dml, h->cur, 0, 1, s);            // all levels by one workgroup
-    else for (int l = 1; l <= L; l++) k_ml_geometry(D, dml, h->cur, l, h->ml_n[l], s);
-    if (timed) h->timer.end(s);
-    for (int f = 0; f < L; f++) {
-        if (timed) h->timer.begin("ml_galerkin", s);
-        k_ml_galerkin(D, dml, f, h->ml_chunks[f + 1], s);
-        if (timed) h->timer.end(s);
-        if (f == 0) shard_allreduce(h, h->mlb[bi].l1_span_ptr, h->l1_span);     // level 1 complete on every rank: levels >= 2 need no exchange
-    }
-}
-}  // namespace uzl
-namespace {
-
-// lambda-dependent part: inverse sibling blocks, top level, dense operator (+ multiplicative cycle, Newton-Schulz refinement)
-}  // namespace
-namespace uzl {
-void ml_setup_trial(uzl_pgo* h, int bi, hipStream_t s, const PgoDev& D, bool timed)
-{
-    uzl_pgo::MlBuf& B = h->mlb[bi];
-    if (timed) h->timer.begin("ml_sibling", s);
-    k_ml_sibling(D, B.dml, h->ml_inner_aggs, s);
-    if (timed) h->timer.end(s);
-    if (h->ml_comp) {
-        if (timed) h->timer.begin("ml_dense", s);
-        const int cl = h->ml_cl, L = h->ml_levels;
-        if (!h->ml_mult) {                                                   // additive operator: Y_l = blockdiag(W_l^-1) + P Y_{l+1} P^T
-            for (int l = L - 1; l >= cl; l--) k_ml_dense_level(B.dml, l, h->ml_n[l], s);
-            k_ml_cmat32(B.hot, 6 * h->ml_n[cl], s);
-            if (timed) h->timer.end(s);
-            return;
-        }
-        // Multiplicative operator.  The cycle X0 = 2S - S A S + Q Y Q^T has eig(X0 A) in (0, 1] - and Newton-Schulz then converges
-        // monotonically - only if its coarse operator Y does not OVER-correct (eig(Y A_c) <= 2).  The additive operator of the
-        // levels above does (eig up to ~3 on chain-like graphs: tests/diag/cycle_spectrum.py), so those levels are built the same
-        // way from the top down: cycle around the (numerically) exact level above, then kUpperNs Newton-Schulz steps.  They are
-        // small ((6 n_l)^2 with n_l <= n_cl / 8): a few launches per level.
-        for (int l = L - 1; l > cl; l--) {
-            k_ml_mult_level(D, B.dml, l, h->ml_n[l], h->ml_n[l + 1], s);
-            double* xa = h->ml_dense_ptr[bi][l]; double* xb = B.nsX;
-            for (int k = 0; k < kUpperNs; k++) { k_ml_ns_step(D, B.dml, l, h->ml_n[l], xa, B.nsT, xb, s); std::swap(xa, xb); }
-        }
-        k_ml_mult_level(D, B.dml, cl, h->ml_n[cl], h->ml_n[cl + 1], s);
-        if (timed) h->timer.end(s);
-        double* xa = B.y1; double* xb = B.nsX;
-        const int ns_now = h->ml_ns_now >= 0 ? h->ml_ns_now : h->ml_ns_steps;    // (the same parity as ml_ns_steps: the result lands in the same buffer)
-        for (int k = 0; k < ns_now; k++) {
-            hipEvent_t ea = nullptr, eb = nullptr;
-            if (timed) h->timer.pair("ml_ns_gemm", &ea, &eb);                  // the f64 matrix-core GEMM of the refinement, on its own
-            const bool last = k == ns_now - 1;                                 // its epilogue also writes the f32 copy the PCG kernels read
-            k_ml_ns_step(D, B.dml, cl, h->ml_n[cl], xa, B.nsT, xb, s, ea, eb, last ? const_cast<float*>(B.hot.Cmat32) : nullptr, B.hot.c32_stride);
-            std::swap(xa, xb);
-        }
-        if (h->ml_ns_steps == 0) k_ml_cmat32(B.hot, 6 * h->ml_n[cl], s);
-    }
 }
 }  // namespace uzl
 namespace {
@@ -871,8 +808,9 @@ void build_structure(uzl_pgo* h)
 }  // namespace uzl
 namespace {
 
-// the multilevel PCG kernels' slot for this handle: its slot (the handle's own flags; rebuilt with the structure - the additive fallback
-// bumps structure_gen when it swaps hot.Cmat), the hierarchy copy in use and pcg_tol^2.  Launch geometry: h->ml_shape
+// the slot twins' slot for this handle: its slot (the handle's own flags; rebuilt with the structure - the additive fallback bumps
+// structure_gen when it swaps hot.Cmat), the hierarchy copy in use, the pose buffer of the current estimate and pcg_tol^2.  Launch
+// geometry: h->ml_shape
 HostSlot host_slot(uzl_pgo* h)
 {
     if (h->ml_slot_gen != h->structure_gen) {
@@ -881,8 +819,13 @@ HostSlot host_slot(uzl_pgo* h)
         h->ml_slot_gen = h->structure_gen;
     }
     HostSlot hs;
-    hs.S = h->ml_slot; hs.ix = h->ml_ix; hs.pad0 = 0; hs.tol2 = h->cfg.pcg_tol * h->cfg.pcg_tol;
+    hs.S = h->ml_slot; hs.ix = h->ml_ix; hs.cur = h->cur == h->pose_b.p ? 1 : 0; hs.tol2 = h->cfg.pcg_tol * h->cfg.pcg_tol;
     return hs;
+}
+// numeric part of the set-up of hierarchy copy hs.ix; a sharded solve all-reduces level 1 on the way (levels >= 2 need no exchange)
+void ml_setup_numeric(uzl_pgo* h, const HostSlot& hs, hipStream_t s, KernelTimer* timer)
+{
+    kl_ml_numeric(hs, h->ml_shape, s, timer, [&] { shard_allreduce(h, h->mlb[hs.ix].l1_span_ptr, h->l1_span); });
 }
 
 // enqueue `pairs` x 2 PCG iterations (p0 -> p1 -> p0); kernels no-op once the device `done` flag is set
@@ -964,8 +907,8 @@ void ensure_pcg_graph(uzl_pgo* h)
     h->structure_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
-// one (H + lambda I) dx = b solve; returns PCG iterations used, sets *converged
-int pcg_solve(uzl_pgo* h, bool* converged)
+// one (H + lambda I) dx = b solve in LM iteration `it`; returns PCG iterations used, sets *converged
+int pcg_solve(uzl_pgo* h, int it, bool* converged)
 {
     hipStream_t s = h->stream;
     const PgoDev& D = h->Dp;
@@ -973,12 +916,12 @@ int pcg_solve(uzl_pgo* h, bool* converged)
     const int max_it = h->cfg.pcg_max_iter > 0 ? h->cfg.pcg_max_iter : 6 * std::max(D.nb, 1);
     const bool timed = h->timer.on || h->no_graph || h->sharded;   // per-kernel events, rocprofv3 and the exchange callback need eager launches
     if (h->ml_levels > 0) {
+        const HostSlot hs = host_slot(h);
         if (h->ml_trial_setup) {
-            ml_setup_trial(h, h->ml_ix, s, D, true);
+            kl_ml_trial(hs, h->ml_shape, ml_ns_steps_at(h->ml_ns_steps, it), s, &h->timer);
             h->ml_trial_setup = false;
             h->mlb[h->ml_ix].lambda_setup = h->lambda_now;
         }
-        const HostSlot hs = host_slot(h);
         { Timed t(h, "pcg_init"); kl_ml_pcg_init(hs, h->ml_shape, s); }
         { Timed t(h, "ml_cg"); UZL_HIP(kl_ml_cg(hs, h->ml_shape, 0, 1, s)); }
     } else {
@@ -1071,10 +1014,7 @@ int do_optimize_host(uzl_pgo* h, int32_t iterations, uzl_pgo_stats* st)
     const SchurDev& SD = h->red.S;
     S.n_eliminated = red ? h->red.n_int : 0; S.reduced_strong = (red && h->red.strong) ? 1 : 0;
     // (H + lambda I) with the chain interiors eliminated: once per lambda, i.e. per LM trial (pgo_schur.hpp)
-    auto schur_reduce = [&]() {
-        { Timed t(h, "schur_eliminate"); k_schur_eliminate(D, SD, s); }
-        { Timed t(h, "schur_assemble"); k_schur_assemble(D, Dp, SD, s); }
-    };
+    auto schur_reduce = [&]() { kl_schur_reduce(host_slot(h), h->ml_shape, s, &h->timer); };
     const double delta = h->cfg.huber_delta;
     h->timer.reset();
     h->prev_pcg_iters = 0;
@@ -1166,11 +1106,12 @@ int do_optimize_host(uzl_pgo* h, int32_t iterations, uzl_pgo_stats* st)
             k_set_scalar(D.scal + 3, lambda, s);
             schur_reduce();
         }
-        h->ml_ns_now = ml_ns_steps_at(h->ml_ns_steps, it);       // synchronous set-ups of this iteration (the device-resident loop: lm_drive)
         if (refresh) {
             S.precond_builds++;
-            if (it == 0 || !async_ok) { ml_setup_numeric(h, h->ml_ix, s, Dp, true); h->ml_trial_setup = true; }
-            else launch_async = true;                                             // needs this iteration's lambda: below
+            if (it == 0 || !async_ok) {
+                if (h->ml_levels > 0) ml_setup_numeric(h, host_slot(h), s, &h->timer);
+                h->ml_trial_setup = true;
+            } else launch_async = true;                                           // needs this iteration's lambda: below
         }
         if ((it == 0 || h->sharded) && !fetched) {     // later iterations carry chi2 over from the accepted trial: no round trip
             fetch_scal(h);
@@ -1185,11 +1126,12 @@ int do_optimize_host(uzl_pgo* h, int32_t iterations, uzl_pgo_stats* st)
             const int nb_ix = h->ml_ix ^ 1;
             UZL_HIP(hipEventRecord(h->ev_lin, s));                                // H, b and the poses of this linearisation are final
             UZL_HIP(hipStreamWaitEvent(h->stream2, h->ev_lin, 0));
-            PgoDev D2 = Dp;
-            D2.scal = h->d_scal2.p;                                               // the trial loop below moves scal[3] on the main stream
-            k_set_scalar(D2.scal + 3, lambda, h->stream2);
-            ml_setup_numeric(h, nb_ix, h->stream2, D2, false);
-            { const int keep = h->ml_ns_now; h->ml_ns_now = -1; ml_setup_trial(h, nb_ix, h->stream2, D2, false); h->ml_ns_now = keep; }      // (a rebuild that runs ahead: the structure's steps)
+            HostSlot hb = host_slot(h);
+            hb.ix = nb_ix;
+            hb.S.Dp.scal = h->d_scal2.p;                                          // the trial loop below moves scal[3] on the main stream
+            k_set_scalar(hb.S.Dp.scal + 3, lambda, h->stream2);
+            ml_setup_numeric(h, hb, h->stream2, nullptr);
+            kl_ml_trial(hb, h->ml_shape, h->ml_ns_steps, h->stream2, nullptr);    // (a rebuild that runs ahead: the structure's steps)
             h->mlb[nb_ix].lambda_setup = lambda;
             UZL_HIP(hipEventRecord(h->ev_setup, h->stream2));
             h->ml_pending = true;
@@ -1209,11 +1151,11 @@ int do_optimize_host(uzl_pgo* h, int32_t iterations, uzl_pgo_stats* st)
             // geometrically and inverses taken at a much smaller lambda stop being a preconditioner at all
             if (h->ml_levels > 0 && lambda > kLambdaRetake * h->mlb[h->ml_ix].lambda_setup) h->ml_trial_setup = true;
             const bool fresh = h->ml_trial_setup || (adopted && qmax == 0);
-            int pcg_its = pcg_solve(h, &conv);                                    // _solver->solve()
+            int pcg_its = pcg_solve(h, it, &conv);                                // _solver->solve()
             S.pcg_iterations += pcg_its;
             if (!conv && !fresh && h->ml_levels > 0) {                            // stale hierarchy: retake the inverses once
                 h->ml_trial_setup = true;
-                pcg_its = pcg_solve(h, &conv);
+                pcg_its = pcg_solve(h, it, &conv);
                 S.pcg_iterations += pcg_its;
             }
             if (!conv && (h->ml_mult || h->ml_ns_steps > 0)) {
@@ -1227,12 +1169,12 @@ int do_optimize_host(uzl_pgo* h, int32_t iterations, uzl_pgo_stats* st)
                     UZL_HIP(hipStreamSynchronize(h->stream2));                    // multiplicative operator: drop it and rebuild
                     h->ml_pending = false; last_rel = 1e300;                      // synchronously at the next linearisation
                 }
-                h->ml_mult = false; h->ml_ns_steps = 0; h->ml_ns_now = -1; h->mult_banned = true;      // (the additive operator takes no refinement steps)
+                h->ml_mult = false; h->ml_ns_steps = 0; h->mult_banned = true;   // (the additive operator takes no refinement steps)
                 for (auto& B : h->mlb) B.hot.Cmat = B.y1;
                 destroy_pcg_graph(h);                                             // MlHot is a by-value kernel argument
                 h->structure_gen++;                                               // (slot tables that carry it are rebuilt: uzl_pgo_lm.hip, batches)
                 h->ml_trial_setup = true;
-                pcg_its = pcg_solve(h, &conv);
+                pcg_its = pcg_solve(h, it, &conv);
                 S.pcg_iterations += pcg_its;
             }
             {
@@ -1245,7 +1187,7 @@ int do_optimize_host(uzl_pgo* h, int32_t iterations, uzl_pgo_stats* st)
             if (!conv) { S.pcg_not_converged++; rc = UZL_ERR_NOT_CONVERGED; }
             S.lm_trials++;
             mark(2);
-            if (red) { Timed t(h, "schur_backsub"); k_schur_backsub(D, Dp, SD, s); }   // dx of the eliminated vertices from the separators'
+            if (red) kl_schur_backsub(host_slot(h), h->ml_shape, s, &h->timer);  // dx of the eliminated vertices from the separators'
             int go, gc;
             { Timed t(h, "oplus"); go = k_oplus(D, h->cur, h->trial, s); }        // push + update
             { Timed t(h, "chi2"); gc = k_chi2_trial(D, h->cur, delta, s); }       // computeActiveErrors (at trial poses made on the fly: the arithmetic of the device-resident loop's eval_lm_kernel)
@@ -1266,7 +1208,6 @@ int do_optimize_host(uzl_pgo* h, int32_t iterations, uzl_pgo_stats* st)
         S.iterations_done = it + 1;
         if (qmax == 10 || rho == 0) { S.terminated_early = 1; break; }           // Terminate
     }
-    h->ml_ns_now = -1;
     S.chi2_final = current_chi;
     S.lambda_final = lambda;
     if (h->ml_pending) { UZL_HIP(hipStreamSynchronize(h->stream2)); h->ml_pending = false; }   // a rebuild nobody will use: let it drain
@@ -1807,6 +1748,16 @@ extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_linearize(uzl_pgo* h, int32_t* size
     UZL_GUARD_END(h)
 }
 
+namespace {
+// the Schur reduction for this lambda, as an LM trial makes it (do_optimize_host: schur_reduce)
+void debug_reduce(uzl_pgo* h, double lambda)
+{
+    if (!h->red.on) return;
+    k_set_scalar(h->D.scal + 3, lambda, h->stream);
+    kl_schur_reduce(host_slot(h), h->ml_shape, h->stream, nullptr);
+}
+}  // namespace
+
 // One linear solve (H + lambda I) dx = b at the current poses, done as the first trial of an LM iteration of the host-driven loop does it
 // (do_optimize_host): linearise, Schur reduction for this lambda (when the structure has one), the preconditioner's set-up (numeric part
 // and lambda-dependent part; the multiplicative operator and its Newton-Schulz steps where the structure selected them), pcg_solve under the
@@ -1827,7 +1778,6 @@ extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_solve(uzl_pgo* h, double lambda, do
     memset(dx, 0, sizeof(double) * 6 * (size_t)n);
     if (h->nb == 0 || h->e == 0) { info[1] = 1.; return UZL_OK; }
     PgoDev& D = h->D;
-    PgoDev& Dp = h->Dp;
     if (lambda < 0.) {
         double sc[16];
         UZL_HIP(hipMemcpyAsync(sc, D.scal, sizeof(sc), hipMemcpyDeviceToHost, s));
@@ -1835,21 +1785,15 @@ extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_solve(uzl_pgo* h, double lambda, do
         lambda = 1e-5 * sc[6];
     }
     h->ml_ix = 0; h->ml_pending = false;
-    if (h->red.on) {
-        k_set_scalar(D.scal + 3, lambda, s);
-        k_schur_eliminate(D, h->red.S, s);
-        k_schur_assemble(D, Dp, h->red.S, s);
-    }
-    h->ml_ns_now = ml_ns_steps_at(h->ml_ns_steps, 0);
-    if (h->ml_levels > 0) { ml_setup_numeric(h, h->ml_ix, s, Dp, false); h->ml_trial_setup = true; }
+    debug_reduce(h, lambda);
+    if (h->ml_levels > 0) { ml_setup_numeric(h, host_slot(h), s, nullptr); h->ml_trial_setup = true; }
     set_lambda(h, lambda, tol_factor2(h->cfg));
     h->prev_pcg_iters = 0;
     const int trips0 = h->guard_trips;
     bool conv = false;
-    const int its = pcg_solve(h, &conv);
-    h->ml_ns_now = -1;
+    const int its = pcg_solve(h, 0, &conv);
     h->prev_pcg_iters = 0;
-    if (h->red.on) k_schur_backsub(D, Dp, h->red.S, s);
+    if (h->red.on) kl_schur_backsub(host_slot(h), h->ml_shape, s, nullptr);
     const size_t nb = (size_t)h->nb;
     std::vector<double> x(nb * 6);
     std::vector<int32_t> v2b((size_t)n);
@@ -1878,18 +1822,10 @@ double debug_lambda(uzl_pgo* h, double lambda)
     UZL_HIP(hipStreamSynchronize(h->stream));
     return 1e-5 * sc[6];                                       // computeLambdaInit
 }
-// the Schur reduction for this lambda, as an LM trial makes it (do_optimize_host: schur_reduce)
-void debug_reduce(uzl_pgo* h, double lambda)
-{
-    if (!h->red.on) return;
-    k_set_scalar(h->D.scal + 3, lambda, h->stream);
-    k_schur_eliminate(h->D, h->red.S, h->stream);
-    k_schur_assemble(h->D, h->Dp, h->red.S, h->stream);
-}
 }  // namespace
 
 // The system the PCG sees when the structure Schur-eliminates chain interiors, for this lambda (< 0: lambda_init): linearisation, then
-// k_schur_eliminate / k_schur_assemble.  sizes[3] = {reduced rows nbr, reduced slots, 1 if the structure has a reduction (0: nothing
+// the Schur reduction (kl_schur_reduce).  sizes[3] = {reduced rows nbr, reduced slots, 1 if the structure has a reduction (0: nothing
 // else is written)}.  sep_rows [nbr]: full-system block row of every reduced row (-1: an empty row of the strong-aggregate numbering);
 // row_ptr [nbr+1], col [slots] (-1: none), blk [slots][36]: off-diagonal blocks (kept and fill); hdiag [nbr][36] and b [nbr][6]: the
 // diagonal blocks and the right-hand side.  lambda is NOT in hdiag: the separators' own lambda I is added by the SpMV (as for the full
@@ -1954,16 +1890,14 @@ extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_apply(uzl_pgo* h, double lambda, in
     h->ml_ix = 0; h->ml_pending = false;
     debug_reduce(h, lam);
     set_lambda(h, lam, tol_factor2(h->cfg));                   // (before the lambda-dependent set-up, as in pcg_solve)
+    const HostSlot hs = ml ? host_slot(h) : HostSlot{};
     if (ml) {
-        h->ml_ns_now = ml_ns_steps_at(h->ml_ns_steps, 0);
-        ml_setup_numeric(h, 0, s, Dp, false);
-        ml_setup_trial(h, 0, s, Dp, false);
-        h->ml_ns_now = -1;
+        ml_setup_numeric(h, hs, s, nullptr);
+        kl_ml_trial(hs, h->ml_shape, ml_ns_steps_at(h->ml_ns_steps, 0), s, nullptr);
         h->ml_trial_setup = true;                              // (the next solve takes its own inverses)
     }
     const size_t n6 = (size_t)Dp.nb * 6;
     const double tol2 = h->cfg.pcg_tol * h->cfg.pcg_tol;
-    const HostSlot hs = ml ? host_slot(h) : HostSlot{};
     DevBuf<double> saved;
     if (op == 0) {
         if (ml) kl_ml_pcg_init(hs, h->ml_shape, s);

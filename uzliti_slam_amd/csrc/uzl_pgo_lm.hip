@@ -94,12 +94,12 @@ void enq_head(LmRun* R, int pass_flags, bool linearized, hipStream_t s)
     const LmShape& sh = R->shape;
     if (!linearized) enq_linearize(R, s);
     k_lm_head(R->d_slots.p, sh.nslots, pass_flags, s);
-    if (sh.red) kl_schur_reduce(R->d_slots.p, sh.nslots, sh.schur_runs, (long)sh.schur_items, s);
+    if (sh.red) kl_schur_reduce(R->d_slots.p, sh, s);
 }
-void enq_setup(LmRun* R, int which, hipStream_t s)
+void enq_setup(LmRun* R, int which, int ns_steps, hipStream_t s)
 {
     kl_ml_numeric(R->d_slots.p, R->shape, which, s);
-    kl_ml_trial(R->d_slots.p, R->shape, which, s);
+    kl_ml_trial(R->d_slots.p, R->shape, which, ns_steps, s);
 }
 const LmSlot* by_value_slot(LmRun* R) { return (R->shape.nslots == 1 && !R->shape.batch_geometry) ? R->slots.data() : nullptr; }
 void enq_init(LmRun* R, hipStream_t s) { UZL_HIP(kl_ml_init(R->d_slots.p, by_value_slot(R), R->shape, s)); }
@@ -107,7 +107,7 @@ void enq_pcg(LmRun* R, int first, int n, hipStream_t s, hipEvent_t* ev = nullptr
 void enq_tail(LmRun* R, hipStream_t s)
 {
     const LmShape& sh = R->shape;
-    if (sh.red) kl_schur_backsub(R->d_slots.p, sh.nslots, sh.schur_backsub_grid, s);
+    if (sh.red) kl_schur_backsub(R->d_slots.p, sh, s);
     kl_eval(R->d_slots.p, sh.nslots, sh.g_edges, sh.g_oplus, s);
     k_lm_tail(R->d_slots.p, sh.nslots, s);
 }
@@ -406,13 +406,13 @@ int lm_drive(LmRun* R, std::vector<LmJob>& jobs, const LmDriveOpts& o)
             // structure asks for four (large loopy graphs): the problem still changes wholesale there and a rougher operator costs no PCG
             // iterations (ml_ns_steps_at, uzl_pgo.hip).  Launched as they are - the captured segment holds the full sequence.
             const int steps = nS == 1 ? ml_ns_steps_at(R->shape.ns_steps, snap[0].lm.it) : R->shape.ns_steps;
-            if (steps != R->shape.ns_steps) { const int keep = R->shape.ns_steps; R->shape.ns_steps = steps; enq_setup(R, 1, s); R->shape.ns_steps = keep; }
-            else run_seg(R->setup, eager, s, [&](hipStream_t q) { enq_setup(R, 1, q); });
+            if (steps != R->shape.ns_steps) enq_setup(R, 1, steps, s);
+            else run_seg(R->setup, eager, s, [&](hipStream_t q) { enq_setup(R, 1, steps, q); });
         }
         if (pf & kPassRebuild) {
             UZL_HIP(hipEventRecord(R->ev_fork, s));
             UZL_HIP(hipStreamWaitEvent(o.s2, R->ev_fork, 0));
-            run_seg(R->reb, eager, o.s2, [&](hipStream_t q) { enq_setup(R, 0, q); });
+            run_seg(R->reb, eager, o.s2, [&](hipStream_t q) { enq_setup(R, 0, R->shape.ns_steps, q); });
             UZL_HIP(hipEventRecord(R->ev_join, o.s2));
             R->join_pending = true;
         }
