@@ -466,3 +466,259 @@ class FilterRef:
                      consensus=c.consensus, changed=int(c.changed), evaluations=c.evals,
                      keys=np.array(list(c.edges), np.uint64), valid=np.array([d["valid_"] for d in c.edges.values()], np.uint8))
                 for c in self.clusters]
+
+
+# ------------------------------------------------------------------------------------------------------------
+# The multilevel preconditioner stage by stage (test_pgo_hierarchy_gpu.py, test_np_reference_system.py): a float64 restatement of the
+# aggregation hierarchy of csrc/pgo_types.hpp.  Level 0 = the rows of a block system (row_ptr, col, blk, hdiag); level l+1 aggregates
+# fan_{l+1} consecutive level-l entities.  Nothing is ever formed densely at level 0; levels >= 1 are, for the dense operators.
+# Every stage has an absolute-value twin (absolute=True, or a *_mag function): the same sums over the magnitudes of their terms, the
+# scale its round-off bound is built from.  `fault` plants one defect ON THE REFERENCE SIDE, so a test can show that the bound would
+# see it; no kernel ever carries one.
+# ------------------------------------------------------------------------------------------------------------
+def skew(d):
+    """[d]x for d [..., 3]"""
+    d = np.asarray(d, np.float64)
+    z = np.zeros(d.shape[:-1])
+    return np.stack([np.stack([z, -d[..., 2], d[..., 1]], -1), np.stack([d[..., 2], z, -d[..., 0]], -1),
+                     np.stack([-d[..., 1], d[..., 0], z], -1)], -2)
+
+
+def ml_level_sizes(nb, fans):
+    """n_l of every level for the fan-outs fans[1..L] (fans[0] is not read)."""
+    n = [int(nb)]
+    for f in fans[1:]:
+        n.append(-(-n[-1] // int(f)))
+    return n
+
+
+def ml_geometry(t, R, fans, fault=None):
+    """Centroids and offsets of a hierarchy over level-0 rows with translations t [n0,3] and rotations R [n0,3,3]; a row whose t is NaN is
+    EMPTY (no pose: weight 0, zero prolongation block).  Returns (cen, geo): cen[l] [n_l,4] = weighted mean of the children's centroids
+    and the vertices underneath (cen[0] is None); geo[0] [n0,12] = R^T | t - c_parent, geo[l] [n_l,3] = c_self - c_parent (l < L),
+    geo[L] = zeros.  fault = ("fan", l): the centroids of level l divide by fan_l children instead of the weight that is there."""
+    t = np.asarray(t, np.float64); R = np.asarray(R, np.float64)
+    live = ~np.isnan(t).any(1)
+    c = np.where(live[:, None], t, 0.0); w = live.astype(np.float64)
+    n = ml_level_sizes(len(t), fans)
+    L = len(fans) - 1
+    cen = [None]; geo = []
+    child_c = c
+    for l in range(1, L + 1):
+        par = np.arange(n[l - 1]) // fans[l]
+        ws = np.bincount(par, w, minlength=n[l])
+        den = np.full(n[l], float(fans[l])) if fault == ("fan", l) else ws
+        cl_ = np.stack([np.bincount(par, w * child_c[:, k], minlength=n[l]) for k in range(3)], 1)
+        cl_ = np.where(ws[:, None] > 0, cl_ / np.where(den > 0, den, 1.0)[:, None], 0.0)
+        d = child_c - cl_[par]
+        if l == 1:
+            g0 = np.zeros((n[0], 12))
+            g0[:, :9] = np.swapaxes(R, 1, 2).reshape(-1, 9); g0[:, 9:] = d
+            g0[~live] = 0.0
+            geo.append(g0)
+        else:
+            geo.append(d)
+        cen.append(np.concatenate([cl_, ws[:, None]], 1))
+        child_c, w = cl_, ws
+    geo.append(np.zeros((n[L], 3)))
+    return cen, geo
+
+
+def ml_prolong_blocks(level, geo, absolute=False):
+    """The 6 x 6 prolongation block of every entity of `level` towards its parent, from the level's geo array:
+    level 0: [[R^T, -R^T [d]x], [0, 1/2 R^T]] (all zero for an EMPTY row); above: [[I, -[d]x], [0, I]]."""
+    geo = np.asarray(geo, np.float64)
+    n = len(geo)
+    P = np.zeros((n, 6, 6))
+    if level == 0:
+        Rt = geo[:, :9].reshape(n, 3, 3)
+        S = -skew(geo[:, 9:])
+        P[:, :3, :3] = Rt; P[:, 3:, 3:] = 0.5 * Rt
+        P[:, :3, 3:] = (np.abs(Rt) @ np.abs(S)) if absolute else (Rt @ S)
+    else:
+        P[:, :3, :3] = np.eye(3); P[:, 3:, 3:] = np.eye(3); P[:, :3, 3:] = -skew(geo[:, :3])
+    return np.abs(P) if absolute else P
+
+
+def ml_coarse_structure(row_ptr, col, fan, n_c):
+    """Slots of level l+1 from those of level l: exactly the pairs (A, C), A != C, of aggregates joined by a level-l slot, rows ascending,
+    columns ascending within a row.  Returns (row_ptr_c, col_c, fine -> coarse slot index or -1)."""
+    row_ptr = np.asarray(row_ptr, np.int64); col = np.asarray(col, np.int64)
+    rows = np.repeat(np.arange(len(row_ptr) - 1), np.diff(row_ptr))
+    A = rows // fan; Cc = np.where(col >= 0, col // fan, -1)
+    off = (col >= 0) & (A != Cc)
+    key = A[off] * n_c + Cc[off]
+    uk, inv = np.unique(key, return_inverse=True)
+    m = np.full(len(col), -1, np.int64); m[off] = inv
+    rp = np.zeros(n_c + 1, np.int64)
+    np.add.at(rp, uk // n_c + 1, 1)
+    return np.cumsum(rp), uk % n_c, m
+
+
+def ml_galerkin(row_ptr, col, blk, G, M, P, fan, absolute=False, fault=None):
+    """A_{l+1}(0) = P^T A_l(0) P in the device's slot structure and the lambda multiplier M_{l+1} = P^T M_l P (M = None: M_0 = I; an EMPTY
+    row has P = 0 and adds nothing).  Returns (row_ptr_c, col_c, blk_c [slots,6,6], G_c [n_c,6,6], M_c [n_c,6,6]).  absolute: |P|^T |A_l| |P|
+    with P = |P| given.  fault = ("drop", q): contribution q (a level-l slot with col >= 0) is left out."""
+    row_ptr = np.asarray(row_ptr, np.int64); col = np.asarray(col, np.int64)
+    blk = np.asarray(blk, np.float64).reshape(-1, 6, 6); G = np.asarray(G, np.float64).reshape(-1, 6, 6)
+    n = len(row_ptr) - 1
+    n_c = -(-n // fan)
+    if absolute:
+        blk, G, P = np.abs(blk), np.abs(G), np.abs(P)
+    Mf = np.tile(np.eye(6), (n, 1, 1)) if M is None else (np.abs(M) if absolute else np.asarray(M, np.float64)).reshape(-1, 6, 6)
+    rows = np.repeat(np.arange(n), np.diff(row_ptr))
+    rp, cc, m = ml_coarse_structure(row_ptr, col, fan, n_c)
+    ok = col >= 0
+    T = np.zeros((len(col), 6, 6))
+    T[ok] = np.swapaxes(P[rows[ok]], 1, 2) @ blk[:len(col)][ok] @ P[col[ok]]
+    if fault is not None and fault[0] == "drop":
+        T[np.nonzero(ok)[0][fault[1]]] = 0.0
+    blk_c = np.zeros((len(cc), 6, 6))
+    np.add.at(blk_c, m[m >= 0], T[m >= 0])
+    par = np.arange(n) // fan
+    G_c = np.zeros((n_c, 6, 6)); M_c = np.zeros((n_c, 6, 6))
+    same = ok & (m < 0)
+    np.add.at(G_c, rows[same] // fan, T[same])
+    Pt = np.swapaxes(P, 1, 2)
+    np.add.at(G_c, par, Pt @ G[:n] @ P)
+    np.add.at(M_c, par, Pt @ Mf @ P)
+    return rp, cc, blk_c, G_c, M_c
+
+
+def ml_sibling_blocks(level, row_ptr, col, blk, G, M, lam, fan, couple=True, fault=None):
+    """A_l(lambda) restricted to the children of every level-(l+1) aggregate: [n_{l+1}, 6 fan, 6 fan].  Diagonal blocks G + lambda M
+    (level 0: G + lambda I); off-diagonal blocks between siblings, multi-edges summed (couple = False: none - the block-diagonal level-0
+    smoother, PgoDev::sibling0 = 0); a missing child (the last aggregate) or a child whose diagonal block is all zero (an aggregate of
+    EMPTY rows of a coarse level) gets identity rows.  Returns (W, padded [n_{l+1}, fan] bool).  fault = ("drop", q): the q-th slot that
+    couples two siblings is left out."""
+    row_ptr = np.asarray(row_ptr, np.int64); col = np.asarray(col, np.int64)
+    blk = np.asarray(blk, np.float64).reshape(-1, 6, 6)
+    n = len(row_ptr) - 1
+    n_c = -(-n // fan)
+    D = np.asarray(G, np.float64).reshape(-1, 6, 6)[:n] + lam * (np.tile(np.eye(6), (n, 1, 1)) if level == 0 else np.asarray(M, np.float64).reshape(-1, 6, 6)[:n])
+    W = np.zeros((n_c, fan, 6, fan, 6))
+    ent = np.arange(n)
+    zero = np.abs(D).reshape(n, -1).max(1) == 0
+    D[zero] = np.eye(6)
+    W[ent // fan, ent % fan, :, ent % fan, :] = D
+    padded = np.ones((n_c, fan), bool)
+    padded[ent // fan, ent % fan] = False
+    for A, j in zip(*np.nonzero(padded)):
+        W[A, j, :, j, :] = np.eye(6)
+    if couple:
+        rows = np.repeat(ent, np.diff(row_ptr))
+        s = (col >= 0) & (rows // fan == col // fan) & (rows != col)
+        if fault is not None and fault[0] == "drop":
+            s[np.nonzero(s)[0][fault[1]]] = False
+        np.add.at(W, (rows[s] // fan, rows[s] % fan, slice(None), col[s] % fan, slice(None)), blk[:len(col)][s])
+    return W.reshape(n_c, 6 * fan, 6 * fan), padded
+
+
+def ml_level_matrix(row_ptr, col, blk, G, M, lam):
+    """A_l(lambda) of a coarse level (l >= 1) as a dense matrix."""
+    D = np.asarray(G, np.float64).reshape(-1, 6, 6) + lam * np.asarray(M, np.float64).reshape(-1, 6, 6)
+    return bcsr_to_sparse(row_ptr, col, blk, diag=D, nrows=len(D)).toarray()
+
+
+def ml_dense_P(geo, fan, absolute=False):
+    """Prolongation from level l+1 to level l (l >= 1) as a dense [6 n_l, 6 n_{l+1}] matrix."""
+    B = ml_prolong_blocks(1, geo, absolute)
+    n = len(B); n_c = -(-n // fan)
+    P = np.zeros((n, 6, n_c, 6))
+    P[np.arange(n), :, np.arange(n) // fan, :] = B
+    return P.reshape(6 * n, 6 * n_c)
+
+
+def ml_dense_S(Winv, n, fault=None):
+    """blockdiag of the sibling inverses Winv [n_{l+1}, m, m], cut to the 6 n rows that exist.  fault = ("transpose", A, i, j): the 6 x 6
+    tile (i, j) of aggregate A is transposed."""
+    Winv = np.array(Winv, np.float64)
+    if fault is not None and fault[0] == "transpose":
+        _, A, i, j = fault
+        Winv[A, 6 * i:6 * i + 6, 6 * j:6 * j + 6] = Winv[A, 6 * i:6 * i + 6, 6 * j:6 * j + 6].T.copy()
+    n_c, m, _ = Winv.shape
+    S = np.zeros((n_c * m, n_c * m))
+    for A in range(n_c):
+        S[A * m:(A + 1) * m, A * m:(A + 1) * m] = Winv[A]
+    return S[:6 * n, :6 * n]
+
+
+def ml_additive(S, P, Yup, absolute=False):
+    """Y_l = blockdiag(W_l^-1) + P Y_{l+1} P^T; absolute: |S| + |P| |Y_{l+1}| |P|^T."""
+    if absolute:
+        S, P, Yup = np.abs(S), np.abs(P), np.abs(Yup)
+    return S + P @ Yup @ P.T
+
+
+def tile_mirror(Z, tile):
+    """Z with every tile x tile tile BELOW the diagonal replaced by the transpose of its partner above (diagonal tiles as they are): what
+    a kernel leaves that computes the tiles on and above the diagonal of a symmetric result and mirrors them."""
+    if not tile:
+        return Z
+    b = np.arange(Z.shape[0]) // tile
+    return np.where(b[:, None] > b[None, :], Z.T, Z)
+
+
+def ml_mult_cycle(S, A, P, Yup, absolute=False, fault=None, tile=None):
+    """X_0 = 2 S - S A S + Q Y_{l+1} Q^T, Q = P - S A P; absolute: 2 |S| + |S| |A| |S| + |Q| |Y| |Q|^T with |Q| = |P| + |S| |A| |P|.
+    tile: the result is tile_mirror'ed (S is symmetric only to the round-off of its inversion, so X_0 is, too: the kernel that adds
+    Q Y Q^T settles which half counts).  fault = ("tile", i, j): the 16 x 16 tile (i, j) of Q Y Q^T is left out."""
+    if absolute:
+        S, A, P, Yup = np.abs(S), np.abs(A), np.abs(P), np.abs(Yup)
+        Q = P + S @ A @ P
+        return 2 * S + S @ A @ S + Q @ Yup @ Q.T
+    Q = P - S @ (A @ P)
+    C = Q @ Yup @ Q.T
+    if fault is not None and fault[0] == "tile":
+        _, i, j = fault
+        C[16 * i:16 * i + 16, 16 * j:16 * j + 16] = 0.0
+    return tile_mirror(2 * S - S @ A @ S + C, tile)
+
+
+def ml_newton_schulz(X, A, steps, skip=None, tile=None):
+    """k steps X <- 2 X - X A X.  tile: as the kernels take a step (ml_ns_ax + ml_ns_gemm / ml_ns_gemm32) - the left factor is read
+    through X's symmetry, X <- 2 X - X^T (A X), on the tiles on and above the diagonal, mirrored (tile_mirror); the same step for a
+    symmetric X, and X is symmetric only to the round-off of the sibling inverses.  Returns (X_k, sum over the steps of
+    2 |X| + |X|^T |A| |X|: the magnitude of the steps' round-off).  skip: a step that is not taken (planted fault)."""
+    X = np.array(X, np.float64)
+    mag = np.zeros_like(X)
+    Aa = np.abs(A)
+    for k in range(steps):
+        if k == skip:
+            continue
+        Xa = np.abs(X)
+        Xl = X.T if tile else X
+        mag += 2 * Xa + np.abs(Xl) @ Aa @ Xa
+        X = tile_mirror(2 * X - Xl @ (A @ X), tile)
+    return X, mag
+
+
+def ml_restrict(P, r, fan):
+    """r_{l+1}[A] = sum over the children c of A of P_c^T r_l[c]"""
+    n = len(P); n_c = -(-n // fan)
+    out = np.zeros((n_c, 6))
+    np.add.at(out, np.arange(n) // fan, np.einsum("nij,ni->nj", P, np.asarray(r, np.float64).reshape(n, 6)))
+    return out
+
+
+def ml_apply(r, Pblk, Winv, fans, top_inv, cl=0, Ycl=None, absolute=False, coarse_from=None):
+    """z = W_0^-1 r + P_1 ( W_1^-1 r_1 + P_2 ( ... ) ), r_{l+1} = P_{l+1}^T r_l, walked to A_L^-1 = top_inv, or with the levels from cl up
+    replaced by the dense operator Ycl (the f32 values, accumulated in float64) when cl > 0.  Pblk[l]: prolongation blocks of level l
+    (ml_prolong_blocks), Winv[l]: [n_{l+1}, 6 fan, 6 fan].  absolute: every operand by magnitude (give |r|) - the application's bound.
+    coarse_from = g: without the smoothers below level g - the part of z that goes through the residual gathered at level g."""
+    a = np.abs if absolute else (lambda x: x)
+    L = len(fans) - 1
+    stop = cl if cl > 0 else L
+    rs = [a(np.asarray(r, np.float64)).reshape(-1, 6)]
+    for l in range(stop):
+        rs.append(ml_restrict(a(Pblk[l]), rs[l], fans[l + 1]))
+    top = a(np.asarray(Ycl, np.float64)) if cl > 0 else a(np.asarray(top_inv, np.float64))
+    z = (top @ rs[stop].reshape(-1)).reshape(-1, 6)
+    for l in range(stop - 1, -1, -1):
+        n = len(rs[l]); fan = fans[l + 1]
+        W = a(np.asarray(Winv[l], np.float64))
+        n_c, m, _ = W.shape
+        rp = np.zeros((n_c * fan, 6)); rp[:n] = rs[l]
+        zl = np.einsum("aij,aj->ai", W, rp.reshape(n_c, m)).reshape(-1, 6)[:n] * (0.0 if (coarse_from is not None and l < coarse_from) else 1.0)
+        z = zl + np.einsum("nij,nj->ni", a(Pblk[l]), z[np.arange(n) // fan])
+    return z

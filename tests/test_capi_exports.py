@@ -38,7 +38,8 @@ def test_stage_hooks_live_in_the_diagnostic_library_only(capi):
     """The stage-level hooks of the pose-graph linear system (test_pgo_system_gpu.py): exported by the diagnostic twin, absent from
     the product library."""
     import subprocess
-    hooks = {"uzl_debug_pgo_linearize", "uzl_debug_pgo_solve", "uzl_debug_pgo_reduced", "uzl_debug_pgo_apply"}
+    hooks = {"uzl_debug_pgo_linearize", "uzl_debug_pgo_solve", "uzl_debug_pgo_reduced", "uzl_debug_pgo_apply", "uzl_debug_pgo_hierarchy",
+             "uzl_debug_pgo_pcg_state", "uzl_debug_pgo_ban_mult"}
 
     def exported(path):
         out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout

@@ -45,6 +45,8 @@ Measured on an MI355X (pytest -s prints the MEASURED table at the end of the mod
   * Schur complement (c), 600 / 630 chain, both numberings: matrix 5.2e-4, right-hand side 2.1e-5 of the bound.
   * Preconditioner (d): block-Jacobi inverse 4.5e-4 of its bound; additive operator symmetric to 3.1e-8 of its bound;
     kappa(M^-1 A) at lambda_init = 15.94 (additive, 59 free vertices) and 19.25 (multiplicative, C1).  Both are asserted at 2x.
+    The float64 reference application of the same hierarchies (hierarchy_checks.apply_reference) has kappa 15.9379 and 19.253; the
+    device's extreme eigenvalues are within 2.3e-6 / 1.7e-6 of the derived margin | |dM| |A| |_2 (1.6e-9 / 3.9e-9) of the reference's.
 """
 import numpy as np
 import pytest
@@ -628,3 +630,48 @@ def test_multiplicative_operator_spectrum_bounded(capi, oracle):
     """The multiplicative cycle + Newton-Schulz operator of small graphs (not SPD by construction): real positive spectrum of M^-1 A and
     kappa bounded."""
     _spectrum_case(capi, oracle, synth.make_pose_graph(100, 300), 2, "multiplicative")
+
+
+@pytest.mark.parametrize("name", ["additive", "multiplicative"])
+def test_spectrum_extremes_are_the_reference_operators(capi, oracle, name):
+    """The two graphs above once more, tied to the mathematics instead of a past run: kappa(M_ref^-1 A) of the float64 reference
+    application (hierarchy_checks.apply_reference on the arrays the set-up kernels left, each of which test_pgo_hierarchy_gpu.py holds
+    against its own float64 stage), computed on the CPU, and the device operator's extreme eigenvalues within | |dM| |A| |_2 of the
+    reference's.  |dM| = the entrywise application bound, C_H eps x the absolute-value application of the unit vectors.  Derivation
+    (Bauer-Fike for the symmetrised pencil): M A is similar to A^1/2 M A^1/2; for a symmetric perturbation E of M that matrix moves
+    by A^1/2 E A^1/2, whose norm is the spectral radius of E A <= |E A|_2 <= | |E| |A| |_2, and the extreme eigenvalues of a symmetric
+    matrix move by at most that (Weyl).  Both operators enter by their symmetric parts (the multiplicative one is symmetric to ~1e-9
+    only, which moves an eigenvalue in second order), |sym(dM)| <= sym(|dM|)."""
+    import hierarchy_checks as HC
+    g = synth.make_pose_graph(60, 180, seed=60) if name == "additive" else synth.make_pose_graph(100, 300)
+    p, lin, R = _system(capi, oracle, g, dict(schur_reduce=-1))
+    try:
+        assert p.apply_info()["op"] == (1 if name == "additive" else 2)
+        h = p.hierarchy()
+        lam = h["lam"]
+        M = dense_operator(p, 1, R.nb, lam)
+        n = 6 * R.nb
+        lv0 = h["lv"][0]
+        A = NP.bcsr_to_sparse(lv0["row_ptr"], lv0["col"], lv0["blk"], diag=lv0["G"] + lam * np.eye(6), nrows=R.nb).toarray()
+        Mref = np.zeros((n, n)); B = np.zeros((n, n))
+        e = np.zeros((R.nb, 6))
+        for c in range(n):
+            e.flat[c] = 1.0
+            Mref[:, c] = HC.apply_reference(h, e).reshape(-1)
+            B[:, c] = C_H * EPS * HC.apply_reference(h, e, absolute=True).reshape(-1)
+            e.flat[c] = 0.0
+        assert (np.abs(M - Mref) <= B).all(), "the device operator is not within the application bound of the reference's"
+        Lc = np.linalg.cholesky(0.5 * (A + A.T))
+        ev = np.linalg.eigvalsh(Lc.T @ (0.5 * (M + M.T)) @ Lc)
+        ev_ref = np.linalg.eigvalsh(Lc.T @ (0.5 * (Mref + Mref.T)) @ Lc)
+        margin = np.linalg.norm(0.5 * (B + B.T) @ np.abs(A), 2)
+        kappa_ref = ev_ref[-1] / ev_ref[0]
+        print("\nkappa(M_ref^-1 A) %s: %.6g (eigenvalues %.6g .. %.6g); device %.6g .. %.6g; margin %.3g" % (
+            name, kappa_ref, ev_ref[0], ev_ref[-1], ev[0], ev[-1], margin))
+        _note("kappa(M_ref^-1 A) %s" % name, kappa_ref)
+        _note("extreme eigenvalues, device - reference / margin (%s)" % name, max(abs(ev[0] - ev_ref[0]), abs(ev[-1] - ev_ref[-1])) / margin)
+        assert ev_ref[0] > 0
+        assert abs(ev[0] - ev_ref[0]) <= margin and abs(ev[-1] - ev_ref[-1]) <= margin, (ev[0] - ev_ref[0], ev[-1] - ev_ref[-1], margin)
+        assert kappa_ref <= 2 * KAPPA[name]
+    finally:
+        p.close()

@@ -672,6 +672,77 @@ class DiagPgo(Pgo):
         assert int(info[3]) == xx.shape[0], "x has %d rows, the system %d" % (xx.shape[0], int(info[3]))
         return y
 
+    def pcg_state(self, k, lam=-1.0):
+        """The PCG's state after k iterations on the system's own right-hand side (uzl_debug_pgo_pcg_state): dict of x, r, z, p [rows,6],
+        rg [n_g,6] (the gather-level residual the next ml_cg would read), gather_level, done, its, lam."""
+        L = self._lib()
+        info = np.zeros(6)
+        self._check(L.uzl_debug_pgo_pcg_state(self._h, C.c_double(lam), C.c_int32(k), None, None, None, None, None, _p(info, c_f64p)))
+        rows, ng = int(info[0]), int(info[2])
+        if rows == 0:
+            return None
+        x, r, z, pp = (np.zeros((rows, 6)) for _ in range(4))
+        rg = np.zeros((ng, 6))
+        self._check(L.uzl_debug_pgo_pcg_state(self._h, C.c_double(lam), C.c_int32(k), _p(x, c_f64p), _p(r, c_f64p), _p(z, c_f64p), _p(pp, c_f64p),
+                                              _p(rg, c_f64p), _p(info, c_f64p)))
+        return dict(x=x, r=r, z=z, p=pp, rg=rg, gather_level=int(info[1]), done=int(info[3]), its=int(info[4]), lam=float(info[5]))
+
+    def ban_mult(self):
+        """Before the first graph: the handle's structures start with the additive dense operator (what a handle does once the
+        multiplicative operator has broken down on one of its graphs)."""
+        self._check(self._lib().uzl_debug_pgo_ban_mult(self._h))
+
+    def _hier_array(self, level, what, dtype, shape):
+        L = self._lib()
+        nbytes = C.c_int64(0)
+        self._check(L.uzl_debug_pgo_hierarchy(self._h, C.c_double(0.0), C.c_int32(0), C.c_int32(level), C.c_int32(what), None, None, None,
+                                              C.byref(nbytes)))
+        out = np.zeros(max(nbytes.value // np.dtype(dtype).itemsize, 1), dtype)
+        if nbytes.value:
+            room = C.c_int64(out.nbytes)
+            self._check(L.uzl_debug_pgo_hierarchy(self._h, C.c_double(0.0), C.c_int32(0), C.c_int32(level), C.c_int32(what), None, None,
+                                                  out.ctypes.data_as(C.c_void_p), C.byref(room)))
+            assert room.value == nbytes.value, "the structure changed between the two calls"
+        out = out[:nbytes.value // np.dtype(dtype).itemsize]
+        return out.reshape(shape) if nbytes.value else None
+
+    def hierarchy(self, lam=-1.0, ns_steps=-1):
+        """The multilevel hierarchy after the set-up an LM trial makes for lam (< 0: lambda_init), with ns_steps Newton-Schulz steps at
+        the composite level (< 0: what the first trial takes; 0: the cycle's X_0), as the set-up kernels left it (uzl_debug_pgo_hierarchy):
+        dict(levels, cl, agg, mult, ns_steps, upper_ns, sibling0, rows, c32_stride, reduced, strong, strong_blocks, structure_ns_steps,
+        cg_variant (LmCgVariant: 0 plain1, 1 comp1, 2 plain4, 3 comp4, 4 comp4 Ypre, 5 comp4 Vpre), lam,
+        b2v [rows] (-1: EMPTY row), top_inv, Cmat32 [6 n_cl, c32_stride] (None without a dense operator), lv = one dict per level of
+        n, fan, nslots, row_ptr, col, blk [nslots,6,6], G [n,6,6], M (levels >= 1), geo ([n,12] at level 0, [n,3] above), cen [n,4]
+        (levels >= 1), Winv [n_{l+1}, 6 fan, 6 fan] (levels < L), Y [(6 n)^2] (cl <= l < L)).  levels = 0: block-Jacobi, nothing else."""
+        info = np.zeros(64, np.int32)
+        lam_used = C.c_double(0.0)
+        self._check(self._lib().uzl_debug_pgo_hierarchy(self._h, C.c_double(lam), C.c_int32(ns_steps), C.c_int32(0), C.c_int32(-1),
+                                                        _p(info, c_i32p), C.byref(lam_used), None, None))
+        keys = ("levels", "cl", "agg", "mult", "ns_steps", "upper_ns", "sibling0", "rows", "c32_stride", "reduced", "strong", "strong_blocks",
+                "structure_ns_steps", "cg_variant")
+        out = dict(zip(keys, (int(v) for v in info[:len(keys)])), lam=lam_used.value, lv=[])
+        L, cl = out["levels"], out["cl"]
+        if L == 0:
+            return out
+        for l in range(L + 1):
+            n, fan, ns = int(info[16 + l]), int(info[32 + l]), int(info[48 + l])
+            m = 6 * int(info[32 + l + 1]) if l < L else 0
+            lv = dict(n=n, fan=fan, nslots=ns, row_ptr=self._hier_array(l, 0, np.int32, (n + 1,)))
+            lv["col"] = self._hier_array(l, 1, np.int32, (ns,)) if ns else np.zeros(0, np.int32)
+            lv["blk"] = self._hier_array(l, 2, np.float64, (ns, 6, 6)) if ns else np.zeros((0, 6, 6))
+            lv["G"] = self._hier_array(l, 3, np.float64, (n, 6, 6))
+            lv["M"] = self._hier_array(l, 4, np.float64, (n, 6, 6))
+            lv["geo"] = self._hier_array(l, 5, np.float64, (n, 12 if l == 0 else 3))
+            lv["cen"] = self._hier_array(l, 6, np.float64, (n, 4))
+            lv["Winv"] = self._hier_array(l, 7, np.float64, (int(info[16 + l + 1]), m, m)) if l < L else None
+            lv["Y"] = self._hier_array(l, 8, np.float64, (6 * n, 6 * n)) if (cl and cl <= l < L) else None
+            out["lv"].append(lv)
+        nt = out["lv"][L]["n"]
+        out["top_inv"] = self._hier_array(L, 9, np.float64, (6 * nt, 6 * nt))
+        out["Cmat32"] = self._hier_array(cl, 10, np.float32, (6 * out["lv"][cl]["n"], out["c32_stride"])) if cl else None
+        out["b2v"] = self._hier_array(0, 11, np.int32, (out["rows"],))
+        return out
+
 
 class _BorrowedPgo(Pgo):
     """A Pgo over a handle the batch owns: neither close() nor the finaliser may destroy it."""

@@ -1221,7 +1221,7 @@ __device__ __forceinline__ void ml_cmat32_body(const double* __restrict__ src, f
 // one memory latency covers them: these kernels are latency-bound, not bandwidth-bound, at pose-graph sizes.
 // ------------------------------------------------------------------------------------------------
 // Two geometries, chosen by graph size (template parameter AGG = level-1 aggregates per workgroup):
-//   AGG = 1 (small graphs, <= 2560 free vertices): a workgroup owns ONE level-1 aggregate (8 rows), the gather
+//   AGG = 1 (small graphs, <= 3072 free vertices, <= 4096 on sparse ones: build_ml's agg1_max): a workgroup owns ONE level-1 aggregate (8 rows), the gather
 //           level is 1, hierarchy fan-outs 8,8,8,..  -> 8x more workgroups, i.e. CUs, for the latency-bound kernels
 //   AGG = 4 (large graphs): a workgroup owns one level-2 aggregate = 4 level-1 aggregates (32 rows), gather level 2,
 //           hierarchy fan-outs 8,4,8,8,..             -> the gathered arrays stay small (n/32 entries)

@@ -1925,6 +1925,147 @@ extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_apply(uzl_pgo* h, double lambda, in
     return UZL_OK;
     UZL_GUARD_END(h)
 }
+
+// The multilevel hierarchy as its set-up kernels leave it (tests/test_pgo_hierarchy_gpu.py), array by array.  Two kinds of call:
+//   what < 0:  the set-up an LM trial of the host-driven loop makes, exactly as uzl_debug_pgo_apply does it (linearisation, Schur reduction,
+//              set_lambda, numeric part, lambda-dependent part) into hierarchy copy 0, for this lambda (< 0: lambda_init) and with ns_steps
+//              Newton-Schulz steps at the composite level (< 0: what the first trial takes, ml_ns_steps_at(.., 0); otherwise even: the
+//              steps ping-pong and an even count ends where MlHot::Cmat points; 0 = the cycle's X_0 as it comes).  Fills
+//              info[64] = {levels, cl, agg, mult, steps taken at cl, upper_ns, sibling0, rows of the system, c32_stride, Schur-reduced,
+//              strong numbering, strong blocks of 4, the structure's own step count, the ml_cg variant (LmCgVariant), 0..; [16 + l] n_l; [32 + l] fan_l; [48 + l] nslots_l}
+//              and *lam_used.  levels = 0 (block-Jacobi): nothing else happens.
+//   what >= 0: copies one array of level `level` of that copy, as the last what < 0 call left it (no kernel runs): 0 row_ptr [n_l + 1],
+//              1 col [nslots_l] (both i32), 2 blk [nslots_l][36], 3 G [n_l][36] (lambda = 0), 4 M [n_l][36] (levels >= 1), 5 geo (level 0:
+//              [n_0][12] = R^T | d, above [n_l][3]), 6 cen [n_l][4] (levels >= 1), 7 Winv [n_{l+1}][(6 fan_{l+1})^2] (levels < L),
+//              8 Ydense [(6 n_l)^2] (cl <= l < L), 9 top_inv [(6 n_L)^2], 10 Cmat32 [6 n_cl][c32_stride] (f32), 11 b2v of the system's rows
+//              [n_0] (i32, -1: EMPTY row).  *nbytes: in = the room at `out` (ignored when out is null), out = the array's size in bytes
+//              (0: that level has no such array).
+// The hook only reads what the production kernels wrote.
+extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_hierarchy(uzl_pgo* h, double lambda, int32_t ns_steps, int32_t level, int32_t what, int32_t* info,
+                                                       double* lam_used, void* out, int64_t* nbytes)
+{
+    UZL_GUARD_BEGIN(h)
+    if (!h->have_graph) return fail(h, UZL_ERR_STATE, "hierarchy before add_graph/set_graph");
+    own_streams(h, true);
+    hipStream_t s = h->stream;
+    if (what < 0) {
+        if (!info || (ns_steps > 0 && (ns_steps & 1))) return fail(h, UZL_ERR_BAD_ARG, "hierarchy: info, and an even step count");
+        debug_linearize(h);
+        for (int i = 0; i < 64; i++) info[i] = 0;
+        if (h->ml_levels == 0 || h->nb == 0 || h->e == 0) { UZL_HIP(hipStreamSynchronize(s)); return UZL_OK; }
+        const double lam = debug_lambda(h, lambda);
+        h->ml_ix = 0; h->ml_pending = false;
+        debug_reduce(h, lam);
+        set_lambda(h, lam, tol_factor2(h->cfg));
+        const HostSlot hs = host_slot(h);
+        const int steps = !h->ml_mult ? 0 : (ns_steps < 0 ? ml_ns_steps_at(h->ml_ns_steps, 0) : ns_steps);
+        ml_setup_numeric(h, hs, s, nullptr);
+        kl_ml_trial(hs, h->ml_shape, steps, s, nullptr);
+        h->ml_trial_setup = true;                              // (the next solve takes its own inverses)
+        UZL_HIP(hipGetLastError());
+        UZL_HIP(hipStreamSynchronize(s));
+        info[0] = h->ml_levels; info[1] = h->ml_comp ? h->ml_cl : 0; info[2] = h->ml_agg; info[3] = h->ml_mult ? 1 : 0; info[4] = steps;
+        info[5] = kUpperNs; info[6] = h->Dp.sibling0; info[7] = h->Dp.nb; info[8] = h->mlb[0].hot.c32_stride;
+        info[9] = h->red.on ? 1 : 0; info[10] = h->red.strong ? 1 : 0; info[11] = h->red.strong_blocks ? 1 : 0; info[12] = h->ml_ns_steps;
+        info[13] = h->ml_shape.cg_variant;
+        for (int l = 0; l <= h->ml_levels; l++) { info[16 + l] = h->ml_n[l]; info[32 + l] = h->ml_fan[l]; info[48 + l] = h->ml_nslots[l]; }
+        if (lam_used) *lam_used = lam;
+        return UZL_OK;
+    }
+    const int L = h->ml_levels, cl = h->ml_comp ? h->ml_cl : 0;
+    if (!nbytes || !h->structure_ready || L == 0 || level < 0 || level > L) return fail(h, UZL_ERR_BAD_ARG, "hierarchy: no such level (or no set-up yet)");
+    MlDev M;
+    UZL_HIP(hipMemcpyAsync(&M, h->mlb[0].dml, sizeof(MlDev), hipMemcpyDeviceToHost, s));
+    UZL_HIP(hipStreamSynchronize(s));
+    const MlLevel& X = M.lv[level];
+    const size_t n = (size_t)X.n, ns = (size_t)X.nslots;
+    const void* src = nullptr;
+    size_t bytes = 0;
+    switch (what) {
+    case 0: src = X.row_ptr; bytes = (n + 1) * 4; break;
+    case 1: src = X.col; bytes = ns * 4; break;
+    case 2: src = X.blk; bytes = ns * 36 * 8; break;
+    case 3: src = X.G; bytes = n * 36 * 8; break;
+    case 4: if (level >= 1) { src = X.M; bytes = n * 36 * 8; } break;
+    case 5: src = X.geo; bytes = n * (level == 0 ? 12 : 3) * 8; break;
+    case 6: if (level >= 1) { src = X.cen; bytes = n * 4 * 8; } break;
+    case 7: if (level < L) { const size_t m = (size_t)6 * M.lv[level + 1].fan; src = X.Winv; bytes = (size_t)M.lv[level + 1].n * m * m * 8; } break;
+    case 8: if (cl > 0 && level >= cl && level < L) { src = M.Ydense[level]; bytes = 36 * n * n * 8; } break;
+    case 9: if (level == L) { src = M.top_inv; bytes = 36 * n * n * 8; } break;
+    case 10: if (cl > 0 && level == cl) { src = h->mlb[0].hot.Cmat32; bytes = 6 * n * (size_t)h->mlb[0].hot.c32_stride * 4; } break;
+    case 11: if (level == 0) { src = h->Dp.b2v; bytes = n * 4; } break;
+    default: return fail(h, UZL_ERR_BAD_ARG, "hierarchy: no such array");
+    }
+    if (out && bytes) {
+        if (*nbytes < (int64_t)bytes || !src) return fail(h, UZL_ERR_BAD_ARG, "hierarchy: the buffer is too small");
+        UZL_HIP(hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, s));
+        UZL_HIP(hipStreamSynchronize(s));
+    }
+    *nbytes = (int64_t)bytes;
+    return UZL_OK;
+    UZL_GUARD_END(h)
+}
+
+// The PCG's state after k iterations on the system's own right-hand side, for this lambda (< 0: lambda_init): the set-up of
+// uzl_debug_pgo_apply, the PCG's init (kl_ml_pcg_init + kl_ml_cg with init = 1), then k times the two launches of an iteration
+// (kl_ml_spmv, kl_ml_cg) one by one as the eager solve enqueues them.  Copies x, r, z [rows][6], the direction p the last iteration
+// formed (k = 0: the init's), and rg [n_g][6]: the gather-level residual buffer the NEXT ml_cg would read.  The stop test runs as in any
+// solve: give the handle a pcg_tol it cannot reach in k iterations (info[3] tells).  Multilevel path only.
+// info[6] = {rows, gather level, n_g, done flag, iterations the kernels counted, lambda}.  x = null: info only (no kernel runs).
+extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_pcg_state(uzl_pgo* h, double lambda, int32_t k, double* x, double* r, double* z, double* p,
+                                                       double* rg, double* info)
+{
+    UZL_GUARD_BEGIN(h)
+    if (!h->have_graph) return fail(h, UZL_ERR_STATE, "pcg_state before add_graph/set_graph");
+    if (!info || k < 0 || (x && !(r && z && p && rg))) return fail(h, UZL_ERR_BAD_ARG, "pcg_state: info, k >= 0, and every array with x");
+    own_streams(h, true);
+    debug_linearize(h);
+    hipStream_t s = h->stream;
+    PgoDev& Dp = h->Dp;
+    const bool ml = h->ml_levels > 0 && h->nb > 0 && h->e > 0;
+    const int gl = !ml ? 0 : ((h->ml_agg == 1 || h->ml_levels < 2) ? 1 : 2);
+    for (int i = 0; i < 6; i++) info[i] = 0.;
+    info[0] = ml ? Dp.nb : 0; info[1] = gl; info[2] = ml ? h->ml_n[gl] : 0;
+    if (!x || !ml) { UZL_HIP(hipStreamSynchronize(s)); return UZL_OK; }
+    const double lam = debug_lambda(h, lambda);
+    h->ml_ix = 0; h->ml_pending = false;
+    debug_reduce(h, lam);
+    set_lambda(h, lam, tol_factor2(h->cfg));
+    const HostSlot hs = host_slot(h);
+    ml_setup_numeric(h, hs, s, nullptr);
+    kl_ml_trial(hs, h->ml_shape, ml_ns_steps_at(h->ml_ns_steps, 0), s, nullptr);
+    h->ml_trial_setup = true;                                  // (the next solve takes its own inverses)
+    kl_ml_pcg_init(hs, h->ml_shape, s);
+    UZL_HIP(kl_ml_cg(hs, h->ml_shape, 0, 1, s));
+    for (int i = 0; i < k; i++) {
+        kl_ml_spmv(hs, h->ml_shape, i & 1, s);
+        UZL_HIP(kl_ml_cg(hs, h->ml_shape, i & 1, 0, s));
+    }
+    const size_t n6 = (size_t)Dp.nb * 6, g6 = (size_t)h->ml_n[gl] * 6;
+    int32_t fl[4] = {0, 0, 0, 0};
+    UZL_HIP(hipMemcpyAsync(x, Dp.x, sizeof(double) * n6, hipMemcpyDeviceToHost, s));
+    UZL_HIP(hipMemcpyAsync(r, Dp.r, sizeof(double) * n6, hipMemcpyDeviceToHost, s));
+    UZL_HIP(hipMemcpyAsync(z, Dp.z, sizeof(double) * n6, hipMemcpyDeviceToHost, s));
+    UZL_HIP(hipMemcpyAsync(p, h->pbuf[k & 1], sizeof(double) * n6, hipMemcpyDeviceToHost, s));
+    UZL_HIP(hipMemcpyAsync(rg, h->mlb[0].rg[(k & 1) ^ 1], sizeof(double) * g6, hipMemcpyDeviceToHost, s));
+    UZL_HIP(hipMemcpyAsync(fl, Dp.flags, sizeof(fl), hipMemcpyDeviceToHost, s));
+    UZL_HIP(hipGetLastError());
+    UZL_HIP(hipStreamSynchronize(s));
+    info[3] = fl[0]; info[4] = fl[1]; info[5] = lam;
+    return UZL_OK;
+    UZL_GUARD_END(h)
+}
+
+// A handle whose later structures start with the additive dense operator: the state the host-driven loop leaves once the multiplicative
+// operator has broken down on one of its graphs (uzl_pgo::mult_banned).  Call before add_graph / set_graph.
+extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_ban_mult(uzl_pgo* h)
+{
+    UZL_GUARD_BEGIN(h)
+    if (h->have_graph) return fail(h, UZL_ERR_STATE, "ban_mult: before the first graph");
+    h->mult_banned = true;
+    return UZL_OK;
+    UZL_GUARD_END(h)
+}
 #endif  // UZL_DIAG
 
 // =====================================================================================================================
