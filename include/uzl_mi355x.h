@@ -874,6 +874,133 @@ int  uzl_grid_read(uzl_grid* h, int64_t cap, int8_t* data);
 int  uzl_grid_counts(uzl_grid* h, int64_t cap, uint32_t* hits, uint32_t* passes);
 
 /* ======================================================================================
+ *  Laser line from depth images: the scans uzl_grid ray-traces, made on the device
+ *
+ *  GraphGridMapper::extractImageLaserLine (map_projection/src/graph_grid_mapper.cpp:420-468, with
+ *  Conversions::toPointCloud, graph_slam_common/src/conversions.cpp:423-454, and
+ *  transformPointCloudInPlace, :470-478): every LaserScan in the reference's graph comes from it,
+ *  per frame and camera in the front end (feature_extraction_service_node.cpp:249-281: extract,
+ *  mergeLaserScans :135-212 over the cameras, scanMean :605-621 -> scan_center) and over the whole
+ *  stored graph when the map is recomputed from the depth images (convertDepthImages2Map, :214-293).
+ *  Every step below is evaluated in the order written with no fused multiply-add, f32 / f64 as
+ *  stated, sqrt and / correctly rounded; the results equal a NumPy restatement
+ *  (tests/laserline_reference.py) bit for bit.
+ *
+ *  1. Angular grid: amin = (float)(-pi), amax = (float)pi, inc = (float)angle_increment,
+ *     n = (uint32)ceilf((amax - amin) / inc) in f32 (:423-431; the defaults give 720).
+ *     theta_k = (double)amin + (double)k (double)inc for k = 0..n; (c_k, s_k) = (cos, sin)(theta_k)
+ *     from the HOST's libm, uploaded as a table - the table rule of the occupancy grid's step 3, so
+ *     the lower edge of bin k is exactly the direction the grid later projects beam k along.
+ *     UZL_ERR_BAD_ARG for n < 8 or n > 4096, NaN anywhere, range_max < range_min, range_min < 0,
+ *     depth_scale <= 0.
+ *  2. Depth of a pixel: 32FC1: d = the f32.  16UC1: d = (float)((double)v * 0.001)
+ *     (depth_image_to_laserscan.cpp:82-84).  Then, if depth_scale != 1, d = (float)((double)d *
+ *     depth_scale).  A pixel is used iff d > 0 and d is finite (the reference's d > 0 && !isnan(d),
+ *     conversions.cpp:442; an infinite d never passes its height test, so this is the same set).
+ *  3. Camera point (conversions.cpp:443-445): z = d, x = (float)((((double)u - cx) * (double)d) / fx),
+ *     y = (float)((((double)v - cy) * (double)d) / fy), u = column, v = row.
+ *  4. Base-frame point (:470-478): T = (float)camera_transform entry by entry;
+ *     q_a = ((T[a][0] x + T[a][1] y) + T[a][2] z) + T[a][3] in f32 for a = x, y, z.  (Eigen's own
+ *     evaluation order is not in the reference tree: this order is this project's reading.)
+ *  5. Height filter (:447): the point is dropped if q_z is NaN, (double)q_z < min_height or
+ *     (double)q_z > max_height.
+ *  6. Bin.  With X = (double)q_x, Y = (double)q_y, boundary k (k = 0..n) HOLDS the point iff it is
+ *     ahead, fl(c_k X) + fl(s_k Y) > 0, and the point is at or past it, fl(c_k Y) >= fl(s_k X): in
+ *     exact arithmetic, theta_k <= angle of the point < theta_k + 90 degrees (mod 2 pi).
+ *       q_y < 0 (below the x axis):  bin = the smallest k in [0, n) whose boundary holds the point
+ *                                    while boundary k + 1 does not;
+ *       otherwise:                   bin = the largest k in [0, n) whose boundary holds the point;
+ *     no such k (only q_x = q_y = 0 or a non-finite coordinate): the point is dropped.  In exact
+ *     arithmetic this is theta_k <= atan2(q_y, q_x) < theta_k+1, i.e. the reference's
+ *     (int)((angle - angle_min) / angle_increment) (:452-458) without its atan2f: a device atan2f
+ *     differs from the host's by an ulp or two, and a bin index must not depend on that.  The two
+ *     cases differ only at the seam, where the boundaries held wrap around: below the negative
+ *     x axis a point that boundary 0 and (when n inc > 2 pi) boundary n - 1 both claim belongs to
+ *     bin 0, as in the reference; on or above the axis the last boundary of [0, n) that holds the
+ *     point has it.  Deliberate divergences: a point on the negative x axis goes to bin n - 1 for
+ *     y = +0 and y = -0 (the reference computes index n there when n inc = 2 pi and writes past the
+ *     array, or bin 0 for y = -0); points whose f32 atan2f angle rounds across a boundary land one
+ *     bin off (fewer than 1 in 5,000: tests/test_laserline_reference.py).
+ *  7. Nearest and farthest per bin (:459-465): s = q_x q_x + q_y q_y in f32.  ranges[k] =
+ *     sqrtf(min s) over the bin's points if that minimum is < hi hi with hi = (float)range_max + 1.0f
+ *     (f32 product), else hi.  intensities[k] = sqrtf(max s) if that maximum is > 0, else 0.  The
+ *     reference updates sequentially (s < ranges[k] * ranges[k] with ranges[k] already a rounded
+ *     square root); because sqrtf is monotone and fl(r r) is within half an ulp of r^2 the
+ *     sequential result is the same for every order (checked by brute force in the tests), which
+ *     makes the step an order-free integer min / max on the bit patterns of non-negative floats.
+ *  8. Merging the cameras of one node (mergeLaserScans(a, b, Identity), :135-212, called at
+ *     feature_extraction_service_node.cpp:255-260): images carry a group; the scans of one group
+ *     are merged in array order into the first.  Per bin i, with lo = (float)range_min,
+ *     hi0 = (float)range_max, r = b.ranges[i]: skip if r is NaN, r < lo or r > hi0; else with
+ *     a = scan.ranges[i]: a NaN, a == 0 or a > hi0 -> r; else |a - r| < 0.1f -> 0.5f (a + r);
+ *     else -> 0.0f.  Intensities, r = b.intensities[i]: skip if NaN or r < lo (no upper test);
+ *     a NaN, a == 0 or a > hi0 -> r; else |a - r| < 0.1f -> 0.5f (a + r); else if a > r -> 0.0f;
+ *     else unchanged.  Divergence: the reference sends beam i of b through cos, sin (angle
+ *     accumulated in f32), atan2f and sqrt to get its bin and range back; with the same angular
+ *     grid and an identity displacement that is bin i and r up to rounding, and here it is bin i
+ *     and r.
+ *  9. Scan centre (scanMean, :605-621): over the merged scan, beams with r not NaN, r > lo,
+ *     r <= hi0; sum_x += c_i (double)r, sum_y += s_i (double)r in f64 in beam order, divided by the
+ *     count, cast to f32 and back to f64; z = 0; all zero when no beam counts.  Divergence: the
+ *     reference sums in f32 with the angle accumulated in f32.
+ *
+ *  The emitted scan is what :422-433 writes: angle_min = amin, angle_max = amax, angle_increment =
+ *  inc, time_increment = 0, scan_time = (float)(1.0 / 30.0), range_min = lo, range_max = hi0,
+ *  n ranges and n intensities (uzl_wire_scan_sensor_encode puts it on the wire).
+ *
+ *  Device side: a bin kernel streams every pixel once (lanes across columns, 16-byte loads, each
+ *  lane walking down a band of rows with the running min / max of its current bin in registers and
+ *  the workgroup's bins in LDS) and folds into per-image arrays with integer atomic min / max; a
+ *  finish kernel (one workgroup per group) does steps 7-9.  The result does not depend on the
+ *  schedule or on how the images were batched.
+ * ====================================================================================== */
+typedef struct uzl_laserline uzl_laserline;
+typedef struct uzl_laserline_cfg {
+    double  min_height;           /* 0.0     OccupancyGridProjector.cfg "min_height" [m]                         */
+    double  max_height;           /* 1.0     "max_height" [m]                                                     */
+    double  angle_increment;      /* pi/360  "angle_increment" [rad]                                              */
+    double  range_min;            /* 0.45    "range_min" [m]                                                      */
+    double  range_max;            /* 5.0     "range_max" [m]                                                      */
+    double  depth_scale;          /* 1.0     the front end's depth_scale (depth_image_to_laserscan.cpp:50-51)    */
+    int32_t device, _pad;
+} uzl_laserline_cfg;
+#define UZL_DEPTH_F32_M  0   /* sensor_msgs/Image 32FC1, metres      */
+#define UZL_DEPTH_U16_MM 1   /* 16UC1, millimetres                   */
+typedef struct uzl_depth_image {
+    const void* data;             /* borrowed for the call; little-endian                                        */
+    int32_t encoding, width, height, step;   /* step = bytes per row                                             */
+    double  fx, fy, cx, cy;       /* PinholeCameraModel fx() fy() cx() cy()                                      */
+    double  camera_transform[12]; /* base frame <- camera frame, 3x4 row-major                                   */
+    int32_t group, _pad;          /* ascending, contiguous: one output scan per group                            */
+} uzl_depth_image;
+void uzl_laserline_cfg_default(uzl_laserline_cfg* cfg);
+/* UZL_ERR_BAD_ARG for the configs step 1 names; UZL_ERR_NO_DEVICE without a GPU (no CPU fallback) */
+int  uzl_laserline_create(const uzl_laserline_cfg* cfg, uzl_laserline** out);
+void uzl_laserline_destroy(uzl_laserline* h);
+const char* uzl_laserline_last_error(uzl_laserline* h);
+/* Same checks as create; takes effect at the next extract (the resident scans keep the grid they were made with). */
+int  uzl_laserline_set_config(uzl_laserline* h, const uzl_laserline_cfg* cfg);
+/* Steps 1-9 over n_images images; replaces the handle's resident result (the scans stay in HBM until the next extract).
+ * *n_scans = number of groups, *n_beams = n (either may be NULL).  UZL_ERR_BAD_ARG, handle unchanged, for n_images < 0, a NULL
+ * array, an image that is neither width, height > 0 with data nor 0 x 0 with NULL data, step smaller than a row, height * step
+ * beyond 2^31 bytes, an unknown encoding, a non-finite or zero fx / fy, a non-finite cx / cy / transform entry, or groups that are not
+ * ascending and contiguous (each group equals the previous one or is it plus one).  n_images = 0 is valid and yields no scans;
+ * a 0 x 0 image yields an empty scan (every range hi, every intensity 0). */
+int  uzl_laserline_extract(uzl_laserline* h, int32_t n_images, const uzl_depth_image* images, int32_t* n_scans, int32_t* n_beams);
+/* The resident scans: ranges, intensities (n_scans x n f32) and scan_center (3 per scan); any output may be NULL.  Returns the
+ * number of scans; UZL_ERR_TRUNCATED when cap_scans is smaller, UZL_ERR_STATE before any extract. */
+int  uzl_laserline_read(uzl_laserline* h, int32_t cap_scans, float* ranges, float* intensities, double* scan_center);
+/* Append the resident scans to a grid handle's store by device-to-device copy, as uzl_grid_add_scans would with displacement =
+ * identity (feature_extraction_service_node.cpp:272), angle_min = amin, angle_increment = inc, range_min = lo and
+ * node = nodes[i] (one per scan, >= 0): the grid built afterwards equals, bit for bit, the grid built from uzl_laserline_read ->
+ * uzl_grid_add_scans.  This is convertDepthImages2Map with the reference's own scan rule; there the scan is projected at
+ * node.pose_ alone (:258) and camera_transform = displacement * sensor transform (:246) is the caller's to compose.
+ * *first_scan (may be NULL) = index of the first scan in the grid's store.  UZL_ERR_BAD_ARG for a NULL grid, NULL nodes with
+ * scans to add, a negative node, or handles on different devices; UZL_ERR_STATE before any extract.  Locks the laser-line
+ * handle, then the grid handle. */
+int  uzl_laserline_to_grid(uzl_laserline* h, uzl_grid* grid, const int32_t* nodes, int32_t* first_scan);
+
+/* ======================================================================================
  *  Wire and disk formats  
  *
  *  The data formats either side of the path: graph_slam_msgs/{Edge,Node,SensorData,Features,
@@ -1021,6 +1148,32 @@ int  uzl_wire_sensor_scan(const uzl_wire_sensor* s, uzl_wire_scan* out);
 uint64_t uzl_wire_scan_sensor_size(uzl_span sensor_frame, const uzl_wire_scan* scan);
 int  uzl_wire_scan_sensor_encode(uint32_t stamp_sec, uint32_t stamp_nsec, uzl_span sensor_frame, const double* displacement,
                                  const uzl_wire_scan* scan, uint8_t* buf, uint64_t cap, uint64_t* written);
+
+/* SensorData.depth_image (graph_slam_msgs/DepthImage = two sensor_msgs/Image: depth, color) and the pinhole intrinsics of
+ * features.camera_model: what DepthImageData::toMsg writes and fromMsg reads (sensor_data.cpp:194-212).  Spans point into s->raw. */
+typedef struct uzl_wire_depth {
+    uint32_t seq, stamp_sec, stamp_nsec;  /* depth.header                                                        */
+    uzl_span frame_id;
+    uint32_t height, width, step;         /* sensor_msgs/Image order is height, width, encoding, is_bigendian, step */
+    uzl_span encoding;                    /* "32FC1", "16UC1", ...                                                 */
+    int32_t  is_bigendian;
+    uzl_span data;
+    uzl_span color;                       /* the color image as one raw sensor_msgs/Image; encode: NULL = default-constructed */
+    double   fx, fy, cx, cy;              /* P[0], P[5], P[2], P[6] of the CameraInfo (decode only)                */
+} uzl_wire_depth;
+/* The depth image of a decoded sensor (any type; re-parsed from s->raw).  fx .. cy follow image_geometry::PinholeCameraModel::
+ * fromCameraInfo (not in the reference tree) for binning 0 or 1 and an empty ROI (offsets, height and width 0); any other
+ * binning or ROI: UZL_ERR_UNSUPPORTED (*out is filled except fx .. cy).  Truncated input: UZL_ERR_TRUNCATED. */
+int  uzl_wire_sensor_depth(const uzl_wire_sensor* s, uzl_wire_depth* out);
+/* The decoded depth image as uzl_laserline_extract takes it (data borrowed from the message): encoding "32FC1" / "16UC1",
+ * little-endian, data of at least height * step bytes; anything else: UZL_ERR_UNSUPPORTED.  camera_transform = 12 doubles. */
+int  uzl_wire_depth_image(const uzl_wire_depth* d, const double* camera_transform, int32_t group, uzl_depth_image* out);
+/* A SENSOR_TYPE_DEPTH_IMAGE SensorData as SensorData::toMsg + DepthImageData::toMsg write it (sensor_data.cpp:40-49, 194-203):
+ * header (stamp, frame_id = sensor_frame), displacement, the depth image, the color image verbatim or default-constructed,
+ * camera_info (raw sensor_msgs/CameraInfo bytes) verbatim or default-constructed; features, gist and scan empty. */
+uint64_t uzl_wire_depth_sensor_size(uzl_span sensor_frame, const uzl_wire_depth* depth, uzl_span camera_info);
+int  uzl_wire_depth_sensor_encode(uint32_t stamp_sec, uint32_t stamp_nsec, uzl_span sensor_frame, const double* displacement,
+                                  const uzl_wire_depth* depth, uzl_span camera_info, uint8_t* buf, uint64_t cap, uint64_t* written);
 
 /* bytes of n Feature records with desc_len descriptor elements each */
 uint64_t uzl_wire_features_size(int32_t n, int32_t desc_len);

@@ -206,6 +206,20 @@ class GridInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class LaserlineCfg(C.Structure):
+    _fields_ = [("min_height", C.c_double), ("max_height", C.c_double), ("angle_increment", C.c_double), ("range_min", C.c_double),
+                ("range_max", C.c_double), ("depth_scale", C.c_double), ("device", C.c_int32), ("_pad", C.c_int32)]
+
+
+DEPTH_F32_M, DEPTH_U16_MM = 0, 1
+
+
+class DepthImage(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("encoding", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("step", C.c_int32),
+                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("camera_transform", C.c_double * 12), ("group", C.c_int32), ("_pad", C.c_int32)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
 
 _lib = None
@@ -231,7 +245,7 @@ def lib():
 
 
 _HANDLES = ("uzl_match", "uzl_pgo", "uzl_pgo_batch", "uzl_filter", "uzl_gate", "uzl_radius", "uzl_places", "uzl_gist")
-_MORE_HANDLES = ("uzl_grid",)       # declared like _HANDLES; kept apart because tests pin _HANDLES to the first eight
+_MORE_HANDLES = ("uzl_grid", "uzl_laserline")       # declared like _HANDLES; kept apart because tests pin _HANDLES to the first eight
 
 
 def _declare(L):
@@ -1147,3 +1161,60 @@ class Grid(_Handle):
         u32p = C.POINTER(C.c_uint32)
         self._check(lib().uzl_grid_counts(self._h, C.c_int64(n), hits.ctypes.data_as(u32p), passes.ctypes.data_as(u32p)))
         return hits.reshape(i["height"], i["width"]), passes.reshape(i["height"], i["width"])
+
+
+class Laserline(_Handle):
+    """uzl_laserline_* (GraphGridMapper::extractImageLaserLine + mergeLaserScans + scanMean, map_projection/src/graph_grid_mapper.cpp:
+    420-468, 135-212, 605-621): depth images binned by bearing into the laser scans the occupancy grid ray-traces."""
+
+    _prefix, _cfg_type = "uzl_laserline", LaserlineCfg
+    set_config = _Handle._set_config
+
+    @staticmethod
+    def pack_images(images):
+        """images: dicts with depth (2-D float32 = 32FC1 metres, or uint16 = 16UC1 millimetres; rows may be strided), fx, fy, cx, cy,
+        camera_transform (12 or 3x4) and optionally group (default: the image's index, one scan per image)
+        -> (DepthImage array, the pixel arrays it points into)"""
+        arr = (DepthImage * max(len(images), 1))()
+        keep = []
+        for i, im in enumerate(images):
+            d = np.asarray(im["depth"])
+            if d.ndim != 2 or d.dtype not in (np.float32, np.uint16):
+                raise ValueError("a depth image is a 2-D float32 or uint16 array")
+            if d.size and (d.strides[1] != d.itemsize or d.strides[0] < d.shape[1] * d.itemsize):
+                d = np.ascontiguousarray(d)
+            keep.append(d)
+            g = arr[i]
+            g.encoding = DEPTH_F32_M if d.dtype == np.float32 else DEPTH_U16_MM
+            if d.size:
+                g.data = d.ctypes.data; g.height, g.width = d.shape; g.step = d.strides[0]
+            g.fx, g.fy, g.cx, g.cy = float(im["fx"]), float(im["fy"]), float(im["cx"]), float(im["cy"])
+            g.camera_transform[:] = np.asarray(im["camera_transform"], np.float64).reshape(12).tolist()
+            g.group = int(im.get("group", i))
+        return arr, keep
+
+    _shape = (0, 0)                   # (scans, beams) of the resident result
+
+    def extract(self, images):
+        """-> (ranges, intensities: float32 (n_scans, n_beams); scan centres: float64 (n_scans, 3)); the scans stay on the device.
+        images: a list of dicts, or what pack_images made of one"""
+        arr, keep = images if isinstance(images, tuple) else self.pack_images(images)
+        ns, nb = C.c_int32(0), C.c_int32(0)
+        self._check(lib().uzl_laserline_extract(self._h, C.c_int32(len(keep)), arr, C.byref(ns), C.byref(nb)))
+        self._shape = (ns.value, nb.value)
+        return self.read()
+
+    def read(self):
+        """the resident scans, as extract returns them"""
+        ns, nb = self._shape
+        f32p = C.POINTER(C.c_float)
+        r = np.zeros((ns, nb), np.float32); it = np.zeros((ns, nb), np.float32); ce = np.zeros((ns, 3), np.float64)
+        self._check(lib().uzl_laserline_read(self._h, C.c_int32(ns), _p(r, f32p), _p(it, f32p), _p(ce, c_f64p)))
+        return r, it, ce
+
+    def to_grid(self, grid, nodes):
+        """append the resident scans to a Grid's store on the device (scan i at node nodes[i]) -> index of the first scan added"""
+        nd = np.ascontiguousarray(nodes, np.int32).reshape(-1)
+        first = C.c_int32(-1)
+        self._check(lib().uzl_laserline_to_grid(self._h, grid._h, _p(nd, c_i32p) if len(nd) else None, C.byref(first)))
+        return first.value

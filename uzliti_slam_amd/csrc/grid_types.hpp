@@ -53,6 +53,11 @@ struct GridStatsArgs {
 void launch_grid_tiles(const GridTileArgs& a, int n_tiles, hipStream_t s);
 void launch_grid_stats(const GridStatsArgs& a, int n_scans, hipStream_t s);
 
+// Append scans that already lie in device memory to a grid handle's store (uzl_grid.hip; used by uzl_laserline_to_grid).  Takes the
+// grid handle's lock; failures are reported through the grid handle's last_error.
+int grid_append_device(uzl_grid* h, int device, int32_t n_scans, int32_t n_beams, const float* d_ranges, float angle_min,
+                       float angle_increment, float range_min, const int32_t* nodes, int32_t* first_scan);
+
 // The part of the ray cell(o) = (x0, y0) -> (x1, y1) (steps 0..L of contract step 5) inside the cell rectangle [ux0, ux1] x
 // [uy0, uy1]: calls visit(x, y) for exactly those cells, in walk order.  Bresenham's state after k steps in closed form: with
 // L = max(|dx|, |dy|) and m = min, the major coordinate moves every step and the minor one has moved floor((2 m k + L) / (2 L))

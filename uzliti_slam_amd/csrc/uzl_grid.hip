@@ -215,6 +215,62 @@ int plan(uzl_grid* h, const uzl_grid_cfg& c, const GridGeom& g, int32_t n_nodes,
     return UZL_OK;
 }
 
+// One scan to append: what uzl_grid_scan says about it, without its ranges.
+struct ScanIn {
+    int32_t node, n;
+    const double* D;
+    float angle_min, angle_increment, range_min;
+};
+
+// Append checked scans to the store: new (cos, sin) tables from the host's libm (contract step 3), the arenas grown, the `total`
+// ranges put at the arena's end by copy(dst, stream) - from the host (uzl_grid_add_scans) or from device memory
+// (grid_append_device) - and the bookkeeping, which changes only when everything before it succeeded.
+template <typename Copy>
+void append(uzl_grid* h, const std::vector<ScanIn>& in, int64_t total, int32_t* first_scan, Copy&& copy)
+{
+    const int32_t n = (int32_t)in.size();
+    UZL_HIP(hipSetDevice(h->cfg.device));
+    hipStream_t st = h->stream;
+    std::vector<double2> trig;
+    std::vector<int64_t> toff(n);
+    auto tables = h->tables;
+    int64_t n_trig = h->n_trig;
+    for (int32_t i = 0; i < n; i++) {
+        const ScanIn& s = in[i];
+        uint32_t ka, ki;
+        memcpy(&ka, &s.angle_min, 4); memcpy(&ki, &s.angle_increment, 4);
+        const auto key = std::make_tuple(ka, ki, s.n);
+        auto it = tables.find(key);
+        if (it == tables.end()) {
+            it = tables.emplace(key, n_trig).first;
+            for (int32_t b = 0; b < s.n; b++) {
+                const double th = (double)s.angle_min + (double)b * (double)s.angle_increment;
+                trig.push_back(make_double2(std::cos(th), std::sin(th)));
+            }
+            n_trig += s.n;
+        }
+        toff[i] = it->second;
+    }
+    h->d_ranges.reserve((size_t)std::max<int64_t>(h->n_ranges + total, 1), true, st);
+    h->d_trig.reserve((size_t)std::max<int64_t>(n_trig, 1), true, st);
+    if (!trig.empty())
+        UZL_HIP(hipMemcpyAsync(h->d_trig.p + h->n_trig, trig.data(), trig.size() * sizeof(double2), hipMemcpyHostToDevice, st));
+    if (total) copy(h->d_ranges.p + h->n_ranges, st);
+    UZL_HIP(hipStreamSynchronize(st));
+    if (first_scan) *first_scan = (int32_t)h->scans.size();
+    int64_t o = h->n_ranges;
+    for (int32_t i = 0; i < n; i++) {
+        GridScanHost g;
+        g.node = in[i].node; g.n = in[i].n; memcpy(g.D, in[i].D, sizeof(g.D));
+        g.range_min = in[i].range_min; g.ranges_off = o; g.trig_off = toff[i];
+        o += g.n;
+        h->scans.push_back(g);
+    }
+    h->n_ranges = o;
+    h->tables.swap(tables);
+    h->n_trig = n_trig;
+}
+
 size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
 // Upload the plan in one copy and run it; fills the call's totals into h->info.
@@ -372,6 +428,7 @@ int uzl_grid_add_scans(uzl_grid* h, int32_t n, const uzl_grid_scan* scans, int32
 {
     UZL_GUARD_BEGIN(h)
     if (n < 0 || (n > 0 && !scans)) return fail(h, UZL_ERR_BAD_ARG, "bad scan count or null scans");
+    std::vector<ScanIn> in(n);
     int64_t total = 0;
     for (int32_t i = 0; i < n; i++) {
         const uzl_grid_scan& s = scans[i];
@@ -379,56 +436,17 @@ int uzl_grid_add_scans(uzl_grid* h, int32_t n, const uzl_grid_scan* scans, int32
         if (!std::isfinite(s.angle_min) || !std::isfinite(s.angle_increment) || !finite12(s.displacement))
             return fail(h, UZL_ERR_BAD_ARG, "non-finite scan angle or displacement");
         if (!(s.range_min >= 0.f)) return fail(h, UZL_ERR_BAD_ARG, "range_min negative or NaN");
+        in[i] = ScanIn{s.node, s.n_ranges, s.displacement, s.angle_min, s.angle_increment, s.range_min};
         total += s.n_ranges;
     }
     if (h->n_ranges + total >= ((int64_t)1 << 40)) return fail(h, UZL_ERR_BAD_ARG, "too many ranges");
-    UZL_HIP(hipSetDevice(h->cfg.device));
-    hipStream_t st = h->stream;
-    // new (cos, sin) tables, host libm (contract step 3)
-    std::vector<double2> trig;
-    std::vector<int64_t> toff(n);
-    auto tables = h->tables;
-    int64_t n_trig = h->n_trig;
-    for (int32_t i = 0; i < n; i++) {
-        const uzl_grid_scan& s = scans[i];
-        uint32_t ka, ki;
-        memcpy(&ka, &s.angle_min, 4); memcpy(&ki, &s.angle_increment, 4);
-        const auto key = std::make_tuple(ka, ki, s.n_ranges);
-        auto it = tables.find(key);
-        if (it == tables.end()) {
-            it = tables.emplace(key, n_trig).first;
-            for (int32_t b = 0; b < s.n_ranges; b++) {
-                const double th = (double)s.angle_min + (double)b * (double)s.angle_increment;
-                trig.push_back(make_double2(std::cos(th), std::sin(th)));
-            }
-            n_trig += s.n_ranges;
-        }
-        toff[i] = it->second;
-    }
-    h->d_ranges.reserve((size_t)std::max<int64_t>(h->n_ranges + total, 1), true, st);
-    h->d_trig.reserve((size_t)std::max<int64_t>(n_trig, 1), true, st);
-    if (!trig.empty())
-        UZL_HIP(hipMemcpyAsync(h->d_trig.p + h->n_trig, trig.data(), trig.size() * sizeof(double2), hipMemcpyHostToDevice, st));
-    if (total) {
+    append(h, in, total, first_scan, [&](float* dst, hipStream_t st) {
         h->h_work.reserve((size_t)total * 4);
         float* w = reinterpret_cast<float*>(h->h_work.p);
         int64_t o = 0;
         for (int32_t i = 0; i < n; i++) { memcpy(w + o, scans[i].ranges, (size_t)scans[i].n_ranges * 4); o += scans[i].n_ranges; }
-        UZL_HIP(hipMemcpyAsync(h->d_ranges.p + h->n_ranges, w, (size_t)total * 4, hipMemcpyHostToDevice, st));
-    }
-    UZL_HIP(hipStreamSynchronize(st));
-    if (first_scan) *first_scan = (int32_t)h->scans.size();
-    int64_t o = h->n_ranges;
-    for (int32_t i = 0; i < n; i++) {
-        GridScanHost g;
-        g.node = scans[i].node; g.n = scans[i].n_ranges; memcpy(g.D, scans[i].displacement, sizeof(g.D));
-        g.range_min = scans[i].range_min; g.ranges_off = o; g.trig_off = toff[i];
-        o += g.n;
-        h->scans.push_back(g);
-    }
-    h->n_ranges = o;
-    h->tables.swap(tables);
-    h->n_trig = n_trig;
+        UZL_HIP(hipMemcpyAsync(dst, w, (size_t)total * 4, hipMemcpyHostToDevice, st));
+    });
     return UZL_OK;
     UZL_GUARD_END(h)
 }
@@ -515,3 +533,30 @@ int uzl_grid_counts(uzl_grid* h, int64_t cap, uint32_t* hits, uint32_t* passes)
 }
 
 }  // extern "C"
+
+// uzl_laserline_to_grid's way into the store (declared in grid_types.hpp): n_scans scans of n_beams ranges each, contiguous in the
+// memory of `device` and complete (the caller has synchronised their producer), appended as uzl_grid_add_scans appends scans
+// with an identity displacement.
+int uzl::grid_append_device(uzl_grid* h, int device, int32_t n_scans, int32_t n_beams, const float* d_ranges, float angle_min,
+                            float angle_increment, float range_min, const int32_t* nodes, int32_t* first_scan)
+{
+    UZL_GUARD_BEGIN(h)
+    if (device != h->cfg.device) return fail(h, UZL_ERR_BAD_ARG, "the scans are on another device than the grid");
+    if (n_scans < 0 || n_beams < 0 || (n_scans > 0 && (!nodes || (n_beams > 0 && !d_ranges))))
+        return fail(h, UZL_ERR_BAD_ARG, "bad scan count or null scans");
+    static const double I[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    std::vector<ScanIn> in(n_scans);
+    for (int32_t i = 0; i < n_scans; i++) {
+        if (nodes[i] < 0) return fail(h, UZL_ERR_BAD_ARG, "bad scan node / ranges");
+        in[i] = ScanIn{nodes[i], n_beams, I, angle_min, angle_increment, range_min};
+    }
+    if (!std::isfinite(angle_min) || !std::isfinite(angle_increment)) return fail(h, UZL_ERR_BAD_ARG, "non-finite scan angle or displacement");
+    if (!(range_min >= 0.f)) return fail(h, UZL_ERR_BAD_ARG, "range_min negative or NaN");
+    const int64_t total = (int64_t)n_scans * n_beams;
+    if (h->n_ranges + total >= ((int64_t)1 << 40)) return fail(h, UZL_ERR_BAD_ARG, "too many ranges");
+    append(h, in, total, first_scan, [&](float* dst, hipStream_t st) {
+        UZL_HIP(hipMemcpyAsync(dst, d_ranges, (size_t)total * 4, hipMemcpyDeviceToDevice, st));
+    });
+    return UZL_OK;
+    UZL_GUARD_END(h)
+}

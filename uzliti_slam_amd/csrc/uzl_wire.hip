@@ -162,6 +162,40 @@ void skip_image(Reader& r)            // sensor_msgs/Image
     r.skip_array<uint8_t>();
 }
 void put_default_image(Writer& w) { w.zeros(16 + 8 + 4 + 1 + 4 + 4); }
+// sensor_msgs/CameraInfo as PinholeCameraModel::fromCameraInfo uses it: P, binning and the region of interest
+struct CameraModel { double P[12]; uint32_t binning_x, binning_y, roi[4]; };
+void get_camera_info(Reader& r, CameraModel* m)
+{
+    get_header(r);
+    r.skip(8);
+    r.str();
+    r.skip_array<double>();
+    r.skip((9 + 9) * 8);
+    for (int i = 0; i < 12; i++) m->P[i] = r.get<double>();
+    m->binning_x = r.get<uint32_t>(); m->binning_y = r.get<uint32_t>();
+    for (int i = 0; i < 4; i++) m->roi[i] = r.get<uint32_t>();
+    r.skip(1);                        // do_rectify
+}
+void get_image(Reader& r, uzl_wire_depth* out)         // sensor_msgs/Image, field for field
+{
+    const Header h = get_header(r);
+    out->seq = h.seq; out->stamp_sec = h.sec; out->stamp_nsec = h.nsec; out->frame_id = h.frame_id;
+    out->height = r.get<uint32_t>(); out->width = r.get<uint32_t>();
+    out->encoding = r.str();
+    out->is_bigendian = (int32_t)r.get<uint8_t>();
+    out->step = r.get<uint32_t>();
+    const uint32_t nd = r.get<uint32_t>();
+    out->data = r.bytes(nd);
+}
+void put_image(Writer& w, const uzl_wire_depth& d)
+{
+    w.val<uint32_t>(d.seq); w.val(d.stamp_sec); w.val(d.stamp_nsec); w.str(d.frame_id);
+    w.val<uint32_t>(d.height); w.val<uint32_t>(d.width);
+    w.str(d.encoding);
+    w.val<uint8_t>((uint8_t)d.is_bigendian);
+    w.val<uint32_t>(d.step);
+    w.val<uint32_t>(d.data.p ? (uint32_t)d.data.n : 0u); w.span(d.data);
+}
 void skip_laser_scan(Reader& r)       // sensor_msgs/LaserScan
 {
     get_header(r);
@@ -194,7 +228,8 @@ constexpr uint64_t kFeatureFixed = 4 + 4 + 1 + 4 + 4 + 24;       // u, v, is_3d,
 
 // graph_slam_msgs/SensorData (SensorData.msg): fields in declaration order; gist (may be NULL) receives the gist_descriptor
 // elements (4 bytes each)
-void get_sensor(Reader& r, uzl_wire_sensor* out, uzl_span* gist = nullptr, uzl_wire_scan* scan = nullptr)
+void get_sensor(Reader& r, uzl_wire_sensor* out, uzl_span* gist = nullptr, uzl_wire_scan* scan = nullptr, uzl_wire_depth* depth = nullptr,
+                CameraModel* model = nullptr)
 {
     uzl_wire_sensor s;
     memset(&s, 0, sizeof(s));
@@ -220,9 +255,16 @@ void get_sensor(Reader& r, uzl_wire_sensor* out, uzl_span* gist = nullptr, uzl_w
     s.n_features = (int32_t)nf;
     if (r.ok) { s.records.p = reinterpret_cast<const char*>(r.b + rec0); s.records.n = r.o - rec0; }
     const uint64_t cam0 = r.o;
-    skip_camera_info(r);
+    if (model) get_camera_info(r, model); else skip_camera_info(r);
     if (r.ok) { s.camera_info.p = reinterpret_cast<const char*>(r.b + cam0); s.camera_info.n = r.o - cam0; }
-    skip_image(r); skip_image(r);                                                // DepthImage: depth, color
+    if (depth) {                                                                 // DepthImage: depth, color
+        get_image(r, depth);
+        const uint64_t col0 = r.o;
+        skip_image(r);
+        if (r.ok) { depth->color.p = reinterpret_cast<const char*>(r.b + col0); depth->color.n = r.o - col0; }
+    } else {
+        skip_image(r); skip_image(r);
+    }
     const uint32_t ng = r.get<uint32_t>();                                       // gist_descriptor
     const uzl_span g = r.bytes((uint64_t)ng * 4);
     if (gist) *gist = g;
@@ -292,6 +334,26 @@ void put_scan_sensor(Writer& w, uint32_t sec, uint32_t nsec, const uzl_span& fra
     w.val<uint32_t>(0);
     put_laser_scan(w, scan);
     for (int i = 0; i < 3; i++) w.val(scan.scan_center[i]);
+}
+
+// SensorData::toMsg (sensor_data.cpp:40-49) + DepthImageData::toMsg (:194-203): a SENSOR_TYPE_DEPTH_IMAGE message; features, gist and scan
+// empty, the camera info and the color image verbatim or default-constructed
+void put_depth_sensor(Writer& w, uint32_t sec, uint32_t nsec, const uzl_span& frame, const double displacement[12], const uzl_wire_depth& d,
+                      const uzl_span& camera_info)
+{
+    put_header(w, sec, nsec, frame);
+    w.val<int32_t>(UZL_SENSOR_TYPE_DEPTH_IMAGE);
+    put_pose(w, displacement);
+    w.str(frame);
+    put_header(w, 0, 0, uzl_span{nullptr, 0});
+    w.val<int32_t>(0);
+    w.val<uint32_t>(0);
+    if (camera_info.p) w.span(camera_info); else put_default_camera_info(w);
+    put_image(w, d);
+    if (d.color.p) w.span(d.color); else put_default_image(w);
+    w.val<uint32_t>(0);
+    put_default_laser_scan(w);
+    w.zeros(24);
 }
 
 // `(unsigned char) msg.gist_descriptor[i]` of BinaryGistData::fromMsg (sensor_data.cpp:238-246), the rule of the Feature unpack
@@ -752,6 +814,68 @@ int uzl_wire_scan_sensor_encode(uint32_t stamp_sec, uint32_t stamp_nsec, uzl_spa
     if (!displacement || !scan_ok(scan) || !buf || (sensor_frame.n && !sensor_frame.p)) return UZL_ERR_BAD_ARG;
     Writer w(buf, cap);
     put_scan_sensor(w, stamp_sec, stamp_nsec, sensor_frame, displacement, *scan);
+    if (written) *written = w.o;
+    return w.fits() ? UZL_OK : UZL_ERR_TRUNCATED;
+}
+
+int uzl_wire_sensor_depth(const uzl_wire_sensor* s, uzl_wire_depth* out)
+{
+    if (!s || !s->raw.p || !out) return UZL_ERR_BAD_ARG;
+    Reader r(reinterpret_cast<const uint8_t*>(s->raw.p), s->raw.n);
+    uzl_wire_depth d;
+    memset(&d, 0, sizeof(d));
+    CameraModel m;
+    memset(&m, 0, sizeof(m));
+    get_sensor(r, nullptr, nullptr, nullptr, &d, &m);
+    if (!r.ok) return UZL_ERR_TRUNCATED;
+    *out = d;
+    if (m.binning_x > 1 || m.binning_y > 1 || m.roi[0] || m.roi[1] || m.roi[2] || m.roi[3]) return UZL_ERR_UNSUPPORTED;
+    out->fx = m.P[0]; out->fy = m.P[5]; out->cx = m.P[2]; out->cy = m.P[6];
+    return UZL_OK;
+}
+
+int uzl_wire_depth_image(const uzl_wire_depth* d, const double* camera_transform, int32_t group, uzl_depth_image* out)
+{
+    if (!d || !camera_transform || !out) return UZL_ERR_BAD_ARG;
+    int32_t enc, bpp;
+    if (d->encoding.n == 5 && d->encoding.p && memcmp(d->encoding.p, "32FC1", 5) == 0) { enc = UZL_DEPTH_F32_M; bpp = 4; }
+    else if (d->encoding.n == 5 && d->encoding.p && memcmp(d->encoding.p, "16UC1", 5) == 0) { enc = UZL_DEPTH_U16_MM; bpp = 2; }
+    else return UZL_ERR_UNSUPPORTED;
+    if (d->is_bigendian) return UZL_ERR_UNSUPPORTED;
+    if (d->width > 0x7fffffffu / 4 || d->height > 0x7fffffffu || d->step > 0x7fffffffu) return UZL_ERR_UNSUPPORTED;
+    if ((uint64_t)d->step < (uint64_t)d->width * bpp || (uint64_t)d->height * d->step > d->data.n) return UZL_ERR_TRUNCATED;
+    memset(out, 0, sizeof(*out));
+    const bool any = d->width > 0 && d->height > 0;
+    out->data = any ? d->data.p : nullptr;
+    out->encoding = enc;
+    out->width = any ? (int32_t)d->width : 0; out->height = any ? (int32_t)d->height : 0; out->step = any ? (int32_t)d->step : 0;
+    out->fx = d->fx; out->fy = d->fy; out->cx = d->cx; out->cy = d->cy;
+    memcpy(out->camera_transform, camera_transform, sizeof(out->camera_transform));
+    out->group = group;
+    return UZL_OK;
+}
+
+static bool depth_ok(const uzl_wire_depth* d, const uzl_span& camera_info)
+{
+    return d && !(d->frame_id.n && !d->frame_id.p) && !(d->encoding.n && !d->encoding.p) && !(d->data.n && !d->data.p) &&
+           !(d->color.n && !d->color.p) && d->data.n <= 0xffffffffull && !(camera_info.n && !camera_info.p);
+}
+
+uint64_t uzl_wire_depth_sensor_size(uzl_span sensor_frame, const uzl_wire_depth* depth, uzl_span camera_info)
+{
+    if (!depth_ok(depth, camera_info)) return 0;
+    Writer w(nullptr, 0);
+    const double I[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    put_depth_sensor(w, 0, 0, sensor_frame, I, *depth, camera_info);
+    return w.o;
+}
+
+int uzl_wire_depth_sensor_encode(uint32_t stamp_sec, uint32_t stamp_nsec, uzl_span sensor_frame, const double* displacement,
+                                 const uzl_wire_depth* depth, uzl_span camera_info, uint8_t* buf, uint64_t cap, uint64_t* written)
+{
+    if (!displacement || !depth_ok(depth, camera_info) || !buf || (sensor_frame.n && !sensor_frame.p)) return UZL_ERR_BAD_ARG;
+    Writer w(buf, cap);
+    put_depth_sensor(w, stamp_sec, stamp_nsec, sensor_frame, displacement, *depth, camera_info);
     if (written) *written = w.o;
     return w.fits() ? UZL_OK : UZL_ERR_TRUNCATED;
 }

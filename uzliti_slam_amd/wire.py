@@ -15,6 +15,7 @@ from . import capi
 UZL_ERR_TRUNCATED = -9
 UZL_ERR_UNSUPPORTED = -10
 SENSOR_TYPE_FEATURE = 1
+SENSOR_TYPE_DEPTH_IMAGE = 2
 SENSOR_TYPE_BINARY_GIST = 3
 SENSOR_TYPE_LASERSCAN = 4
 
@@ -43,6 +44,12 @@ class WireScan(C.Structure):
                 ("angle_min", C.c_float), ("angle_max", C.c_float), ("angle_increment", C.c_float), ("time_increment", C.c_float),
                 ("scan_time", C.c_float), ("range_min", C.c_float), ("range_max", C.c_float), ("n_ranges", C.c_int32),
                 ("n_intensities", C.c_int32), ("ranges", Span), ("intensities", Span), ("scan_center", C.c_double * 3)]
+
+
+class WireDepth(C.Structure):
+    _fields_ = [("seq", C.c_uint32), ("stamp_sec", C.c_uint32), ("stamp_nsec", C.c_uint32), ("frame_id", Span),
+                ("height", C.c_uint32), ("width", C.c_uint32), ("step", C.c_uint32), ("encoding", Span), ("is_bigendian", C.c_int32),
+                ("data", Span), ("color", Span), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double)]
 
 
 _SCAN_F32 = ("angle_min", "angle_max", "angle_increment", "time_increment", "scan_time", "range_min", "range_max")
@@ -76,7 +83,7 @@ def _lib():
     L = capi.lib()
     if not _proto_done:
         for f in ("uzl_wire_edge_size", "uzl_wire_node_size", "uzl_wire_meta_size", "uzl_wire_features_size", "uzl_bag_single_size",
-                  "uzl_wire_gist_sensor_size", "uzl_wire_scan_sensor_size"):
+                  "uzl_wire_gist_sensor_size", "uzl_wire_scan_sensor_size", "uzl_wire_depth_sensor_size"):
             getattr(L, f).restype = C.c_uint64
         L.uzl_wire_scan_sensor_size.argtypes = [Span, C.c_void_p]
         L.uzl_wire_scan_sensor_encode.argtypes = [C.c_uint32, C.c_uint32, Span, C.POINTER(C.c_double), C.c_void_p, C.POINTER(C.c_uint8),
@@ -84,6 +91,9 @@ def _lib():
         L.uzl_wire_gist_sensor_size.argtypes = [Span, C.c_int32]
         L.uzl_wire_gist_sensor_encode.argtypes = [C.c_uint32, C.c_uint32, Span, C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.c_int32,
                                                   C.POINTER(C.c_uint8), C.c_uint64, C.POINTER(C.c_uint64)]
+        L.uzl_wire_depth_sensor_size.argtypes = [Span, C.c_void_p, Span]
+        L.uzl_wire_depth_sensor_encode.argtypes = [C.c_uint32, C.c_uint32, Span, C.POINTER(C.c_double), C.c_void_p, Span,
+                                                   C.POINTER(C.c_uint8), C.c_uint64, C.POINTER(C.c_uint64)]
         _proto_done = True
     return L
 
@@ -333,6 +343,54 @@ def encode_scan_sensor(stamp_sec, stamp_nsec, sensor_frame, displacement, scan):
     wr = C.c_uint64(0)
     _check(L.uzl_wire_scan_sensor_encode(stamp_sec, stamp_nsec, fr, disp, C.byref(w), buf, C.c_uint64(size), C.byref(wr)),
            "scan_sensor_encode")
+    assert wr.value == size
+    return bytes(buf)[:size]
+
+
+_DEPTH_NUM = ("seq", "stamp_sec", "stamp_nsec", "height", "width", "step", "is_bigendian")
+
+
+def sensor_depth(sensor_c, camera_transform=None, group=0):
+    """SensorData.depth_image and the pinhole intrinsics of a decoded sensor (a WireSensor of DecodedNode.sensors_c), as
+    DepthImageData::fromMsg reads them (sensor_data.cpp:205-212): a dict of the depth Image's fields (`data` bytes, `color` = the
+    raw color Image) with fx, fy, cx, cy.  With camera_transform it also carries `image`: the dict capi.Laserline.extract takes
+    (depth as a numpy view of the message's pixels); UZL_ERR_UNSUPPORTED for encodings other than 32FC1 / 16UC1."""
+    L = _lib()
+    w = WireDepth()
+    _check(L.uzl_wire_sensor_depth(C.byref(sensor_c), C.byref(w)), "sensor_depth")
+    d = {k: getattr(w, k) for k in _DEPTH_NUM + ("fx", "fy", "cx", "cy")}
+    d.update(frame_id=_bytes(w.frame_id), encoding=_bytes(w.encoding), data=_bytes(w.data), color=_bytes(w.color))
+    if camera_transform is not None:
+        im = capi.DepthImage()
+        T = (C.c_double * 12)(*_arr(camera_transform, 12))
+        _check(L.uzl_wire_depth_image(C.byref(w), T, C.c_int32(group), C.byref(im)), "depth_image")
+        dt = np.dtype("<f4") if im.encoding == capi.DEPTH_F32_M else np.dtype("<u2")
+        rows = np.frombuffer(d["data"], np.uint8, im.height * im.step).reshape(im.height, im.step) if im.height else np.zeros((0, 0), np.uint8)
+        depth = rows[:, :im.width * dt.itemsize].view(dt) if im.height else np.zeros((0, 0), dt)
+        d["image"] = dict(depth=depth, fx=im.fx, fy=im.fy, cx=im.cx, cy=im.cy, camera_transform=np.array(im.camera_transform[:]),
+                          group=im.group)
+    return d
+
+
+def encode_depth_sensor(stamp_sec, stamp_nsec, sensor_frame, displacement, depth, camera_info=None):
+    """A SENSOR_TYPE_DEPTH_IMAGE graph_slam_msgs/SensorData (SensorData::toMsg + DepthImageData::toMsg); depth = dict as
+    sensor_depth returns (missing fields default to 0 / empty; `color` = raw sensor_msgs/Image bytes or None), camera_info = raw
+    sensor_msgs/CameraInfo bytes or None.  The bytes go into a sensor dict's `raw` for encode_node."""
+    L = _lib()
+    k = _Keep()
+    w = WireDepth()
+    for f in _DEPTH_NUM:
+        setattr(w, f, int(depth.get(f, 0)))
+    w.frame_id = k.span(depth.get("frame_id")); w.encoding = k.span(depth.get("encoding"))
+    w.data = k.span(depth.get("data") or None); w.color = k.span(depth.get("color") or None)
+    fr = k.span(sensor_frame)
+    ci = k.span(camera_info or None)
+    disp = (C.c_double * 12)(*_arr(displacement, 12))
+    size = L.uzl_wire_depth_sensor_size(fr, C.byref(w), ci)
+    buf = (C.c_uint8 * max(size, 1))()
+    wr = C.c_uint64(0)
+    _check(L.uzl_wire_depth_sensor_encode(stamp_sec, stamp_nsec, fr, disp, C.byref(w), ci, buf, C.c_uint64(size), C.byref(wr)),
+           "depth_sensor_encode")
     assert wr.value == size
     return bytes(buf)[:size]
 
