@@ -48,7 +48,7 @@ def fans_of(h):
 
 
 def check_structure(h):
-    """build_ml (host), exact: n_l = ceil(n_{l-1} / fan_l); fans 8, and 4 at level 2 iff agg = 4; the slots of level l+1 are exactly the
+    """ml_plan (host), exact: n_l = ceil(n_{l-1} / fan_l); fans 8, and 4 at level 2 iff agg = 4; the slots of level l+1 are exactly the
     pairs of aggregates joined by a level-l slot, sorted by column."""
     L = h["levels"]
     lv = h["lv"]

@@ -1,5 +1,5 @@
 """Admission boundaries of the dense level-2 operator's PCG variant (csrc/pgo_types.hpp: kMlLdsLimit, ml_comp4_lds; pgo_ml_kernels.hip:
-ml_comp4_fits) - ONE statement of the LDS budget that build_ml, ml_cg_variant and ml_fits_lds read (round 5 had four copies).
+ml_comp4_fits) - ONE statement of the LDS budget that ml_plan, ml_cg_variant and ml_fits_lds read (round 5 had four copies).
 Host arithmetic of the diagnostic build: runs without a device."""
 import ctypes as C
 import os

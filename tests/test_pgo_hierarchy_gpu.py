@@ -5,7 +5,7 @@ test_pgo_system_gpu.py pins H, the SpMV, the Schur complement and whole solves; 
 SPD-ish operator achieves.  Here every set-up kernel's OUTPUT is compared with the float64 reference applied to that kernel's INPUTS as
 the device holds them (the dumped arrays of the level below / the level above), so a failure names one stage, one level and one entry:
 
-  structure (build_ml)                      exact
+  structure (ml_plan)                       exact
   geometry (ml_geometry, both forms)        C_H eps (|t|_max + |c|); weights exact; EMPTY rows zero
   Galerkin (ml_galerkin)                    C_H eps |P|^T |A_l| |P|
   sibling / top inverses                    C_H eps |W|_2 |row i of W^-1|_2 |column j of W^-1|_2 (hierarchy_checks.inverse_bound);
@@ -27,7 +27,7 @@ C_H = 1e3 (test_pgo_system_gpu.py); no other tolerance.  test_np_reference_syste
 contribution, a centroid over fan, a sibling coupling left out of W, a transposed sibling tile, a skipped Newton-Schulz step and a
 missing 16 x 16 tile of Q Y Q^T each exceed these bounds by >= 1e8.
 
-Every case asserts the class build_ml gave it (levels, cl, agg, mult, step count, sizes per level) - a case that falls to another path
+Every case asserts the class ml_plan gave it (levels, cl, agg, mult, step count, sizes per level) - a case that falls to another path
 fails, the ml_cg variant included (cg_variant).  Every case runs at lambda = lambda_init and 1e3 max diag; poses after optimize(5) once
 per class.  The 4-step refinement production takes at the composite level from LM iteration 2 on is held against the reference on
 4000 / 16000.
@@ -66,6 +66,7 @@ import pytest
 
 import hierarchy_checks as HC
 import np_reference as NP
+from ml_classes import DENSE1, levels1 as _levels1, levels4 as _levels4      # the class rules restated (shared with test_ml_plan.py)
 from uzliti_slam_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -192,21 +193,6 @@ def test_one_coarse_level_no_dense_operator(capi, nb):
 
 
 # ------------------------------------------------------------------------------------------------------------------ agg = 1, dense level 1
-def _levels1(nb):
-    """build_ml, agg = 1: levels of 8 until <= 8 aggregates remain, <= kMlTopWide = 16 above the dense level 1."""
-    n = [nb, -(-nb // 8)]
-    if n[1] > 8:
-        n.append(-(-n[1] // 8))
-        while n[-1] > 16:
-            n.append(-(-n[-1] // 8))
-    return n
-
-
-# (free vertices, edges): 65 the first with two levels; C1; 1024 / 1025: n_2 = 16, the 96-row top level, against 17, which adds a level;
-# C2 and 1281: 6 n_1 = 750 / 966 (<= kGemm32Max: ml_ns_gemm32); 2049 and 3072: the general GEMM, 6 n_1 = 1542 / 2304
-DENSE1 = [(65, 200), (99, 300), (513, 2000), (1024, 4000), (1025, 4000), (999, 5000), (1281, 5000), (2049, 8000), (3072, 12400)]
-
-
 @pytest.mark.parametrize("nb,e", DENSE1)
 def test_dense_level1_multiplicative(capi, nb, e):
     n = _levels1(nb)
@@ -235,17 +221,6 @@ def test_dense_level1_additive_fallback(capi, nb, e):
 
 
 # ------------------------------------------------------------------------------------------------------------------ agg = 4, dense level 2
-def _levels4(nb):
-    """build_ml, agg = 4: fans 8, 4, 8, ..; <= 16 aggregates at the top above the dense level 2."""
-    n = [nb, -(-nb // 8)]
-    n.append(-(-n[-1] // 4))
-    if n[2] > 8:
-        n.append(-(-n[2] // 8))
-        while n[-1] > 16:
-            n.append(-(-n[-1] // 8))
-    return n
-
-
 @pytest.mark.parametrize("nodes,e,steps,cfg", [(3074, 12300, 4, NO_SCHUR), (4000, 16000, 4, NO_SCHUR), (5000, 5600, 2, NO_SCHUR)])
 def test_dense_level2(capi, nodes, e, steps, cfg):
     n = _levels4(nodes - 1)
@@ -357,7 +332,7 @@ def test_reduced_system_strong_blocks_with_empty_rows(capi):
 CG_PLAIN1, CG_COMP1, CG_PLAIN4, CG_COMP4, CG_COMP4_YPRE, CG_COMP4_VPRE = range(6)       # pgo_types.hpp: LmCgVariant
 # ml_cg_variant: no dense operator - plain1 / plain4 (the walked hierarchy: _hierarchy_worker.py); dense level 1 - comp1; dense level 2 -
 # Ypre while 6 n_2 <= 2304 (4000 / 16000, C4), the ml_alpha variant Vpre above (14k / 60k).  kCgComp4 itself is what a hierarchy without
-# a Vg buffer would take: build_ml always gives one, so no graph reaches it.
+# a Vg buffer would take: upload_ml always gives one, so no graph reaches it.
 STEADY = {"59 one level": (60, 180, 59, {}, dict(cl=0, agg=1, cg_variant=CG_PLAIN1)),
           "513": (514, 2000, 513, {}, dict(cl=1, agg=1, cg_variant=CG_COMP1)), "C2": (1000, 5000, 2, {}, dict(cl=1, agg=1, cg_variant=CG_COMP1)),
           "4000/16000": (4000, 16000, 40, {}, dict(cl=2, agg=4, cg_variant=CG_COMP4_YPRE)),

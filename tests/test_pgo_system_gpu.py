@@ -451,7 +451,7 @@ def check_spmv(p, lin, R, key):
         assert w <= 1.0, "SpMV differs by %.3g x its bound at lambda %.3g" % (w, lam)
 
 
-# (AGG = 4 starts above 3072 free vertices on graphs with >= 6 slots per row, above 4096 otherwise - build_ml: agg1_max; 3073 is the first)
+# (AGG = 4 starts above 3072 free vertices on graphs with >= 6 slots per row, above 4096 otherwise - ml_plan: agg1_max; 3073 is the first)
 @pytest.mark.parametrize("case", ["C1", "agg4-3073", "agg4-4000", "hub-long-rows", "block-Jacobi", "nb=85"])
 def test_spmv(capi, oracle, case):
     graphs = {"C1": (synth.make_pose_graph(100, 300), {}), "agg4-3073": (synth.make_pose_graph(3074, 12300, seed=3073), {}),

@@ -940,6 +940,42 @@ def schur_plan_strong(row_ptr, col, slot_w, cap=24, strong_min=1, theta=0.25, on
                 n_blocks=int(counts[3]), contiguous=counts[4] / 1000.)
 
 
+def ml_plan(row_ptr, col, precond_on=True, strong_blocks=False, mult_banned=False, comp4_off=False, arrays=True):
+    """uzl_debug_ml_plan (diagnostic library, host only): the hierarchy plan of the block system row_ptr / col ->
+    dict(levels, cl, agg, mult, ns_steps (the structure's), gather_level, lds, rows, lv = one dict per level of n, fan, nslots and - with
+    arrays - row_ptr, col), the part of DiagPgo.hierarchy()'s dict that hierarchy_checks.check_structure reads.  levels = 0: block-Jacobi."""
+    rp = np.ascontiguousarray(row_ptr, np.int32); cl = np.ascontiguousarray(col, np.int32)
+    nb = len(rp) - 1
+    flags = C.c_int32((1 if precond_on else 0) | (2 if strong_blocks else 0) | (4 if mult_banned else 0) | (8 if comp4_off else 0))
+    L = diag_lib()
+
+    def call(level, what, info, out, nbytes):
+        rc = L.uzl_debug_ml_plan(C.c_int32(nb), _p(rp, c_i32p), _p(cl, c_i32p), flags, C.c_int32(level), C.c_int32(what), _p(info, c_i32p),
+                                 out.ctypes.data_as(C.c_void_p) if out is not None else None, C.byref(nbytes) if nbytes is not None else None)
+        if rc != UZL_OK:
+            raise UzlError(rc, "uzl_debug_ml_plan")
+
+    def array(level, what):
+        nbytes = C.c_int64(0)
+        call(level, what, None, None, nbytes)
+        out = np.zeros(nbytes.value // 4, np.int32)
+        if nbytes.value:
+            call(level, what, None, out, nbytes)
+        return out
+
+    info = np.zeros(64, np.int32)
+    call(0, -1, info, None, None)
+    out = dict(levels=int(info[0]), cl=int(info[1]), agg=int(info[2]), mult=int(info[3]), ns_steps=int(info[12]), gather_level=int(info[14]),
+               lds=int(info[15]), rows=nb, lv=[])
+    for l in range(out["levels"] + 1):
+        lv = dict(n=int(info[16 + l]), fan=int(info[32 + l]), nslots=int(info[48 + l]))
+        if arrays:
+            lv["row_ptr"] = rp if l == 0 else array(l, 0)
+            lv["col"] = cl if l == 0 else array(l, 1)
+        out["lv"].append(lv)
+    return out
+
+
 # --------------------------------------------------------------------------------------- distance loop-closure candidates
 class Radius(_Handle):
     """uzl_radius_* (SlamGraph::getNodesWithinRadius + the caller's filters, graph_slam_node.cpp:272-289)."""

@@ -5,6 +5,7 @@
 #include "uzl_common.hpp"
 #include "pgo_types.hpp"
 #include "pgo_schur.hpp"
+#include "pgo_ml_plan.hpp"
 #include "pgo_lm.hpp"
 
 #include <algorithm>
@@ -40,15 +41,7 @@ int k_pcg_spmv(const PgoDev& D, const double* p_old, double* p_new, int n_part, 
 int k_pcg_update(const PgoDev& D, const double* p, int n_part, hipStream_t s);
 int g_pcg_spmv(int nb);
 int g_pcg_update(int nb);
-int g_ml_rows(int nb, int agg);
-int g_ml_spmv(int nb, int agg);
-size_t ml_cg_lds_bytes(const int* n, int levels, int agg);
-bool ml_fits_lds(const int* n_per_level, int levels, int agg);
-// The ONE statement of the PCG kernels' LDS budget and of what ml_cg stages when the dense level-2 operator is present (the gather-level
-// vector and nothing else): build_ml's admission test, ml_cg_variant and ml_fits_lds all read these (tests/test_ml_admission.py
-// holds the boundaries through uzl_debug_ml_admission)
-// (kMlLdsLimit, ml_comp4_lds: pgo_types.hpp)
-bool ml_comp4_fits(int nb, int n2);          // LDS of the comp4 variant and ml_spmv's partial count
+// (g_ml_rows, g_ml_spmv, ml_cg_lds_bytes, ml_fits_lds, ml_comp4_fits: pgo_ml_plan.hpp)
 int k_oplus(const PgoDev& D, const double* pose_in, double* pose_out, hipStream_t s);
 int g_edges_for(int e);
 void k_slot_records(const double* zinv, const double* info, int e, const int32_t* slot_edge, int nslots, double* srec, hipStream_t s);
@@ -86,6 +79,42 @@ hipError_t kl_ml_cg(const HostSlot& hs, const LmShape& sh, int parity, int init,
 namespace uzl { struct LmRun; }
 using namespace uzl;      // (private header of the uzl_pgo_* translation units; the handle itself is the C ABI's global-namespace type)
 
+// The device buffers of one block system the PCG can run on: the full system over the free vertices, or the Schur-reduced one over the
+// separators (uzl_pgo::Reduced).  build_structure sizes, fills and binds either with the same calls.
+struct SysBufs {
+    DevBuf<int32_t> row_ptr, col, rowhdr, b2v;
+    DevBuf<double> blk, hdiag, minv, x, xs, r, z, p, p2, ap;
+    // sizes for nb rows, then the index arrays and the row headers made of them; returns the headers' staging vector: keep it (and the
+    // arguments) until the stream has been synchronised
+    std::vector<int32_t> upload(int nb, const std::vector<int32_t>& h_row_ptr, const std::vector<int32_t>& h_col, const std::vector<int32_t>& h_b2v, hipStream_t s)
+    {
+        const int nslots = h_row_ptr[nb];
+        const size_t nbz = std::max(nb, 1), nsz = std::max(nslots, 1);
+        b2v.reserve(nbz); row_ptr.reserve(nbz + 1); col.reserve(nsz); rowhdr.reserve(nbz * kRowHdr);
+        blk.reserve(nsz * 36);
+        hdiag.reserve(nbz * 42); minv.reserve(nbz * 36);               // [H_aa | b] contiguous: one all-reduce when sharded
+        x.reserve(nbz * 6); xs.reserve(nbz * 6); r.reserve(nbz * 6); z.reserve(nbz * 6); p.reserve(nbz * 6); p2.reserve(nbz * 6);
+        ap.reserve(nbz * 12 + kMaxPartials);                           // [A p | restricted A p | partials]
+        std::vector<int32_t> hdr(nbz * kRowHdr, -1);
+        for (int a = 0; a < nb; a++) {
+            hdr[(size_t)a * kRowHdr] = h_row_ptr[a]; hdr[(size_t)a * kRowHdr + 1] = h_row_ptr[a + 1];
+            for (int k = 0; k < 20 && h_row_ptr[a] + k < h_row_ptr[a + 1]; k++) hdr[(size_t)a * kRowHdr + 2 + k] = h_col[h_row_ptr[a] + k];
+        }
+        if (nb > 0) UZL_HIP(hipMemcpyAsync(b2v.p, h_b2v.data(), sizeof(int32_t) * nb, hipMemcpyHostToDevice, s));
+        UZL_HIP(hipMemcpyAsync(row_ptr.p, h_row_ptr.data(), sizeof(int32_t) * (nb + 1), hipMemcpyHostToDevice, s));
+        if (nslots > 0) UZL_HIP(hipMemcpyAsync(col.p, h_col.data(), sizeof(int32_t) * nslots, hipMemcpyHostToDevice, s));
+        UZL_HIP(hipMemcpyAsync(rowhdr.p, hdr.data(), sizeof(int32_t) * hdr.size(), hipMemcpyHostToDevice, s));
+        return hdr;
+    }
+    void bind(PgoDev& D, int nb, int nslots) const
+    {
+        D.nb = nb; D.nslots = nslots;
+        D.b2v = b2v.p; D.row_ptr = row_ptr.p; D.col = col.p; D.rowhdr = rowhdr.p;
+        D.blk = blk.p; D.hdiag = hdiag.p; D.minv = minv.p; D.b = hdiag.p + (size_t)nb * 36;
+        D.x = x.p; D.xs = xs.p; D.r = r.p; D.z = z.p; D.p = p.p; D.ap = ap.p; D.part_a = ap.p + (size_t)std::max(nb, 1) * 12;
+    }
+};
+
 struct uzl_pgo : uzl::HandleBase {
     uzl_pgo_cfg cfg;
     hipStream_t stream = nullptr;
@@ -107,12 +136,13 @@ struct uzl_pgo : uzl::HandleBase {
     DevBuf<double> pose_a, pose_b, pose_init;
     double* cur = nullptr;
     double* trial = nullptr;
-    DevBuf<int32_t> d_v2b, d_b2v, d_ei, d_ej, d_row_ptr, d_col, d_rowhdr, d_src, d_flags;
+    DevBuf<int32_t> d_v2b, d_ei, d_ej, d_src, d_flags;
+    SysBufs sys;                               // the full system over the free vertices
     DevBuf<int32_t> d_slot_edge, d_rb_ptr;
     DevBuf<double> d_srec;                     // slot records (pgo_kernels.hip: slot_records_kernel): values of the edges in the order of the structure's slots
     DevBuf<int4> d_smeta;
     bool srec_stale = true;                    // edges' values or the structure changed since d_srec was written
-    DevBuf<double> d_zinv, d_info, d_blk, d_hdiag, d_minv, d_b, d_x, d_xs, d_r, d_z, d_p, d_p2, d_ap;
+    DevBuf<double> d_zinv, d_info;
     DevBuf<double> d_part_a, d_part_b, d_part_c, d_scal, d_err, d_out12, d_stage;
     DevBuf<uint8_t> d_robust;
     DevBuf<uzl_node> d_nodes;
@@ -129,21 +159,22 @@ struct uzl_pgo : uzl::HandleBase {
     struct Reduced {
         bool on = false, strong = false, strong_blocks = false;      // strong: numbered by strong aggregates, with empty rows (SchurPlan); _blocks: in blocks of 4 groups
         int32_t n_int = 0, n_runs = 0, longest_run = 0, n_sep = 0;
-        DevBuf<int32_t> run_ptr, run_rows, slotP, slotN, endL, endR, sep_rows, rsrc, inc_ptr, inc, row_ptr, col, rowhdr, b2v;
-        DevBuf<double> elim, runout, runblk, blk, hdiag, minv, x, xs, r, z, p, p2, ap;
+        DevBuf<int32_t> run_ptr, run_rows, slotP, slotN, endL, endR, sep_rows, rsrc, inc_ptr, inc;
+        DevBuf<double> elim, runout, runblk;
+        SysBufs sys;                           // the reduced system over the separators
         SchurDev S;
     } red;
     int prev_pcg_iters = 0;
     double num_its[2] = {-1., -1.};            // PCG iterations per LM trial of the last solve with the reduced system in row order / by strong aggregates
     int num_last = -1;                         // numbering of that solve (-1: none yet); see build_structure
-    // multilevel preconditioner
-    int ml_levels = 0;
-    std::vector<int32_t> ml_n, ml_nslots, ml_chunks;       // per level: entities, off-diagonal blocks, work chunks of ml_galerkin_kernel
-    int ml_inner_aggs = 0;
+    // multilevel preconditioner: the class and per-level sizes of this structure's hierarchy as ml_plan decided them (its index arrays
+    // released once uploaded); levels = 0: block-Jacobi
+    MlPlan mlp;
+    // STATE, not plan: initialised from mlp.mult / mlp.ns_steps with every multilevel structure, then changed for the life of the
+    // structure by the additive fallback (do_optimize_host).  Everything else about the class is read from mlp.
+    bool ml_mult = false;            // the dense operator in use is the multiplicative cycle's (pgo_ml_kernels.hip)
+    int ml_ns_steps = 0;             // Newton-Schulz refinements of the dense operator per rebuild
     bool ml_trial_setup = false;     // the preconditioner's per-trial part (sibling inverses, top, dense levels) is due
-    bool ml_comp = false;
-    int ml_cl = 0;                   // level of the dense operator (1: small graphs, 2: AGG = 4), 0 = none
-    int ml_ns_steps = 0;             // Newton-Schulz refinements of the dense level-1 operator per rebuild
     // Two complete copies of the preconditioner's numeric state (arena, device descriptor, kernel-argument block, PCG graph): the
     // solver applies copy `ml_ix` while a rebuild for the next LM iteration runs on `stream2` into the other one.
     struct MlBuf {
@@ -164,10 +195,6 @@ struct uzl_pgo : uzl::HandleBase {
     hipEvent_t ev_lin = nullptr, ev_setup = nullptr;
     DevBuf<double> d_scal2;                    // lambda slot (scal[3]) for the kernels of an asynchronous rebuild
     double lambda_now = 0.;          // lambda of the current trial
-    bool ml_mult = false;            // level 1 of the composite operator is multiplicative (pgo_ml_kernels.hip)            // small graphs: hierarchy above level 1 folded into a dense operator (pgo_ml_kernels.hip)
-    std::vector<int32_t> ml_fan;
-    int ml_agg = 4;                            // level-1 aggregates per PCG workgroup (1: small graphs, 4: large)
-    size_t ml_lds = 0;
     DevBuf<uint8_t> ml_arena;
     size_t ml_copy_stride = 0;                 // bytes between the two hierarchy copies inside ml_arena
     DevBuf<MlDev> d_ml;
@@ -207,7 +234,7 @@ inline double pgo_eps_t(const uzl_pgo_cfg& c) { return c.pcg_stop == 1 ? 0. : kS
 inline double pgo_eps_r(const uzl_pgo_cfg& c) { return c.pcg_stop == 1 ? 0. : kStepR * c.pcg_tol; }
 // ---- shared host-side pieces (uzl_pgo.hip)
 int32_t gauge_fix(uzl_pgo* h);                        // G2: setFixedNodes (g2o_optimizer.cpp:301-349)
-void build_structure(uzl_pgo* h);                     // block-CSR, Schur plan, hierarchy; bumps structure_gen
+void build_structure(uzl_pgo* h);                     // block-CSR, Schur plan, hierarchy plan, uploads; bumps structure_gen
 void destroy_pcg_graph(uzl_pgo* h);
 bool ml_async_level(const uzl_pgo* h);
 double ml_rate_drop(const uzl_pgo* h);

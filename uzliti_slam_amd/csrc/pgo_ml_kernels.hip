@@ -206,7 +206,7 @@ __device__ __forceinline__ void ml_geometry_kernel_body(PgoDev D, const MlDev* _
 }
 
 // ---- the same Galerkin product as ONE kernel per level: a GATHER.  The host cuts the coarse level's output blocks into chunks of
-//      consecutive blocks with <= kGalItems contributions (MlLevel::chunk / cslot, build_ml); a workgroup transforms its chunk's
+//      consecutive blocks with <= kGalItems contributions (MlLevel::chunk / cslot, ml_plan); a workgroup transforms its chunk's
 //      contributions into LDS (one lane each, through its two prolongation blocks) and sums them per output block in contribution
 //      order - the sums of rounds 1-3's transform + ordered-reduce pair in the same order, the same bits - with no contribution array in
 //      memory and one launch per level instead of two.  A block with more contributions than fit (the top of a dense hierarchy) is a
@@ -1221,7 +1221,7 @@ __device__ __forceinline__ void ml_cmat32_body(const double* __restrict__ src, f
 // one memory latency covers them: these kernels are latency-bound, not bandwidth-bound, at pose-graph sizes.
 // ------------------------------------------------------------------------------------------------
 // Two geometries, chosen by graph size (template parameter AGG = level-1 aggregates per workgroup):
-//   AGG = 1 (small graphs, <= 3072 free vertices, <= 4096 on sparse ones: build_ml's agg1_max): a workgroup owns ONE level-1 aggregate (8 rows), the gather
+//   AGG = 1 (small graphs, <= 3072 free vertices, <= 4096 on sparse ones: ml_plan's agg1_max): a workgroup owns ONE level-1 aggregate (8 rows), the gather
 //           level is 1, hierarchy fan-outs 8,8,8,..  -> 8x more workgroups, i.e. CUs, for the latency-bound kernels
 //   AGG = 4 (large graphs): a workgroup owns one level-2 aggregate = 4 level-1 aggregates (32 rows), gather level 2,
 //           hierarchy fan-outs 8,4,8,8,..             -> the gathered arrays stay small (n/32 entries)
@@ -1763,7 +1763,7 @@ __device__ __forceinline__ void ml_cg_kernel_body(PgoDev D, MlHot H, const doubl
     __shared__ double syc[6];
     __shared__ double szj[kRowsPerBlk * 6];
     __shared__ double spm[6];
-    constexpr int kFan2 = (AGG == 1) ? kMlFanout : kMlFanout2;    // children of a level-2 aggregate (build_ml)
+    constexpr int kFan2 = (AGG == 1) ? kMlFanout : kMlFanout2;    // children of a level-2 aggregate (ml_plan)
     if (D.flags[0]) return;               // (kept first: post-convergence launches of a graph batch must stay cheap no-ops)
     STAMP_DECL
     const int tid = threadIdx.x;
@@ -2308,7 +2308,7 @@ int g_ml_spmv(int nb, int agg) { return agg == 1 ? g_ml_rows(nb, 1) : g_ml_rows(
 // dynamic LDS of ml_cg for a hierarchy (n[0..levels]) and workgroup geometry agg
 size_t ml_cg_lds_bytes(const int* n, int levels, int agg)
 {
-    const int g = (agg == 1 || levels < 2) ? 1 : 2;
+    const int g = ml_gather_level(agg, levels);
     size_t d = 0;
     for (int l = g; l <= levels; l++) d += 6 * (size_t)n[l];
     for (int l = g; l < levels; l++) d += 3 * (size_t)n[l];
@@ -2617,7 +2617,7 @@ static hipError_t kl_ml_cg_t(SLOT sl, const LmShape& sh, int parity, int init, h
     constexpr int kSlotKind = std::is_pointer<SLOT>::value ? 0 : (std::is_same<SLOT, LmSlot>::value ? 1 : 2);
     const dim3 g(sh.g_rows, 1, sh.nslots), t(kCgBlk);
     const size_t lds = (size_t)sh.cg_lds;
-    if (lds > kMlLdsLimit) return hipErrorInvalidValue;                             // (build_ml admits no such hierarchy)
+    if (lds > kMlLdsLimit) return hipErrorInvalidValue;                             // (ml_plan admits no such hierarchy)
     auto cg = [&](auto kernel) {
         const hipError_t e = lm_cg_lds(reinterpret_cast<const void*>(kernel), 8 * kSlotKind + sh.cg_variant, lds);
         if (e == hipSuccess) launch(kernel, g, t, lds, s, ev_a, ev_b, sl, parity, init);
@@ -2771,7 +2771,7 @@ extern "C" UZL_DIAG_EXPORT int uzl_debug_ns_gemm(int n, const double* X, const d
     return e == hipSuccess ? 0 : -3;
 }
 // admission of the dense level-2 operator's PCG variant (host arithmetic only: runs without a device - tests/test_ml_admission.py):
-// the LDS ml_cg asks for with n2 level-2 aggregates, ml_spmv's workgroups (= partials) for nb free vertices, and build_ml's verdict
+// the LDS ml_cg asks for with n2 level-2 aggregates, ml_spmv's workgroups (= partials) for nb free vertices, and ml_plan's verdict
 extern "C" UZL_DIAG_EXPORT int uzl_debug_ml_admission(int nb, int n2, uint64_t* lds, int* spmv_groups, int* fits)
 {
     if (nb <= 0 || n2 <= 0) return -1;

@@ -85,6 +85,14 @@ constexpr int kGalOutputs = 64;       // output blocks per chunk
 constexpr int kMlTopMax = 8;          // aggregates at the top level (<= 48 dof dense) when the PCG kernels walk the hierarchy themselves
 constexpr int kMlTopWide = 16;        // ... when they apply the dense composite operator instead: the top level is then only ever touched by
                                       // the rebuild, whose one-workgroup inverse (ml_top_kernel) takes 96 rows as readily as 48
+// Class thresholds of ml_plan (pgo_ml_plan.hip, where the measurements behind them are written down):
+constexpr int kMlAgg1MaxLoopy = 3072;   // free vertices up to which a graph takes AGG = 1, with >= 6 slots per row ...
+constexpr int kMlAgg1MaxSparse = 4096;  // ... and with fewer
+constexpr int kMlComp1Max = 3072;       // rows (6 n_1) of the dense level-1 operator: ml_cg_comp_lm_kernel<5> / <8> / <12> / <16>
+constexpr int kMlComp4Max = 18432;      // rows (6 n_2) of the dense level-2 operator (the LDS limit binds first: tests/test_ml_admission.py)
+// The level whose residual the PCG kernels gather: level 1 with one aggregate per workgroup (or a single coarse level), else level 2,
+// the workgroup's own 32-row aggregate.  ml_plan stores it (MlPlan::gather_level); ml_cg_lds_bytes sizes the LDS by it.
+__host__ __device__ inline int ml_gather_level(int agg, int levels) { return (agg == 1 || levels < 2) ? 1 : 2; }
 
 struct MlLevel {
     int32_t n;                 // entities at this level (level 0: nb)

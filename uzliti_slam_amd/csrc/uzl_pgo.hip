@@ -9,6 +9,8 @@
 #include "pgo_lm.hpp"
 #include "uzl_streams.hpp"
 
+#include <array>
+
 using namespace uzl;
 
 // ---- RCCL through dlopen: the collective library is only loaded by processes that shard a graph -----------------------------
@@ -49,26 +51,6 @@ RcclApi& rccl()
     });
     return api;
 }
-}  // namespace
-
-namespace uzl {
-const int kUpperNs = 4;                   // Newton-Schulz steps of the dense levels above the composite level (even: the result ends in Ydense[l])
-// the rate rule where the rebuild is synchronous: with the dense operator of that class a rebuild pays as soon as the rate has fallen to
-// 0.75 of the fresh one (0.6 elsewhere; -3 ... -8 % on eight of nine such shapes, the 30k / 150k graph - no dense operator - +14 %)
-constexpr double kRateDropSyncDense = 0.75;
-// Newton-Schulz steps of a synchronous set-up at LM iteration `it` for a structure that asks for `structure_steps` (4 on large loopy
-// graphs): 2 in the first kNsEarlyIts iterations (against the full count from the start: -3.4 % over fourteen large shapes at the same
-// PCG iteration count; 4 iterations instead of 2 gain on the largest and lose at 10k, 8 lose everywhere; NO step at all in those two - the
-// cycle's operator as it comes - another -2.5 %, not taken: that operator is what the residual guard exists for)
-int ml_ns_steps_at(int structure_steps, int it)
-{
-    constexpr int kNsEarlyIts = 2, kNsEarlySteps = 2;
-    return (structure_steps > 2 && it < kNsEarlyIts) ? kNsEarlySteps : structure_steps;
-}
-double ml_rate_drop(const uzl_pgo* h) { return (!ml_async_level(h) && h->ml_comp) ? kRateDropSyncDense : kRateDrop; }
-}  // namespace uzl
-
-namespace {
 
 struct Timed {
     uzl_pgo* h;
@@ -212,188 +194,38 @@ void upload_edges_common(uzl_pgo* h)
     }
 }
 
-// G2: setFixedNodes (g2o_optimizer.cpp:301-349): per connected component (over the system edges) without a
-// fixed vertex, fix the vertex with the smallest index (= lexicographically smallest node id, :338).
+// union-find root with path halving (gauge_fix)
 int32_t uf_find(std::vector<int32_t>& p, int32_t x)
 {
     while (p[x] != x) { p[x] = p[p[x]]; x = p[x]; }
     return x;
 }
-}  // namespace
-namespace uzl {
-int32_t gauge_fix(uzl_pgo* h)
-{
-    const int n = h->n;
-    std::vector<int32_t> p((size_t)n);
-    std::iota(p.begin(), p.end(), 0);
-    for (int k = 0; k < h->e; k++) {
-        int32_t a = uf_find(p, h->ij[2 * k]), b = uf_find(p, h->ij[2 * k + 1]);
-        if (a != b) { if (a < b) p[b] = a; else p[a] = b; }
-    }
-    std::vector<uint8_t> has((size_t)n, 0);
-    for (int v = 0; v < n; v++) if (h->fixed_eff[v]) has[uf_find(p, v)] = 1;
-    int32_t cnt = 0;
-    for (int v = 0; v < n; v++) {
-        const int32_t r = uf_find(p, v);
-        if (!has[r]) { h->fixed_eff[r] = 1; has[r] = 1; cnt++; }
-    }
-    return cnt;
-}
-}  // namespace uzl
-namespace {
 
-// block-CSR structure over the free vertices: one slot per (free endpoint, system edge)
-
-// Aggregation hierarchy of the multilevel preconditioner (pgo_types.hpp): symbolic part, once per structure.
-// (nb, nslots, d_*: the block system the PCG solves - the full one or the Schur-reduced one)
-void build_ml(uzl_pgo* h, const std::vector<int32_t>& row_ptr0, const std::vector<int32_t>& col0, int nb, int nslots,
-              const int32_t* d_row_ptr, const int32_t* d_col, double* d_blk, double* d_hdiag)
+// The hierarchy a plan describes (pgo_ml_plan.hpp), on the device: one arena holding both hierarchy copies, the two MlDev / MlHot
+// descriptors, one staged copy of the index arrays.  Reads the plan and decides nothing.
+// (d_*: the block system the PCG solves - the full one or the Schur-reduced one)
+void upload_ml(uzl_pgo* h, const MlPlan& P, const int32_t* d_row_ptr, const int32_t* d_col, double* d_blk, double* d_hdiag)
 {
-    h->ml_levels = 0; h->ml_n.assign(1, nb); h->ml_nslots.assign(1, nslots); h->ml_chunks.assign(1, 0); h->ml_inner_aggs = 0;
-    if (h->cfg.preconditioner == 0 || nb <= kMlTopMax) return;
-    // Up to here the level-1 dense operator applies (6 n_1 <= 3072: ml_cg_comp_lm_kernel<16, ...>); above, AGG = 4 with the level-2 one.  Its
-    // rebuild (Newton-Schulz GEMMs, n^3) outgrows what the exact level-1 solve saves in PCG iterations between 3000 and 4000 vertices on
-    // loopy graphs (>= 3 edges per vertex: 3000/12000 20.6 -> 18.3 ms, 4000/16000 24.5 -> 26.3 ms) and later on sparse ones - the shape of a
-    // Schur-reduced online graph (4000/6000 26.0 -> 17.2 ms; config 5's last solve 2328 -> 1288 PCG iterations).
-    const int agg1_max = nslots >= 6 * nb ? 3072 : 4096;
-    h->ml_agg = (nb <= agg1_max && !h->red.strong_blocks) ? 1 : 4;           // (strong aggregates in blocks of 4 x 8 rows are laid out for AGG = 4)
-    int L = 0;
-    h->ml_fan.assign(1, 1);
-    // composite path: one aggregate per workgroup, at least two coarse levels, 6 n_1 <= 960 (<= 1280 free vertices)
-    // large graphs (AGG = 4, gather level 2): the same construction one level up - the hierarchy above level 2 as one dense
-    // operator that ml_cg_lm_kernel<4, true, ...> applies instead of its LDS walk (measured 733 -> 332 ms at 20k / 100k, the rebuild's
-    // Newton-Schulz GEMMs take 7 ms there).  6 n_2 <= 18432 - the cap was 4096 (21.8k vertices)
-    // until round 5, and a 30k / 150k graph took 2.39 s (11.9 k PCG iterations on the walked hierarchy) where it takes 0.32 s with the
-    // operator (1.8 k), 40k / 200k 5.13 -> 0.62 s, 50k / 250k 10.9 -> 1.56 s (tests/diag/big_graphs.py; at n = 7500 a GEMM is 10 ms, half of
-    // that solve), 64k / 320k ~11 -> 2.3 s, 90k / 450k 29.3 -> 6.3 s.  The path ends where ml_cg's gather-level vector no longer fits the LDS
-    // (95k vertices: 6 n_2 = 17.9k, 2.6 GB per matrix, a GEMM 136 ms); kMaxPartials ml_spmv workgroups admit 131k
-    static const bool comp4_off = diag_flag("UZL_ML_NO_COMP4");             // the walked hierarchy instead (tests/test_ab_paths_gpu.py)
-    constexpr int kComp4Max = 18432;
-    // A level above the composite one may be the top with up to kMlTopWide aggregates: config 2 (1000 vertices: 125 / 16 / 2) loses its
-    // 2-aggregate level and with it ten launches per rebuild (the cycle around it and four Newton-Schulz steps of the 96-row level)
-    auto top_max = [&](int lvl) {
-        const bool comp_here = h->ml_agg == 1 ? (lvl >= 2 && 6 * h->ml_n[1] <= 3072) : (!comp4_off && lvl >= 3 && 6 * h->ml_n[2] <= kComp4Max);
-        return comp_here ? kMlTopWide : kMlTopMax;
-    };
-    while (h->ml_n.back() > top_max(L) && L < kMlMaxLevels) {
-        const int fan = (L == 1 && h->ml_agg == 4) ? kMlFanout2 : kMlFanout;     // large graphs: level 2 = 4 level-1 aggregates
-        h->ml_fan.push_back(fan);
-        h->ml_n.push_back((h->ml_n.back() + fan - 1) / fan);
-        L++;
-    }
-    // the PCG kernels' LDS: with the dense level-2 operator ml_cg stages nothing but the gather-level vector (ml_cg_variant); the walked
-    // hierarchy needs every level above the gather level.  Beyond either limit (and beyond kMaxPartials ml_spmv workgroups = 131k
-    // vertices): block-Jacobi
-    const bool comp4_here = !comp4_off && h->ml_agg == 4 && L >= 3 && 6 * h->ml_n[2] <= kComp4Max;
-    const bool fits = comp4_here ? ml_comp4_fits(nb, h->ml_n[2]) : ml_fits_lds(h->ml_n.data(), L, h->ml_agg);
-    if (!fits) { h->ml_n.assign(1, nb); return; }
-    h->ml_levels = L;
-    h->ml_lds = comp4_here ? ml_comp4_lds(h->ml_n[2]) : ml_cg_lds_bytes(h->ml_n.data(), L, h->ml_agg);      // what the variant in use asks for: never above kMlLdsLimit
-    // per-level host index arrays
-    struct Lv { std::vector<int32_t> row_ptr, col, srow, off_ptr, diag_ptr, cslot, chunk; int32_t n_off = 0; };      // cslot / chunk: ml_galerkin_kernel's work list
-    std::vector<Lv> lv((size_t)L + 1);
-    lv[0].col = col0;
-    lv[0].srow.resize(col0.size());
-    for (int a = 0; a < nb; a++) for (int s = row_ptr0[a]; s < row_ptr0[a + 1]; s++) lv[0].srow[s] = a;
-    for (int f = 0; f < L; f++) {
-        Lv& F = lv[f]; Lv& C = lv[f + 1];
-        const int nc = h->ml_n[f + 1];
-        const int ns = (int)F.col.size();
-        const int fan_c = h->ml_fan[f + 1];
-        struct Off { int32_t A, C, s; };
-        std::vector<Off> off; std::vector<std::pair<int32_t, int32_t>> dg;
-        for (int s = 0; s < ns; s++) {
-            const int c = F.col[s];
-            if (c < 0) continue;
-            const int A = F.srow[s] / fan_c, Cc = c / fan_c;
-            if (A != Cc) off.push_back({A, Cc, s}); else dg.push_back({A, s});
-        }
-        // order by (A, C, s) / (A, s).  The slots come in ascending s and a coarse row holds a few dozen of them: a stable counting pass by A,
-        // then a small sort inside every row (one std::sort over all of level 0's 100k slots was most of the 4 ms this function took at 10k / 50k)
-        {
-            std::vector<int32_t> cnt((size_t)nc + 1, 0);
-            for (const Off& o : off) cnt[o.A + 1]++;
-            for (int a = 0; a < nc; a++) cnt[a + 1] += cnt[a];
-            std::vector<Off> tmp(off.size());
-            std::vector<int32_t> pos(cnt.begin(), cnt.end() - 1);
-            for (const Off& o : off) tmp[pos[o.A]++] = o;
-            off.swap(tmp);
-            for (int a = 0; a < nc; a++)
-                std::sort(off.begin() + cnt[a], off.begin() + cnt[a + 1], [](const Off& x, const Off& y) { return x.C != y.C ? x.C < y.C : x.s < y.s; });
-            std::fill(cnt.begin(), cnt.end(), 0);
-            for (const auto& d : dg) cnt[d.first + 1]++;
-            for (int a = 0; a < nc; a++) cnt[a + 1] += cnt[a];
-            std::vector<std::pair<int32_t, int32_t>> dt(dg.size());
-            pos.assign(cnt.begin(), cnt.end() - 1);
-            for (const auto& d : dg) dt[pos[d.first]++] = d;                  // (s ascending within A already)
-            dg.swap(dt);
-        }
-        C.row_ptr.assign((size_t)nc + 1, 0);
-        for (size_t k = 0; k < off.size(); k++) {
-            if (k == 0 || off[k].A != off[k - 1].A || off[k].C != off[k - 1].C) {
-                C.srow.push_back(off[k].A); C.col.push_back(off[k].C); C.off_ptr.push_back((int32_t)k);
-                C.row_ptr[off[k].A + 1]++;
-            }
-        }
-        C.off_ptr.push_back((int32_t)off.size());
-        for (int a = 0; a < nc; a++) C.row_ptr[a + 1] += C.row_ptr[a];
-        C.n_off = (int32_t)off.size();
-        C.diag_ptr.assign((size_t)nc + 1, 0);
-        for (size_t k = 0; k < dg.size(); k++) C.diag_ptr[dg[k].first + 1]++;
-        for (int a = 0; a < nc; a++) C.diag_ptr[a + 1] += C.diag_ptr[a];
-        // The Galerkin product as a GATHER (ml_galerkin_kernel): contribution q comes from fine slot cslot[q]; a workgroup takes a chunk of
-        // consecutive output blocks whose contributions (<= kGalItems) it transforms into LDS and sums in order.  chunk = {kind (0: off-
-        // diagonal blocks, 1: diagonal blocks), first output, outputs, first contribution, contributions}.
-        C.cslot.resize(off.size() + dg.size());
-        for (size_t k = 0; k < off.size(); k++) C.cslot[k] = off[k].s;
-        for (size_t k = 0; k < dg.size(); k++) C.cslot[off.size() + k] = dg[k].second;
-        {
-            const int nso = (int)C.col.size();
-            for (int b = 0; b < nso;) {                                      // off-diagonal outputs
-                int e = b, items = 0;
-                while (e < nso && (e == b || items + (C.off_ptr[e + 1] - C.off_ptr[e]) <= kGalItems) && e - b < kGalOutputs) { items += C.off_ptr[e + 1] - C.off_ptr[e]; e++; }
-                const int32_t c5[5] = {0, b, e - b, C.off_ptr[b], items};
-                C.chunk.insert(C.chunk.end(), c5, c5 + 5);
-                b = e;
-            }
-            const int nf = h->ml_n[f];
-            for (int a = 0; a < nc;) {                                       // diagonal outputs: + two items (G, M) per child
-                int e = a, items = 0;
-                auto cost = [&](int A) { return (C.diag_ptr[A + 1] - C.diag_ptr[A]) + 2 * (std::min(nf, (A + 1) * fan_c) - A * fan_c); };
-                while (e < nc && (e == a || items + cost(e) <= kGalItems) && e - a < kGalOutputs) { items += cost(e); e++; }
-                const int32_t c5[5] = {1, a, e - a, C.n_off + C.diag_ptr[a], C.diag_ptr[e] - C.diag_ptr[a]};
-                C.chunk.insert(C.chunk.end(), c5, c5 + 5);
-                a = e;
-            }
-        }
-        h->ml_nslots.push_back((int32_t)C.col.size());
-        h->ml_chunks.push_back((int32_t)(C.chunk.size() / 5));
-        h->ml_inner_aggs += nc;                                   // one sibling block per aggregate of every coarse level
-    }
+    const int L = P.levels, cl = P.cl;
+    if (L == 0) return;
+    const std::vector<MlPlan::Level>& lv = P.lv;
     // ---- one arena for everything: first the int arrays (staged on the host), then the doubles
     size_t bytes = 0;
     auto take = [&](size_t b) { size_t o = bytes; bytes = (bytes + b + 255) / 256 * 256; return o; };
-    struct IntOff { size_t row_ptr, col, srow, off_ptr, diag_ptr, cslot, chunk; };
-    std::vector<IntOff> io((size_t)L + 1);
-    for (int l = 0; l <= L; l++) {
-        Lv& X = lv[l];
-        io[l].row_ptr = take(std::max<size_t>(X.row_ptr.size(), 1) * 4);
-        io[l].col = take(std::max<size_t>(X.col.size(), 1) * 4);
-        io[l].srow = take(std::max<size_t>(X.srow.size(), 1) * 4);
-        io[l].off_ptr = take(std::max<size_t>(X.off_ptr.size(), 1) * 4);
-        io[l].diag_ptr = take(std::max<size_t>(X.diag_ptr.size(), 1) * 4);
-        io[l].cslot = take(std::max<size_t>(X.cslot.size(), 1) * 4);
-        io[l].chunk = take(std::max<size_t>(X.chunk.size(), 1) * 4);
-    }
+    enum { iRowPtr, iCol, iSrow, iOffPtr, iDiagPtr, iCslot, iChunk, kIdx };
+    static constexpr std::vector<int32_t> MlPlan::Level::* idx[kIdx] = {&MlPlan::Level::row_ptr, &MlPlan::Level::col, &MlPlan::Level::srow, &MlPlan::Level::off_ptr,
+                                                                        &MlPlan::Level::diag_ptr, &MlPlan::Level::cslot, &MlPlan::Level::chunk};
+    std::vector<std::array<size_t, kIdx>> io((size_t)L + 1);
+    for (int l = 0; l <= L; l++) for (int k = 0; k < kIdx; k++) io[l][k] = take(std::max<size_t>((lv[l].*idx[k]).size(), 1) * 4);
     const size_t int_bytes = bytes;
     struct DblOff { size_t blk, G, M, Winv, geo, cen, r, y; };
     std::vector<DblOff> dof((size_t)L + 1);
     for (int l = 0; l <= L; l++) {
-        const size_t n = (size_t)std::max(h->ml_n[l], 1), ns = (size_t)std::max(h->ml_nslots[l], 1);
+        const size_t n = (size_t)std::max(P.n[l], 1), ns = (size_t)std::max(P.nslots[l], 1);
         dof[l].blk = (l == 0) ? 0 : take(ns * 36 * 8);
         dof[l].G = (l == 0) ? 0 : take(n * 36 * 8);
         dof[l].M = (l == 0) ? 0 : take(n * 36 * 8);
-        dof[l].Winv = (l < L) ? take((size_t)std::max(h->ml_n[l + 1], 1) * (size_t)(36 * h->ml_fan[l + 1] * h->ml_fan[l + 1]) * 8) : 0;
+        dof[l].Winv = (l < L) ? take((size_t)std::max(P.n[l + 1], 1) * (size_t)(36 * P.fan[l + 1] * P.fan[l + 1]) * 8) : 0;
         dof[l].geo = (l == 0) ? take(n * 12 * 8) : 0;          // levels >= 1: one contiguous blob (geo_blob below)
         dof[l].cen = take(n * 4 * 8);
         dof[l].r = take(n * 6 * 8);
@@ -401,62 +233,27 @@ void build_ml(uzl_pgo* h, const std::vector<int32_t>& row_ptr0, const std::vecto
     }
     size_t geo_blob_doubles = 0;
     std::vector<size_t> geo_sub((size_t)L + 1, 0);
-    for (int l = 1; l <= L; l++) { geo_sub[l] = geo_blob_doubles; geo_blob_doubles += (size_t)std::max(h->ml_n[l], 1) * 3; }
+    for (int l = 1; l <= L; l++) { geo_sub[l] = geo_blob_doubles; geo_blob_doubles += (size_t)std::max(P.n[l], 1) * 3; }
     const size_t o_geo_blob = take(geo_blob_doubles * 8 + 64);     // ml_cg copies levels g..L-1 with one linear loop
-    const bool comp1 = h->ml_agg == 1 && L >= 2 && 6 * h->ml_n[1] <= 3072;     // ml_cg_comp_lm_kernel<5> / <8> / <12> / <16>
-    const bool comp4 = comp4_here;                  // (one predicate: the admission test above)
-    h->ml_comp = comp1 || comp4;
-    h->ml_cl = comp1 ? 1 : (comp4 ? 2 : 0);
-    const int cl = h->ml_cl;
     std::vector<size_t> o_dense((size_t)L + 1, 0);
-    if (h->ml_comp) for (int l = cl; l < L; l++) o_dense[l] = take((size_t)(6 * h->ml_n[l]) * (size_t)(6 * h->ml_n[l]) * 8);
-    // A handle whose graphs made the multiplicative operator break down (chain-like graphs: few loop closures per vertex, the
-    // shape of an online run) keeps the additive operator for its later structures instead of failing once per add_graph.
-    h->ml_mult = h->ml_comp && !h->mult_banned;
-    const size_t n12 = h->ml_mult ? (size_t)h->ml_n[cl] * h->ml_n[cl + 1] * 36 * 8 : 0;
+    if (cl) for (int l = cl; l < L; l++) o_dense[l] = take((size_t)(6 * P.n[l]) * (size_t)(6 * P.n[l]) * 8);
+    const size_t n12 = P.mult ? (size_t)P.n[cl] * P.n[cl + 1] * 36 * 8 : 0;
     const size_t o_mQ = take(n12), o_mQY = take(n12);
-    // Newton-Schulz steps of the composite operator per rebuild: 2; 4 on large loopy graphs (AGG = 4, >= 6 slots per row), where two
-    // more GEMM pairs per rebuild buy a quarter of the PCG iterations (10k/50k 1882 -> 1455 per solve, 107.7 -> 94.1 ms; 5k/25k 68.6 ->
-    // 62.3; 20k/100k 242 -> 224) - on chain-like graphs of that size they cost more than they save (20k/21.7k: 209 -> 261 ms), on
-    // small graphs the count barely moves (config 2: 538 -> 511 for +0.3 ms)
-    h->ml_ns_steps = h->ml_mult ? ((h->ml_agg == 4 && nslots >= 6 * nb) ? 4 : 2) : 0;
-    const size_t nsq = h->ml_mult ? (size_t)(6 * h->ml_n[cl]) * (size_t)(6 * h->ml_n[cl]) * 8 : 0;     // also the scratch of the levels above cl
+    const size_t nsq = P.mult ? (size_t)(6 * P.n[cl]) * (size_t)(6 * P.n[cl]) * 8 : 0;     // also the scratch of the levels above cl
     const size_t o_nsT = take(nsq), o_nsX = take(nsq);
-    const int c32_stride = h->ml_comp ? ((6 * h->ml_n[cl] + 3) & ~3) : 0;
-    const size_t o_c32 = take(h->ml_comp ? (size_t)(6 * h->ml_n[cl]) * c32_stride * 4 + 16384 : 0);      // f32 copy of Y_cl: what the PCG kernels read (+ slack: ml_cg_lm_kernel<4, true, true, ...> prefetches 18 x 512 B per row unconditionally)
-    // slot ranges by parent aggregate, for every level the multiplicative cycle is built at (cl .. L-1): [n_l*n_{l+1}] begin | end
-    std::vector<std::vector<int32_t>> grp((size_t)L + 1);
+    const int c32_stride = cl ? ((6 * P.n[cl] + 3) & ~3) : 0;
+    const size_t o_c32 = take(cl ? (size_t)(6 * P.n[cl]) * c32_stride * 4 + 16384 : 0);      // f32 copy of Y_cl: what the PCG kernels read (+ slack: ml_cg_lm_kernel<4, true, true, ...> prefetches 18 x 512 B per row unconditionally)
     std::vector<size_t> o_grp((size_t)L + 1, 0);
-    if (h->ml_mult) {
-        for (int l = cl; l < L; l++) {
-            const int n1 = h->ml_n[l], n2 = h->ml_n[l + 1], fan2 = h->ml_fan[l + 1];
-            grp[l].assign((size_t)2 * n1 * n2, 0);
-            for (int i = 0; i < n1; i++) {
-                int s = lv[l].row_ptr[i];
-                const int send = lv[l].row_ptr[i + 1];
-                for (int p = 0; p < n2; p++) {
-                    grp[l][(size_t)i * n2 + p] = s;
-                    while (s < send && lv[l].col[s] / fan2 == p) s++;
-                    grp[l][(size_t)n1 * n2 + (size_t)i * n2 + p] = s;
-                }
-            }
-            o_grp[l] = take(grp[l].size() * 4);
-        }
-    }
+    if (P.mult) for (int l = cl; l < L; l++) o_grp[l] = take(lv[l].grp.size() * 4);
     const size_t o_top = take((size_t)(6 * kMlTopWide) * (6 * kMlTopWide) * 8);
-    const int gl = (h->ml_agg == 1 || L < 2) ? 1 : 2;
-    const size_t ngz = (size_t)std::max(h->ml_n[gl], 1) * 6 * 8 * 2;          // (x 2: the gather-level-2 Sg holds two parts per entity)
+    const size_t ngz = (size_t)std::max(P.n[P.gather_level], 1) * 6 * 8 * 2;          // (x 2: the gather-level-2 Sg holds two parts per entity)
     const size_t o_sg = take(ngz), o_rga = take(ngz), o_rgb = take(ngz), o_vg = take(ngz);
     const size_t buf_bytes = (bytes + 255) / 256 * 256;
     h->ml_arena.reserve(2 * buf_bytes);
     h->ml_copy_stride = buf_bytes;
     std::vector<uint8_t> stage(int_bytes, 0);
-    auto put = [&](size_t o, const std::vector<int32_t>& v) { if (!v.empty()) memcpy(stage.data() + o, v.data(), v.size() * 4); };
-    for (int l = 0; l <= L; l++) {
-        put(io[l].row_ptr, lv[l].row_ptr); put(io[l].col, lv[l].col); put(io[l].srow, lv[l].srow);
-        put(io[l].off_ptr, lv[l].off_ptr); put(io[l].diag_ptr, lv[l].diag_ptr);
-        put(io[l].cslot, lv[l].cslot); put(io[l].chunk, lv[l].chunk);
-    }
+    for (int l = 0; l <= L; l++)
+        for (int k = 0; k < kIdx; k++) { const std::vector<int32_t>& v = lv[l].*idx[k]; if (!v.empty()) memcpy(stage.data() + io[l][k], v.data(), v.size() * 4); }
     hipStream_t s = h->stream;
     h->d_ml.reserve(2);
     h->d_scal2.reserve(16);
@@ -470,18 +267,15 @@ void build_ml(uzl_pgo* h, const std::vector<int32_t>& row_ptr0, const std::vecto
         M.levels = L;
         for (int l = 0; l <= L; l++) {
             MlLevel& X = M.lv[l];
-            X.n = h->ml_n[l]; X.nslots = h->ml_nslots[l];
-            X.fan = h->ml_fan[l];
-            X.span = 1; for (int q = 1; q <= l; q++) X.span *= h->ml_fan[q];
-            X.row_ptr = (l == 0) ? d_row_ptr : reinterpret_cast<const int32_t*>(base + io[l].row_ptr);
-            X.col = (l == 0) ? d_col : reinterpret_cast<const int32_t*>(base + io[l].col);
-            X.srow = reinterpret_cast<const int32_t*>(base + io[l].srow);
-            X.off_ptr = reinterpret_cast<const int32_t*>(base + io[l].off_ptr);
-            X.diag_ptr = reinterpret_cast<const int32_t*>(base + io[l].diag_ptr);
+            X.n = P.n[l]; X.nslots = P.nslots[l];
+            X.fan = P.fan[l];
+            X.span = 1; for (int q = 1; q <= l; q++) X.span *= P.fan[q];
+            auto ints = [&](int k) { return reinterpret_cast<const int32_t*>(base + io[l][k]); };
+            X.row_ptr = (l == 0) ? d_row_ptr : ints(iRowPtr);
+            X.col = (l == 0) ? d_col : ints(iCol);
+            X.srow = ints(iSrow); X.off_ptr = ints(iOffPtr); X.diag_ptr = ints(iDiagPtr); X.cslot = ints(iCslot); X.chunk = ints(iChunk);
             X.n_off_contrib = lv[l].n_off;
-            X.cslot = reinterpret_cast<const int32_t*>(base + io[l].cslot);
-            X.chunk = reinterpret_cast<const int32_t*>(base + io[l].chunk);
-            X.n_chunks = (int32_t)(lv[l].chunk.size() / 5);
+            X.n_chunks = P.chunks[l];
             X.blk = (l == 0) ? d_blk : reinterpret_cast<double*>(base + dof[l].blk);
             X.G = (l == 0) ? d_hdiag : reinterpret_cast<double*>(base + dof[l].G);
             X.M = (l == 0) ? nullptr : reinterpret_cast<double*>(base + dof[l].M);
@@ -492,14 +286,14 @@ void build_ml(uzl_pgo* h, const std::vector<int32_t>& row_ptr0, const std::vecto
             X.y = reinterpret_cast<double*>(base + dof[l].y);
         }
         M.top_inv = reinterpret_cast<double*>(base + o_top);
-        for (int l = 1; l < L; l++) M.Ydense[l] = (h->ml_comp && l >= cl) ? reinterpret_cast<double*>(base + o_dense[l]) : nullptr;
+        for (int l = 1; l < L; l++) M.Ydense[l] = (cl && l >= cl) ? reinterpret_cast<double*>(base + o_dense[l]) : nullptr;
         for (int l = 0; l <= kMlMaxLevels; l++) h->ml_dense_ptr[bi][l] = (l >= 1 && l < L) ? M.Ydense[l] : nullptr;
         M.comp_level = cl;
-        if (h->ml_mult) {
+        if (P.mult) {
             for (int l = cl; l < L; l++) {
-                UZL_HIP(hipMemcpyAsync(base + o_grp[l], grp[l].data(), grp[l].size() * 4, hipMemcpyHostToDevice, s));
+                UZL_HIP(hipMemcpyAsync(base + o_grp[l], lv[l].grp.data(), lv[l].grp.size() * 4, hipMemcpyHostToDevice, s));
                 M.grp_beg[l] = reinterpret_cast<const int32_t*>(base + o_grp[l]);
-                M.grp_end[l] = M.grp_beg[l] + (size_t)h->ml_n[l] * h->ml_n[l + 1];
+                M.grp_end[l] = M.grp_beg[l] + (size_t)P.n[l] * P.n[l + 1];
             }
         }
         M.nsT = reinterpret_cast<double*>(base + o_nsT); M.nsX = reinterpret_cast<double*>(base + o_nsX);
@@ -507,36 +301,25 @@ void build_ml(uzl_pgo* h, const std::vector<int32_t>& row_ptr0, const std::vecto
         M.Sg = reinterpret_cast<double*>(base + o_sg);
         uzl_pgo::MlBuf& B = h->mlb[bi];
         B.dml = h->d_ml.p + bi;
-        B.nsT = M.nsT; B.nsX = M.nsX; B.y1 = h->ml_comp ? M.Ydense[cl] : nullptr;
+        B.nsT = M.nsT; B.nsX = M.nsX; B.y1 = cl ? M.Ydense[cl] : nullptr;
         B.rg[0] = reinterpret_cast<double*>(base + o_rga);
         B.rg[1] = reinterpret_cast<double*>(base + o_rgb);
         B.lambda_setup = 0.;
         MlHot& Hh = B.hot;
         memset(&Hh, 0, sizeof(Hh));
         Hh.levels = L;
-        for (int l = 0; l <= L; l++) { Hh.n[l] = h->ml_n[l]; Hh.fan[l] = h->ml_fan[l]; Hh.geo[l] = M.lv[l].geo; Hh.Winv[l] = M.lv[l].Winv; }
+        for (int l = 0; l <= L; l++) { Hh.n[l] = P.n[l]; Hh.fan[l] = P.fan[l]; Hh.geo[l] = M.lv[l].geo; Hh.Winv[l] = M.lv[l].Winv; }
         Hh.geo0 = M.lv[0].geo; Hh.top_inv = M.top_inv; Hh.Sg = M.Sg; Hh.Vg = reinterpret_cast<double*>(base + o_vg);
-        Hh.Cmat = h->ml_comp ? ((h->ml_ns_steps & 1) ? M.nsX : M.Ydense[cl]) : nullptr;   // Newton-Schulz steps ping-pong Y_cl <-> nsX
-        Hh.Cmat32 = h->ml_comp ? reinterpret_cast<const float*>(base + o_c32) : nullptr;
+        Hh.Cmat = cl ? ((P.ns_steps & 1) ? M.nsX : M.Ydense[cl]) : nullptr;   // Newton-Schulz steps ping-pong Y_cl <-> nsX
+        Hh.Cmat32 = cl ? reinterpret_cast<const float*>(base + o_c32) : nullptr;
         Hh.c32_stride = c32_stride;
         B.l1_span_ptr = M.lv[1].blk;
-        h->l1_span = (int64_t)((M.lv[1].M + (size_t)std::max(h->ml_n[1], 1) * 36) - M.lv[1].blk);
+        h->l1_span = (int64_t)((M.lv[1].M + (size_t)std::max(P.n[1], 1) * 36) - M.lv[1].blk);
     }
     h->ml_ix = 0; h->ml_pending = false;
     UZL_HIP(hipMemcpyAsync(h->d_ml.p, Mh, sizeof(Mh), hipMemcpyHostToDevice, s));
     UZL_HIP(hipStreamSynchronize(s));      // stage / Mh are locals
 }
-}  // namespace
-namespace uzl {
-// Asynchronous rebuild (second stream, second copy of the hierarchy) pays on the composite level-1 path, and for the reduced system of a
-// chain-like graph on the level-2 path: there a rebuild (0.8 ms) is as long as the LM iteration it would otherwise hold up.  (Other
-// level-2 graphs - config 4 - measured +9 % PCG iterations for no net gain.)
-bool ml_async_level(const uzl_pgo* h)
-{
-    return h->ml_cl == 1 || (h->ml_cl == 2 && h->red.on && h->red.strong);
-}
-}  // namespace uzl
-namespace {
 
 // Order of the free vertices in the block system.  The multilevel preconditioner aggregates 8 CONSECUTIVE blocks, which is only a
 // good coarse space when consecutive blocks are strongly coupled.  In a single session the node ids are time-ordered (std::map
@@ -592,8 +375,196 @@ std::vector<int32_t> aggregation_order(const uzl_pgo* h)
     return order;
 }
 
+// the slot twins' slot for this handle: its slot (the handle's own flags; rebuilt with the structure - the additive fallback bumps
+// structure_gen when it swaps hot.Cmat), the hierarchy copy in use, the pose buffer of the current estimate and pcg_tol^2.  Launch
+// geometry: h->ml_shape
+HostSlot host_slot(uzl_pgo* h)
+{
+    if (h->ml_slot_gen != h->structure_gen) {
+        h->ml_slot = make_slot(h, nullptr, nullptr);
+        h->ml_shape = make_shape({h}, 1, false);
+        h->ml_slot_gen = h->structure_gen;
+    }
+    HostSlot hs;
+    hs.S = h->ml_slot; hs.ix = h->ml_ix; hs.cur = h->cur == h->pose_b.p ? 1 : 0; hs.tol2 = h->cfg.pcg_tol * h->cfg.pcg_tol;
+    return hs;
+}
+// numeric part of the set-up of hierarchy copy hs.ix; a sharded solve all-reduces level 1 on the way (levels >= 2 need no exchange)
+void ml_setup_numeric(uzl_pgo* h, const HostSlot& hs, hipStream_t s, KernelTimer* timer)
+{
+    kl_ml_numeric(hs, h->ml_shape, s, timer, [&] { shard_allreduce(h, h->mlb[hs.ix].l1_span_ptr, h->l1_span); });
+}
+
+// enqueue `pairs` x 2 PCG iterations (p0 -> p1 -> p0); kernels no-op once the device `done` flag is set
+void enqueue_pcg_pairs(uzl_pgo* h, int pairs, bool timed)
+{
+    hipStream_t s = h->stream;
+    const PgoDev& D = h->Dp;
+    const double tol2 = h->cfg.pcg_tol * h->cfg.pcg_tol;
+    const bool ml = h->mlp.levels > 0;
+    const HostSlot hs = ml ? host_slot(h) : HostSlot{};
+    const int ga = g_pcg_spmv(D.nb), gu = g_pcg_update(D.nb);                     // block-Jacobi: partials written by spmv / by update
+    double* pb[2] = {h->pbuf[0], h->pbuf[1]};
+    auto progress = [&]() {                                                         // how far is x from settled: the stop test (pgo_kernels.hip)
+        if (timed) h->timer.begin("pcg_progress", s);
+        k_pcg_progress(D, s);
+        if (timed) h->timer.end(s);
+    };
+    for (int i = 0; i < 2 * pairs; i++) {
+        if (!ml && i > 0 && i % kProgressEveryBJ == 0) progress();
+        double* po = pb[i & 1];
+        double* pn = pb[(i & 1) ^ 1];
+        hipEvent_t ea = nullptr, eb = nullptr;
+        if (ml) {
+            if (timed) h->timer.pair("pcg_spmv", &ea, &eb);                      // dispatch timestamps: agree with rocprofv3
+            kl_ml_spmv(hs, h->ml_shape, i & 1, s, ea, eb);
+            shard_allreduce(h, D.ap, h->iter_span);                              // the one exchange per PCG iteration
+            ea = eb = nullptr;
+            if (timed) h->timer.pair("ml_cg", &ea, &eb);
+            UZL_HIP(kl_ml_cg(hs, h->ml_shape, i & 1, 0, s, ea, eb));
+        } else {
+            if (timed) h->timer.begin("pcg_spmv", s);
+            k_pcg_spmv(D, po, pn, gu, tol2, s);
+            if (timed) h->timer.end(s);
+            if (timed) h->timer.begin("pcg_update", s);
+            k_pcg_update(D, pn, ga, s);
+            if (timed) h->timer.end(s);
+        }
+    }
+    if (!ml) progress();
+}
+
+// |r|^2 / |b|^2 a solve under the multiplicative operator must reach.  Deliberately loose: legitimate solves end at 1e-10 .. 1e-6 while
+// the linearisation moves and at ~1e-3 once LM has converged and b itself is rounding noise (a 1e-4 guard tripped there and threw a
+// healthy operator away); an operator that is not SPD leaves |r| of the order of |b| or above.
+// (kResidualGuard = 0.25: pgo_lm.hpp)
+
+// The launch-bound inner loop is captured once per problem structure and preconditioner copy: every kernel argument (pointers,
+// partial counts, tolerance) is fixed, lambda and the CG scalars live in device memory.  Two lengths: 2 x kGraphPairs iterations,
+// and 2 x kShortPairs for solves expected to end at once (a launch behind convergence is a no-op, but still ~1.2 us of stream time:
+// a converged LM iteration's solve of 2 - 4 iterations used to pay for 28 of them).
+void ensure_pcg_graph(uzl_pgo* h)
+{
+    uzl_pgo::MlBuf& B = h->mlb[h->ml_ix];
+    if (B.graph_exec) return;
+    const auto t0 = std::chrono::steady_clock::now();
+    UZL_HIP(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
+    enqueue_pcg_pairs(h, kGraphPairs, false);
+    UZL_HIP(hipStreamEndCapture(h->stream, &B.graph));
+    UZL_HIP(hipGraphInstantiate(&B.graph_exec, B.graph, nullptr, nullptr, 0));
+    UZL_HIP(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
+    enqueue_pcg_pairs(h, kShortPairs, false);
+    UZL_HIP(hipStreamEndCapture(h->stream, &B.graph_s));
+    UZL_HIP(hipGraphInstantiate(&B.graph_exec_s, B.graph_s, nullptr, nullptr, 0));
+    if (h->cfg.verbose) fprintf(stderr, "[uzl_pgo] structure: %-28s %.3f ms\n", "PCG graphs of one copy", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    h->structure_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// one (H + lambda I) dx = b solve in LM iteration `it`; returns PCG iterations used, sets *converged
+int pcg_solve(uzl_pgo* h, int it, bool* converged)
+{
+    hipStream_t s = h->stream;
+    const PgoDev& D = h->Dp;
+    if (D.nb == 0) { *converged = true; h->prev_pcg_iters = 0; h->last_residual_ratio = 0.; return 0; }     // every free vertex was Schur-eliminated: nothing left to iterate on
+    const int max_it = h->cfg.pcg_max_iter > 0 ? h->cfg.pcg_max_iter : 6 * std::max(D.nb, 1);
+    const bool timed = h->timer.on || h->no_graph || h->sharded;   // per-kernel events, rocprofv3 and the exchange callback need eager launches
+    if (h->mlp.levels > 0) {
+        const HostSlot hs = host_slot(h);
+        if (h->ml_trial_setup) {
+            kl_ml_trial(hs, h->ml_shape, ml_ns_steps_at(h->ml_ns_steps, it), s, &h->timer);
+            h->ml_trial_setup = false;
+            h->mlb[h->ml_ix].lambda_setup = h->lambda_now;
+        }
+        { Timed t(h, "pcg_init"); kl_ml_pcg_init(hs, h->ml_shape, s); }
+        { Timed t(h, "ml_cg"); UZL_HIP(kl_ml_cg(hs, h->ml_shape, 0, 1, s)); }
+    } else {
+        { Timed t(h, "precond"); k_precond(D, s); }
+        Timed t(h, "pcg_init"); k_pcg_init(D, h->pbuf[0], h->pbuf[1], s);
+    }
+    if (!timed) ensure_pcg_graph(h);
+    int launched = 0;
+    // first batch sized from the previous solve (in steps of 2 x kShortPairs iterations), then two short ones, then long ones; the
+    // kernels no-op once `done` is set
+    constexpr int kFirstPct = 95;                                           // the first batch: 95 % of the previous solve's count
+    constexpr int kStep = 2 * kShortPairs;
+    const int kLong = 2 * kGraphPairs;
+    auto round_up = [](int v) { return ((v + kStep - 1) / kStep) * kStep; };
+    // (+ 1: a solve that ends by the stop test after k iterations is declared done by the ml_spmv of iteration k + 1)
+    int want = h->prev_pcg_iters > 0 ? std::max(kStep, round_up((h->prev_pcg_iters * kFirstPct) / 100 + 1)) : kLong;
+    for (int round = 0;; round++) {
+        want = round_up(std::max(1, std::min(want, max_it - launched)));
+        if (timed) enqueue_pcg_pairs(h, want / 2, h->timer.on);
+        else {
+            for (int i = 0; i < want / kLong; i++) UZL_HIP(hipGraphLaunch(h->mlb[h->ml_ix].graph_exec, s));
+            for (int i = 0; i < (want % kLong + kStep - 1) / kStep; i++) UZL_HIP(hipGraphLaunch(h->mlb[h->ml_ix].graph_exec_s, s));
+        }
+        launched += want;
+        k_residual_guard(D, s);                                   // a no-op until `done` is set
+        fetch_scal(h);
+        if (h->h_scal.p->flags[0] || launched >= max_it) break;
+        want = round < 2 ? kStep : kLong;
+    }
+    UZL_HIP(hipGetLastError());
+    *converged = h->h_scal.p->flags[0] != 0 && h->h_scal.p->flags[2] == 0;
+    // The multiplicative cycle / Newton-Schulz operator is not SPD by construction (see the fallback in do_optimize).  The
+    // recurrence residual r is the true residual of x whatever the preconditioner did, so a solve under that operator which
+    // claims convergence in the M^-1 norm while |r| has not come down by kResidualGuard relative to |b| is refused and the
+    // caller falls back to the additive operator (a sum of SPD terms, whose M^-1 norm is a norm).
+    h->last_residual_ratio = h->h_scal.p->scal[7];
+    if (*converged && (h->ml_mult || h->ml_ns_steps > 0) && !(h->last_residual_ratio <= kResidualGuard)) { *converged = false; h->guard_trips++; }
+    const int iters = h->h_scal.p->flags[1];
+    h->prev_pcg_iters = iters;
+    return iters;
+}
 }  // namespace
+
 namespace uzl {
+const int kUpperNs = 4;                   // Newton-Schulz steps of the dense levels above the composite level (even: the result ends in Ydense[l])
+// the rate rule where the rebuild is synchronous: with the dense operator of that class a rebuild pays as soon as the rate has fallen to
+// 0.75 of the fresh one (0.6 elsewhere; -3 ... -8 % on eight of nine such shapes, the 30k / 150k graph - no dense operator - +14 %)
+constexpr double kRateDropSyncDense = 0.75;
+// Newton-Schulz steps of a synchronous set-up at LM iteration `it` for a structure that asks for `structure_steps` (4 on large loopy
+// graphs): 2 in the first kNsEarlyIts iterations (against the full count from the start: -3.4 % over fourteen large shapes at the same
+// PCG iteration count; 4 iterations instead of 2 gain on the largest and lose at 10k, 8 lose everywhere; NO step at all in those two - the
+// cycle's operator as it comes - another -2.5 %, not taken: that operator is what the residual guard exists for)
+int ml_ns_steps_at(int structure_steps, int it)
+{
+    constexpr int kNsEarlyIts = 2, kNsEarlySteps = 2;
+    return (structure_steps > 2 && it < kNsEarlyIts) ? kNsEarlySteps : structure_steps;
+}
+double ml_rate_drop(const uzl_pgo* h) { return (!ml_async_level(h) && h->mlp.cl > 0) ? kRateDropSyncDense : kRateDrop; }
+
+// G2: setFixedNodes (g2o_optimizer.cpp:301-349): per connected component (over the system edges) without a
+// fixed vertex, fix the vertex with the smallest index (= lexicographically smallest node id, :338).
+int32_t gauge_fix(uzl_pgo* h)
+{
+    const int n = h->n;
+    std::vector<int32_t> p((size_t)n);
+    std::iota(p.begin(), p.end(), 0);
+    for (int k = 0; k < h->e; k++) {
+        int32_t a = uf_find(p, h->ij[2 * k]), b = uf_find(p, h->ij[2 * k + 1]);
+        if (a != b) { if (a < b) p[b] = a; else p[a] = b; }
+    }
+    std::vector<uint8_t> has((size_t)n, 0);
+    for (int v = 0; v < n; v++) if (h->fixed_eff[v]) has[uf_find(p, v)] = 1;
+    int32_t cnt = 0;
+    for (int v = 0; v < n; v++) {
+        const int32_t r = uf_find(p, v);
+        if (!has[r]) { h->fixed_eff[r] = 1; has[r] = 1; cnt++; }
+    }
+    return cnt;
+}
+
+// Asynchronous rebuild (second stream, second copy of the hierarchy) pays on the composite level-1 path, and for the reduced system of a
+// chain-like graph on the level-2 path: there a rebuild (0.8 ms) is as long as the LM iteration it would otherwise hold up.  (Other
+// level-2 graphs - config 4 - measured +9 % PCG iterations for no net gain.)
+bool ml_async_level(const uzl_pgo* h)
+{
+    return h->mlp.cl == 1 || (h->mlp.cl == 2 && h->red.on && h->red.strong);
+}
+
+// block-CSR structure over the free vertices (one slot per (free endpoint, system edge)), then the three steps of DESIGN.md section 6:
+// Schur plan -> hierarchy plan -> upload
 void build_structure(uzl_pgo* h)
 {
     auto t_prev = std::chrono::steady_clock::now();
@@ -629,9 +600,8 @@ void build_structure(uzl_pgo* h)
         if (b >= 0) { const int s = fill[b]++; slot_j[k] = s; col[s] = a; slot_edge[s] = 2 * k + 1; }
     }
     hipStream_t s = h->stream;
-    const size_t nbz = std::max(nb, 1), nsz = std::max(nslots, 1);
-    h->d_b2v.reserve(nbz); h->d_row_ptr.reserve(nbz + 1); h->d_col.reserve(nsz);
-    h->d_blk.reserve(nsz * 36); h->d_slot_edge.reserve(nsz); h->d_srec.reserve(nsz * 44); h->d_smeta.reserve(nsz);
+    const size_t nsz = std::max(nslots, 1);
+    h->d_slot_edge.reserve(nsz); h->d_srec.reserve(nsz * 44); h->d_smeta.reserve(nsz);
     h->srec_stale = true;
     std::vector<int4> smeta(nsz);
     for (int q = 0; q < nslots; q++) {
@@ -639,18 +609,9 @@ void build_structure(uzl_pgo* h)
         smeta[q] = make_int4(slot_edge[q], h->ij[2 * k], h->ij[2 * k + 1], (other + 1) | (h->robust[k] ? 1 << 30 : 0));
     }
     if (nslots > 0) UZL_HIP(hipMemcpyAsync(h->d_smeta.p, smeta.data(), sizeof(int4) * nslots, hipMemcpyHostToDevice, s));
-    h->d_hdiag.reserve(nbz * 42); h->d_minv.reserve(nbz * 36);              // [H_aa | b] contiguous: one all-reduce when sharded
-    h->d_x.reserve(nbz * 6); h->d_xs.reserve(nbz * 6); h->d_r.reserve(nbz * 6); h->d_z.reserve(nbz * 6); h->d_p.reserve(nbz * 6); h->d_p2.reserve(nbz * 6); h->d_ap.reserve(nbz * 12 + kMaxPartials);   // [A p | restricted A p | partials]
     if (n > 0) UZL_HIP(hipMemcpyAsync(h->d_v2b.p, v2b.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
-    if (nb > 0) UZL_HIP(hipMemcpyAsync(h->d_b2v.p, b2v.data(), sizeof(int32_t) * nb, hipMemcpyHostToDevice, s));
-    UZL_HIP(hipMemcpyAsync(h->d_row_ptr.p, row_ptr.data(), sizeof(int32_t) * (nb + 1), hipMemcpyHostToDevice, s));
-    if (nslots > 0) UZL_HIP(hipMemcpyAsync(h->d_col.p, col.data(), sizeof(int32_t) * nslots, hipMemcpyHostToDevice, s));
+    const std::vector<int32_t> rowhdr = h->sys.upload(nb, row_ptr, col, b2v, s);
     if (nslots > 0) UZL_HIP(hipMemcpyAsync(h->d_slot_edge.p, slot_edge.data(), sizeof(int32_t) * nslots, hipMemcpyHostToDevice, s));
-    std::vector<int32_t> rowhdr((size_t)nbz * kRowHdr, -1);
-    for (int a = 0; a < nb; a++) {
-        rowhdr[(size_t)a * kRowHdr] = row_ptr[a]; rowhdr[(size_t)a * kRowHdr + 1] = row_ptr[a + 1];
-        for (int k = 0; k < 20 && row_ptr[a] + k < row_ptr[a + 1]; k++) rowhdr[(size_t)a * kRowHdr + 2 + k] = col[row_ptr[a] + k];
-    }
     // row blocks of the Hessian build: consecutive rows with <= 256 slots and <= 42 rows, so that a workgroup makes one pass (a row with
     // more slots is a block of its own and loops); beyond kMaxPartials blocks (> ~1M slots) blocks hold more and loop as well
     std::vector<int32_t> rb_ptr(1, 0);
@@ -667,22 +628,19 @@ void build_structure(uzl_pgo* h)
     }
     h->d_rb_ptr.reserve(rb_ptr.size());
     UZL_HIP(hipMemcpyAsync(h->d_rb_ptr.p, rb_ptr.data(), sizeof(int32_t) * rb_ptr.size(), hipMemcpyHostToDevice, s));
-    h->d_rowhdr.reserve(nbz * kRowHdr);
-    UZL_HIP(hipMemcpyAsync(h->d_rowhdr.p, rowhdr.data(), sizeof(int32_t) * nbz * kRowHdr, hipMemcpyHostToDevice, s));
     // blocks of slots whose neighbour is fixed are never written: keep them defined
-    if (nslots > 0) UZL_HIP(hipMemsetAsync(h->d_blk.p, 0, sizeof(double) * 36 * (size_t)nslots, s));      // (and slots of edges other ranks own stay 0)
+    if (nslots > 0) UZL_HIP(hipMemsetAsync(h->sys.blk.p, 0, sizeof(double) * 36 * (size_t)nslots, s));      // (and slots of edges other ranks own stay 0)
     UZL_HIP(hipStreamSynchronize(s));       // host vectors go out of scope
     PgoDev& D = h->D;
-    D.n = n; D.nb = nb; D.e = e; D.nslots = nslots;
+    D.n = n; D.e = e;
+    h->sys.bind(D, nb, nslots);
     D.pose = h->cur; D.pose_trial = h->trial;
-    D.v2b = h->d_v2b.p; D.b2v = h->d_b2v.p; D.ei = h->d_ei.p; D.ej = h->d_ej.p;
+    D.v2b = h->d_v2b.p; D.ei = h->d_ei.p; D.ej = h->d_ej.p;
     D.zinv = h->d_zinv.p; D.info = h->d_info.p; D.robust = h->d_robust.p;
-    D.row_ptr = h->d_row_ptr.p; D.col = h->d_col.p; D.rowhdr = h->d_rowhdr.p;
-    D.rb_ptr = h->d_rb_ptr.p; D.n_rb = (int32_t)rb_ptr.size() - 1; D.pad_rb = 0; D.srec = h->d_srec.p; D.smeta = h->d_smeta.p; D.blk = h->d_blk.p; D.hdiag = h->d_hdiag.p; D.minv = h->d_minv.p;
-    D.b = h->d_hdiag.p + (size_t)nb * 36; D.x = h->d_x.p; D.xs = h->d_xs.p; D.r = h->d_r.p; D.z = h->d_z.p; D.p = h->d_p.p; D.ap = h->d_ap.p;
-    D.part_a = h->d_ap.p + (size_t)nbz * 12; D.part_b = h->d_part_b.p; D.part_c = h->d_part_c.p;
+    D.rb_ptr = h->d_rb_ptr.p; D.n_rb = (int32_t)rb_ptr.size() - 1; D.pad_rb = 0; D.srec = h->d_srec.p; D.smeta = h->d_smeta.p;
+    D.part_b = h->d_part_b.p; D.part_c = h->d_part_c.p;
     D.scal = h->d_scal.p; D.flags = h->d_flags.p;
-    D.e_begin = 0; D.e_end = e; D.diag_owner = 1; D.sibling0 = 1;      // sibling0 finalised after build_ml
+    D.e_begin = 0; D.e_end = e; D.diag_owner = 1; D.sibling0 = 1;      // sibling0 finalised once the hierarchy is planned
     // ---- Schur reduction of the chain interiors (pgo_schur.hpp): when a third or more of the free vertices carry nothing but their two
     //      chain edges, the PCG runs on the Schur complement over the others (sharded solves included: see SchurDev::runblk).
     uzl_pgo::Reduced& Rd = h->red;
@@ -733,24 +691,18 @@ void build_structure(uzl_pgo* h)
         tick("Schur plan");
         if (P.n_int >= 64 && (int64_t)100 * P.n_int >= (int64_t)kSchurMinPct * nb) {
             Rd.on = true; Rd.n_int = P.n_int; Rd.n_runs = P.n_runs; Rd.longest_run = P.longest_run; Rd.strong = P.strong; Rd.strong_blocks = P.strong && P.n_strong2 > 0; Rd.n_sep = P.n_sep;
-            const size_t nr = (size_t)std::max(P.nbr, 1), nsr = (size_t)std::max(P.nslots_r, 1), ni = (size_t)P.n_int, nru = (size_t)P.n_runs;
+            const size_t ni = (size_t)P.n_int, nru = (size_t)P.n_runs;
             auto up = [&](DevBuf<int32_t>& b, const std::vector<int32_t>& v, size_t min_n) {
                 b.reserve(std::max(v.size(), min_n));
                 if (!v.empty()) UZL_HIP(hipMemcpyAsync(b.p, v.data(), sizeof(int32_t) * v.size(), hipMemcpyHostToDevice, s));
             };
             up(Rd.run_ptr, P.run_ptr, 1); up(Rd.run_rows, P.run_rows, 1); up(Rd.slotP, P.slotP, 1); up(Rd.slotN, P.slotN, 1);
             up(Rd.endL, P.endL, 1); up(Rd.endR, P.endR, 1); up(Rd.sep_rows, P.sep_rows, 1); up(Rd.rsrc, P.rsrc, 1);
-            up(Rd.inc_ptr, P.inc_ptr, 1); up(Rd.inc, P.inc, 1); up(Rd.row_ptr, P.row_ptr, 1); up(Rd.col, P.col, 1);
-            std::vector<int32_t> rb2v((size_t)P.nbr), rhdr(nr * kRowHdr, -1);
-            for (int i = 0; i < P.nbr; i++) {
-                rb2v[i] = P.sep_rows[i] >= 0 ? b2v[P.sep_rows[i]] : -1;
-                rhdr[(size_t)i * kRowHdr] = P.row_ptr[i]; rhdr[(size_t)i * kRowHdr + 1] = P.row_ptr[i + 1];
-                for (int k = 0; k < 20 && P.row_ptr[i] + k < P.row_ptr[i + 1]; k++) rhdr[(size_t)i * kRowHdr + 2 + k] = P.col[P.row_ptr[i] + k];
-            }
-            up(Rd.b2v, rb2v, 1); up(Rd.rowhdr, rhdr, 1);
+            up(Rd.inc_ptr, P.inc_ptr, 1); up(Rd.inc, P.inc, 1);
+            std::vector<int32_t> rb2v((size_t)P.nbr);
+            for (int i = 0; i < P.nbr; i++) rb2v[i] = P.sep_rows[i] >= 0 ? b2v[P.sep_rows[i]] : -1;
+            const std::vector<int32_t> rhdr = Rd.sys.upload(P.nbr, P.row_ptr, P.col, rb2v, s);
             Rd.elim.reserve(std::max<size_t>(ni, 1) * kSchurElim); Rd.runout.reserve(std::max<size_t>(nru, 1) * kSchurRunOut);
-            Rd.blk.reserve(nsr * 36); Rd.hdiag.reserve(nr * 42); Rd.minv.reserve(nr * 36);
-            Rd.x.reserve(nr * 6); Rd.xs.reserve(nr * 6); Rd.r.reserve(nr * 6); Rd.z.reserve(nr * 6); Rd.p.reserve(nr * 6); Rd.p2.reserve(nr * 6); Rd.ap.reserve(nr * 12 + kMaxPartials);
             UZL_HIP(hipStreamSynchronize(s));                                  // P's vectors and the two locals go out of scope
             SchurDev& S = Rd.S;
             S.n_runs = P.n_runs; S.n_int = P.n_int; S.nbr = P.nbr; S.nslots_r = P.nslots_r;
@@ -762,33 +714,42 @@ void build_structure(uzl_pgo* h)
             S.runblk = nullptr;
             if (may_shard) { Rd.runblk.reserve((ni + nru) * 36); S.runblk = Rd.runblk.p; }
             Dp = D;
-            Dp.nb = P.nbr; Dp.nslots = P.nslots_r; Dp.b2v = Rd.b2v.p; Dp.row_ptr = Rd.row_ptr.p; Dp.col = Rd.col.p; Dp.rowhdr = Rd.rowhdr.p;
-            Dp.blk = Rd.blk.p; Dp.hdiag = Rd.hdiag.p; Dp.minv = Rd.minv.p; Dp.b = Rd.hdiag.p + (size_t)P.nbr * 36;
-            Dp.x = Rd.x.p; Dp.xs = Rd.xs.p; Dp.r = Rd.r.p; Dp.z = Rd.z.p; Dp.p = Rd.p.p; Dp.ap = Rd.ap.p; Dp.part_a = Rd.ap.p + nr * 12;
+            Rd.sys.bind(Dp, P.nbr, P.nslots_r);
             Dp.smeta = nullptr; Dp.srec = nullptr;                            // the reduced system is assembled by schur_assemble_kernel
             rrow_ptr.swap(P.row_ptr); rcol.swap(P.col);
         }
     }
     PgoDev& Dsys = Rd.on ? Dp : D;                                             // what the PCG kernels get
     const int nbp = Dsys.nb;
-    double* apbuf = Rd.on ? Rd.ap.p : h->d_ap.p;
+    const SysBufs& Bsys = Rd.on ? Rd.sys : h->sys;
+    double* apbuf = Bsys.ap.p;
     tick("reduced system uploads");
-    if (Rd.on) build_ml(h, rrow_ptr, rcol, nbp, Dsys.nslots, Rd.row_ptr.p, Rd.col.p, Rd.blk.p, Rd.hdiag.p);
-    else build_ml(h, row_ptr, col, nb, nslots, h->d_row_ptr.p, h->d_col.p, h->d_blk.p, h->d_hdiag.p);
-    tick("hierarchy (host index arrays + uploads)");
+    {
+        static const bool comp4_off = diag_flag("UZL_ML_NO_COMP4");          // the walked hierarchy instead (tests/test_ab_paths_gpu.py)
+        MlPlanIn in;
+        in.nb = nbp; in.nslots = Dsys.nslots;
+        in.precond_on = h->cfg.preconditioner != 0; in.strong_blocks = Rd.strong_blocks; in.mult_banned = h->mult_banned; in.comp4_off = comp4_off;
+        h->mlp = ml_plan(in, Rd.on ? rrow_ptr : row_ptr, Rd.on ? rcol : col);
+        tick("hierarchy plan (host index arrays)");
+        upload_ml(h, h->mlp, Dsys.row_ptr, Dsys.col, Dsys.blk, Dsys.hdiag);
+        h->mlp.release_indices();
+        // (a block-Jacobi structure leaves the two as the structure before it had them, as it always did: pcg_solve's residual guard reads them)
+        if (h->mlp.levels > 0) { h->ml_mult = h->mlp.mult; h->ml_ns_steps = h->mlp.ns_steps; }
+    }
+    tick("hierarchy uploads");
     {   // per-iteration exchange buffer: [A p (6 nb) | restricted A p (6 n_g) | p.Ap partials]
-        const int gl = (h->ml_levels == 0) ? 0 : ((h->ml_agg == 1 || h->ml_levels < 2) ? 1 : 2);
-        const size_t ng6 = gl ? (size_t)h->ml_n[gl] * 6 * (gl == 2 ? 2 : 1) : 0;      // gather level 2: two half-aggregate parts per entity (sg_at)
+        const int gl = h->mlp.gather_level;
+        const size_t ng6 = gl ? (size_t)h->mlp.n[gl] * 6 * (gl == 2 ? 2 : 1) : 0;      // gather level 2: two half-aggregate parts per entity (sg_at)
         if (gl) { h->mlb[0].hot.Sg = apbuf + (size_t)nbp * 6; h->mlb[1].hot.Sg = h->mlb[0].hot.Sg; }
         Dsys.part_a = apbuf + (size_t)nbp * 6 + ng6;
-        h->iter_span = (int64_t)((size_t)nbp * 6 + ng6 + (gl ? (size_t)g_ml_spmv(nbp, h->ml_agg) : 0));
+        h->iter_span = (int64_t)((size_t)nbp * 6 + ng6 + (gl ? (size_t)g_ml_spmv(nbp, h->mlp.agg) : 0));
     }
-    Dsys.sibling0 = (h->ml_levels > 0 && h->ml_agg == 1) ? 1 : 0;     // large graphs keep the level-0 smoother block-diagonal
+    Dsys.sibling0 = (h->mlp.levels > 0 && h->mlp.agg == 1) ? 1 : 0;     // large graphs keep the level-0 smoother block-diagonal
     D.sibling0 = Dsys.sibling0;
     // ---- sharded solve (BASELINE config 4): this rank linearises a contiguous range of the system edges
     // (a callback with world_size 1 still runs every exchange step: that is how the RCCL callback is tested on one GPU;
     //  graphs too small for the multilevel path are simply solved redundantly by every rank)
-    h->sharded = h->ml_levels > 0 && may_shard;
+    h->sharded = h->mlp.levels > 0 && may_shard;
     if (h->sharded) {
         const int base = e / h->world, rem = e % h->world;
         D.e_begin = h->rank * base + std::min(h->rank, rem);
@@ -801,79 +762,11 @@ void build_structure(uzl_pgo* h)
         Rd.S.runblk = h->sharded ? Rd.runblk.p : nullptr;
     }
     if (!Rd.on) Dp = D;
-    h->pbuf[0] = Rd.on ? Rd.p.p : h->d_p.p; h->pbuf[1] = Rd.on ? Rd.p2.p : h->d_p2.p;
+    h->pbuf[0] = Bsys.p.p; h->pbuf[1] = Bsys.p2.p;
     h->structure_ready = true;
     h->structure_gen++;
 }
-}  // namespace uzl
-namespace {
 
-// the slot twins' slot for this handle: its slot (the handle's own flags; rebuilt with the structure - the additive fallback bumps
-// structure_gen when it swaps hot.Cmat), the hierarchy copy in use, the pose buffer of the current estimate and pcg_tol^2.  Launch
-// geometry: h->ml_shape
-HostSlot host_slot(uzl_pgo* h)
-{
-    if (h->ml_slot_gen != h->structure_gen) {
-        h->ml_slot = make_slot(h, nullptr, nullptr);
-        h->ml_shape = make_shape({h}, 1, false);
-        h->ml_slot_gen = h->structure_gen;
-    }
-    HostSlot hs;
-    hs.S = h->ml_slot; hs.ix = h->ml_ix; hs.cur = h->cur == h->pose_b.p ? 1 : 0; hs.tol2 = h->cfg.pcg_tol * h->cfg.pcg_tol;
-    return hs;
-}
-// numeric part of the set-up of hierarchy copy hs.ix; a sharded solve all-reduces level 1 on the way (levels >= 2 need no exchange)
-void ml_setup_numeric(uzl_pgo* h, const HostSlot& hs, hipStream_t s, KernelTimer* timer)
-{
-    kl_ml_numeric(hs, h->ml_shape, s, timer, [&] { shard_allreduce(h, h->mlb[hs.ix].l1_span_ptr, h->l1_span); });
-}
-
-// enqueue `pairs` x 2 PCG iterations (p0 -> p1 -> p0); kernels no-op once the device `done` flag is set
-void enqueue_pcg_pairs(uzl_pgo* h, int pairs, bool timed)
-{
-    hipStream_t s = h->stream;
-    const PgoDev& D = h->Dp;
-    const double tol2 = h->cfg.pcg_tol * h->cfg.pcg_tol;
-    const bool ml = h->ml_levels > 0;
-    const HostSlot hs = ml ? host_slot(h) : HostSlot{};
-    const int ga = g_pcg_spmv(D.nb), gu = g_pcg_update(D.nb);                     // block-Jacobi: partials written by spmv / by update
-    double* pb[2] = {h->pbuf[0], h->pbuf[1]};
-    auto progress = [&]() {                                                         // how far is x from settled: the stop test (pgo_kernels.hip)
-        if (timed) h->timer.begin("pcg_progress", s);
-        k_pcg_progress(D, s);
-        if (timed) h->timer.end(s);
-    };
-    for (int i = 0; i < 2 * pairs; i++) {
-        if (!ml && i > 0 && i % kProgressEveryBJ == 0) progress();
-        double* po = pb[i & 1];
-        double* pn = pb[(i & 1) ^ 1];
-        hipEvent_t ea = nullptr, eb = nullptr;
-        if (ml) {
-            if (timed) h->timer.pair("pcg_spmv", &ea, &eb);                      // dispatch timestamps: agree with rocprofv3
-            kl_ml_spmv(hs, h->ml_shape, i & 1, s, ea, eb);
-            shard_allreduce(h, D.ap, h->iter_span);                              // the one exchange per PCG iteration
-            ea = eb = nullptr;
-            if (timed) h->timer.pair("ml_cg", &ea, &eb);
-            UZL_HIP(kl_ml_cg(hs, h->ml_shape, i & 1, 0, s, ea, eb));
-        } else {
-            if (timed) h->timer.begin("pcg_spmv", s);
-            k_pcg_spmv(D, po, pn, gu, tol2, s);
-            if (timed) h->timer.end(s);
-            if (timed) h->timer.begin("pcg_update", s);
-            k_pcg_update(D, pn, ga, s);
-            if (timed) h->timer.end(s);
-        }
-    }
-    if (!ml) progress();
-}
-
-// |r|^2 / |b|^2 a solve under the multiplicative operator must reach.  Deliberately loose: legitimate solves end at 1e-10 .. 1e-6 while
-// the linearisation moves and at ~1e-3 once LM has converged and b itself is rounding noise (a 1e-4 guard tripped there and threw a
-// healthy operator away); an operator that is not SPD leaves |r| of the order of |b| or above.
-// (kResidualGuard = 0.25: pgo_lm.hpp)
-
-}  // namespace
-namespace uzl {
 void destroy_pcg_graph(uzl_pgo* h)
 {
     for (auto& B : h->mlb) {
@@ -883,89 +776,7 @@ void destroy_pcg_graph(uzl_pgo* h)
         if (B.graph_s) { (void)hipGraphDestroy(B.graph_s); B.graph_s = nullptr; }
     }
 }
-}  // namespace uzl
-namespace {
 
-// The launch-bound inner loop is captured once per problem structure and preconditioner copy: every kernel argument (pointers,
-// partial counts, tolerance) is fixed, lambda and the CG scalars live in device memory.  Two lengths: 2 x kGraphPairs iterations,
-// and 2 x kShortPairs for solves expected to end at once (a launch behind convergence is a no-op, but still ~1.2 us of stream time:
-// a converged LM iteration's solve of 2 - 4 iterations used to pay for 28 of them).
-void ensure_pcg_graph(uzl_pgo* h)
-{
-    uzl_pgo::MlBuf& B = h->mlb[h->ml_ix];
-    if (B.graph_exec) return;
-    const auto t0 = std::chrono::steady_clock::now();
-    UZL_HIP(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-    enqueue_pcg_pairs(h, kGraphPairs, false);
-    UZL_HIP(hipStreamEndCapture(h->stream, &B.graph));
-    UZL_HIP(hipGraphInstantiate(&B.graph_exec, B.graph, nullptr, nullptr, 0));
-    UZL_HIP(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-    enqueue_pcg_pairs(h, kShortPairs, false);
-    UZL_HIP(hipStreamEndCapture(h->stream, &B.graph_s));
-    UZL_HIP(hipGraphInstantiate(&B.graph_exec_s, B.graph_s, nullptr, nullptr, 0));
-    if (h->cfg.verbose) fprintf(stderr, "[uzl_pgo] structure: %-28s %.3f ms\n", "PCG graphs of one copy", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-    h->structure_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
-// one (H + lambda I) dx = b solve in LM iteration `it`; returns PCG iterations used, sets *converged
-int pcg_solve(uzl_pgo* h, int it, bool* converged)
-{
-    hipStream_t s = h->stream;
-    const PgoDev& D = h->Dp;
-    if (D.nb == 0) { *converged = true; h->prev_pcg_iters = 0; h->last_residual_ratio = 0.; return 0; }     // every free vertex was Schur-eliminated: nothing left to iterate on
-    const int max_it = h->cfg.pcg_max_iter > 0 ? h->cfg.pcg_max_iter : 6 * std::max(D.nb, 1);
-    const bool timed = h->timer.on || h->no_graph || h->sharded;   // per-kernel events, rocprofv3 and the exchange callback need eager launches
-    if (h->ml_levels > 0) {
-        const HostSlot hs = host_slot(h);
-        if (h->ml_trial_setup) {
-            kl_ml_trial(hs, h->ml_shape, ml_ns_steps_at(h->ml_ns_steps, it), s, &h->timer);
-            h->ml_trial_setup = false;
-            h->mlb[h->ml_ix].lambda_setup = h->lambda_now;
-        }
-        { Timed t(h, "pcg_init"); kl_ml_pcg_init(hs, h->ml_shape, s); }
-        { Timed t(h, "ml_cg"); UZL_HIP(kl_ml_cg(hs, h->ml_shape, 0, 1, s)); }
-    } else {
-        { Timed t(h, "precond"); k_precond(D, s); }
-        Timed t(h, "pcg_init"); k_pcg_init(D, h->pbuf[0], h->pbuf[1], s);
-    }
-    if (!timed) ensure_pcg_graph(h);
-    int launched = 0;
-    // first batch sized from the previous solve (in steps of 2 x kShortPairs iterations), then two short ones, then long ones; the
-    // kernels no-op once `done` is set
-    constexpr int kFirstPct = 95;                                           // the first batch: 95 % of the previous solve's count
-    constexpr int kStep = 2 * kShortPairs;
-    const int kLong = 2 * kGraphPairs;
-    auto round_up = [](int v) { return ((v + kStep - 1) / kStep) * kStep; };
-    // (+ 1: a solve that ends by the stop test after k iterations is declared done by the ml_spmv of iteration k + 1)
-    int want = h->prev_pcg_iters > 0 ? std::max(kStep, round_up((h->prev_pcg_iters * kFirstPct) / 100 + 1)) : kLong;
-    for (int round = 0;; round++) {
-        want = round_up(std::max(1, std::min(want, max_it - launched)));
-        if (timed) enqueue_pcg_pairs(h, want / 2, h->timer.on);
-        else {
-            for (int i = 0; i < want / kLong; i++) UZL_HIP(hipGraphLaunch(h->mlb[h->ml_ix].graph_exec, s));
-            for (int i = 0; i < (want % kLong + kStep - 1) / kStep; i++) UZL_HIP(hipGraphLaunch(h->mlb[h->ml_ix].graph_exec_s, s));
-        }
-        launched += want;
-        k_residual_guard(D, s);                                   // a no-op until `done` is set
-        fetch_scal(h);
-        if (h->h_scal.p->flags[0] || launched >= max_it) break;
-        want = round < 2 ? kStep : kLong;
-    }
-    UZL_HIP(hipGetLastError());
-    *converged = h->h_scal.p->flags[0] != 0 && h->h_scal.p->flags[2] == 0;
-    // The multiplicative cycle / Newton-Schulz operator is not SPD by construction (see the fallback in do_optimize).  The
-    // recurrence residual r is the true residual of x whatever the preconditioner did, so a solve under that operator which
-    // claims convergence in the M^-1 norm while |r| has not come down by kResidualGuard relative to |b| is refused and the
-    // caller falls back to the additive operator (a sum of SPD terms, whose M^-1 norm is a norm).
-    h->last_residual_ratio = h->h_scal.p->scal[7];
-    if (*converged && (h->ml_mult || h->ml_ns_steps > 0) && !(h->last_residual_ratio <= kResidualGuard)) { *converged = false; h->guard_trips++; }
-    const int iters = h->h_scal.p->flags[1];
-    h->prev_pcg_iters = iters;
-    return iters;
-}
-
-}  // namespace
-namespace uzl {
 // optimizeImpl's front part (initializeOptimization :139, setFixedNodes :144-146): the structure, cached until the next add_graph / set_graph
 void prepare_optimize(uzl_pgo* h)
 {
@@ -1043,7 +854,7 @@ int do_optimize_host(uzl_pgo* h, int32_t iterations, uzl_pgo_stats* st)
     static const bool async_off = diag_flag("UZL_ML_SYNC_REBUILD");             // diagnostic build: every rebuild synchronous (tests/test_ab_paths_gpu.py)
     // (small graphs only: at 10k vertices the rebuild's Newton-Schulz GEMMs take more from the overlapped PCG than they give back:
     // 113.2 -> 115.1 ms; config 2: 11.09 -> 10.67 ms with 540 instead of 517 PCG iterations)
-    const bool async_ok = !async_off && h->ml_levels > 0 && ml_async_level(h) && !h->sharded && !h->timer.on && h->stream2 != nullptr;
+    const bool async_ok = !async_off && h->mlp.levels > 0 && ml_async_level(h) && !h->sharded && !h->timer.on && h->stream2 != nullptr;
     bool adopted = false;
     h->ml_ix = 0; h->ml_pending = false;
     struct DrainRebuild {                      // an exception must not leave a rebuild running on stream2 behind the handle's back
@@ -1078,7 +889,7 @@ int do_optimize_host(uzl_pgo* h, int32_t iterations, uzl_pgo_stats* st)
             UZL_HIP(k_hessian(D, h->cur, delta, &gl, &ga, s, it == 0 || h->sharded, ea, eb));
         }
         if (h->sharded) {                                                         // H_aa, b: sums over all ranks' edges
-            shard_allreduce(h, h->d_hdiag.p, (int64_t)h->nb * 42);
+            shard_allreduce(h, h->sys.hdiag.p, (int64_t)h->nb * 42);
             ga = k_diagmax(D, s);
         }
         { Timed t(h, "finalize"); k_finalize(D, gl, 0, ga, 2, s); }
@@ -1109,7 +920,7 @@ int do_optimize_host(uzl_pgo* h, int32_t iterations, uzl_pgo_stats* st)
         if (refresh) {
             S.precond_builds++;
             if (it == 0 || !async_ok) {
-                if (h->ml_levels > 0) ml_setup_numeric(h, host_slot(h), s, &h->timer);
+                if (h->mlp.levels > 0) ml_setup_numeric(h, host_slot(h), s, &h->timer);
                 h->ml_trial_setup = true;
             } else launch_async = true;                                           // needs this iteration's lambda: below
         }
@@ -1149,11 +960,11 @@ int do_optimize_host(uzl_pgo* h, int32_t iterations, uzl_pgo_stats* st)
             bool conv = false;
             // the lambda-dependent inverses of the hierarchy are kept across trials; after rejected steps lambda grows
             // geometrically and inverses taken at a much smaller lambda stop being a preconditioner at all
-            if (h->ml_levels > 0 && lambda > kLambdaRetake * h->mlb[h->ml_ix].lambda_setup) h->ml_trial_setup = true;
+            if (h->mlp.levels > 0 && lambda > kLambdaRetake * h->mlb[h->ml_ix].lambda_setup) h->ml_trial_setup = true;
             const bool fresh = h->ml_trial_setup || (adopted && qmax == 0);
             int pcg_its = pcg_solve(h, it, &conv);                                // _solver->solve()
             S.pcg_iterations += pcg_its;
-            if (!conv && !fresh && h->ml_levels > 0) {                            // stale hierarchy: retake the inverses once
+            if (!conv && !fresh && h->mlp.levels > 0) {                            // stale hierarchy: retake the inverses once
                 h->ml_trial_setup = true;
                 pcg_its = pcg_solve(h, it, &conv);
                 S.pcg_iterations += pcg_its;
@@ -1233,9 +1044,6 @@ int do_optimize_host(uzl_pgo* h, int32_t iterations, uzl_pgo_stats* st)
     return rc;
 }
 }  // namespace uzl
-namespace {
-
-}  // namespace
 
 // what the structure of a handle was built from (moved out before a new graph is read in, compared afterwards)
 struct StructureKey {
@@ -1701,6 +1509,21 @@ void debug_linearize(uzl_pgo* h)
     UZL_HIP(k_hessian(D, h->cur, h->cfg.huber_delta, &gl, &ga, h->stream, true));
     k_finalize(D, gl, 0, ga, 2, h->stream);
 }
+// the Schur reduction for this lambda, as an LM trial makes it (do_optimize_host: schur_reduce)
+void debug_reduce(uzl_pgo* h, double lambda)
+{
+    if (!h->red.on) return;
+    k_set_scalar(h->D.scal + 3, lambda, h->stream);
+    kl_schur_reduce(host_slot(h), h->ml_shape, h->stream, nullptr);
+}
+double debug_lambda(uzl_pgo* h, double lambda)
+{
+    if (lambda >= 0.) return lambda;
+    double sc[16];
+    UZL_HIP(hipMemcpyAsync(sc, h->D.scal, sizeof(sc), hipMemcpyDeviceToHost, h->stream));
+    UZL_HIP(hipStreamSynchronize(h->stream));
+    return 1e-5 * sc[6];                                       // computeLambdaInit
+}
 }  // namespace
 
 // sizes[4] = {n, nb, nslots, e}.  v2b [n]: vertex -> block row (-1: fixed); row_ptr [nb+1]; col [nslots] (-1: the neighbour is fixed, the
@@ -1725,9 +1548,9 @@ extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_linearize(uzl_pgo* h, int32_t* size
     if (!blk) { UZL_HIP(hipStreamSynchronize(s)); return UZL_OK; }
     const size_t nb = (size_t)h->nb, ns = (size_t)h->nslots;
     if (v2b && h->n) UZL_HIP(hipMemcpyAsync(v2b, h->d_v2b.p, sizeof(int32_t) * (size_t)h->n, hipMemcpyDeviceToHost, s));
-    if (row_ptr) UZL_HIP(hipMemcpyAsync(row_ptr, h->d_row_ptr.p, sizeof(int32_t) * (nb + 1), hipMemcpyDeviceToHost, s));
+    if (row_ptr) UZL_HIP(hipMemcpyAsync(row_ptr, h->sys.row_ptr.p, sizeof(int32_t) * (nb + 1), hipMemcpyDeviceToHost, s));
     if (ns) {
-        if (col) UZL_HIP(hipMemcpyAsync(col, h->d_col.p, sizeof(int32_t) * ns, hipMemcpyDeviceToHost, s));
+        if (col) UZL_HIP(hipMemcpyAsync(col, h->sys.col.p, sizeof(int32_t) * ns, hipMemcpyDeviceToHost, s));
         UZL_HIP(hipMemcpyAsync(blk, h->D.blk, sizeof(double) * 36 * ns, hipMemcpyDeviceToHost, s));
     }
     if (nb) {
@@ -1747,16 +1570,6 @@ extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_linearize(uzl_pgo* h, int32_t* size
     return UZL_OK;
     UZL_GUARD_END(h)
 }
-
-namespace {
-// the Schur reduction for this lambda, as an LM trial makes it (do_optimize_host: schur_reduce)
-void debug_reduce(uzl_pgo* h, double lambda)
-{
-    if (!h->red.on) return;
-    k_set_scalar(h->D.scal + 3, lambda, h->stream);
-    kl_schur_reduce(host_slot(h), h->ml_shape, h->stream, nullptr);
-}
-}  // namespace
 
 // One linear solve (H + lambda I) dx = b at the current poses, done as the first trial of an LM iteration of the host-driven loop does it
 // (do_optimize_host): linearise, Schur reduction for this lambda (when the structure has one), the preconditioner's set-up (numeric part
@@ -1786,7 +1599,7 @@ extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_solve(uzl_pgo* h, double lambda, do
     }
     h->ml_ix = 0; h->ml_pending = false;
     debug_reduce(h, lambda);
-    if (h->ml_levels > 0) { ml_setup_numeric(h, host_slot(h), s, nullptr); h->ml_trial_setup = true; }
+    if (h->mlp.levels > 0) { ml_setup_numeric(h, host_slot(h), s, nullptr); h->ml_trial_setup = true; }
     set_lambda(h, lambda, tol_factor2(h->cfg));
     h->prev_pcg_iters = 0;
     const int trips0 = h->guard_trips;
@@ -1812,17 +1625,6 @@ extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_solve(uzl_pgo* h, double lambda, do
     return UZL_OK;
     UZL_GUARD_END(h)
 }
-
-namespace {
-double debug_lambda(uzl_pgo* h, double lambda)
-{
-    if (lambda >= 0.) return lambda;
-    double sc[16];
-    UZL_HIP(hipMemcpyAsync(sc, h->D.scal, sizeof(sc), hipMemcpyDeviceToHost, h->stream));
-    UZL_HIP(hipStreamSynchronize(h->stream));
-    return 1e-5 * sc[6];                                       // computeLambdaInit
-}
-}  // namespace
 
 // The system the PCG sees when the structure Schur-eliminates chain interiors, for this lambda (< 0: lambda_init): linearisation, then
 // the Schur reduction (kl_schur_reduce).  sizes[3] = {reduced rows nbr, reduced slots, 1 if the structure has a reduction (0: nothing
@@ -1882,8 +1684,8 @@ extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_apply(uzl_pgo* h, double lambda, in
     debug_linearize(h);
     hipStream_t s = h->stream;
     PgoDev& Dp = h->Dp;
-    const bool ml = h->ml_levels > 0;
-    info[0] = ml ? ((h->ml_mult || h->ml_ns_steps > 0) ? 2. : 1.) : 0.; info[1] = ml ? h->ml_agg : 0; info[2] = ml ? h->ml_cl : 0;
+    const bool ml = h->mlp.levels > 0;
+    info[0] = ml ? ((h->ml_mult || h->ml_ns_steps > 0) ? 2. : 1.) : 0.; info[1] = ml ? h->mlp.agg : 0; info[2] = ml ? h->mlp.cl : 0;
     info[3] = (h->nb > 0 && h->e > 0) ? Dp.nb : 0;
     if (!x || info[3] == 0) { UZL_HIP(hipStreamSynchronize(s)); return UZL_OK; }
     const double lam = debug_lambda(h, lambda);
@@ -1952,7 +1754,7 @@ extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_hierarchy(uzl_pgo* h, double lambda
         if (!info || (ns_steps > 0 && (ns_steps & 1))) return fail(h, UZL_ERR_BAD_ARG, "hierarchy: info, and an even step count");
         debug_linearize(h);
         for (int i = 0; i < 64; i++) info[i] = 0;
-        if (h->ml_levels == 0 || h->nb == 0 || h->e == 0) { UZL_HIP(hipStreamSynchronize(s)); return UZL_OK; }
+        if (h->mlp.levels == 0 || h->nb == 0 || h->e == 0) { UZL_HIP(hipStreamSynchronize(s)); return UZL_OK; }
         const double lam = debug_lambda(h, lambda);
         h->ml_ix = 0; h->ml_pending = false;
         debug_reduce(h, lam);
@@ -1964,15 +1766,15 @@ extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_hierarchy(uzl_pgo* h, double lambda
         h->ml_trial_setup = true;                              // (the next solve takes its own inverses)
         UZL_HIP(hipGetLastError());
         UZL_HIP(hipStreamSynchronize(s));
-        info[0] = h->ml_levels; info[1] = h->ml_comp ? h->ml_cl : 0; info[2] = h->ml_agg; info[3] = h->ml_mult ? 1 : 0; info[4] = steps;
+        info[0] = h->mlp.levels; info[1] = h->mlp.cl; info[2] = h->mlp.agg; info[3] = h->ml_mult ? 1 : 0; info[4] = steps;
         info[5] = kUpperNs; info[6] = h->Dp.sibling0; info[7] = h->Dp.nb; info[8] = h->mlb[0].hot.c32_stride;
         info[9] = h->red.on ? 1 : 0; info[10] = h->red.strong ? 1 : 0; info[11] = h->red.strong_blocks ? 1 : 0; info[12] = h->ml_ns_steps;
         info[13] = h->ml_shape.cg_variant;
-        for (int l = 0; l <= h->ml_levels; l++) { info[16 + l] = h->ml_n[l]; info[32 + l] = h->ml_fan[l]; info[48 + l] = h->ml_nslots[l]; }
+        for (int l = 0; l <= h->mlp.levels; l++) { info[16 + l] = h->mlp.n[l]; info[32 + l] = h->mlp.fan[l]; info[48 + l] = h->mlp.nslots[l]; }
         if (lam_used) *lam_used = lam;
         return UZL_OK;
     }
-    const int L = h->ml_levels, cl = h->ml_comp ? h->ml_cl : 0;
+    const int L = h->mlp.levels, cl = h->mlp.cl;
     if (!nbytes || !h->structure_ready || L == 0 || level < 0 || level > L) return fail(h, UZL_ERR_BAD_ARG, "hierarchy: no such level (or no set-up yet)");
     MlDev M;
     UZL_HIP(hipMemcpyAsync(&M, h->mlb[0].dml, sizeof(MlDev), hipMemcpyDeviceToHost, s));
@@ -2022,10 +1824,10 @@ extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_pcg_state(uzl_pgo* h, double lambda
     debug_linearize(h);
     hipStream_t s = h->stream;
     PgoDev& Dp = h->Dp;
-    const bool ml = h->ml_levels > 0 && h->nb > 0 && h->e > 0;
-    const int gl = !ml ? 0 : ((h->ml_agg == 1 || h->ml_levels < 2) ? 1 : 2);
+    const bool ml = h->mlp.levels > 0 && h->nb > 0 && h->e > 0;
+    const int gl = !ml ? 0 : h->mlp.gather_level;
     for (int i = 0; i < 6; i++) info[i] = 0.;
-    info[0] = ml ? Dp.nb : 0; info[1] = gl; info[2] = ml ? h->ml_n[gl] : 0;
+    info[0] = ml ? Dp.nb : 0; info[1] = gl; info[2] = ml ? h->mlp.n[gl] : 0;
     if (!x || !ml) { UZL_HIP(hipStreamSynchronize(s)); return UZL_OK; }
     const double lam = debug_lambda(h, lambda);
     h->ml_ix = 0; h->ml_pending = false;
@@ -2041,7 +1843,7 @@ extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_pcg_state(uzl_pgo* h, double lambda
         kl_ml_spmv(hs, h->ml_shape, i & 1, s);
         UZL_HIP(kl_ml_cg(hs, h->ml_shape, i & 1, 0, s));
     }
-    const size_t n6 = (size_t)Dp.nb * 6, g6 = (size_t)h->ml_n[gl] * 6;
+    const size_t n6 = (size_t)Dp.nb * 6, g6 = (size_t)h->mlp.n[gl] * 6;
     int32_t fl[4] = {0, 0, 0, 0};
     UZL_HIP(hipMemcpyAsync(x, Dp.x, sizeof(double) * n6, hipMemcpyDeviceToHost, s));
     UZL_HIP(hipMemcpyAsync(r, Dp.r, sizeof(double) * n6, hipMemcpyDeviceToHost, s));
@@ -2097,9 +1899,7 @@ struct uzl_pgo_batch : HandleBase {
     KernelTimer timer;                    // profiling (uzl_pgo_batch_set_profiling): the two PCG kernels, launched eagerly with event pairs
 };
 
-namespace {
-
-int batch_optimize(uzl_pgo_batch* b, int32_t iterations, uzl_pgo_stats* stats, int32_t* n_batched)
+static int batch_optimize(uzl_pgo_batch* b, int32_t iterations, uzl_pgo_stats* stats, int32_t* n_batched)
 {
     const int B = (int)b->h.size();
     if (n_batched) *n_batched = 0;
@@ -2116,8 +1916,8 @@ int batch_optimize(uzl_pgo_batch* b, int32_t iterations, uzl_pgo_stats* stats, i
     if (!lm_batch_eligible(b->h)) {      // not one class / one shape: every graph through the single-graph path
         if (b->cfg.verbose)
             for (const uzl_pgo* h : b->h)
-                fprintf(stderr, "[uzl_pgo_batch] not batched: levels %d agg %d comp %d mult %d cl %d sharded %d nb %d (pcg system %d) e %d timer %d n1 %d ns %d\n", h->ml_levels,
-                        h->ml_agg, (int)h->ml_comp, (int)h->ml_mult, h->ml_cl, (int)h->sharded, h->nb, h->Dp.nb, h->e, (int)h->timer.on, h->ml_n.size() > 1 ? h->ml_n[1] : -1, h->ml_ns_steps);
+                fprintf(stderr, "[uzl_pgo_batch] not batched: levels %d agg %d mult %d cl %d sharded %d nb %d (pcg system %d) e %d timer %d n1 %d ns %d\n", h->mlp.levels,
+                        h->mlp.agg, (int)h->ml_mult, h->mlp.cl, (int)h->sharded, h->nb, h->Dp.nb, h->e, (int)h->timer.on, h->mlp.n.size() > 1 ? h->mlp.n[1] : -1, h->ml_ns_steps);
         for (int g = 0; g < B; g++) {
             uzl_pgo* h = b->h[g];
             h->t_start = std::chrono::steady_clock::now();
@@ -2184,8 +1984,6 @@ int batch_optimize(uzl_pgo_batch* b, int32_t iterations, uzl_pgo_stats* stats, i
     if (n_batched) *n_batched = total;
     return rc_all;
 }
-
-}  // namespace
 
 extern "C" {
 

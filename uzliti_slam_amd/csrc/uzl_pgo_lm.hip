@@ -154,7 +154,7 @@ LmSlot make_slot(const uzl_pgo* h, LmDev* d_lm, LmHost* d_pub)
     S.pbuf[0] = h->pbuf[0]; S.pbuf[1] = h->pbuf[1];
     S.pose[0] = h->pose_a.p; S.pose[1] = h->pose_b.p;
     S.g_edges = g_edges_for(h->e); S.g_asm = h->D.n_rb; S.g_oplus = g_oplus_for(h->n);
-    S.g_rows = g_ml_rows(h->Dp.nb, h->ml_agg); S.g_spmv = g_ml_spmv(h->Dp.nb, h->ml_agg);
+    S.g_rows = g_ml_rows(h->Dp.nb, h->mlp.agg); S.g_spmv = g_ml_spmv(h->Dp.nb, h->mlp.agg);
     S.copy_stride = (int64_t)h->ml_copy_stride;
     return S;
 }
@@ -163,18 +163,18 @@ LmSlot make_slot(const uzl_pgo* h, LmDev* d_lm, LmHost* d_pub)
 LmShape make_shape(const std::vector<uzl_pgo*>& hs, int nslots, bool batch_geometry)
 {
     const uzl_pgo* h = hs[0];
-    for (const uzl_pgo* g : hs) if (g->ml_levels >= 1 && g->ml_n[1] > h->ml_n[1]) h = g;       // the ml_cg variant that covers the largest level 1
+    for (const uzl_pgo* g : hs) if (g->mlp.levels >= 1 && g->mlp.n[1] > h->mlp.n[1]) h = g;       // the ml_cg variant that covers the largest level 1
     LmShape sh;
     memset(&sh, 0, sizeof(sh));
     sh.nslots = nslots; sh.batch_geometry = batch_geometry ? 1 : 0;
-    sh.levels = h->ml_levels; sh.cl = h->ml_comp ? h->ml_cl : 0; sh.agg = h->ml_agg;
+    sh.levels = h->mlp.levels; sh.cl = h->mlp.cl; sh.agg = h->mlp.agg;
     sh.mult = h->ml_mult ? 1 : 0; sh.ns_steps = h->ml_ns_steps; sh.upper_ns = kUpperNs;
-    ml_cg_variant(h->mlb[0].hot, h->ml_agg, h->ml_lds, &sh.cg_variant, &sh.comp_u, &sh.cg_lds);
+    ml_cg_variant(h->mlb[0].hot, h->mlp.agg, h->mlp.lds, &sh.cg_variant, &sh.comp_u, &sh.cg_lds);
     for (const uzl_pgo* g : hs) {
-        for (int l = 0; l <= g->ml_levels; l++) { sh.n_lv[l] = std::max(sh.n_lv[l], g->ml_n[l]); sh.work_t[l] = std::max(sh.work_t[l], g->ml_nslots[l] + g->ml_n[l]); sh.chunks[l] = std::max(sh.chunks[l], g->ml_chunks[l]); }
-        sh.inner_aggs = std::max(sh.inner_aggs, g->ml_inner_aggs);
+        for (int l = 0; l <= g->mlp.levels; l++) { sh.n_lv[l] = std::max(sh.n_lv[l], g->mlp.n[l]); sh.work_t[l] = std::max(sh.work_t[l], g->mlp.nslots[l] + g->mlp.n[l]); sh.chunks[l] = std::max(sh.chunks[l], g->mlp.chunks[l]); }
+        sh.inner_aggs = std::max(sh.inner_aggs, g->mlp.inner_aggs);
         sh.g_edges = std::max(sh.g_edges, g_edges_for(g->e)); sh.g_asm = std::max(sh.g_asm, g->D.n_rb); sh.g_oplus = std::max(sh.g_oplus, g_oplus_for(g->n));
-        sh.g_rows = std::max(sh.g_rows, g_ml_rows(g->Dp.nb, g->ml_agg)); sh.g_spmv = std::max(sh.g_spmv, g_ml_spmv(g->Dp.nb, g->ml_agg));
+        sh.g_rows = std::max(sh.g_rows, g_ml_rows(g->Dp.nb, g->mlp.agg)); sh.g_spmv = std::max(sh.g_spmv, g_ml_spmv(g->Dp.nb, g->mlp.agg));
         if (g->red.on) {
             const SchurDev& SD = g->red.S;
             sh.red = 1;
@@ -200,7 +200,7 @@ LmDev initial_state(const uzl_pgo* h, int iterations)
     I.max_it = h->cfg.pcg_max_iter > 0 ? h->cfg.pcg_max_iter : 6 * std::max(h->Dp.nb, 1);
     // (do_optimize_host's async_ok: rebuilds run ahead for the small-graph class only - at 10k vertices the rebuild's GEMMs take more from
     //  the overlapped PCG than they give back)
-    I.sync_rebuild = (h->ml_comp && ml_async_level(h)) ? 0 : 1;
+    I.sync_rebuild = ml_async_level(h) ? 0 : 1;
     I.guarded = (h->ml_mult || h->ml_ns_steps > 0) ? 1 : 0;
     I.ni = 2.; I.last_rel = 1e300; I.rate_ref = -1.; I.rate_last = -1.;
     I.tol_f2 = pgo_tol_f2(h->cfg); I.eps_t = pgo_eps_t(h->cfg); I.eps_r = pgo_eps_r(h->cfg);
@@ -524,7 +524,7 @@ void finish_job(LmJob& J, uzl_pgo_stats* st, double wall_ms)
 // which solves take the device-resident loop
 bool lm_eligible(const uzl_pgo* h)
 {
-    return h->cfg.lm_loop != 1 && h->ml_levels > 0 && !h->sharded && h->nb > 0 && h->e > 0 && h->Dp.nb > 0 && !h->timer.on &&
+    return h->cfg.lm_loop != 1 && h->mlp.levels > 0 && !h->sharded && h->nb > 0 && h->e > 0 && h->Dp.nb > 0 && !h->timer.on &&
            h->stream2 != nullptr;
 }
 
@@ -576,11 +576,11 @@ bool lm_batch_eligible(const std::vector<uzl_pgo*>& hs)
     if (hs.empty() || (int)hs.size() > kBatchMax) return false;
     const uzl_pgo* a = hs[0];
     for (const uzl_pgo* h : hs) {
-        if (!(h->cfg.lm_loop != 1 && h->ml_levels > 0 && h->ml_agg == 1 && h->ml_comp && h->ml_mult && h->ml_cl == 1 && 6 * h->ml_n[1] <= 1536 && !h->sharded && h->nb > 0 &&
+        if (!(h->cfg.lm_loop != 1 && h->mlp.levels > 0 && h->mlp.agg == 1 && h->ml_mult && h->mlp.cl == 1 && 6 * h->mlp.n[1] <= 1536 && !h->sharded && h->nb > 0 &&
               h->e > 0 && h->Dp.nb > 0 && !h->timer.on)) return false;
         // one depth of the hierarchy (the launch sequence of a pass): sizes may differ - every launch takes the largest graph's grid and a
         // twin leaves past its own graph's extent
-        if (h->ml_levels != a->ml_levels || h->ml_ns_steps != a->ml_ns_steps || h->cfg.device != a->cfg.device) return false;
+        if (h->mlp.levels != a->mlp.levels || h->ml_ns_steps != a->ml_ns_steps || h->cfg.device != a->cfg.device) return false;
     }
     return true;
 }
