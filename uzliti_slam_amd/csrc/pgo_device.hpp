@@ -425,7 +425,8 @@ __device__ __forceinline__ double progress_unit(const double* __restrict__ scal,
 // ------------------------------------------------------------------------------------------------
 // Slot twins serve both LM loops.  SLOT = `const LmSlot*` (the device-resident loop's table: blockIdx.z picks the graph), `LmSlot` BY VALUE
 // (a pass of one graph), or `HostSlot` (by value: the host-driven loop) - a slot by value sits in the kernel-argument segment: no pointer
-// hop in front of the first loads.
+// hop in front of the first loads.  (The PCG launches of the small-graph class take neither by value but PcgArgs, pgo_types.hpp: a
+// 1.5-KB slot is fetched from that segment batch by batch.)
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ const LmSlot& slot_of(const LmSlot* __restrict__ slots) { return slots[blockIdx.z]; }
 __device__ __forceinline__ const LmSlot& slot_of(const LmSlot& slot) { return slot; }

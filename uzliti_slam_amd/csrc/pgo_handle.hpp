@@ -66,8 +66,8 @@ void kl_ml_trial(const LmSlot* sl, const LmShape& sh, int which, int ns_steps, h
 void kl_ml_numeric(const HostSlot& hs, const LmShape& sh, hipStream_t s, KernelTimer* timer, const std::function<void()>& level1_done);
 void kl_ml_trial(const HostSlot& hs, const LmShape& sh, int ns_steps, hipStream_t s, KernelTimer* timer);
 void ml_cg_variant(const MlHot& ml, int agg, size_t lds_full, int32_t* variant, int32_t* comp_u, uint64_t* lds);
-hipError_t kl_ml_init(const LmSlot* sl, const LmSlot* by_value, const LmShape& sh, hipStream_t s);
-hipError_t kl_ml_pcg_its(const LmSlot* sl, const LmSlot* by_value, const LmShape& sh, int first, int n, hipStream_t s, hipEvent_t* ev = nullptr);
+hipError_t kl_ml_init(const LmSlot* sl, const LmSlot* by_value, const LmShape& sh, int ix, hipStream_t s);
+hipError_t kl_ml_pcg_its(const LmSlot* sl, const LmSlot* by_value, const LmShape& sh, int ix, double tol2, int first, int n, hipStream_t s, hipEvent_t* ev = nullptr);
 // the same PCG kernels for the host-driven loop (pgo_types.hpp: HostSlot): init, and the two launches of iteration `parity` one by one
 void kl_ml_pcg_init(const HostSlot& hs, const LmShape& sh, hipStream_t s);
 void kl_ml_spmv(const HostSlot& hs, const LmShape& sh, int parity, hipStream_t s, hipEvent_t ev_a = nullptr, hipEvent_t ev_b = nullptr);

@@ -72,6 +72,11 @@ UZL_HD bool lm_refresh(int it, int iterations, bool may_run_last, double last_re
                        (may_run_last || it + 1 < iterations));
 }
 
+// The hierarchy copy a graph's PCG applies in the pass that finds it in this state: a copy that was rebuilt ahead is adopted when the
+// pass linearises, and at no other time.  lm_head_kernel moves LmDev::ix by this rule; the host applies it to the snapshot it holds
+// before it enqueues the pass, and hands the small-graph class's PCG launches the result by value (pgo_types.hpp: PcgArgs).
+UZL_HD int lm_pass_ix(int phase, int ix, int pending) { return (phase == kLmLin && pending) ? (ix ^ 1) : ix; }
+
 // the step control of one evaluated trial: rho from chi2 before / after and computeScale() + 1e-3; updates lambda, ni; returns rho
 struct LmStep { double rho; bool accepted; double last_rel; };
 UZL_HD LmStep lm_step(double current_chi, double temp_chi, double scale_sum, double& lambda, double& ni)

@@ -31,8 +31,9 @@ __device__ __forceinline__ void lm_head_decide(const LmSlot& S, LmDev* lm, int p
             lm->lambda = 1e-5 * dmax;                        // computeLambdaInit: tau * max diag
             lm->ni = 2.;
         }
-        lm->adopted = 0;
-        if (lm->pending) { lm->ix ^= 1; lm->pending = 0; lm->adopted = 1; }      // the copy built during the last iteration
+        lm->adopted = lm->pending ? 1 : 0;                   // the copy built during the last iteration
+        lm->ix = lm_pass_ix(phase, lm->ix, lm->pending);
+        lm->pending = 0;
         if (lm_refresh(lm->it, lm->iterations, lm->sync_rebuild != 0, lm->last_rel, lm->refresh_rel, lm->rate_ref, lm->rate_last, lm->rate_drop)) {
             lm->st_precond_builds++;
             need |= (lm->it == 0 || lm->sync_rebuild) ? (kNeedNumeric | kNeedTrial) : kNeedRebuild;
@@ -160,7 +161,7 @@ __global__ __launch_bounds__(kTailBlk) void lm_tail_kernel(const LmSlot* __restr
             bool conv = lm->flags[2] == 0;
             if (conv) scal[7] = ratio;
             if (conv && lm->guarded && !(ratio <= kResidualGuard)) conv = false;      // (DESIGN.md "Safeguards": not SPD by construction)
-            if (!conv) { lm->phase = kLmAnomaly; lm->anomaly_code = lm->flags[2] ? 2 : 3; }
+            if (!conv) { lm->phase = kLmAnomaly; lm->anomaly_code = lm->flags[2] == kBreakdownIx ? 4 : (lm->flags[2] ? 2 : 3); }      // 4: PcgArgs::ix was not the state's
             else {
                 scal[4] = chi_t; scal[5] = sc;
                 lm->st_pcg_iterations += its; lm->st_lm_trials++; lm->pcg_last = its;

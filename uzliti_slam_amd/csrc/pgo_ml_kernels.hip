@@ -1369,6 +1369,13 @@ __device__ __forceinline__ void ml_init_kernel_body(PgoDev D, MlHot H, double* _
     if (blockIdx.x == 0 && tid == 0) { D.flags[0] = 0; D.flags[1] = 0; D.flags[2] = 0; D.flags[3] = 0; D.scal[2] = 1.; }
 }
 
+// A launch that was given another hierarchy copy than the graph's LM state names (pgo_types.hpp: PcgArgs) does no work and ends the
+// solve as an anomaly
+__device__ __forceinline__ void pcg_ix_mismatch(int32_t* flags)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) { flags[0] = 1; flags[2] = kBreakdownIx; }
+}
+
 // This file is compiled with -ffp-contract=off (two geometries of one kernel body must give the same bits): the products that matter
 // for speed say fma() themselves.
 __device__ __forceinline__ double dot6(double2 a0, double2 a1, double2 a2, double v0, double v1, double v2, double v3, double v4, double v5)
@@ -1407,7 +1414,8 @@ __device__ __forceinline__ int xcd_contiguous(int b, int g)
 // components, then rows pairwise by index; the r.z partials in groups of 64, then groups in order).
 template <int AGG, int RPW = AGG, int WAVES = (AGG == 1 ? 8 : kSpmvWaves4)>
 __device__ __forceinline__ void ml_spmv_kernel_body(PgoDev D, MlHot H, const double* __restrict__ p_old,
-                                                     double* __restrict__ p_new, int n_part, double tol2)
+                                                     double* __restrict__ p_new, int n_part, double tol2,
+                                                     const int32_t* ix_word = nullptr, int ix = 0, bool ix_check = false)
 {
     constexpr int kWaves = WAVES, kRowsPerWave = RPW;
     constexpr bool kLds = (WAVES == 2);          // the batched geometry: wave sums through the LDS crossbar (wave_sum, pgo_device.hpp)
@@ -1426,6 +1434,10 @@ __device__ __forceinline__ void ml_spmv_kernel_body(PgoDev D, MlHot H, const dou
     __shared__ double sg1[kAggPerBlk * 3];
     const int done = D.flags[0];            // looked at behind the first loads (below): its round trip runs beside theirs, not in front
     STAMP_DECL
+    // (a PcgArgs launch of the device-resident loop, ix_check: the hierarchy copy the state says - ix_word = &LmDev::ix, the done flag's
+    //  cache line - against the one the host chose for this launch; compared where `done` is.  The load is unconditional - the
+    //  host-driven loop hands over a readable word and no check: a branch here would end the block the argument fetch is gathered in)
+    const int ix_dev = ix_word ? *ix_word : 0;
     const int gl = (AGG == 1 || H.levels < 2) ? 1 : 2;
     // (the wave index as a scalar: rows, row headers and the loops over partial groups are then uniform to the compiler as well)
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), g = lane / 6, r = lane % 6;
@@ -1469,6 +1481,7 @@ __device__ __forceinline__ void ml_spmv_kernel_body(PgoDev D, MlHot H, const dou
     // (a launch after convergence must stay cheap: 16-iteration graph batches overshoot.  Leaving here costs it the issue of the loads
     //  above - nothing waits for them - and saves every working launch the done flag's round trip in front of its first load.)
     if (done) return;
+    if (ix_check && ix_dev != ix) { pcg_ix_mismatch(D.flags); return; }
     // offsets of the workgroup's level-1 aggregates (the restriction of A p at the end): the LOAD here, the store into LDS behind the
     // prefetch below.  (Rounds 1-5 stored at once: a full `s_waitcnt vmcnt(0)` between the row headers and the diagonal blocks, and - the
     // counts of loads in flight do not survive the divergent `dact` block - a second one behind the diagonal blocks' loads, in front of
@@ -2170,10 +2183,16 @@ __device__ __forceinline__ void ml_alpha_kernel_body(PgoDev D, MlHot H, const do
 // rounding as the walked AGG = 1 variant of ml_cg.
 // ------------------------------------------------------------------------------------------------
 // kCompU gather-level values per lane: 5 covers 6 n_1 <= 960 (<= 1280 free vertices), 8 covers 6 n_1 <= 1536 (<= 2048), 12 <= 2304 (3072), 16 <= 3072 (4096)
-template <int kCompU, bool kLds = false>
+// kLate (the by-value launches of a one-graph pass, PcgArgs): nothing that can end the kernel is looked at before every operand load
+// has been sent - the done flag, the hierarchy copy of the LM state (*ix_word against ix, if ix_check) and whether the init application
+// is due (init with an LM state only) are fetched first and tested behind the loads, as ml_spmv does with its done flag.  A launch
+// after convergence then costs the issue of its loads; a slot table's launches (batches: 16-iteration graphs overshoot by many
+// launches) keep the flag in front.
+template <int kCompU, bool kLds = false, bool kLate = false>
 __device__ __forceinline__ void ml_cg_comp_kernel_body(PgoDev D, MlHot H, const double* __restrict__ p,
                                                            const double* __restrict__ rg_old, double* __restrict__ rg_new,
-                                                           int n_part, int init)
+                                                           int n_part, int init, const int32_t* ix_word = nullptr, int ix = 0,
+                                                           bool ix_check = false, const LmDev* lm = nullptr)
 {
     __shared__ double s3[3];
     __shared__ double sv[kCgBlk];
@@ -2182,7 +2201,12 @@ __device__ __forceinline__ void ml_cg_comp_kernel_body(PgoDev D, MlHot H, const 
     __shared__ double szj[48];
     __shared__ double scomp[3][6];
     __shared__ double spm[6];
-    if (D.flags[0]) return;
+    STAMP_DECL
+    if (!kLate && D.flags[0]) return;
+    const int done = kLate ? D.flags[0] : 0;
+    const int ix_dev = kLate ? *ix_word : 0;                 // (one unconditional load: ml_spmv_kernel_body)
+    int ph = kLmSolve, ip = 0, ps = 0;                       // (init_due's words)
+    if (kLate && lm && init) { ph = lm->phase; ip = lm->init_pass; ps = lm->pass; }
     const int tid = threadIdx.x;
     const int a = blockIdx.x * kMlFanout + tid / 6, r = tid % 6;
     const bool act = tid < 48 && a < D.nb;
@@ -2221,6 +2245,14 @@ __device__ __forceinline__ void ml_cg_comp_kernel_body(PgoDev D, MlHot H, const 
         sgreg[u] = (!init && in) ? H.Sg[t] : 0.;
 #pragma unroll
         for (int q = 0; q < 6; q++) { const float y = crow[(size_t)q * cst + (in ? t : 0)]; cm[q][u] = in ? y : 0.f; }   // unconditional loads: all 30 in flight together
+    }
+    STAMP(32);     // 32: prefetch issue (kernel entry -> every operand load sent)
+#ifdef UZL_STAMPS
+    if (blockIdx.x == 0 && tid == 0) atomicAdd(&g_stamps[46], 1ull);
+#endif
+    if (kLate) {
+        if (ix_check && ix_dev != ix) { pcg_ix_mismatch(D.flags); return; }
+        if (done || !(ph == kLmSolve && ip == ps)) return;
     }
     double alpha = 0.;
     bool bad = false;
@@ -2518,7 +2550,8 @@ void kl_ml_trial(const HostSlot& hs, const LmShape& sh, int ns_steps, hipStream_
 // ---- PCG: init + the two iteration kernels, for both LM loops (SLOT as above; by value, a slot spares kernels that are a chain of
 // round trips the pointer hop).  What they read of the graph's LM state, through `lm`: the hierarchy copy the PCG applies (ix),
 // pcg_tol^2 (tol2), and whether its solve starts in this pass (init_due).  A HostSlot has no LM state behind it: it carries ix and tol2
-// itself, and its init always runs
+// itself, and its init always runs.  One graph of the small-graph class (AGG = 1, dense level-1 operator), in either loop, goes through
+// the PcgArgs kernels further down instead: same bodies, 232 bytes of arguments.
 template <class SLOT> __device__ __forceinline__ const LmDev* state_of(const LmSlot& S, const SLOT&) { return S.lm; }
 __device__ __forceinline__ const HostSlot* state_of(const LmSlot&, const HostSlot& hs) { return &hs; }
 __device__ __forceinline__ bool init_due(const LmDev* lm) { return lm->phase == kLmSolve && lm->init_pass == lm->pass; }
@@ -2593,6 +2626,73 @@ __global__ __launch_bounds__(256) void ml_alpha_lm_kernel(const SLOT slots, int 
     ml_alpha_kernel_body(S.Dp, hot_of(S, lm->ix), rg_of(S, lm->ix, parity ^ 1), S.g_spmv);
 }
 
+// ---- the same three bodies behind PcgArgs (pgo_types.hpp): a one-graph pass of the small-graph class, both LM loops.  The bodies take
+// a PgoDev / MlHot rebuilt from the arguments - the fields they do not read are zero and fold away - so arithmetic and summation order
+// are the slot twins'.  The launch's grid is the graph's own (g_rows / g_spmv workgroups): no workgroup beyond the rows.
+__device__ __forceinline__ PgoDev pcg_dev(const PcgArgs& A)
+{
+    PgoDev D = {};
+    D.nb = A.nb; D.diag_owner = A.diag_owner;
+    D.col = A.col; D.rowhdr = A.rowhdr; D.blk = A.blk; D.hdiag = A.hdiag;
+    D.b = A.b; D.x = A.x; D.xs = A.xs; D.r = A.r; D.z = A.z; D.ap = A.ap;
+    D.part_a = A.part_a; D.part_b = A.part_b; D.part_c = A.part_c; D.scal = A.scal; D.flags = A.flags;
+    return D;
+}
+__device__ __forceinline__ MlHot pcg_hot(const PcgArgs& A)
+{
+    MlHot H = {};
+    H.levels = 1; H.n[1] = A.n1;
+    H.geo0 = A.geo0; H.Winv[0] = A.Winv0; H.Cmat32 = A.Cmat32; H.c32_stride = A.c32_stride; H.Sg = A.Sg;
+    return H;
+}
+__global__ __launch_bounds__(kCgBlk) void ml_init_pcg_kernel(const PcgArgs A)
+{
+    if (A.lm) {                                              // (once per solve: its tests stay in front)
+        if (A.lm->ix != A.ix) { pcg_ix_mismatch(A.flags); return; }
+        if (!init_due(A.lm)) return;
+    }
+    ml_init_kernel_body<1>(pcg_dev(A), pcg_hot(A), A.pbuf[0], A.pbuf[1], A.rg[0]);
+}
+// The compiler fetches an argument where its first use is, block by block - each batch a scalar round trip with a wait of its own in
+// front of the loads behind it.  One asm statement at the kernel's entry that takes every argument of the working path as a register
+// operand makes the fetch ONE batch with one wait.  It returns a zero the compiler cannot see through, which is added to the pointers
+// of the first loads: they cannot be sent before it, and stay what they were - global, uniform, read with scalar loads where they
+// were.  (Not `volatile`, no memory clobber: behind such a statement the row header's slot range and the scalars are no longer fetched
+// with scalar loads.  Not the pointers themselves through the statement: they come back generic, and the loads become flat ones.)
+// (both buffers' addresses and a select: indexing the argument block with `parity` would be a second, dependent scalar load)
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void ml_spmv_pcg_kernel(const PcgArgs A, int parity)
+{
+    double* const p0 = A.pbuf[0]; double* const p1 = A.pbuf[1];
+    int zero;
+    asm("s_mov_b32 %0, 0 ; ml_spmv: arguments fetched" : "=s"(zero)
+        : "s"(A.flags), "s"(A.lm), "s"(A.scal), "s"(A.part_b), "s"(A.rowhdr), "s"(A.part_a), "s"(A.part_c), "s"(A.hdiag),
+          "s"(A.z), "s"(A.blk), "s"(p0), "s"(p1), "s"(A.ap), "s"(A.geo0), "s"(A.Sg), "s"(A.col), "s"(__double_as_longlong(A.tol2)),
+          "s"(A.nb), "s"(A.n1), "s"(A.diag_owner), "s"(A.g_rows), "s"(A.ix), "s"(parity), "s"((int)gridDim.x));
+    PgoDev D = pcg_dev(A);
+    D.flags += zero; D.scal += zero; D.part_b += zero; D.part_c += zero; D.rowhdr += zero;
+    const int32_t* ix_word = (A.lm ? &A.lm->ix : A.flags) + zero;
+    ml_spmv_kernel_body<1, 1, 8>(D, pcg_hot(A), parity ? p1 : p0, parity ? p0 : p1, A.g_rows, A.tol2, ix_word, A.ix, A.lm != nullptr);
+}
+// (kInit, the first application, at compile time: the working launch is then one straight line from its entry to its last operand load)
+template <int kCompU, bool kInit>
+__global__ __launch_bounds__(kCgBlk) void ml_cg_comp_pcg_kernel(const PcgArgs A, int parity)
+{
+    constexpr int init = kInit ? 1 : 0;
+    double* const p0 = A.pbuf[0]; double* const p1 = A.pbuf[1];
+    double* const r0 = A.rg[0]; double* const r1 = A.rg[1];
+    int zero;
+    asm("s_mov_b32 %0, 0 ; ml_cg_comp: arguments fetched" : "=s"(zero)
+        : "s"(A.flags), "s"(A.lm), "s"(A.scal), "s"(A.part_a), "s"(A.r), "s"(A.part_b), "s"(A.part_c), "s"(A.z), "s"(p0), "s"(p1),
+          "s"(A.x), "s"(A.xs), "s"(A.ap), "s"(A.geo0), "s"(A.Winv0), "s"(A.Cmat32), "s"(r0), "s"(r1), "s"(A.Sg),
+          "s"(A.nb), "s"(A.n1), "s"(A.c32_stride), "s"(A.g_spmv), "s"(A.ix), "s"(parity));
+    PgoDev D = pcg_dev(A);
+    D.flags += zero; D.scal += zero; D.part_a += zero; D.r += zero;
+    const int32_t* ix_word = (A.lm ? &A.lm->ix : A.flags) + zero;
+    const bool odd = init || parity;                         // (init: p = pbuf[0], rg_old = rg[0], rg_new = rg[1], an odd iteration's buffers)
+    ml_cg_comp_kernel_body<kCompU, false, true>(D, pcg_hot(A), odd ? p0 : p1, odd ? r0 : r1, odd ? r1 : r0, init ? 0 : A.g_spmv, init,
+                                                ix_word, A.ix, A.lm != nullptr, A.lm);
+}
+
 // raises the dynamic-LDS limit of an ml_cg variant once per device (a function attribute is per device)
 static hipError_t lm_cg_lds(const void* fn, int variant_ix, size_t lds)
 {
@@ -2624,7 +2724,9 @@ static hipError_t kl_ml_cg_t(SLOT sl, const LmShape& sh, int parity, int init, h
         return e;
     };
     switch (sh.cg_variant) {
-    case kCgComp1: {                                                                  // (no dynamic LDS)
+    case kCgComp1:                                                                    // (no dynamic LDS)
+        if constexpr (!std::is_pointer<SLOT>::value) return hipErrorInvalidValue;     // one graph by value: PcgArgs (pcg_cg below)
+        else {
         const int u = sh.comp_u;
         auto kernel = sh.batch_geometry ? (u <= 5 ? ml_cg_comp_lm_kernel<5, true, SLOT> : ml_cg_comp_lm_kernel<8, true, SLOT>)
                     : u <= 5 ? ml_cg_comp_lm_kernel<5, false, SLOT> : u <= 8 ? ml_cg_comp_lm_kernel<8, false, SLOT>
@@ -2683,23 +2785,64 @@ void ml_cg_variant(const MlHot& ml, int agg, size_t lds_full, int32_t* variant, 
     const bool ypre = ml.levels >= 2 && 6 * ml.n[2] <= 4 * 32 * kYU;
     *variant = ypre ? kCgComp4Ypre : (ml.Vg != nullptr ? kCgComp4Vpre : kCgComp4);
 }
-// x = 0, r = b, first application of the preconditioner - for the graphs whose solve starts in this pass.  by_value: the pass has one
-// graph and `by_value` is its slot (the device table `sl` is what every other twin reads)
-hipError_t kl_ml_init(const LmSlot* sl, const LmSlot* by_value, const LmShape& sh, hipStream_t s)
+// ---- PcgArgs launches (pgo_types.hpp): which shapes take them, the argument block of a slot for hierarchy copy ix, the three launches
+static bool pcg_args_shape(const LmShape& sh) { return sh.nslots == 1 && !sh.batch_geometry && sh.agg == 1 && sh.cg_variant == kCgComp1; }
+static PcgArgs make_pcg_args(const LmSlot& S, const LmDev* lm, int ix, double tol2)
 {
+    const int64_t off = ix ? S.copy_stride : 0;              // (both copies in one arena: hot_of above)
+    auto at = [off](auto* q) { return q ? reinterpret_cast<decltype(q)>(reinterpret_cast<uintptr_t>(q) + (uintptr_t)off) : q; };
+    const PgoDev& D = S.Dp;
+    const MlHot& H = S.hot[0];
+    PcgArgs A;
+    memset(&A, 0, sizeof(A));
+    A.flags = D.flags; A.scal = D.scal; A.part_a = D.part_a; A.part_b = D.part_b; A.part_c = D.part_c;
+    A.rowhdr = D.rowhdr; A.hdiag = D.hdiag; A.z = D.z; A.blk = D.blk; A.pbuf[0] = S.pbuf[0]; A.pbuf[1] = S.pbuf[1];
+    A.r = D.r; A.x = D.x; A.xs = D.xs; A.ap = D.ap;
+    A.geo0 = at(H.geo0); A.Winv0 = at(H.Winv[0]); A.Cmat32 = at(H.Cmat32); A.rg[0] = at(S.rg[0][0]); A.rg[1] = at(S.rg[0][1]);
+    A.Sg = H.Sg; A.lm = lm; A.col = D.col; A.b = D.b; A.tol2 = tol2;
+    A.nb = D.nb; A.n1 = H.n[1]; A.c32_stride = H.c32_stride; A.diag_owner = D.diag_owner;
+    A.g_rows = S.g_rows; A.g_spmv = S.g_spmv; A.ix = ix;
+    return A;
+}
+static void pcg_init(const PcgArgs& A, hipStream_t s) { hipLaunchKernelGGL(ml_init_pcg_kernel, dim3(A.g_rows), dim3(kCgBlk), 0, s, A); }
+static void pcg_spmv(const PcgArgs& A, int parity, hipStream_t s, hipEvent_t ev_a = nullptr, hipEvent_t ev_b = nullptr)
+{
+    launch(ml_spmv_pcg_kernel, dim3(A.g_spmv), dim3(512), 0, s, ev_a, ev_b, A, parity);
+}
+static void pcg_cg(const PcgArgs& A, int comp_u, int parity, int init, hipStream_t s, hipEvent_t ev_a = nullptr, hipEvent_t ev_b = nullptr)
+{
+    auto pick = [&](auto k5, auto k8, auto k12, auto k16) { return comp_u <= 5 ? k5 : comp_u <= 8 ? k8 : comp_u <= 12 ? k12 : k16; };
+    auto kernel = init ? pick(ml_cg_comp_pcg_kernel<5, true>, ml_cg_comp_pcg_kernel<8, true>, ml_cg_comp_pcg_kernel<12, true>, ml_cg_comp_pcg_kernel<16, true>)
+                       : pick(ml_cg_comp_pcg_kernel<5, false>, ml_cg_comp_pcg_kernel<8, false>, ml_cg_comp_pcg_kernel<12, false>, ml_cg_comp_pcg_kernel<16, false>);
+    launch(kernel, dim3(A.g_rows), dim3(kCgBlk), 0, s, ev_a, ev_b, A, parity);
+}
+
+// x = 0, r = b, first application of the preconditioner - for the graphs whose solve starts in this pass.  by_value: the pass has one
+// graph and `by_value` is its slot (the device table `sl` is what every other twin reads); ix: the hierarchy copy its PCG applies in
+// this pass, as the host predicts it (pgo_lm.hpp: lm_pass_ix) - the small-graph class hands it over by value and checks it on the device
+hipError_t kl_ml_init(const LmSlot* sl, const LmSlot* by_value, const LmShape& sh, int ix, hipStream_t s)
+{
+    if (by_value && pcg_args_shape(sh)) {
+        const PcgArgs A = make_pcg_args(*by_value, by_value->lm, ix, 0.);     // (tol2 is ml_spmv's)
+        pcg_init(A, s); pcg_cg(A, sh.comp_u, 0, 1, s);
+        return hipSuccess;
+    }
     if (by_value && sh.nslots == 1) { kl_ml_init_t<LmSlot>(*by_value, sh, s); return kl_ml_cg_t<LmSlot>(*by_value, sh, 0, 1, s); }
     kl_ml_init_t<const LmSlot*>(sl, sh, s);
     return kl_ml_cg_t<const LmSlot*>(sl, sh, 0, 1, s);
 }
 // PCG iterations first .. first + n - 1 of a solve (iteration i: p_old = pbuf[i & 1], p_new = pbuf[(i & 1) ^ 1]).  ev (profiling only, may
 // be null): 4 events per iteration - spmv start / stop, cg start / stop (dispatch timestamps; the batch's kernels)
-hipError_t kl_ml_pcg_its(const LmSlot* sl, const LmSlot* by_value, const LmShape& sh, int first, int n, hipStream_t s, hipEvent_t* ev)
+hipError_t kl_ml_pcg_its(const LmSlot* sl, const LmSlot* by_value, const LmShape& sh, int ix, double tol2, int first, int n, hipStream_t s, hipEvent_t* ev)
 {
     const bool one = by_value && sh.nslots == 1 && !ev;
+    const bool args = one && pcg_args_shape(sh);
+    const PcgArgs A = args ? make_pcg_args(*by_value, by_value->lm, ix, tol2) : PcgArgs{};
     for (int q = 0; q < n; q++) {
         const int par = (first + q) & 1;
         hipError_t e;
-        if (ev) { kl_ml_spmv_t<const LmSlot*>(sl, sh, par, s, ev[4 * q], ev[4 * q + 1]); e = kl_ml_cg_t<const LmSlot*>(sl, sh, par, 0, s, ev[4 * q + 2], ev[4 * q + 3]); }
+        if (args) { pcg_spmv(A, par, s); pcg_cg(A, sh.comp_u, par, 0, s); e = hipSuccess; }
+        else if (ev) { kl_ml_spmv_t<const LmSlot*>(sl, sh, par, s, ev[4 * q], ev[4 * q + 1]); e = kl_ml_cg_t<const LmSlot*>(sl, sh, par, 0, s, ev[4 * q + 2], ev[4 * q + 3]); }
         else if (one) { kl_ml_spmv_t<LmSlot>(*by_value, sh, par, s); e = kl_ml_cg_t<LmSlot>(*by_value, sh, par, 0, s); }
         else { kl_ml_spmv_t<const LmSlot*>(sl, sh, par, s); e = kl_ml_cg_t<const LmSlot*>(sl, sh, par, 0, s); }
         if (e != hipSuccess) return e;
@@ -2708,10 +2851,20 @@ hipError_t kl_ml_pcg_its(const LmSlot* sl, const LmSlot* by_value, const LmShape
 }
 // the host-driven loop (uzl_pgo.hip): the init kernel, and the two launches of a PCG iteration one by one - a sharded solve all-reduces
 // A p between them, a profiled one times each
-void kl_ml_pcg_init(const HostSlot& hs, const LmShape& sh, hipStream_t s) { kl_ml_init_t<HostSlot>(hs, sh, s); }
-void kl_ml_spmv(const HostSlot& hs, const LmShape& sh, int parity, hipStream_t s, hipEvent_t ev_a, hipEvent_t ev_b) { kl_ml_spmv_t<HostSlot>(hs, sh, parity, s, ev_a, ev_b); }
+// (the small-graph class: the same PcgArgs kernels as the device-resident loop, with no LM state behind them)
+void kl_ml_pcg_init(const HostSlot& hs, const LmShape& sh, hipStream_t s)
+{
+    if (pcg_args_shape(sh)) pcg_init(make_pcg_args(hs.S, nullptr, hs.ix, hs.tol2), s);
+    else kl_ml_init_t<HostSlot>(hs, sh, s);
+}
+void kl_ml_spmv(const HostSlot& hs, const LmShape& sh, int parity, hipStream_t s, hipEvent_t ev_a, hipEvent_t ev_b)
+{
+    if (pcg_args_shape(sh)) pcg_spmv(make_pcg_args(hs.S, nullptr, hs.ix, hs.tol2), parity, s, ev_a, ev_b);
+    else kl_ml_spmv_t<HostSlot>(hs, sh, parity, s, ev_a, ev_b);
+}
 hipError_t kl_ml_cg(const HostSlot& hs, const LmShape& sh, int parity, int init, hipStream_t s, hipEvent_t ev_a, hipEvent_t ev_b)
 {
+    if (pcg_args_shape(sh)) { pcg_cg(make_pcg_args(hs.S, nullptr, hs.ix, hs.tol2), sh.comp_u, parity, init, s, ev_a, ev_b); return hipSuccess; }
     return kl_ml_cg_t<HostSlot>(hs, sh, parity, init, s, ev_a, ev_b);
 }
 

@@ -134,8 +134,10 @@ struct MlDev {
     double* Sg;                // [n_g][6] restriction of A p at the gather level (written by ml_spmv)
 };
 
-// Hot subset of MlDev passed BY VALUE to the per-iteration kernels (kernel arguments are preloaded; going
-// through the MlDev pointer costs one extra dependent scalar-load round trip per first use).
+// Hot subset of MlDev passed BY VALUE to the per-iteration kernels.  Kernel arguments are NOT preloaded into registers: the ISA fetches
+// them from the kernel-argument segment with s_load, in batches, each behind an s_waitcnt lgkmcnt(0) - one scalar round trip per batch,
+// and a batch per basic block that first uses a field.  Going through the MlDev pointer costs one more dependent round trip per first
+// use on top.  (The small-graph PCG pair takes PcgArgs below: one batch.)
 struct MlHot {
     int32_t levels;
     int32_t n[kMlMaxLevels + 1];
@@ -251,6 +253,48 @@ struct HostSlot {
     int32_t ix, cur;
     double tol2;
 };
+
+// The PCG launches of a ONE-GRAPH pass of the small-graph class (AGG = 1 with the dense level-1 operator: ml_init<1>, ml_spmv<1, 1, 8>,
+// ml_cg_comp<U>), BY VALUE, for both LM loops: exactly what those three bodies read, with the hierarchy copy already chosen on the host
+// (`ix`: Winv0 / geo0 / Cmat32 / rg are that copy's arrays - no pointer arithmetic behind a load of LmDev::ix in the kernel).  A slot by
+// value is 1.5 KB of kernel-argument memory whose fields the compiler fetches batch by batch, each behind a wait of its own, the branches
+// between them included (ISA: three batches in front of ml_spmv's row header, six dependent round trips in front of ml_cg_comp's first
+// operand load); these 232 bytes are four 64-byte lines, fetched at entry in one go, and every test that can end the kernel early sits
+// behind the issue of the operand loads.
+//   lm != null (device-resident loop): the kernels compare `ix` with LmDev::ix - loaded beside the done flag, same 64-byte line - and on
+//   a mismatch do no work and raise an anomaly (flags[0] = 1, flags[2] = kBreakdownIx: lm_tail_kernel -> anomaly_code 4, the host-driven
+//   loop takes the graph over).  A stale `ix` can cost time, never change a result.
+//   lm == null (host-driven loop): flags / scal are the handle's own, the init always runs.
+constexpr int32_t kBreakdownIx = 2;      // PgoDev::flags[2]: 1 = PCG breakdown, 2 = the launch's hierarchy copy is not the state's
+struct PcgArgs {
+    // ml_spmv's and ml_cg_comp's first loads
+    int32_t* flags;            // [4]  (device-resident loop: = lm->flags)
+    double* scal;
+    double* part_a;
+    double* part_b;
+    double* part_c;
+    const int32_t* rowhdr;
+    double* hdiag;
+    double* z;
+    double* blk;
+    double* pbuf[2];
+    double* r;
+    double* x;
+    double* xs;
+    double* ap;
+    const double* geo0;        // hierarchy copy ix
+    const double* Winv0;       //   "
+    const float* Cmat32;       //   "
+    double* rg[2];             //   "
+    double* Sg;
+    const LmDev* lm;
+    const int32_t* col;        // rows beyond 20 slots only
+    double* b;                 // ml_init only
+    double tol2;
+    int32_t nb, n1, c32_stride, diag_owner;
+    int32_t g_rows, g_spmv, ix, pad0;
+};
+static_assert(sizeof(PcgArgs) <= 256, "PcgArgs: four cache lines of kernel-argument memory");
 
 // launch geometry of a pass: what the host needs besides the slot table (one structure, or the common shape of a batch)
 enum LmCgVariant : int32_t { kCgPlain1 = 0, kCgComp1 = 1, kCgPlain4 = 2, kCgComp4 = 3, kCgComp4Ypre = 4, kCgComp4Vpre = 5 };

@@ -48,9 +48,9 @@ struct LmRun {
     std::vector<std::vector<int>> trial_its_prev, trial_its_cur;      // [job][trial]
     std::vector<uint64_t> hist_gen;          // structure generation of every job the counts belong to (a batch: its graphs in order)
     struct Seg { hipGraph_t g = nullptr; hipGraphExec_t x = nullptr; };
-    Seg setup, reb, pcg_long;
+    Seg setup, reb, pcg_long[2];            // pcg_long: per hierarchy copy (a one-graph pass's PCG launches carry the copy's arrays by value)
     void drop(Seg& q) { if (q.x) { (void)hipGraphExecDestroy(q.x); q.x = nullptr; } if (q.g) { (void)hipGraphDestroy(q.g); q.g = nullptr; } }
-    void drop_all() { drop(setup); drop(reb); drop(pcg_long); }
+    void drop_all() { drop(setup); drop(reb); drop(pcg_long[0]); drop(pcg_long[1]); }
 };
 
 void lm_run_destroy(LmRun* r)
@@ -102,8 +102,12 @@ void enq_setup(LmRun* R, int which, int ns_steps, hipStream_t s)
     kl_ml_trial(R->d_slots.p, R->shape, which, ns_steps, s);
 }
 const LmSlot* by_value_slot(LmRun* R) { return (R->shape.nslots == 1 && !R->shape.batch_geometry) ? R->slots.data() : nullptr; }
-void enq_init(LmRun* R, hipStream_t s) { UZL_HIP(kl_ml_init(R->d_slots.p, by_value_slot(R), R->shape, s)); }
-void enq_pcg(LmRun* R, int first, int n, hipStream_t s, hipEvent_t* ev = nullptr) { UZL_HIP(kl_ml_pcg_its(R->d_slots.p, by_value_slot(R), R->shape, first, n, s, ev)); }
+// ix, tol2: the hierarchy copy of a one-graph pass (lm_pass_ix) and its pcg_tol^2, by value to the small-graph class's launches
+void enq_init(LmRun* R, int ix, hipStream_t s) { UZL_HIP(kl_ml_init(R->d_slots.p, by_value_slot(R), R->shape, ix, s)); }
+void enq_pcg(LmRun* R, int ix, double tol2, int first, int n, hipStream_t s, hipEvent_t* ev = nullptr)
+{
+    UZL_HIP(kl_ml_pcg_its(R->d_slots.p, by_value_slot(R), R->shape, ix, tol2, first, n, s, ev));
+}
 void enq_tail(LmRun* R, hipStream_t s)
 {
     const LmShape& sh = R->shape;
@@ -395,6 +399,11 @@ int lm_drive(LmRun* R, std::vector<LmJob>& jobs, const LmDriveOpts& o)
         // iteration index of the pass's first PCG launch: a single graph's continuation goes on where its solve stands (its count may be
         // odd); in a batch every pass holds whole pairs, so every solve stands at an even count
         const int base = (nS == 1 && slot_job[0] >= 0 && snap[0].lm.phase == kLmSolve) ? snap[0].lm.flags[1] : 0;
+        // the hierarchy copy a one-graph pass applies: lm_head_kernel's rule on the snapshot this pass starts from (the kernels hold it
+        // against LmDev::ix and end the solve as an anomaly if it is not the state's).  Diagnostic build, UZL_LM_WRONG_IX=1: the other copy
+        static const bool wrong_ix = diag_flag("UZL_LM_WRONG_IX");
+        const int pass_ix = lm_pass_ix(snap[0].lm.phase, snap[0].lm.ix, snap[0].lm.pending) ^ (wrong_ix ? 1 : 0);
+        const double tol2 = snap[0].lm.tol2;
         mark(0);
         if (any_start && R->join_pending) { UZL_HIP(hipStreamWaitEvent(s, R->ev_join, 0)); R->join_pending = false; }      // the rebuild of an earlier pass reads H and the poses
         mark(1);
@@ -417,19 +426,19 @@ int lm_drive(LmRun* R, std::vector<LmJob>& jobs, const LmDriveOpts& o)
             R->join_pending = true;
         }
         mark(3);
-        if (any_start) enq_init(R, s);
+        if (any_start) enq_init(R, pass_ix, s);
         mark(4);
         // short solves are launched kernel by kernel, long ones as captured replays of 2 x kGraphPairs iterations plus a remainder
         if (o.timer && o.timer->on) {
             std::vector<hipEvent_t> ev((size_t)4 * want);
             for (int q = 0; q < want; q++) { o.timer->pair(o.spmv_name, &ev[4 * q], &ev[4 * q + 1]); o.timer->pair(o.cg_name, &ev[4 * q + 2], &ev[4 * q + 3]); }
-            enq_pcg(R, base, want, s, ev.data());
+            enq_pcg(R, pass_ix, tol2, base, want, s, ev.data());
         } else {
             int first = base, left = want;
-            if (!eager && (first & 1)) { enq_pcg(R, first, 1, s); first++; left--; }      // (the captured replay starts at an even iteration)
+            if (!eager && (first & 1)) { enq_pcg(R, pass_ix, tol2, first, 1, s); first++; left--; }      // (the captured replay starts at an even iteration)
             const int n_long = eager ? 0 : left / kLong, rem = left - n_long * kLong;
-            for (int i = 0; i < n_long; i++) run_seg(R->pcg_long, false, s, [&](hipStream_t q) { enq_pcg(R, 0, kLong, q); });
-            if (rem > 0) enq_pcg(R, first + n_long * kLong, rem, s);
+            for (int i = 0; i < n_long; i++) run_seg(R->pcg_long[pass_ix], false, s, [&](hipStream_t q) { enq_pcg(R, pass_ix, tol2, 0, kLong, q); });
+            if (rem > 0) enq_pcg(R, pass_ix, tol2, first + n_long * kLong, rem, s);
         }
         mark(5);
         enq_tail(R, s);
