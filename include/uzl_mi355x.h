@@ -752,6 +752,108 @@ int  uzl_gist_add_batch(uzl_gist* h, int32_t n, const uint8_t* desc, const uint8
 int  uzl_gist_last_knn(uzl_gist* h, int32_t cap, int32_t* place, int32_t* dist);
 
 /* ======================================================================================
+ *  Appearance-based candidate pairs from a repository of every distinct feature seen so far
+ *
+ *  GlobalFeatureRepositoryRecognizer (place_recognition/src/global_feature_repository_recognizer.cpp:30-158)
+ *  over GlobalFeatureRepository (global_feature_repository.cpp:29-149), the reference's
+ *  place_recognition_method "gfr" (graph_slam/src/graph_slam_node.cpp:102-108), behind the filters of
+ *  PlaceRecognizer (place_recognizer.cpp:71-180).
+ *
+ *  Handle state: a running place count with a stamp and a live flag per place index; a feature
+ *  repository of F descriptor rows, all of one byte length; per feature a multiset of place indices
+ *  (the reference's `links`); the stored descriptor type, initially -1.  One node carries one
+ *  FeatureData (the restriction of uzl_places_*); a node without one (desc == NULL or rows == 0) takes a
+ *  place index and touches nothing else.
+ *
+ *  Contract: the reference searches with FLANN's LSH index (approximate, not reproducible); here the
+ *  search is EXACT.  A match, given rows x bytes descriptors and a feature_type:
+ *    a. If feature_type differs from the stored type, store it and clear the repository: features,
+ *       links and the byte length (global_feature_repository.cpp:49-52).  Place indices, stamps and
+ *       live flags stay.  This happens on search as well, as in the reference.
+ *    b. Each row's nearest feature is the minimum of (Hamming distance, feature index): exact, ties
+ *       go to the lower index.  The row is matched iff F > 0 and distance < max_distance (:89,
+ *       strict; the reference's constant 40 is the cfg field's default).
+ *    c. Every matched row adds one to votes[p] for every entry p of its feature's link multiset
+ *       (:58-63); duplicates count again.
+ *    d. Candidates are the places with votes[p] > 0 and votes[p] >= T (recognizer.cpp:55-61; T is a
+ *       double, so T = 10.5 acts as 11), ordered by (votes descending, place index ascending).  The
+ *       reference orders them with an unstable std::sort on the votes alone: the order among equal
+ *       votes is undefined there and fixed here.
+ *    e. Then PlaceRecognizer's filters, exactly those of uzl_gist_* step 3 (place_recognizer.cpp:87-114,
+ *       157-180): live, |stamp - query stamp| > min_time_gap, the k cut, reported once per (neighbour,
+ *       query place) pair.  The cut is tested after a neighbour is taken, so k_nearest_neighbors = 0
+ *       lets one through.
+ *  Integration follows for rows 0..rows-1 in row order (recognizer.cpp:76-82, 105-111).  Every row was
+ *  matched against the repository as it stood before this node, so two similar rows of one node both
+ *  become features.  An unmatched row becomes feature F++ with the one link {this place} if
+ *  popcount(row) > 3 * bytes (global_feature_repository.cpp:117-136), else it is dropped silently; a
+ *  matched row appends this place to its feature's links (two rows matched to one feature append twice).
+ *    search_and_add = match a-e, integration, place_count++.
+ *    add            = match a-b, integration, place_count++; no votes (the reference's addPlaceImpl hands
+ *                     match() an empty vote vector that global_feature_repository.cpp:60-62 then writes
+ *                     out of bounds; nothing is counted here).
+ *    search         = a-e only; with no live place it returns nothing and touches nothing
+ *                     (place_recognizer.cpp:153-156).
+ *    remove         = clears the live flag and nothing else (removePlaceImpl is a TODO, recognizer.cpp:
+ *                     155-158): a removed place still collects votes and is dropped by the live filter,
+ *                     before the k count.
+ *  Limits: the byte length is fixed by the first stored feature after a clear and may be 1-64; rows are
+ *  zero-padded to 16 bytes in the store, which changes neither distances nor popcounts.  Another length
+ *  returns UZL_ERR_BAD_ARG and changes nothing; so do rows outside 0-4096 and a feature or link index
+ *  that would reach 2^31.
+ *
+ *  Device side: gfr_nearest_kernel keeps one packed key (distance << 32 | feature) per row, the
+ *  repository staged tile by tile in LDS and read by every lane at the same address, partial minima
+ *  merged with a 64-bit atomicMin; gfr_vote_kernel walks link chains in an append-only arena;
+ *  gfr_select_kernel compacts the candidates in place order; gfr_integrate_kernel gives new features
+ *  and links their indices by ballot prefix in row order.  Integer only: results equal the CPU
+ *  restatement exactly, and two runs leave identical stores.
+ * ====================================================================================== */
+typedef struct uzl_gfr uzl_gfr;
+typedef struct uzl_gfr_cfg {
+    double  T;                    /* 10    PlaceRecognizer.cfg "T": minimum votes                        */
+    int32_t k_nearest_neighbors;  /* 10    PlaceRecognizer.cfg (0-256 accepted here)                     */
+    int32_t max_distance;         /* 40    a row matches below this distance (:89), 1-512                */
+    int32_t device;
+    double  min_time_gap;         /* 5.0   s, place_recognizer.cpp:93                                    */
+    int32_t initial_features;     /* 65536 first capacity of the store (>= 1); doubles when full         */
+} uzl_gfr_cfg;
+void uzl_gfr_cfg_default(uzl_gfr_cfg* cfg);
+/* UZL_ERR_BAD_ARG for T or min_time_gap = NaN, k_nearest_neighbors outside 0-256, max_distance outside 1-512, initial_features
+ * outside 1-2^30; UZL_ERR_NO_DEVICE without a GPU (no CPU fallback) */
+int  uzl_gfr_create(const uzl_gfr_cfg* cfg, uzl_gfr** out);
+void uzl_gfr_destroy(uzl_gfr* h);
+const char* uzl_gfr_last_error(uzl_gfr* h);
+/* PlaceRecognizer::searchAndAddPlace: desc = rows x bytes descriptors of the node's FeatureData (NULL or rows = 0: none),
+ * feature_type = FeatureData::feature_type_, stamp = node.stamps_.front().  neighbors (capacity cap) receives the place indices,
+ * *n_neighbors their number (all of them written when cap allows), *place_index (may be NULL) the index given to this place. */
+int  uzl_gfr_search_and_add(uzl_gfr* h, const uint8_t* desc, int32_t rows, int32_t bytes, int32_t feature_type, int64_t stamp_ns,
+                            int32_t cap, int32_t* neighbors, int32_t* n_neighbors, int32_t* place_index);
+/* PlaceRecognizer::addPlace */
+int  uzl_gfr_add(uzl_gfr* h, const uint8_t* desc, int32_t rows, int32_t bytes, int32_t feature_type, int64_t stamp_ns,
+                 int32_t* place_index);
+/* PlaceRecognizer::searchPlace; query_place = the querying node's place index (for the reported-once filter), -1 if none */
+int  uzl_gfr_search(uzl_gfr* h, const uint8_t* desc, int32_t rows, int32_t bytes, int32_t feature_type, int64_t stamp_ns,
+                    int32_t query_place, int32_t cap, int32_t* neighbors, int32_t* n_neighbors);
+/* PlaceRecognizer::removePlace; UZL_ERR_NOT_FOUND for a place index never given or already removed */
+int  uzl_gfr_remove(uzl_gfr* h, int32_t place_index);
+/* places given an index so far (removed ones included) / features in the repository / link entries of all features */
+int  uzl_gfr_count(uzl_gfr* h);
+int  uzl_gfr_feature_count(uzl_gfr* h);
+int  uzl_gfr_link_count(uzl_gfr* h);
+/* For the parity tests; each is copied from the device only when asked for.
+ * last_matches: per row of the last call that matched rows, the matched feature or -1, and the nearest distance (-1 when F was 0);
+ * returns the number of rows, writes at most cap entries (feature or dist may be NULL).
+ * last_votes: one count per place index (place count + 1 of them) of the last search / search_and_add that matched rows; returns
+ * their number.
+ * get_feature: the stored bytes of `feature` (desc_out, byte-length bytes, may be NULL) and its links in ascending place order with
+ * duplicates - place indices only grow, so that is the reference's insertion order; *n_places their number (at most cap are
+ * written); UZL_ERR_NOT_FOUND for a feature index outside the repository. */
+int  uzl_gfr_last_matches(uzl_gfr* h, int32_t cap, int32_t* feature, int32_t* dist);
+int  uzl_gfr_last_votes(uzl_gfr* h, int32_t cap, int32_t* votes);
+int  uzl_gfr_get_feature(uzl_gfr* h, int32_t feature, uint8_t* desc_out, int32_t cap, int32_t* places, int32_t* n_places);
+
+/* ======================================================================================
  *  Occupancy-grid map from the stored laser scans at the solved poses
  *
  *  GraphGridMapper::convertLaserScans2Map (map_projection/src/graph_grid_mapper.cpp:295-400), which

@@ -188,6 +188,11 @@ class GistCfg(C.Structure):
     _fields_ = [("T", C.c_double), ("k_nearest_neighbors", C.c_int32), ("device", C.c_int32), ("min_time_gap", C.c_double)]
 
 
+class GfrCfg(C.Structure):
+    _fields_ = [("T", C.c_double), ("k_nearest_neighbors", C.c_int32), ("max_distance", C.c_int32), ("device", C.c_int32),
+                ("min_time_gap", C.c_double), ("initial_features", C.c_int32)]
+
+
 class GridCfg(C.Structure):
     _fields_ = [("resolution", C.c_double), ("range_max", C.c_double), ("occupancy_threshold", C.c_double), ("max_distance", C.c_double),
                 ("known_free_radius", C.c_double), ("min_pass_through", C.c_int32), ("device", C.c_int32), ("max_cells", C.c_int64)]
@@ -245,7 +250,7 @@ def lib():
 
 
 _HANDLES = ("uzl_match", "uzl_pgo", "uzl_pgo_batch", "uzl_filter", "uzl_gate", "uzl_radius", "uzl_places", "uzl_gist")
-_MORE_HANDLES = ("uzl_grid", "uzl_laserline")       # declared like _HANDLES; kept apart because tests pin _HANDLES to the first eight
+_MORE_HANDLES = ("uzl_grid", "uzl_laserline", "uzl_gfr")       # declared like _HANDLES; kept apart because tests pin _HANDLES to the first eight
 
 
 def _declare(L):
@@ -258,7 +263,8 @@ def _declare(L):
         getattr(L, p + "_destroy").argtypes = [C.c_void_p]
         if hasattr(L, p + "_cfg_default"):          # (a batch takes uzl_pgo_cfg)
             getattr(L, p + "_cfg_default").restype = None
-    for f in ("uzl_places_count", "uzl_gist_count", "uzl_grid_scan_count", "uzl_gate_edge_count", "uzl_filter_cluster_count"):
+    for f in ("uzl_places_count", "uzl_gist_count", "uzl_grid_scan_count", "uzl_gate_edge_count", "uzl_filter_cluster_count",
+              "uzl_gfr_count", "uzl_gfr_feature_count", "uzl_gfr_link_count"):
         getattr(L, f).argtypes = [C.c_void_p]
     L.uzl_pgo_batch_graph.restype = C.c_void_p
     L.uzl_pgo_batch_graph.argtypes = [C.c_void_p, C.c_int32]
@@ -1124,6 +1130,83 @@ class Gist(_Handle):
         pl = np.zeros(max(n, 1), np.int32); di = np.zeros(max(n, 1), np.int32)
         self._check(lib().uzl_gist_last_knn(self._h, C.c_int32(n), _p(pl, c_i32p), _p(di, c_i32p)))
         return pl[:n], di[:n]
+
+
+class Gfr(_Handle):
+    """uzl_gfr_* (GlobalFeatureRepositoryRecognizer / PlaceRecognizer, place_recognition/src): every row of a node finds its nearest
+    feature in a repository of all distinct features seen so far, matched rows vote for the places linked to their feature.
+    desc = (rows, bytes) u8, or None for a node without a FeatureData."""
+
+    _prefix, _cfg_type = "uzl_gfr", GfrCfg
+
+    @staticmethod
+    def _d(desc):
+        if desc is None:
+            return None, None, 0, 0
+        d = np.ascontiguousarray(desc, np.uint8)
+        d = d.reshape(d.shape[0], -1) if d.ndim >= 2 else d.reshape(1, -1)
+        return d, _p(d, c_u8p), d.shape[0], d.shape[1]
+
+    def _cap(self, cap):
+        return self.count() + 1 if cap is None else cap
+
+    def search_and_add(self, desc, stamp_ns, feature_type=2, cap=None):
+        d, dp, rows, nb = self._d(desc)
+        cap = self._cap(cap)
+        out = np.zeros(max(cap, 1), np.int32); n = C.c_int32(); idx = C.c_int32()
+        self._check(lib().uzl_gfr_search_and_add(self._h, dp, C.c_int32(rows), C.c_int32(nb), C.c_int32(feature_type), C.c_int64(int(stamp_ns)),
+                                                 C.c_int32(cap), _p(out, c_i32p), C.byref(n), C.byref(idx)))
+        return out[:min(n.value, cap)].copy(), idx.value
+
+    def add(self, desc, stamp_ns, feature_type=2):
+        d, dp, rows, nb = self._d(desc)
+        idx = C.c_int32()
+        self._check(lib().uzl_gfr_add(self._h, dp, C.c_int32(rows), C.c_int32(nb), C.c_int32(feature_type), C.c_int64(int(stamp_ns)),
+                                      C.byref(idx)))
+        return idx.value
+
+    def search(self, desc, stamp_ns, feature_type=2, query_place=-1, cap=None):
+        d, dp, rows, nb = self._d(desc)
+        cap = self._cap(cap)
+        out = np.zeros(max(cap, 1), np.int32); n = C.c_int32()
+        self._check(lib().uzl_gfr_search(self._h, dp, C.c_int32(rows), C.c_int32(nb), C.c_int32(feature_type), C.c_int64(int(stamp_ns)),
+                                         C.c_int32(query_place), C.c_int32(cap), _p(out, c_i32p), C.byref(n)))
+        return out[:min(n.value, cap)].copy()
+
+    def remove(self, place):
+        self._check(lib().uzl_gfr_remove(self._h, C.c_int32(place)))
+
+    def count(self):
+        return self._check(lib().uzl_gfr_count(self._h))
+
+    def feature_count(self):
+        return self._check(lib().uzl_gfr_feature_count(self._h))
+
+    def link_count(self):
+        return self._check(lib().uzl_gfr_link_count(self._h))
+
+    def last_matches(self):
+        """(matched feature or -1, nearest distance or -1) per row of the last call that matched rows"""
+        n = self._check(lib().uzl_gfr_last_matches(self._h, C.c_int32(0), None, None))
+        ft = np.zeros(max(n, 1), np.int32); di = np.zeros(max(n, 1), np.int32)
+        self._check(lib().uzl_gfr_last_matches(self._h, C.c_int32(n), _p(ft, c_i32p), _p(di, c_i32p)))
+        return ft[:n], di[:n]
+
+    def last_votes(self):
+        """votes per place index of the last search / search_and_add that matched rows"""
+        n = self._check(lib().uzl_gfr_last_votes(self._h, C.c_int32(0), None))
+        v = np.zeros(max(n, 1), np.int32)
+        self._check(lib().uzl_gfr_last_votes(self._h, C.c_int32(n), _p(v, c_i32p)))
+        return v[:n]
+
+    def get_feature(self, feature, nbytes=64):
+        """(stored bytes, links in ascending place order with duplicates); nbytes = the repository's byte length (the library
+        writes that many; the default returns them zero-padded to 64)"""
+        d = np.zeros(64, np.uint8); n = C.c_int32()
+        self._check(lib().uzl_gfr_get_feature(self._h, C.c_int32(feature), _p(d, c_u8p), C.c_int32(0), None, C.byref(n)))
+        pl = np.zeros(max(n.value, 1), np.int32)
+        self._check(lib().uzl_gfr_get_feature(self._h, C.c_int32(feature), _p(d, c_u8p), C.c_int32(n.value), _p(pl, c_i32p), C.byref(n)))
+        return d[:nbytes], pl[:n.value]
 
 
 class Grid(_Handle):

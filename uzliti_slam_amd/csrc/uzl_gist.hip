@@ -8,6 +8,7 @@
 // The kernel (gist_kernels.hip) returns per query the <= k nearest live places within T in (distance, place) order; the time gap,
 // k and reported-once filters run here, in the reference's order, node after node.
 #include "gist_types.hpp"
+#include "place_filters.hpp"
 #include "uzl_common.hpp"
 #include "uzl_streams.hpp"
 
@@ -117,26 +118,11 @@ void run_knn(uzl_gist* h, const uint8_t* queries, const uint8_t* qvalid, int32_t
     UZL_HIP(hipStreamSynchronize(s));
 }
 
-// PlaceRecognizer::searchAndAddPlace / searchPlace after the impl (place_recognizer.cpp:87-114, 157-180): live, time gap,
-// k cut, reported once.  knn = the impl's result (k nearest within T, nearest first).
+// PlaceRecognizer's filters (place_filters.hpp) over knn = the impl's result (k nearest within T, nearest first)
 void finish(uzl_gist* h, const int2* knn, int32_t n, int64_t stamp_q, int32_t id_q, std::vector<int32_t>& res)
 {
-    int32_t pr = 0;
-    for (int32_t j = 0; j < n; j++) {
-        const int32_t nb = knn[j].x;
-        if (nb < 0 || nb >= (int32_t)h->alive.size() || !h->alive[nb]) continue;
-        if (!(std::fabs((double)(h->stamp[nb] - stamp_q) * 1e-9) > h->cfg.min_time_gap)) continue;
-        pr++;
-        const uint64_t pair = ((uint64_t)(uint32_t)nb << 32) | (uint32_t)id_q;
-        if (h->checked.insert(pair).second) res.push_back(nb);
-        if (pr >= h->cfg.k_nearest_neighbors) break;
-    }
-}
-
-void write_out(const std::vector<int32_t>& res, int64_t at, int64_t cap, int32_t* out)
-{
-    for (size_t j = 0; j < res.size(); j++)
-        if (at + (int64_t)j < cap && out) out[at + j] = res[j];
+    place_filters(h->stamp, h->alive, h->checked, h->cfg.min_time_gap, h->cfg.k_nearest_neighbors, n,
+                  [knn](int32_t j) { return knn[j].x; }, stamp_q, id_q, res);
 }
 
 int check_batch(uzl_gist* h, int32_t n, const uint8_t* desc, const uint8_t* has_gist, int32_t bytes, const int64_t* stamps_ns)
@@ -165,7 +151,7 @@ void search_and_add_n(uzl_gist* h, int32_t n, const uint8_t* desc, const uint8_t
         commit_place(h, has(desc, has_gist, i), stamps_ns[i]);                // inserted before the filters run (:84-85)
         res.clear();
         finish(h, knn, nk, stamps_ns[i], base + i, res);
-        write_out(res, total, cap, neighbors);
+        write_places(res, total, cap, neighbors);
         if (count_per_node) count_per_node[i] = (int32_t)res.size();
         total += (int64_t)res.size();
         if (i == n - 1) h->last_knn.assign(knn, knn + nk);
@@ -259,7 +245,7 @@ int uzl_gist_search(uzl_gist* h, const uint8_t* desc, int32_t bytes, int64_t sta
     h->last_knn.assign(knn, knn + nk);
     std::vector<int32_t> res;
     finish(h, knn, nk, stamp_ns, query_place, res);
-    write_out(res, 0, cap, neighbors);
+    write_places(res, 0, cap, neighbors);
     *n_neighbors = (int32_t)res.size();
     return UZL_OK;
     UZL_GUARD_END(h)
