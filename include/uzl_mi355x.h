@@ -620,7 +620,12 @@ typedef struct uzl_radius uzl_radius;
 typedef struct uzl_radius_cfg {
     double  radius;               /* 0.5   distance_loop_closure_radius, GraphSlam.cfg:15 */
     double  new_edge_time;        /* 5.0   s, GraphSlam.cfg:21                             */
-    double  max_rotation_deg;     /* 30.0  graph_slam_node.cpp:282                        */
+    double  max_rotation_deg;     /* 30.0  graph_slam_node.cpp:282.  The angle of R_close^T R_query is the reference's
+                                   *       Eigen 3.2 AngleAxisd(Quaterniond(R)).angle() = 2 acos(clamp(w)): theta while the
+                                   *       quaternion conversion returns w >= 0 (always for a positive trace), but
+                                   *       360 deg - theta where its trace <= 0 branch (theta >= 120 deg) returns w < 0.
+                                   *       Below 120 deg this is the plain rotation angle; above, a bound such as 170 deg
+                                   *       rejects the pairs with w < 0 whatever their theta.                          */
     int32_t device;
     int32_t _pad;
 } uzl_radius_cfg;
@@ -640,7 +645,9 @@ int  uzl_radius_query(uzl_radius* h, int32_t n_queries, const int32_t* query_nod
  *
  *  LshSetRecognizer / FastLshSet (place_recognition/src/lsh_set_recognizer.cpp:46-310) behind
  *  PlaceRecognizer (place_recognizer.cpp:71-215): every place's binary descriptors are cut into
- *  key_width-byte keys (one exact-match table per byte offset 0, kw, 2 kw, ... below 32); a
+ *  key_width-byte keys (one exact-match table per byte offset 0, kw, 2 kw, ... < 32 - kw + 1:
+ *  32 / 16 / 10 / 8 / 6 / 5 / 4 / 4 tables for key_width 1 .. 8; descriptor bytes from 32 up are
+ *  never read); a
  *  query counts, per earlier place, how many (descriptor, table) keys it shares; places whose
  *  count / tables reaches T are neighbours, best first, subject to a time gap, a k-nearest
  *  cut and a reported-once filter.  Here the tables are open-addressing hash tables in HBM
@@ -649,12 +656,13 @@ int  uzl_radius_query(uzl_radius* h, int32_t n_queries, const int32_t* query_nod
  * ====================================================================================== */
 typedef struct uzl_places uzl_places;
 typedef struct uzl_places_cfg {
-    int32_t key_width;            /* 8     FastLshSet(key_width = 8), lsh_set_recognizer.h:66           */
+    int32_t key_width;            /* 8     FastLshSet(key_width = 8), lsh_set_recognizer.h:66; 1 .. 8    */
     int32_t min_rows_to_add;      /* 150   a frame is indexed only with more rows (:66, :111)            */
     double  T;                    /* 10    cfg/PlaceRecognizer.cfg "T": minimum count / tables           */
     int32_t k_nearest_neighbors;  /* 10    cfg "k_nearest_neighbors"                                     */
     int32_t device;
-    double  min_time_gap;         /* 5.0   s, place_recognizer.cpp:90                                    */
+    double  min_time_gap;         /* 5.0   s, place_recognizer.cpp:90 (hard-coded there); >= 0, else     *
+                                   *       create returns UZL_ERR_BAD_ARG: see uzl_places_last_counts    */
 } uzl_places_cfg;
 void uzl_places_cfg_default(uzl_places_cfg* cfg);
 int  uzl_places_create(const uzl_places_cfg* cfg, uzl_places** out);
@@ -673,7 +681,10 @@ int  uzl_places_search(uzl_places* h, const uint8_t* desc, int32_t rows, int32_t
 /* PlaceRecognizer::removePlace: needs the descriptors the place was added with (as the reference does) */
 int  uzl_places_remove(uzl_places* h, int32_t place_index, const uint8_t* desc, int32_t rows, int32_t bytes);
 int  uzl_places_count(uzl_places* h);
-/* collision counts per place of the last search / search_and_add (parity tests); returns their number */
+/* collision counts per place of the last search / search_and_add (parity tests); returns their number.
+ * After search_and_add the last slot is the new place's own: the device counts before it inserts, so it is 0
+ * where the reference holds the frame's collisions with itself.  Nothing reads that slot: a place is 0 s away
+ * from itself and min_time_gap >= 0, so it is never a neighbour. */
 int  uzl_places_last_counts(uzl_places* h, int32_t cap, int32_t* counts);
 
 /* ======================================================================================

@@ -18,6 +18,7 @@
 namespace uzl {
 
 constexpr int kPlBlk = 256;
+constexpr int kPlMaxTables = 32;                                      // key_width 1: one table per byte offset 0 .. 31
 constexpr unsigned long long kEmptyKey = 0xFFFFFFFFFFFFFFFFull;       // a real all-ones key lives in the extra slot `cap`
 
 struct PlEntry { int32_t place; int32_t next; };
@@ -30,12 +31,12 @@ struct PlTable {
 };
 
 struct PlArgs {
-    PlTable tab[8];
+    PlTable tab[kPlMaxTables];
     int32_t nt, rows, bytes, key_width, id, popcount_min;      // popcount_min: keys with fewer set bits + 1 are skipped (-1: none)
     const uint8_t* desc;
     PlEntry* entries;
     int32_t* n_entries;           // [1]
-    int32_t* used;                // [8] occupied slots per table
+    int32_t* used;                // [kPlMaxTables] occupied slots per table
     int32_t* counts;              // [places]
 };
 
@@ -148,7 +149,7 @@ struct uzl_places : HandleBase {
     hipStream_t stream = nullptr;
     int nt = 0;
     struct Tab { DevBuf<unsigned long long> keys; DevBuf<int32_t> head; uint32_t cap = 0; int32_t used = 0; };
-    Tab tab[8];
+    Tab tab[kPlMaxTables];
     DevBuf<PlEntry> entries; size_t entry_cap = 0; int64_t n_entries = 0;
     DevBuf<int32_t> d_n_entries, d_used, d_counts;
     DevBuf<uint8_t> d_desc;
@@ -229,12 +230,12 @@ void run_insert(uzl_places* h, int rows, int bytes, int id, int popcount_min)
     ensure_room(h, rows);
     PlArgs a; fill_args(h, a, rows, bytes, id, popcount_min);
     hipLaunchKernelGGL(places_insert_kernel, dim3((rows * h->nt + kPlBlk - 1) / kPlBlk), dim3(kPlBlk), 0, s, a);
-    UZL_HIP(hipMemcpyAsync(h->h_small.p, h->d_used.p, 8 * 4, hipMemcpyDeviceToHost, s));
-    UZL_HIP(hipMemcpyAsync(h->h_small.p + 8, h->d_n_entries.p, 4, hipMemcpyDeviceToHost, s));
+    UZL_HIP(hipMemcpyAsync(h->h_small.p, h->d_used.p, (size_t)h->nt * 4, hipMemcpyDeviceToHost, s));
+    UZL_HIP(hipMemcpyAsync(h->h_small.p + kPlMaxTables, h->d_n_entries.p, 4, hipMemcpyDeviceToHost, s));
     UZL_HIP(hipStreamSynchronize(s));
     UZL_HIP(hipGetLastError());
     for (int t = 0; t < h->nt; t++) h->tab[t].used = h->h_small.p[t];
-    h->n_entries = h->h_small.p[8];
+    h->n_entries = h->h_small.p[kPlMaxTables];
 }
 
 // thresholds, sort and the self / time / knn / reported-once filters (lsh_set_recognizer.cpp:73-92, place_recognizer.cpp:87-114)
@@ -285,18 +286,18 @@ int uzl_places_create(const uzl_places_cfg* cfg, uzl_places** out)
     uzl_places_cfg c;
     if (cfg) c = *cfg; else uzl_places_cfg_default(&c);
     if (c.key_width < 1 || c.key_width > 8) return UZL_ERR_BAD_ARG;
+    if (!(c.min_time_gap >= 0.)) return UZL_ERR_BAD_ARG;       // a place is 0 s from itself: only a gap >= 0 keeps the own slot out
     if (check_device(c.device) != UZL_OK) return UZL_ERR_NO_DEVICE;
     uzl_places* h = new (std::nothrow) uzl_places();
     if (!h) return UZL_ERR_OOM;
     h->cfg = c;
-    for (int i = 0; i < 32 - c.key_width + 1; i += c.key_width) h->nt++;                     // FastLshSet::clear :258-263
-    if (h->nt > 8) h->nt = 8;
+    for (int i = 0; i < 32 - c.key_width + 1; i += c.key_width) h->nt++;                     // FastLshSet::clear :253-259: 32 .. 4 tables
     try {
         open_handle_stream(c.device, false, &h->stream);
         for (int t = 0; t < h->nt; t++) alloc_table(h, h->tab[t], 1u << 16);
-        h->d_n_entries.reserve(1); h->d_used.reserve(8); h->h_small.reserve(16);
+        h->d_n_entries.reserve(1); h->d_used.reserve(kPlMaxTables); h->h_small.reserve(kPlMaxTables + 1);
         UZL_HIP(hipMemsetAsync(h->d_n_entries.p, 0, 4, h->stream));
-        UZL_HIP(hipMemsetAsync(h->d_used.p, 0, 32, h->stream));
+        UZL_HIP(hipMemsetAsync(h->d_used.p, 0, kPlMaxTables * 4, h->stream));
         h->entries.reserve(1 << 16); h->entry_cap = 1 << 16;
         UZL_HIP(hipStreamSynchronize(h->stream));
     } catch (...) {
