@@ -1114,6 +1114,159 @@ int  uzl_laserline_read(uzl_laserline* h, int32_t cap_scans, float* ranges, floa
 int  uzl_laserline_to_grid(uzl_laserline* h, uzl_grid* grid, const int32_t* nodes, int32_t* first_scan);
 
 /* ======================================================================================
+ *  Laser scan matching: TYPE_2D_LASER edges by point-to-line ICP, many pairs at once
+ *
+ *  LaserTransformationEstimator (transformation_estimation/src/laser_transformation_estimator.cpp:
+ *  134-443) aligns the scans of two nodes with csm's sm_icp (PLICP) and emits a TYPE_2D_LASER edge
+ *  with a 3-DoF information block; GraphSlamNode::estimateScanEdge (graph_slam/src/
+ *  graph_slam_node.cpp:1180-1246) picks the pairs.  csm is not part of the reference tree, so the
+ *  algorithm below is THIS PROJECT'S READING of PLICP with the reference's parameters
+ *  (use_corr_tricks 0, outliers_remove_doubles 1, use_sigma_weights 1, :35-124), pinned by a NumPy
+ *  restatement (tests/laser_reference.py).  All arithmetic is f64, evaluated in the order written
+ *  with no fused multiply-add; / and sqrt are correctly rounded.  Steps 1-4 equal the restatement
+ *  bit for bit; the rest differs from it by the order of the sums only.
+ *
+ *  1. Points.  theta_k = (double)angle_min + k (double)angle_increment; (c_k, s_k) = (cos, sin)
+ *     (theta_k) from the HOST's libm, uploaded as a table per distinct (angle_min, angle_increment,
+ *     n_beams) - the table rule of the occupancy grid and the laser line.  Beam k is valid iff
+ *     range_min <= r_k <= range_max in f32 (:415; NaN is invalid); p_k = (c_k r, s_k r) with
+ *     r = (double)r_k.  The rotation of the estimate is carried as a pair (c, s), never through
+ *     device trigonometry: the host takes (cos, sin)(theta0) of the first guess, and theta =
+ *     atan2(s, c) on the host when results are read.
+ *  2. Correspondences (brute force, use_corr_tricks = 0).  Each valid beam i of `to` is moved into
+ *     `from`'s frame: w = ((c x - s y) + tx, (s x + c y) + ty).  j1 = the valid beam of `from` with
+ *     the smallest squared distance dx dx + dy dy (dx = w_x - q_x), ties to the lowest index; kept
+ *     iff that distance <= max_correspondence_dist^2.  j2: the nearest valid beam index above j1
+ *     and the nearest below; the one whose point is closer to w, ties to the upper one; neither, or
+ *     points j1 and j2 coincide: no correspondence.  Divergence: csm searches an angular window
+ *     derived from the correction limits; here every beam is searched (within 0.3 m the sets
+ *     differ only for points next to the sensor).
+ *  3. Doubles (outliers_remove_doubles).  Correspondence i is dropped iff another correspondence
+ *     with the same j1 has a strictly smaller squared distance.
+ *  4. Trim.  With l = q_j2 - q_j1, len = sqrt(l_x l_x + l_y l_y), n = (-l_y / len, l_x / len):
+ *     d_i = |n_x (w_x - q_j1.x) + n_y (w_y - q_j1.y)|.  Over the k correspondences left, sorted
+ *     ascending: limit1 = d[clamp(floor(k outliers_max_perc), 0, k - 1)], limit2 =
+ *     outliers_adaptive_mult d[clamp(floor(k outliers_adaptive_order), 0, k - 1)]; i is dropped iff
+ *     d_i > min(limit1, limit2).
+ *  5. Failure.  No correspondence left, or fewer than fail_fraction n_beams(to):
+ *     UZL_LASER_FEW_CORR, the pair stops (pose = the estimate it stopped at).
+ *  6. Step.  Minimise sum w_i (n_i . (R p_i + t - q_i))^2 over (t, c, s) with c^2 + s^2 = 1,
+ *     q_i = point j1, w_i = 1 / r_i^2 with r_i the reading of beam i of `to` (use_sigma_weights with
+ *     readings_sigma = r, :420), EXACTLY (Censi's closed form, no small-angle linearisation): the
+ *     residual is a . x - b with x = (tx, ty, c, s), a = (n_x, n_y, n . p, n_y p_x - n_x p_y),
+ *     b = n . q.  Sums M = sum (w a_r) a_c (10), v = sum (w b) a (4), each reduced in a fixed order:
+ *     beam order within a lane's strip (lane t of 256 owns beams t, t + 256, ...), a butterfly
+ *     over the 64 lanes of a wave, then (w0 + w1) + (w2 + w3) - so a result depends neither on the
+ *     schedule nor on the batch nor on the other pairs of the call.  With A, B, D the 2x2 blocks
+ *     of M: E = A^-1 B, f = A^-1 v_t (by the adjugate over det A; det A <= 0: UZL_LASER_DEGENERATE),
+ *     Q = D - B^T E, h = -2 (v_r - B^T f); the minimiser over the circle is r = -(adj Q + lambda I) h
+ *     / (2 det(Q + lambda I)) at the largest real root lambda of the quartic det(Q + lambda I)^2 =
+ *     |(adj Q + lambda I) h|^2 / 4, the only one above -e_min(Q).  Root finder: 64 bisections of
+ *     [-e_min, -e_min + |h|] on the sign of that difference (e_min by the 2x2 eigenvalue formula);
+ *     r is then divided by its norm and t = f - E r.  |h| = 0 or a non-finite value:
+ *     UZL_LASER_DEGENERATE.
+ *  7. Convergence.  Stop when |dt|^2 < epsilon_xy^2 and |cross| < sin(epsilon_theta) (computed on
+ *     the host) with cross = c s' - s c' and c c' + s s' > 0, or after max_iterations steps.
+ *     `iterations` counts the steps taken.  The correspondences of the last step taken (made at the
+ *     estimate before it) are the final correspondences, as in csm; the pose is the estimate after
+ *     it.  Divergence: csm's loop detection is left out.
+ *  8. Scores (:334-392).  nvalid = the number of final correspondences, scan_valid = the valid beams
+ *     of `to`; deg_count walks the final correspondences in beam order with last = -1: +1 when j1 >
+ *     last, -1 when j1 < last.  deg_count <= 0: UZL_LASER_VIEWPOINT, score 0.  min_valid_fraction
+ *     scan_valid > nvalid: UZL_LASER_FEW_MATCHES, score 0.  Otherwise matching_score = nvalid.
+ *     error = sum (n_i . (w_i - q_i))^2 over the final correspondences with w at the final estimate.
+ *  9. Information (:357-376).  inf3 = the Gauss-Newton Hessian sum w_i J_i^T J_i of step 6's
+ *     residuals in (x, y, theta) at the final estimate over the final correspondences (J_i = (n_x,
+ *     n_y, a . (0, 0, -s, c))), scaled by goal_trace / trace.  The 6x6 is other_information I with
+ *     (0,0), (0,1), (1,0), (1,1) from inf3 and (5,5) = inf3(2,2).  Divergence: the reference inverts
+ *     csm's closed-form ICP covariance (do_compute_covariance), which is not in its tree; after the
+ *     rescale to a fixed trace only the SHAPE of the matrix survives, and for small residuals that
+ *     covariance is the inverse of this Hessian up to a factor, so the two agree.
+ * 10. Plausibility (:162-168), on the host from the returned numbers: diff = T_guess^-1 T;
+ *     1.5 |diff.t| > max_linear_correction or 1.5 angle_deg(diff) > max_angular_correction_deg:
+ *     UZL_LASER_TOO_FAR, score 0.
+ *  A status other than 0 is the first reason met in the order 5, 6, 8, 10.  Not here: the debug
+ *  match count and markers of :171-283, estimateScanEdge's neighbour choice (uzl_radius_* and
+ *  scan_center serve it) and the merge re-queue of newCloudEdgeCallback.
+ *
+ *  Device side: one 256-thread workgroup per pair and the whole ICP inside one kernel.  `from`'s
+ *  points live in LDS (invalid beams as NaN); lanes own strips of `to` beams and read `from` at a
+ *  wave-uniform address; doubles are a 64-bit integer min per j1 in LDS on the distance's bit
+ *  pattern; the trim's order statistics are a rank count in LDS.  At 4096 beams a workgroup uses
+ *  144.5 KiB of the 160 KiB of LDS, at 720 beams 25.8 KiB.
+ * ====================================================================================== */
+typedef struct uzl_laser uzl_laser;
+typedef struct uzl_laser_cfg {
+    int32_t max_iterations;             /* 10     laser_transformation_estimator.cpp:35-124                     */
+    int32_t device;
+    double  epsilon_xy;                 /* 0.01   [m]                                                           */
+    double  epsilon_theta;              /* 0.02   [rad]                                                         */
+    double  max_correspondence_dist;    /* 0.3    [m]                                                           */
+    double  outliers_max_perc;          /* 0.80                                                                 */
+    double  outliers_adaptive_order;    /* 0.7                                                                  */
+    double  outliers_adaptive_mult;     /* 2.0                                                                  */
+    double  max_angular_correction_deg; /* 45                                                                   */
+    double  max_linear_correction;      /* 1.5    [m]                                                           */
+    double  min_valid_fraction;         /* 0.25   :383                                                          */
+    double  fail_fraction;              /* 0.05   step 5                                                        */
+    double  goal_trace;                 /* 10000  :364                                                          */
+    double  other_information;          /* 100    :371                                                          */
+} uzl_laser_cfg;
+typedef struct uzl_laser_scan {
+    const float* values;          /* n_beams readings, borrowed for the call: LaserScan.intensities (farthest, the reference's
+                                   * default) or .ranges (do_near_), as laserScanToLDP :400-443 chooses                       */
+    int32_t n_beams;              /* 8..4096                                                                                  */
+    float   angle_min, angle_increment, range_min, range_max;
+    int32_t _pad;
+} uzl_laser_scan;
+typedef struct uzl_laser_pair {
+    int32_t scan_from, scan_to;   /* indices into the handle's store                                                         */
+    double  first_guess[12];      /* T_diff of :148-152, composed by the caller, 3x4 row-major: x0 = (T[0][3], T[1][3],
+                                   * atan2(T[1][0], T[0][0])), :325-327                                                       */
+} uzl_laser_pair;
+#define UZL_LASER_OK          0
+#define UZL_LASER_FEW_CORR    1   /* step 5  */
+#define UZL_LASER_VIEWPOINT   2   /* step 8  */
+#define UZL_LASER_FEW_MATCHES 3   /* step 8  */
+#define UZL_LASER_TOO_FAR     4   /* step 10 */
+#define UZL_LASER_DEGENERATE  5   /* step 6  */
+typedef struct uzl_laser_edge {
+    int32_t status;               /* UZL_LASER_*                                                                             */
+    int32_t nvalid, scan_valid, deg_count, iterations, _pad;
+    double  matching_score;       /* nvalid, or 0 when status != 0                                                           */
+    double  error;                /* sum of squared point-to-line distances over the final correspondences                  */
+    double  transform[12];        /* Translation(x, y, 0) * RotZ(theta), :378-380, 3x4 row-major                             */
+    double  information[36];      /* step 9, row-major 6x6                                                                   */
+} uzl_laser_edge;
+void uzl_laser_cfg_default(uzl_laser_cfg* cfg);
+/* UZL_ERR_BAD_ARG for a NaN or negative threshold, a fraction outside [0, 1] or max_iterations < 1 (before the device is looked
+ * for); UZL_ERR_NO_DEVICE without a GPU (no CPU fallback) */
+int  uzl_laser_create(const uzl_laser_cfg* cfg, uzl_laser** out);
+void uzl_laser_destroy(uzl_laser* h);
+const char* uzl_laser_last_error(uzl_laser* h);
+/* Same checks as create; takes effect at the next estimate. */
+int  uzl_laser_set_config(uzl_laser* h, const uzl_laser_cfg* cfg);
+/* Append scans to the handle's append-only device store; *first_scan (may be NULL) = index of the first one.  UZL_ERR_BAD_ARG
+ * (nothing stored) for n < 0, a NULL array, n_beams outside 8..4096, NULL values, a non-finite angle_min / angle_increment /
+ * range_max, or range_min negative or NaN. */
+int  uzl_laser_add_scans(uzl_laser* h, int32_t n, const uzl_laser_scan* scans, int32_t* first_scan);
+int  uzl_laser_scan_count(uzl_laser* h);
+/* Device-to-device append of a laser-line handle's resident scans: their intensities, or their ranges when use_near != 0, with
+ * the angular grid and (range_min, range_max) = ((float)range_min, (float)range_max) they were extracted with.  The store then
+ * holds, bit for bit, what uzl_laserline_read -> uzl_laser_add_scans would have put there.  UZL_ERR_BAD_ARG for a NULL laser
+ * handle or handles on different devices; UZL_ERR_STATE before any extract.  Locks the laser-line handle, then the laser handle. */
+int  uzl_laserline_to_laser(uzl_laserline* h, uzl_laser* laser, int32_t use_near, int32_t* first_scan);
+/* Steps 1-10 for n_pairs pairs in one launch; results[i] belongs to pairs[i] and does not depend on the other pairs.
+ * UZL_ERR_BAD_ARG, handle unchanged, for n_pairs < 0, NULL arrays with pairs to solve, a scan index outside the store or a
+ * non-finite first guess.  n_pairs = 0 is valid. */
+int  uzl_laser_estimate(uzl_laser* h, int32_t n_pairs, const uzl_laser_pair* pairs, uzl_laser_edge* results);
+/* Stage entry: steps 2-4 evaluated once for one pair at the estimate x = (tx, ty, theta) (the pair's first_guess is checked but
+ * not used).  Per beam of `to` (any output may be NULL): j1, j2 of step 2 (-1: none), valid = 1 iff the correspondence is left
+ * after step 4, dist = d_i of step 4 for a correspondence left after step 3, else 0.  Returns n_beams(to); errors as estimate. */
+int  uzl_laser_correspondences(uzl_laser* h, const uzl_laser_pair* pair, const double* x, int32_t* j1, int32_t* j2, int32_t* valid,
+                               double* dist);
+
+/* ======================================================================================
  *  Wire and disk formats  
  *
  *  The data formats either side of the path: graph_slam_msgs/{Edge,Node,SensorData,Features,

@@ -225,6 +225,34 @@ class DepthImage(C.Structure):
                 ("camera_transform", C.c_double * 12), ("group", C.c_int32), ("_pad", C.c_int32)]
 
 
+class LaserCfg(C.Structure):
+    _fields_ = [("max_iterations", C.c_int32), ("device", C.c_int32), ("epsilon_xy", C.c_double), ("epsilon_theta", C.c_double),
+                ("max_correspondence_dist", C.c_double), ("outliers_max_perc", C.c_double), ("outliers_adaptive_order", C.c_double),
+                ("outliers_adaptive_mult", C.c_double), ("max_angular_correction_deg", C.c_double), ("max_linear_correction", C.c_double),
+                ("min_valid_fraction", C.c_double), ("fail_fraction", C.c_double), ("goal_trace", C.c_double),
+                ("other_information", C.c_double)]
+
+
+class LaserScanIn(C.Structure):
+    _fields_ = [("values", C.POINTER(C.c_float)), ("n_beams", C.c_int32), ("angle_min", C.c_float), ("angle_increment", C.c_float),
+                ("range_min", C.c_float), ("range_max", C.c_float), ("_pad", C.c_int32)]
+
+
+class LaserPair(C.Structure):
+    _fields_ = [("scan_from", C.c_int32), ("scan_to", C.c_int32), ("first_guess", C.c_double * 12)]
+
+
+class LaserEdge(C.Structure):
+    _fields_ = [("status", C.c_int32), ("nvalid", C.c_int32), ("scan_valid", C.c_int32), ("deg_count", C.c_int32),
+                ("iterations", C.c_int32), ("_pad", C.c_int32), ("matching_score", C.c_double), ("error", C.c_double),
+                ("transform", C.c_double * 12), ("information", C.c_double * 36)]
+
+
+LASER_OK, LASER_FEW_CORR, LASER_VIEWPOINT, LASER_FEW_MATCHES, LASER_TOO_FAR, LASER_DEGENERATE = range(6)
+LASER_EDGE_DTYPE = np.dtype([("status", "<i4"), ("nvalid", "<i4"), ("scan_valid", "<i4"), ("deg_count", "<i4"), ("iterations", "<i4"),
+                             ("_pad", "<i4"), ("matching_score", "<f8"), ("error", "<f8"), ("transform", "<f8", (12,)),
+                             ("information", "<f8", (36,))])
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
 
 _lib = None
@@ -250,7 +278,7 @@ def lib():
 
 
 _HANDLES = ("uzl_match", "uzl_pgo", "uzl_pgo_batch", "uzl_filter", "uzl_gate", "uzl_radius", "uzl_places", "uzl_gist")
-_MORE_HANDLES = ("uzl_grid", "uzl_laserline", "uzl_gfr")       # declared like _HANDLES; kept apart because tests pin _HANDLES to the first eight
+_MORE_HANDLES = ("uzl_grid", "uzl_laserline", "uzl_gfr", "uzl_laser")      # declared like _HANDLES; kept apart because tests pin _HANDLES to the first eight
 
 
 def _declare(L):
@@ -264,7 +292,7 @@ def _declare(L):
         if hasattr(L, p + "_cfg_default"):          # (a batch takes uzl_pgo_cfg)
             getattr(L, p + "_cfg_default").restype = None
     for f in ("uzl_places_count", "uzl_gist_count", "uzl_grid_scan_count", "uzl_gate_edge_count", "uzl_filter_cluster_count",
-              "uzl_gfr_count", "uzl_gfr_feature_count", "uzl_gfr_link_count"):
+              "uzl_gfr_count", "uzl_gfr_feature_count", "uzl_gfr_link_count", "uzl_laser_scan_count"):
         getattr(L, f).argtypes = [C.c_void_p]
     L.uzl_pgo_batch_graph.restype = C.c_void_p
     L.uzl_pgo_batch_graph.argtypes = [C.c_void_p, C.c_int32]
@@ -1337,3 +1365,70 @@ class Laserline(_Handle):
         first = C.c_int32(-1)
         self._check(lib().uzl_laserline_to_grid(self._h, grid._h, _p(nd, c_i32p) if len(nd) else None, C.byref(first)))
         return first.value
+
+    def to_laser(self, laser, use_near=False):
+        """append the resident scans (intensities, or ranges with use_near) to a Laser's store on the device -> index of the first"""
+        first = C.c_int32(-1)
+        self._check(lib().uzl_laserline_to_laser(self._h, laser._h, C.c_int32(1 if use_near else 0), C.byref(first)))
+        return first.value
+
+
+class Laser(_Handle):
+    """uzl_laser_* (LaserTransformationEstimator, transformation_estimation/src/laser_transformation_estimator.cpp:134-443): stored
+    laser scans aligned pair by pair with point-to-line ICP into TYPE_2D_LASER edges, all pairs of a call in one launch."""
+
+    _prefix, _cfg_type = "uzl_laser", LaserCfg
+    set_config = _Handle._set_config
+
+    @staticmethod
+    def pack_scans(scans):
+        """scans: dicts with values (f32: intensities, or ranges for do_near_), angle_min, angle_increment, range_min, range_max
+        -> (LaserScanIn array, the values it points into)"""
+        arr = (LaserScanIn * max(len(scans), 1))()
+        keep = []
+        for i, s in enumerate(scans):
+            v = np.ascontiguousarray(s["values"], np.float32).reshape(-1)
+            keep.append(v)
+            g = arr[i]
+            g.n_beams = len(v)
+            g.angle_min = float(s["angle_min"]); g.angle_increment = float(s["angle_increment"])
+            g.range_min = float(s["range_min"]); g.range_max = float(s["range_max"])
+            g.values = v.ctypes.data_as(C.POINTER(C.c_float)) if len(v) else None
+        return arr, keep
+
+    def add_scans(self, scans):
+        """-> index of the first scan added"""
+        arr, keep = self.pack_scans(scans)
+        first = C.c_int32(-1)
+        self._check(lib().uzl_laser_add_scans(self._h, C.c_int32(len(scans)), arr, C.byref(first)))
+        return first.value
+
+    def scan_count(self):
+        return self._check(lib().uzl_laser_scan_count(self._h))
+
+    @staticmethod
+    def pack_pairs(pairs):
+        """pairs: (scan_from, scan_to, first_guess as 12 or 3x4) -> LaserPair array"""
+        arr = (LaserPair * max(len(pairs), 1))()
+        for i, (f, t, guess) in enumerate(pairs):
+            arr[i].scan_from = int(f); arr[i].scan_to = int(t)
+            arr[i].first_guess[:] = np.asarray(guess, np.float64).reshape(12).tolist()
+        return arr
+
+    def estimate(self, pairs):
+        """-> one LASER_EDGE_DTYPE record per pair.  pairs: a list of (scan_from, scan_to, first_guess), or what pack_pairs made of one"""
+        arr = pairs if isinstance(pairs, C.Array) else self.pack_pairs(pairs)
+        n = len(pairs) if not isinstance(pairs, C.Array) else len(arr)
+        out = np.zeros(max(n, 1), LASER_EDGE_DTYPE)
+        self._check(lib().uzl_laser_estimate(self._h, C.c_int32(n), arr, out.ctypes.data_as(C.POINTER(LaserEdge))))
+        return out[:n]
+
+    def correspondences(self, scan_from, scan_to, x, n_beams):
+        """steps 2-4 once at x = (tx, ty, theta) -> (j1, j2, valid: int32; dist: float64), one entry per beam of scan_to"""
+        pair = self.pack_pairs([(scan_from, scan_to, np.eye(3, 4))])
+        xx = (C.c_double * 3)(*[float(v) for v in x])
+        j1 = np.zeros(n_beams, np.int32); j2 = np.zeros(n_beams, np.int32); valid = np.zeros(n_beams, np.int32)
+        dist = np.zeros(n_beams, np.float64)
+        n = self._check(lib().uzl_laser_correspondences(self._h, pair, xx, _p(j1, c_i32p), _p(j2, c_i32p), _p(valid, c_i32p), _p(dist, c_f64p)))
+        assert n == n_beams, (n, n_beams)
+        return j1, j2, valid, dist

@@ -6,6 +6,7 @@
 // chunk's image records in front of its pixels so that a chunk is one copy; the per-image bins (min s / max s, u32) and the scans
 // stay in HBM, and uzl_laserline_to_grid hands the scans to a grid handle's store without leaving the device.
 #include "grid_types.hpp"
+#include "laser_types.hpp"
 #include "laserline_types.hpp"
 #include "uzl_common.hpp"
 #include "uzl_streams.hpp"
@@ -41,7 +42,7 @@ struct uzl_laserline : HandleBase {
     bool have = false;
     int32_t n_scans = 0;
     LaserGrid grid{};
-    float lo = 0.f;
+    float lo = 0.f, hi0 = 0.f;
     DevBuf<float> d_ranges, d_intensities;
     DevBuf<double> d_centers;
     // work
@@ -291,6 +292,7 @@ int uzl_laserline_extract(uzl_laserline* h, int32_t n_images, const uzl_depth_im
     h->n_scans = ns;
     h->grid = g;
     h->lo = (float)h->cfg.range_min;
+    h->hi0 = (float)h->cfg.range_max;
     h->have = true;
     if (n_scans) *n_scans = ns;
     if (n_beams) *n_beams = g.n;
@@ -324,6 +326,19 @@ int uzl_laserline_to_grid(uzl_laserline* h, uzl_grid* grid, const int32_t* nodes
     const int rc = grid_append_device(grid, h->cfg.device, h->n_scans, h->grid.n, h->d_ranges.p, h->grid.amin, h->grid.inc, h->lo,
                                       nodes, first_scan);
     if (rc != UZL_OK) return fail(h, rc, "the grid handle refused the scans (see its last_error)");
+    return UZL_OK;
+    UZL_GUARD_END(h)
+}
+
+int uzl_laserline_to_laser(uzl_laserline* h, uzl_laser* laser, int32_t use_near, int32_t* first_scan)
+{
+    UZL_GUARD_BEGIN(h)
+    if (!laser) return fail(h, UZL_ERR_BAD_ARG, "null laser handle");
+    if (!h->have) return fail(h, UZL_ERR_STATE, "no extract yet");
+    // the scans are complete (extract synchronises); the laser handle's lock is taken inside, after this handle's
+    const int rc = laser_append_device(laser, h->cfg.device, h->n_scans, h->grid.n, use_near ? h->d_ranges.p : h->d_intensities.p,
+                                       h->grid.amin, h->grid.inc, h->lo, h->hi0, first_scan);
+    if (rc != UZL_OK) return fail(h, rc, "the laser handle refused the scans (see its last_error)");
     return UZL_OK;
     UZL_GUARD_END(h)
 }
