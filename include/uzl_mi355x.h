@@ -1267,6 +1267,116 @@ int  uzl_laser_correspondences(uzl_laser* h, const uzl_laser_pair* pair, const d
                                double* dist);
 
 /* ======================================================================================
+ *  Depth refinement and 3-D keypoint lifting: the depth image the front end stores and reads
+ *
+ *  feature_extraction_service_node.cpp:120-149 scales the depth image and, with use_bilateral_filter
+ *  (FeatureExtraction.cfg:13, default True), refines it: jointBilateralFilter(depth, grey, Size(7,7),
+ *  5.0, 3.0, BILATERAL_SEPARABLE) then jointNearestFilter(filtered, depth, Size(5,5))
+ *  (external/DepthMapRefinement/jointBilateralFilter.cpp, jointNearest.cpp).  The refined image is
+ *  SensorData.depth_image, what extractImageLaserLine bins (:253) and what
+ *  FeatureExtractionCore::extract3dFeatures (feature_extraction_core.cpp:254-295) lifts the keypoints
+ *  with (:189).  Every step below is evaluated in the order written with no fused multiply-add, in
+ *  f32 unless stated, / correctly rounded; the results equal a NumPy restatement
+ *  (tests/depthfilter_reference.py) bit for bit.
+ *
+ *  1. Depth of a pixel: step 2 of the laser line's contract.  32FC1: d = the f32.  16UC1:
+ *     d = (float)((double)v * 0.001).  Then, if depth_scale != 1, d = (float)((double)d *
+ *     depth_scale).  Divergence: the reference scales through OpenCV's MatExpr (`0.001 * depth_img`,
+ *     `depth_img *= depth_scale`, :127-131), whose rounding is not in the reference tree; this is the
+ *     laser line's rule, so both handles see one image.  The guide is a mono8 image of the depth
+ *     image's width and height (a different size: UZL_ERR_BAD_ARG); g below is its value as an
+ *     integer 0..255.
+ *  2. Tables, made on the HOST with the host's libm and uploaded (the table rule of the occupancy
+ *     grid and the laser line): cw[i] = (float)exp((double)(i i) * (-0.5 / (sigma_color
+ *     sigma_color))) for i = 0..255; sw[k] = (float)exp(r r * (-0.5 / (sigma_space sigma_space)))
+ *     with r = (double)|k| for k = -R..R (jointBilateralFilter.cpp:2902-2930; R = radius).  A sigma
+ *     <= 0 becomes 1 (:2902-2905).  Defaults R = 3, sigma_space = 3.0, sigma_color = 5.0, nearest
+ *     radius P = 2 (feature_extraction_service_node.cpp:134-140).  Divergence: the reference sizes
+ *     its colour table cvRound(max - min) of the guide and reads one element past it when a window
+ *     spans the guide's full range; here the table always has 256 entries.
+ *  3. Horizontal pass (jointBilateralFilter_32f with Size(2R+1, 1), cn = cng = 1, the SSE loop at
+ *     :1586-1612).  For pixel (y, x) the taps run k = -R..R in that order over columns
+ *     clamp(x + k, 0, width - 1) (BORDER_REPLICATE) with v the step-1 depth there:
+ *     w = sw[k] * cw[|g(y, x+k) - g(y, x)|];  t = t + w * v (product rounded, then the sum);
+ *     ws = ws + w;  t and ws start at 0.  One further tap follows with w = 0.0f * cw[0] and v the
+ *     centre pixel (the reference's loop runs k <= maxk over a zero-initialised weight and offset):
+ *     it turns an infinite centre into NaN and changes nothing else.  Output t / ws.  No test for 0,
+ *     NaN or range: an invalid 0 is averaged in and a NaN poisons its window, as in the reference.
+ *  4. Vertical pass: step 3 over rows clamp(y + k, 0, height - 1) (Size(1, 2R+1)), its source the
+ *     output of step 3, its guide unchanged.
+ *  5. Snap to an original value (jointNearestFilter_32f, jointNearest.cpp:58-114).  before = the
+ *     step-1 image addressed with BORDER_REFLECT_101 (-1 -> 1, n -> n - 2, repeated while outside; a
+ *     dimension of 1 maps everything to 0).  The taps (i, j) run i = -P..P, then j = -P..P, with
+ *     sqrt(i i + j j) <= P (13 taps for P = 2), in that order: a = |before(y+i, x+j) -
+ *     filtered(y, x)|; minv starts at FLT_MAX and out at 0.0f; if a < minv then minv = a and out =
+ *     before(y+i, x+j).  NaN and infinity never win, so a non-finite filtered pixel becomes 0, the
+ *     invalid value, and every output is 0 or one of the disc's original values.
+ *  6. With use_bilateral_filter = 0 the resident image is the step-1 image.
+ *  7. Lift (extract3dFeatures, feature_extraction_core.cpp:254-295): u, v int32 (Feature.msg),
+ *     clamped to the image; d = (double)image(v, u); valid iff d != 0 && !isnan(d) && (max_depth == 0
+ *     || d <= max_depth).  Valid: z = d, x = (((double)u - cx) * d) / fx, y = (((double)v - cy) * d)
+ *     / fy in f64 with the clamped u, v.  Invalid: (0, 0, -1).  pos_xyz is 3 x n column-major f64 and
+ *     valid3d n x u8 in the caller's order, the layout uzl_frame takes (the reference emits the list
+ *     reversed: INTEGRATION.md).
+ *
+ *  Device side: one fused kernel, one 256-thread workgroup per 64 x 32 output tile and image
+ *  (gridDim.z = image, so many small images share one launch): the depth tile with its halo
+ *  (replicate-clamped) and the guide tile go to LDS, the horizontal pass runs over the tile's rows
+ *  plus halo into LDS, the vertical pass and the snap in registers, the snap reading the depth tile
+ *  already in LDS at reflect-101 indices.  Each image is read once and written once.  A pixel's
+ *  value depends only on its own fixed tap order: not on tile size, batching or schedule.
+ * ====================================================================================== */
+typedef struct uzl_depthfilter uzl_depthfilter;
+typedef struct uzl_depthfilter_cfg {
+    int32_t radius;               /* 3     R, feature_extraction_service_node.cpp:134                              */
+    int32_t nearest_radius;       /* 2     P, :137                                                                  */
+    double  sigma_space;          /* 3.0   :138                                                                     */
+    double  sigma_color;          /* 5.0   :139                                                                     */
+    double  depth_scale;          /* 1.0   FeatureExtraction.cfg "depth_scale"                                      */
+    int32_t use_bilateral_filter; /* 1     FeatureExtraction.cfg:13 "use_bilateral_filter"                          */
+    int32_t device;
+} uzl_depthfilter_cfg;
+typedef struct uzl_guide_image {
+    const void* data;             /* mono8, borrowed for the call                                                  */
+    int32_t width, height, step, _pad;   /* step = bytes per row                                                   */
+} uzl_guide_image;
+void uzl_depthfilter_cfg_default(uzl_depthfilter_cfg* cfg);
+/* UZL_ERR_BAD_ARG for radius outside [0, 15], nearest_radius outside [0, 7], a NaN sigma or depth_scale, or depth_scale <= 0
+ * (before the device is looked for); UZL_ERR_NO_DEVICE without a GPU (no CPU fallback) */
+int  uzl_depthfilter_create(const uzl_depthfilter_cfg* cfg, uzl_depthfilter** out);
+void uzl_depthfilter_destroy(uzl_depthfilter* h);
+const char* uzl_depthfilter_last_error(uzl_depthfilter* h);
+/* Same checks as create; takes effect at the next refine (the resident images stay as they are). */
+int  uzl_depthfilter_set_config(uzl_depthfilter* h, const uzl_depthfilter_cfg* cfg);
+/* Steps 1-6 over n_images images; replaces the handle's resident set with compact f32 images in HBM, each kept with its depth
+ * image's intrinsics, transform and group.  guides may be NULL when use_bilateral_filter = 0.  UZL_ERR_BAD_ARG, resident set
+ * unchanged, for what uzl_laserline_extract refuses in its images (n_images < 0, a NULL array, an image that is neither
+ * width, height > 0 with data nor 0 x 0 with NULL data, step smaller than a row, height * step beyond 2^31 bytes, an unknown
+ * encoding, a non-finite or zero fx / fy, a non-finite cx / cy / transform entry, groups not ascending and contiguous), a
+ * NULL guide array with the filter on, a guide whose width or height differs from its depth image's, whose data is NULL for a
+ * non-empty image, whose step is smaller than its width or whose height * step is beyond 2^31 bytes.  n_images = 0 and 0 x 0
+ * images are valid. */
+int  uzl_depthfilter_refine(uzl_depthfilter* h, int32_t n_images, const uzl_depth_image* images, const uzl_guide_image* guides);
+/* Number of resident images; UZL_ERR_STATE before any refine. */
+int  uzl_depthfilter_image_count(uzl_depthfilter* h);
+/* Resident image `image` as width * height f32, row-major, the reference's stored depth image (uzl_wire_depth_sensor_encode takes
+ * it as 32FC1), with the width and height given to refine.  Returns the number of pixels; out = NULL only asks for that number.
+ * UZL_ERR_BAD_ARG for an image outside the set or a negative cap_pixels, UZL_ERR_TRUNCATED when out is given and cap_pixels is
+ * smaller, UZL_ERR_STATE before any refine. */
+int  uzl_depthfilter_read(uzl_depthfilter* h, int32_t image, float* out, int64_t cap_pixels);
+/* Step 7 for n keypoints of resident image `image` with that image's fx, fy, cx, cy.  UZL_ERR_BAD_ARG for an image outside the
+ * set, n < 0, NULL arrays with n > 0, a NaN or negative max_depth, or a 0 x 0 image with n > 0; UZL_ERR_STATE before any
+ * refine.  n = 0 is valid. */
+int  uzl_depthfilter_lift(uzl_depthfilter* h, int32_t image, int32_t n, const int32_t* u, const int32_t* v, double max_depth,
+                          double* pos_xyz, uint8_t* valid3d);
+/* The laser-line handle runs its steps 1-9 over the resident images where they lie (their intrinsics, transforms and groups as
+ * given to refine) and keeps the scans as after an extract: the result equals, bit for bit, uzl_laserline_extract on the images
+ * uzl_depthfilter_read returns.  *n_scans, *n_beams as there.  UZL_ERR_BAD_ARG for a NULL laser-line handle, one whose
+ * depth_scale is not 1 (the scale was applied in step 1) or one on another device; UZL_ERR_STATE before any refine.  Locks the
+ * filter handle, then the laser-line handle. */
+int  uzl_depthfilter_to_laserline(uzl_depthfilter* h, uzl_laserline* laserline, int32_t* n_scans, int32_t* n_beams);
+
+/* ======================================================================================
  *  Wire and disk formats  
  *
  *  The data formats either side of the path: graph_slam_msgs/{Edge,Node,SensorData,Features,

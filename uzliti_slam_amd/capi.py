@@ -225,6 +225,15 @@ class DepthImage(C.Structure):
                 ("camera_transform", C.c_double * 12), ("group", C.c_int32), ("_pad", C.c_int32)]
 
 
+class DepthFilterCfg(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("nearest_radius", C.c_int32), ("sigma_space", C.c_double), ("sigma_color", C.c_double),
+                ("depth_scale", C.c_double), ("use_bilateral_filter", C.c_int32), ("device", C.c_int32)]
+
+
+class GuideImage(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("step", C.c_int32), ("_pad", C.c_int32)]
+
+
 class LaserCfg(C.Structure):
     _fields_ = [("max_iterations", C.c_int32), ("device", C.c_int32), ("epsilon_xy", C.c_double), ("epsilon_theta", C.c_double),
                 ("max_correspondence_dist", C.c_double), ("outliers_max_perc", C.c_double), ("outliers_adaptive_order", C.c_double),
@@ -278,7 +287,7 @@ def lib():
 
 
 _HANDLES = ("uzl_match", "uzl_pgo", "uzl_pgo_batch", "uzl_filter", "uzl_gate", "uzl_radius", "uzl_places", "uzl_gist")
-_MORE_HANDLES = ("uzl_grid", "uzl_laserline", "uzl_gfr", "uzl_laser")      # declared like _HANDLES; kept apart because tests pin _HANDLES to the first eight
+_MORE_HANDLES = ("uzl_grid", "uzl_laserline", "uzl_gfr", "uzl_laser", "uzl_depthfilter")      # declared like _HANDLES; kept apart because tests pin _HANDLES to the first eight
 
 
 def _declare(L):
@@ -292,7 +301,7 @@ def _declare(L):
         if hasattr(L, p + "_cfg_default"):          # (a batch takes uzl_pgo_cfg)
             getattr(L, p + "_cfg_default").restype = None
     for f in ("uzl_places_count", "uzl_gist_count", "uzl_grid_scan_count", "uzl_gate_edge_count", "uzl_filter_cluster_count",
-              "uzl_gfr_count", "uzl_gfr_feature_count", "uzl_gfr_link_count", "uzl_laser_scan_count"):
+              "uzl_gfr_count", "uzl_gfr_feature_count", "uzl_gfr_link_count", "uzl_laser_scan_count", "uzl_depthfilter_image_count"):
         getattr(L, f).argtypes = [C.c_void_p]
     L.uzl_pgo_batch_graph.restype = C.c_void_p
     L.uzl_pgo_batch_graph.argtypes = [C.c_void_p, C.c_int32]
@@ -1371,6 +1380,71 @@ class Laserline(_Handle):
         first = C.c_int32(-1)
         self._check(lib().uzl_laserline_to_laser(self._h, laser._h, C.c_int32(1 if use_near else 0), C.byref(first)))
         return first.value
+
+
+class DepthFilter(_Handle):
+    """uzl_depthfilter_* (feature_extraction_service_node.cpp:120-149: depth scaling, jointBilateralFilter, jointNearestFilter;
+    FeatureExtractionCore::extract3dFeatures, feature_extraction_core.cpp:254-295): depth images refined against their grey images
+    into the images the front end stores, bins into laser scans and lifts its keypoints with; they stay on the device."""
+
+    _prefix, _cfg_type = "uzl_depthfilter", DepthFilterCfg
+    set_config = _Handle._set_config
+
+    @staticmethod
+    def pack_guides(guides):
+        """guides: 2-D uint8 arrays (rows may be strided) -> (GuideImage array, the pixel arrays it points into)"""
+        arr = (GuideImage * max(len(guides), 1))()
+        keep = []
+        for i, g in enumerate(guides):
+            g = np.asarray(g)
+            if g.ndim != 2 or g.dtype != np.uint8:
+                raise ValueError("a guide image is a 2-D uint8 array")
+            if g.size and (g.strides[1] != 1 or g.strides[0] < g.shape[1]):
+                g = np.ascontiguousarray(g)
+            keep.append(g)
+            if g.size:
+                arr[i].data = g.ctypes.data; arr[i].height, arr[i].width = g.shape; arr[i].step = g.strides[0]
+        return arr, keep
+
+    _sizes = ()                       # (height, width) of the resident images
+
+    def refine(self, images, guides=None):
+        """images: what Laserline.pack_images takes (the intrinsics, transform and group stay with the refined image); guides: one
+        2-D uint8 array per image (None only with use_bilateral_filter = 0).  The refined images stay on the device."""
+        arr, keep = Laserline.pack_images(images)
+        garr, gkeep = self.pack_guides(guides) if guides is not None else (None, None)
+        if guides is not None and len(gkeep) != len(keep):
+            raise ValueError("one guide per depth image")
+        self._check(lib().uzl_depthfilter_refine(self._h, C.c_int32(len(keep)), arr, garr))
+        self._sizes = tuple(d.shape for d in keep)
+
+    def image_count(self):
+        return self._check(lib().uzl_depthfilter_image_count(self._h))
+
+    def read(self, image):
+        """resident image `image` -> float32 (height, width)"""
+        h, w = self._sizes[image]
+        out = np.zeros((h, w), np.float32)
+        n = self._check(lib().uzl_depthfilter_read(self._h, C.c_int32(image), _p(out, C.POINTER(C.c_float)), C.c_int64(out.size)))
+        assert n == out.size, (n, out.shape)
+        return out
+
+    def lift(self, image, u, v, max_depth=0.0):
+        """keypoints (u, v: int32) on resident image `image` -> (pos (3, n) float64, valid (n) uint8), as Match.add_frame takes them"""
+        u = np.ascontiguousarray(u, np.int32).reshape(-1); v = np.ascontiguousarray(v, np.int32).reshape(-1)
+        if len(u) != len(v):
+            raise ValueError("u and v differ in length")
+        pos = np.zeros((len(u), 3), np.float64); valid = np.zeros(len(u), np.uint8)
+        self._check(lib().uzl_depthfilter_lift(self._h, C.c_int32(image), C.c_int32(len(u)), _p(u, c_i32p), _p(v, c_i32p),
+                                               C.c_double(max_depth), _p(pos, c_f64p), _p(valid, c_u8p)))
+        return pos.T, valid
+
+    def to_laserline(self, laserline):
+        """the laser-line handle extracts from the resident images on the device -> what Laserline.extract returns"""
+        ns, nb = C.c_int32(0), C.c_int32(0)
+        self._check(lib().uzl_depthfilter_to_laserline(self._h, laserline._h, C.byref(ns), C.byref(nb)))
+        laserline._shape = (ns.value, nb.value)
+        return laserline.read()
 
 
 class Laser(_Handle):

@@ -52,4 +52,18 @@ void laser_prepare();             // on the current device: allows the bin kerne
 void launch_laser_bin(const LaserBinArgs& a, int max_bands, int n_images, hipStream_t s);
 void launch_laser_finish(const LaserFinishArgs& a, int n_groups, hipStream_t s);
 
+struct HandleBase;
+// What uzl_laserline_extract refuses in its images (the header names the set); the message goes to h.  Shared with uzl_depthfilter_refine.
+int depth_images_check(HandleBase* h, int32_t n, const uzl_depth_image* images);
+// bytes of an image from its first to its last pixel
+size_t depth_image_bytes(const uzl_depth_image& im);
+
+// Steps 1-9 of the laser-line handle over n_images f32 images that already lie on its device (uzl_depthfilter_to_laserline):
+// recs[i] has data_off = the byte offset of image i in d_pixels (16-byte aligned), step = 4 * width, encoding f32, the intrinsics
+// and T; lanes and out are filled in here.  groups[i] as uzl_depth_image.group, already checked.  Takes the handle's lock; the
+// handle's depth_scale must be 1 and its device `device` (else UZL_ERR_BAD_ARG).  The result is the handle's resident result,
+// as after an extract of the same images from the host.
+int laserline_extract_device(uzl_laserline* h, int device, int32_t n_images, LaserImageRec* recs, const int32_t* groups,
+                             const uint8_t* d_pixels, int32_t* n_scans, int32_t* n_beams);
+
 }  // namespace uzl

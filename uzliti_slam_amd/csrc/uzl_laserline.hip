@@ -79,14 +79,15 @@ size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
 int bytes_per_pixel(int32_t encoding) { return encoding == UZL_DEPTH_F32_M ? 4 : 2; }
 
-// bytes of an image from its first to its last pixel
-size_t image_bytes(const uzl_depth_image& im)
+}  // namespace
+
+size_t uzl::depth_image_bytes(const uzl_depth_image& im)
 {
     if (im.height <= 0) return 0;
     return (size_t)(im.height - 1) * (size_t)im.step + (size_t)im.width * bytes_per_pixel(im.encoding);
 }
 
-int check_images(uzl_laserline* h, int32_t n, const uzl_depth_image* images)
+int uzl::depth_images_check(HandleBase* h, int32_t n, const uzl_depth_image* images)
 {
     if (n < 0 || (n > 0 && !images)) return fail(h, UZL_ERR_BAD_ARG, "bad image count or null images");
     for (int32_t i = 0; i < n; i++) {
@@ -105,6 +106,8 @@ int check_images(uzl_laserline* h, int32_t n, const uzl_depth_image* images)
     }
     return UZL_OK;
 }
+
+namespace {
 
 // Lanes across a row of nvec vectors: among 1..8 passes over the row, the split that keeps most of the workgroup's lanes busy
 // (kLaserBlock / lanes rows are walked side by side).
@@ -137,6 +140,23 @@ void upload_table(uzl_laserline* h, const LaserGrid& g)
     h->have_table = true;
 }
 
+// One launch of the bin kernel over `count` image records on the device, their pixels at d_pixels (`rows` rows in all).
+void launch_bin(uzl_laserline* h, const LaserImageRec* d_recs, const uint8_t* d_pixels, int32_t count, int64_t rows, int32_t max_height,
+                const LaserGrid& g)
+{
+    LaserBinArgs a;
+    a.pixels = d_pixels;
+    a.images = d_recs;
+    a.trig = h->d_trig.p;
+    a.smin = h->d_smin.p; a.smax = h->d_smax.p;
+    a.min_height = h->cfg.min_height; a.max_height = h->cfg.max_height; a.depth_scale = h->cfg.depth_scale;
+    a.amin = g.amin; a.inc = g.inc; a.n = g.n;
+    // bands: about 2,048 workgroups per chunk, 8 to 64 rows each (any split gives the same bins)
+    a.band_rows = (int32_t)std::min<int64_t>(std::max<int64_t>((rows + 2047) / 2048, 8), 64);
+    launch_laser_bin(a, (max_height + a.band_rows - 1) / a.band_rows, count, h->stream);
+    UZL_HIP(hipGetLastError());
+}
+
 // Images [i0, i1) through staging half `half`: records and pixels packed, one copy, one launch of the bin kernel.
 void run_chunk(uzl_laserline* h, const uzl_depth_image* images, int32_t i0, int32_t i1, int half, const LaserGrid& g)
 {
@@ -144,7 +164,7 @@ void run_chunk(uzl_laserline* h, const uzl_depth_image* images, int32_t i0, int3
     const size_t recs_bytes = align256((size_t)(i1 - i0) * sizeof(LaserImageRec));
     size_t total = recs_bytes;
     int64_t rows = 0;
-    for (int32_t i = i0; i < i1; i++) { total += align256(image_bytes(images[i])); rows += images[i].height; }
+    for (int32_t i = i0; i < i1; i++) { total += align256(depth_image_bytes(images[i])); rows += images[i].height; }
     UZL_HIP(hipEventSynchronize(h->copied[half]));         // the previous copy out of this half
     h->h_chunk[half].reserve(total);
     h->d_chunk[half].reserve(total);
@@ -161,24 +181,59 @@ void run_chunk(uzl_laserline* h, const uzl_depth_image* images, int32_t i0, int3
         r.out = i;
         r.fx = im.fx; r.fy = im.fy; r.cx = im.cx; r.cy = im.cy;
         for (int k = 0; k < 12; k++) r.T[k] = (float)im.camera_transform[k];
-        const size_t nb = image_bytes(im);
+        const size_t nb = depth_image_bytes(im);
         if (nb) memcpy(w + recs_bytes + off, im.data, nb);
         off += align256(nb);
         max_height = std::max(max_height, im.height);
     }
     UZL_HIP(hipMemcpyAsync(h->d_chunk[half].p, w, total, hipMemcpyHostToDevice, s));
     UZL_HIP(hipEventRecord(h->copied[half], s));
-    LaserBinArgs a;
-    a.pixels = h->d_chunk[half].p + recs_bytes;
-    a.images = reinterpret_cast<const LaserImageRec*>(h->d_chunk[half].p);
-    a.trig = h->d_trig.p;
-    a.smin = h->d_smin.p; a.smax = h->d_smax.p;
-    a.min_height = h->cfg.min_height; a.max_height = h->cfg.max_height; a.depth_scale = h->cfg.depth_scale;
-    a.amin = g.amin; a.inc = g.inc; a.n = g.n;
-    // bands: about 2,048 workgroups per chunk, 8 to 64 rows each (any split gives the same bins)
-    a.band_rows = (int32_t)std::min<int64_t>(std::max<int64_t>((rows + 2047) / 2048, 8), 64);
-    launch_laser_bin(a, (max_height + a.band_rows - 1) / a.band_rows, i1 - i0, s);
-    UZL_HIP(hipGetLastError());
+    launch_bin(h, reinterpret_cast<const LaserImageRec*>(h->d_chunk[half].p), h->d_chunk[half].p + recs_bytes, i1 - i0, rows, max_height, g);
+}
+
+// Steps 1-9 over n_images images, image i in group group_of(i): feed(grid) queues the bin launches of every image on the handle's
+// stream (from the host through the staging halves, or over pixels that already lie on the device); the rest is the same.
+template <typename GroupOf, typename Feed>
+void extract_with(uzl_laserline* h, int32_t n_images, GroupOf&& group_of, Feed&& feed, int32_t* n_scans, int32_t* n_beams)
+{
+    LaserGrid g;
+    angular_grid(h->cfg, &g);
+    std::vector<int32_t> first;                            // images first[s] .. first[s + 1] make scan s
+    for (int32_t i = 0; i < n_images; i++)
+        if (i == 0 || group_of(i) != group_of(i - 1)) first.push_back(i);
+    const int32_t ns = (int32_t)first.size();
+    first.push_back(n_images);
+    UZL_HIP(hipSetDevice(h->cfg.device));
+    hipStream_t s = h->stream;
+    h->have = false;                                       // a failure below leaves no half-made result behind
+    upload_table(h, g);
+    const size_t bins = (size_t)n_images * g.n, beams = (size_t)ns * g.n;
+    h->d_smin.reserve(std::max<size_t>(bins, 1)); h->d_smax.reserve(std::max<size_t>(bins, 1));
+    h->d_ranges.reserve(std::max<size_t>(beams, 1)); h->d_intensities.reserve(std::max<size_t>(beams, 1));
+    h->d_centers.reserve(std::max<size_t>(3 * (size_t)ns, 1));
+    h->d_first.reserve(first.size());
+    if (bins) {
+        UZL_HIP(hipMemsetD32Async((hipDeviceptr_t)h->d_smin.p, (int)kLaserInfBits, bins, s));
+        UZL_HIP(hipMemsetAsync(h->d_smax.p, 0, bins * 4, s));
+    }
+    feed(g);
+    if (ns) {
+        UZL_HIP(hipMemcpyAsync(h->d_first.p, first.data(), first.size() * 4, hipMemcpyHostToDevice, s));
+        LaserFinishArgs f;
+        f.smin = h->d_smin.p; f.smax = h->d_smax.p; f.group_first = h->d_first.p; f.trig = h->d_trig.p;
+        f.ranges = h->d_ranges.p; f.intensities = h->d_intensities.p; f.centers = h->d_centers.p;
+        f.lo = (float)h->cfg.range_min; f.hi0 = (float)h->cfg.range_max; f.n = g.n;
+        launch_laser_finish(f, ns, s);
+        UZL_HIP(hipGetLastError());
+    }
+    UZL_HIP(hipStreamSynchronize(s));                      // `first` and the caller's images are free again
+    h->n_scans = ns;
+    h->grid = g;
+    h->lo = (float)h->cfg.range_min;
+    h->hi0 = (float)h->cfg.range_max;
+    h->have = true;
+    if (n_scans) *n_scans = ns;
+    if (n_beams) *n_beams = g.n;
 }
 
 }  // namespace
@@ -244,58 +299,23 @@ int uzl_laserline_set_config(uzl_laserline* h, const uzl_laserline_cfg* cfg)
 int uzl_laserline_extract(uzl_laserline* h, int32_t n_images, const uzl_depth_image* images, int32_t* n_scans, int32_t* n_beams)
 {
     UZL_GUARD_BEGIN(h)
-    if (int rc = check_images(h, n_images, images)) return rc;
-    LaserGrid g;
-    angular_grid(h->cfg, &g);
-    std::vector<int32_t> first;                            // images first[s] .. first[s + 1] make scan s
-    for (int32_t i = 0; i < n_images; i++)
-        if (i == 0 || images[i].group != images[i - 1].group) first.push_back(i);
-    const int32_t ns = (int32_t)first.size();
-    first.push_back(n_images);
-    UZL_HIP(hipSetDevice(h->cfg.device));
-    hipStream_t s = h->stream;
-    h->have = false;                                       // a failure below leaves no half-made result behind
-    upload_table(h, g);
-    const size_t bins = (size_t)n_images * g.n, beams = (size_t)ns * g.n;
-    h->d_smin.reserve(std::max<size_t>(bins, 1)); h->d_smax.reserve(std::max<size_t>(bins, 1));
-    h->d_ranges.reserve(std::max<size_t>(beams, 1)); h->d_intensities.reserve(std::max<size_t>(beams, 1));
-    h->d_centers.reserve(std::max<size_t>(3 * (size_t)ns, 1));
-    h->d_first.reserve(first.size());
-    if (bins) {
-        UZL_HIP(hipMemsetD32Async((hipDeviceptr_t)h->d_smin.p, (int)kLaserInfBits, bins, s));
-        UZL_HIP(hipMemsetAsync(h->d_smax.p, 0, bins * 4, s));
-    }
-    int half = 0;
-    for (int32_t i0 = 0; i0 < n_images;) {
-        int32_t i1 = i0;
-        size_t bytes = 0;
-        while (i1 < n_images && i1 - i0 < kLaserChunkImages) {
-            const size_t nb = align256(image_bytes(images[i1]));
-            if (i1 > i0 && bytes + nb > kLaserChunkBytes) break;
-            bytes += nb;
-            i1++;
+    if (int rc = depth_images_check(h, n_images, images)) return rc;
+    extract_with(h, n_images, [&](int32_t i) { return images[i].group; }, [&](const LaserGrid& g) {
+        int half = 0;
+        for (int32_t i0 = 0; i0 < n_images;) {
+            int32_t i1 = i0;
+            size_t bytes = 0;
+            while (i1 < n_images && i1 - i0 < kLaserChunkImages) {
+                const size_t nb = align256(depth_image_bytes(images[i1]));
+                if (i1 > i0 && bytes + nb > kLaserChunkBytes) break;
+                bytes += nb;
+                i1++;
+            }
+            run_chunk(h, images, i0, i1, half, g);
+            half ^= 1;
+            i0 = i1;
         }
-        run_chunk(h, images, i0, i1, half, g);
-        half ^= 1;
-        i0 = i1;
-    }
-    if (ns) {
-        UZL_HIP(hipMemcpyAsync(h->d_first.p, first.data(), first.size() * 4, hipMemcpyHostToDevice, s));
-        LaserFinishArgs f;
-        f.smin = h->d_smin.p; f.smax = h->d_smax.p; f.group_first = h->d_first.p; f.trig = h->d_trig.p;
-        f.ranges = h->d_ranges.p; f.intensities = h->d_intensities.p; f.centers = h->d_centers.p;
-        f.lo = (float)h->cfg.range_min; f.hi0 = (float)h->cfg.range_max; f.n = g.n;
-        launch_laser_finish(f, ns, s);
-        UZL_HIP(hipGetLastError());
-    }
-    UZL_HIP(hipStreamSynchronize(s));                      // `first` and the caller's images are free again
-    h->n_scans = ns;
-    h->grid = g;
-    h->lo = (float)h->cfg.range_min;
-    h->hi0 = (float)h->cfg.range_max;
-    h->have = true;
-    if (n_scans) *n_scans = ns;
-    if (n_beams) *n_beams = g.n;
+    }, n_scans, n_beams);
     return UZL_OK;
     UZL_GUARD_END(h)
 }
@@ -344,3 +364,36 @@ int uzl_laserline_to_laser(uzl_laserline* h, uzl_laser* laser, int32_t use_near,
 }
 
 }  // extern "C"
+
+int uzl::laserline_extract_device(uzl_laserline* h, int device, int32_t n_images, LaserImageRec* recs, const int32_t* groups,
+                                  const uint8_t* d_pixels, int32_t* n_scans, int32_t* n_beams)
+{
+    UZL_GUARD_BEGIN(h)
+    if (device != h->cfg.device) return fail(h, UZL_ERR_BAD_ARG, "the images are on another device than the laser-line handle");
+    if (h->cfg.depth_scale != 1.0) return fail(h, UZL_ERR_BAD_ARG, "depth_scale must be 1: the images on the device are already scaled");
+    if (n_images < 0 || (n_images > 0 && (!recs || !groups || !d_pixels))) return fail(h, UZL_ERR_BAD_ARG, "bad image count or null images");
+    extract_with(h, n_images, [&](int32_t i) { return groups[i]; }, [&](const LaserGrid& g) {
+        if (n_images == 0) return;
+        // all records in one copy through staging half 0, then one launch per kLaserChunkImages of them
+        const size_t bytes = (size_t)n_images * sizeof(LaserImageRec);
+        UZL_HIP(hipEventSynchronize(h->copied[0]));
+        h->h_chunk[0].reserve(bytes);
+        h->d_chunk[0].reserve(bytes);
+        for (int32_t i = 0; i < n_images; i++) {
+            recs[i].lanes = lanes_for((recs[i].width + kLaserVec - 1) / kLaserVec);
+            recs[i].out = i;
+        }
+        memcpy(h->h_chunk[0].p, recs, bytes);
+        UZL_HIP(hipMemcpyAsync(h->d_chunk[0].p, h->h_chunk[0].p, bytes, hipMemcpyHostToDevice, h->stream));
+        UZL_HIP(hipEventRecord(h->copied[0], h->stream));
+        for (int32_t i0 = 0; i0 < n_images; i0 += kLaserChunkImages) {
+            const int32_t i1 = std::min(n_images, i0 + kLaserChunkImages);
+            int64_t rows = 0;
+            int32_t max_height = 0;
+            for (int32_t i = i0; i < i1; i++) { rows += recs[i].height; max_height = std::max(max_height, recs[i].height); }
+            launch_bin(h, reinterpret_cast<const LaserImageRec*>(h->d_chunk[0].p) + i0, d_pixels, i1 - i0, rows, max_height, g);
+        }
+    }, n_scans, n_beams);
+    return UZL_OK;
+    UZL_GUARD_END(h)
+}
