@@ -257,11 +257,13 @@ def step_error(dx, dx_ref):
     return float(d[:, :3].max()), float(d[:, 3:].max())
 
 
-def system_magnitudes(poses, fixed, ij, meas, info, robust, jac, delta=1.0):
+def system_magnitudes(poses, fixed, ij, meas, info, robust, jac, delta=1.0, extra=None):
     """Per entry, the sum of the magnitudes of the terms behind H and b (as build_system adds them, with |J| + s, |Omega'|): the scale of
     the round-off an evaluation of H and b in another order or at poses rounded once differently can show.  b's terms carry |e| + s,
     s = 1 + |t_i| + |t_j| + |t_z|: the error of an edge is a difference of translations of that size, so it is only known to eps s
-    absolutely however small it is (at the LM fixed point, b itself is rounding noise).  Returns (|H| terms as CSR, |b| terms [6 n])."""
+    absolutely however small it is (at the LM fixed point, b itself is rounding noise).  extra [E], when given, is added to s: the
+    translation norms of further factors a measurement was composed from (sensor transforms, displacements), whose rounding the
+    measurement carries even where its own translation cancels.  Returns (|H| terms as CSR, |b| terms [6 n])."""
     P = np.asarray(poses, np.float64).reshape(-1, 3, 4); Z = np.asarray(meas, np.float64).reshape(-1, 3, 4)
     ij = np.asarray(ij).reshape(-1, 2)
     e = edge_errors(poses, ij, meas)
@@ -270,6 +272,8 @@ def system_magnitudes(poses, fixed, ij, meas, info, robust, jac, delta=1.0):
     _, r1 = huber(c, delta)
     w = np.where(np.asarray(robust) != 0, r1, 1.0)
     s = 1.0 + np.abs(P[ij[:, 0], :, 3]).max(1) + np.abs(P[ij[:, 1], :, 3]).max(1) + np.abs(Z[:, :, 3]).max(1)
+    if extra is not None:
+        s = s + np.asarray(extra, np.float64)
     # a Jacobian entry is built from rotations (|.| <= 1) and relative translations (|.| <= s): rounded once differently it moves by a few
     # eps s whatever its own size (a coupling term 2 R [t_b]x of two nearby vertices far from the origin cancels): |J| + s bounds its terms
     Ji, Jj = (np.abs(np.asarray(j)) + s[:, None, None] for j in jac)

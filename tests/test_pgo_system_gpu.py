@@ -185,18 +185,25 @@ def everything_eliminated():
 class System:
     """The reference system at the poses the handle linearised at, in the handle's row numbering."""
 
-    def __init__(self, oracle, g, lin, xy=False, sensors=None):
-        fl = oracle.flatten_graph(g["nodes_pose"], g["nodes_fixed"], g["edges"], sensors=sensors, optimize_xy_only=xy)
+    def __init__(self, oracle, g, lin, xy=False, sensors=None, use_odometry_parameters=False, extra=None):
+        """extra [input edges]: a magnitude added to s of every edge (np_reference.system_magnitudes), e.g. the translation norms of the
+        sensor and displacement factors its measurement was composed from."""
+        fl = oracle.flatten_graph(g["nodes_pose"], g["nodes_fixed"], g["edges"], sensors=sensors, optimize_xy_only=xy,
+                                  use_odometry_parameters=use_odometry_parameters)
+        extra = None if extra is None else np.asarray(extra, np.float64)[fl["src_edge"]]
         fixed, _ = oracle.set_fixed_nodes(fl["fixed"], fl["ij"])
         X = lin["poses"].reshape(-1, 3, 4)
         ij, Z = fl["ij"], fl["meas"].reshape(-1, 3, 4)
         J = [oracle.edge_jacobians(X[i], X[j], Z[k]) for k, (i, j) in enumerate(ij)]
         jac = (np.array([a for a, _ in J]).reshape(-1, 6, 6), np.array([b for _, b in J]).reshape(-1, 6, 6))
         H, b, chi = NP.build_system(lin["poses"], fixed, ij, fl["meas"], fl["info"], fl["robust"], jac=jac)
-        Hm, bm = NP.system_magnitudes(lin["poses"], fixed, ij, fl["meas"], fl["info"], fl["robust"], jac)
+        Hm, bm = NP.system_magnitudes(lin["poses"], fixed, ij, fl["meas"], fl["info"], fl["robust"], jac, extra=extra)
         e = NP.edge_errors(lin["poses"], ij, fl["meas"])
         P = X
         s = 1.0 + np.abs(P[ij[:, 0], :, 3]).max(1) + np.abs(P[ij[:, 1], :, 3]).max(1) + np.abs(Z[:, :, 3]).max(1)
+        if extra is not None:
+            s = s + extra
+        self.fl, self.e, self.s = fl, e, s
         ae = np.abs(e) + s[:, None]
         self.chi_mag = float(np.einsum("ki,kij,kj->", ae, np.abs(fl["info"]).reshape(-1, 6, 6), ae))
         v2b = lin["v2b"]
@@ -237,18 +244,19 @@ def check_linearization(lin, R, key):
     assert wc <= 1.0, (lin["chi2"], R.chi)
 
 
-def _linearize_case(capi, oracle, g, key, cfg=None, sensors=None, after=0):
+def _linearize_case(capi, oracle, g, key, cfg=None, sensors=None, after=0, extra=None):
     xy = bool((cfg or {}).get("optimize_xy_only", 0))
+    kw = dict(use_odometry_parameters=bool((cfg or {}).get("use_odometry_parameters", 0)), extra=extra)
     p = capi.DiagPgo(**(cfg or {}))
     try:
         p.add_graph(g["nodes_pose"], g["nodes_fixed"], g["edges"], sensors=sensors)
         lin = p.linearize()
-        check_linearization(lin, System(oracle, g, lin, xy, sensors), key + " initial")
+        check_linearization(lin, System(oracle, g, lin, xy, sensors, **kw), key + " initial")
         if after:
             st = p.optimize(after)
             assert st["status"] == 0
             lin = p.linearize()
-            check_linearization(lin, System(oracle, g, lin, xy, sensors), key + " after optimize(%d)" % after)
+            check_linearization(lin, System(oracle, g, lin, xy, sensors, **kw), key + " after optimize(%d)" % after)
         return lin
     finally:
         p.close()

@@ -749,6 +749,25 @@ class DiagPgo(Pgo):
         multiplicative operator has broken down on one of its graphs)."""
         self._check(self._lib().uzl_debug_pgo_ban_mult(self._h))
 
+    def trial(self, dx, lam=0.0):
+        """One LM trial's retraction and evaluation for the step dx [n,6] (rows of fixed vertices are ignored), from the current poses,
+        which stay as they are (uzl_debug_pgo_trial): dict of poses [n,12] (what oplus_kernel stored, as store() writes poses),
+        part_inlane / part_stored (the per-workgroup chi2 partials of chi2_trial_kernel - poses retracted in the edge lane - and of
+        chi2_kernel on the stored trial poses, same grid), scale (computeScale = sum dx (lam dx + b)), chi2_inlane, chi2_stored."""
+        L = self._lib()
+        n = self.n
+        d = np.ascontiguousarray(dx, np.float64).reshape(-1, 6)
+        assert d.shape[0] == n, "dx has %d rows, the graph %d vertices" % (d.shape[0], n)
+        sz = np.zeros(1, np.int32)
+        self._check(L.uzl_debug_pgo_trial(self._h, None, C.c_double(lam), _p(sz, c_i32p), None, None, None, None))
+        g = int(sz[0])
+        P = np.zeros((max(n, 1), 12)); pa = np.zeros(max(g, 1)); pb = np.zeros(max(g, 1)); info = np.zeros(4)
+        self._check(L.uzl_debug_pgo_trial(self._h, _p(d, c_f64p), C.c_double(lam), _p(sz, c_i32p), _p(P, c_f64p), _p(pa, c_f64p),
+                                          _p(pb, c_f64p), _p(info, c_f64p)))
+        assert int(sz[0]) == g, "the structure changed between the two calls"
+        return dict(poses=P[:n], part_inlane=pa[:g], part_stored=pb[:g], scale=float(info[0]), chi2_inlane=float(info[1]),
+                    chi2_stored=float(info[2]))
+
     def _hier_array(self, level, what, dtype, shape):
         L = self._lib()
         nbytes = C.c_int64(0)

@@ -1868,6 +1868,76 @@ extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_ban_mult(uzl_pgo* h)
     return UZL_OK;
     UZL_GUARD_END(h)
 }
+
+// One LM trial's retraction and evaluation for a step the caller gives (tests/test_pgo_geometry_gpu.py): linearise at the current poses,
+// write the free vertices' rows of dx [n][6] into D.x (rows of fixed vertices are ignored), scal[3] = lambda, then the launches of a
+// trial of the host-driven loop - oplus_kernel from the current poses into the trial buffer, chi2_trial_kernel on the current poses
+// (the in-lane retraction) - and chi2_kernel on the stored trial poses with the same grid.  poses [n][12]: the trial poses as
+// uzl_pgo_store would write them; part_inlane / part_stored [sizes[0]]: part_a after chi2_trial_kernel / after chi2_kernel;
+// info[4] = {computeScale (sum of part_b), chi2 of the in-lane launch, chi2 of the stored poses, 0}.  sizes[1] = {workgroups of the
+// two chi2 launches}; a call with null poses returns sizes only.  The current poses are not touched.
+extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_trial(uzl_pgo* h, const double* dx, double lambda, int32_t* sizes, double* poses,
+                                                   double* part_inlane, double* part_stored, double* info)
+{
+    UZL_GUARD_BEGIN(h)
+    if (!h->have_graph) return fail(h, UZL_ERR_STATE, "trial before add_graph/set_graph");
+    if (!sizes) return fail(h, UZL_ERR_BAD_ARG, "sizes is required");
+    own_streams(h, true);
+    hipStream_t s = h->stream;
+    if (!poses) {
+        UZL_HIP(hipSetDevice(h->cfg.device));
+        prepare_optimize(h);
+        sizes[0] = (h->nb && h->e) ? g_edges_for(h->D.e_end - h->D.e_begin) : 0;
+        UZL_HIP(hipStreamSynchronize(s));
+        return UZL_OK;
+    }
+    if (!dx || !part_inlane || !part_stored || !info) return fail(h, UZL_ERR_BAD_ARG, "dx, the partial arrays and info are required");
+    debug_linearize(h);
+    const int n = h->n;
+    const size_t nb = (size_t)h->nb;
+    for (int i = 0; i < 4; i++) info[i] = 0.;
+    sizes[0] = 0;
+    h->d_out12.reserve((size_t)n * 12);
+    if (h->nb == 0 || h->e == 0) {
+        k_poses_out(h->cur, n, h->d_out12.p, s);
+        UZL_HIP(hipMemcpyAsync(poses, h->d_out12.p, sizeof(double) * 12 * (size_t)n, hipMemcpyDeviceToHost, s));
+        UZL_HIP(hipGetLastError());
+        UZL_HIP(hipStreamSynchronize(s));
+        return UZL_OK;
+    }
+    PgoDev& D = h->D;
+    std::vector<int32_t> v2b((size_t)n);
+    UZL_HIP(hipMemcpyAsync(v2b.data(), h->d_v2b.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
+    UZL_HIP(hipStreamSynchronize(s));
+    std::vector<double> x(nb * 6, 0.);
+    for (int v = 0; v < n; v++) {
+        const int32_t a = v2b[(size_t)v];
+        if (a < 0 || (size_t)a >= nb) continue;
+        for (int c = 0; c < 6; c++) x[(size_t)a * 6 + c] = dx[(size_t)v * 6 + c];
+    }
+    UZL_HIP(hipMemcpyAsync(D.x, x.data(), sizeof(double) * 6 * nb, hipMemcpyHostToDevice, s));
+    k_set_scalar(D.scal + 3, lambda, s);
+    const double delta = h->cfg.huber_delta;
+    const int go = k_oplus(D, h->cur, h->trial, s);
+    const int gc = k_chi2_trial(D, h->cur, delta, s);
+    UZL_HIP(hipMemcpyAsync(part_inlane, D.part_a, sizeof(double) * (size_t)gc, hipMemcpyDeviceToHost, s));
+    k_finalize(D, gc, go, 0, 1, s);
+    double sc[16] = {}, sc2[16] = {};
+    UZL_HIP(hipMemcpyAsync(sc, D.scal, sizeof(sc), hipMemcpyDeviceToHost, s));
+    const int gs = k_chi2(D, h->trial, delta, s);
+    if (gs != gc) { UZL_HIP(hipStreamSynchronize(s)); return fail(h, UZL_ERR_STATE, "trial: the two chi2 launches differ in their grids"); }
+    UZL_HIP(hipMemcpyAsync(part_stored, D.part_a, sizeof(double) * (size_t)gs, hipMemcpyDeviceToHost, s));
+    k_finalize(D, gs, 0, 0, 0, s);
+    UZL_HIP(hipMemcpyAsync(sc2, D.scal, sizeof(sc2), hipMemcpyDeviceToHost, s));
+    k_poses_out(h->trial, n, h->d_out12.p, s);
+    UZL_HIP(hipMemcpyAsync(poses, h->d_out12.p, sizeof(double) * 12 * (size_t)n, hipMemcpyDeviceToHost, s));
+    UZL_HIP(hipGetLastError());
+    UZL_HIP(hipStreamSynchronize(s));
+    sizes[0] = gc;
+    info[0] = sc[5]; info[1] = sc[4]; info[2] = sc2[4];
+    return UZL_OK;
+    UZL_GUARD_END(h)
+}
 #endif  // UZL_DIAG
 
 // =====================================================================================================================
