@@ -131,7 +131,7 @@ __global__ __launch_bounds__(kWireBlk) void wire_pack_kernel(const uint8_t* __re
     const uint32_t* pos = reinterpret_cast<const uint32_t*>(arena + sg.pos_off);
     const uint8_t* valid = arena + sg.valid_off;
     const int D = 4 * sg.words;
-    const uint32_t byte = 4u * (uint32_t)j;                          // one frame: < 16384 * 549 bytes
+    const uint32_t byte = 4u * (uint32_t)j;                          // one frame: <= 16384 * 2073 bytes (D = 508), below 2^32
     uint32_t i = byte / sg.stride;
     uint32_t q = byte - i * sg.stride;
     uint32_t word = 0;
