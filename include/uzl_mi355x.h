@@ -1377,6 +1377,209 @@ int  uzl_depthfilter_lift(uzl_depthfilter* h, int32_t image, int32_t n, const in
 int  uzl_depthfilter_to_laserline(uzl_depthfilter* h, uzl_laserline* laserline, int32_t* n_scans, int32_t* n_beams);
 
 /* ======================================================================================
+ *  Colour point-cloud registration: TYPE_3D_FULL edges by GICP-6D, many pairs at once
+ *
+ *  CloudTransformationEstimator (transformation_estimation/src/cloud_transformation_estimator.cpp:
+ *  40-161) registers the colour point clouds of two nodes with GeneralizedIterativeClosestPoint6D
+ *  (transformation_estimation/external/gicp6d/gicp6d.cpp) and emits a TYPE_3D_FULL edge; it is on
+ *  in every deployed configuration (use_cloud_registration, iti_slam_launch/yaml/slam.yaml:29).
+ *  PCL is not part of the reference tree: only gicp6d.{h,cpp} and the estimator are.  So the
+ *  covariance rule and the inner optimiser below are THIS PROJECT'S READING of PCL's
+ *  GeneralizedIterativeClosestPoint with the reference's parameters, pinned by a NumPy restatement
+ *  (tests/cloud_reference.py).  Every formula is evaluated in the order written with no fused
+ *  multiply-add; / and sqrt are correctly rounded; there is no device trigonometry, pow or cbrt.
+ *  Steps 3 and 6 equal the restatement bit for bit; the rest differs from it by the order of the
+ *  sums only.  The voxel grid of step 2 is likewise this project's reading of pcl::VoxelGrid.
+ *
+ *  1. Cloud from images (Conversions::toPointCloudColor, conversions.cpp:362-421).  The depth d of
+ *     a pixel is step 1 of the depth filter's contract without its scale (32FC1: the f32; 16UC1:
+ *     (float)((double)v * 0.001)).  Pixel (u, v) is a point iff d > 0 and d is not NaN, in f32:
+ *     z = d, x = (float)((((double)u - cx) * (double)d) / fx), y likewise with v, cy, fy; its
+ *     colour is the BGR8 pixel at (v, u) (an rgb8 image has its channels swapped when it is
+ *     uploaded).  Other pixels give no point (the NaN points of the reference never survive step 2).
+ *  2. Voxel grid (pcl::VoxelGrid, leaf 0.05 f32, field "z" limits [0, 5], :118-129).  Kept: the
+ *     points with finite x, y, z and z_min <= z <= z_max.  Over them the bounding box in f32;
+ *     inv_leaf = 1.0f / leaf_size; per axis min_b = floor(min * inv_leaf), max_b = floor(max *
+ *     inv_leaf) (the product in f32), d = max_b - min_b + 1; dx dy dz beyond int32: the cloud is
+ *     refused, as PCL refuses it.  ijk = floor(p * inv_leaf) - min_b, key = i + j dx + k dx dy.
+ *     One output point per occupied voxel, in ascending key: six f32 sums (x, y, z, r, g, b) over
+ *     the voxel's points IN ASCENDING PIXEL INDEX (v width + u), each divided by the count in f32,
+ *     the colour channels truncated to uint8.  The order is this project's choice: PCL's std::sort
+ *     leaves it undefined.  The result does not depend on the schedule (a stable sort by (image,
+ *     key), then one thread per voxel).  An image may give any number of points, also none; a
+ *     cloud with fewer than k_neighbours points is stored without covariances and refused by
+ *     estimate and correspondences.
+ *  3. CIELAB (RGB2Lab, gicp6d.cpp:44-110), per point from its BGR8 colour, in f64.  lin[v] for
+ *     v = 0..255 is a table made by the HOST's libm and uploaded (the table rule of the occupancy
+ *     grid): x = v / 255.0; lin = x > 0.04045 ? pow((x + 0.055) / 1.055, 2.4) : x / 12.92.  With
+ *     R, G, B = lin[r], lin[g], lin[b]:  X = ((R 0.4124 + G 0.3576) + B 0.1805) / 0.95047,
+ *     Y = (R 0.2126 + G 0.7152) + B 0.0722, Z = ((R 0.0193 + G 0.1192) + B 0.9505) / 1.08883;
+ *     f(x) = x > 0.008856 ? cbrt(x) : 7.787 x + 16.0 / 116.0, where cbrt replaces the reference's
+ *     pow(x, 1.0 / 3.0) by this recipe: y = 0.35 + 0.7 x, then 6 Halley steps y3 = (y y) y,
+ *     y = (y (y3 + (x + x))) / ((y3 + y3) + x) (x lies in (0.008856, 1.09]; the seed is within a
+ *     factor 1.75 of the root, the steps converge cubically and the result is within 1 ulp of
+ *     cbrt: tests/test_cloud_reference.py).  L = (float)(116.0 f(Y) - 16.0), a = (float)(500.0
+ *     (f(X) - f(Y))), b = (float)(200.0 (f(Y) - f(Z))).  The search uses the scaled colour
+ *     lab_weight * (L, a, b) in f32 (lab_weight = 0.024f, cloud_transformation_estimator.cpp:145,
+ *     gicp6d.cpp:136-137).
+ *  4. Covariances (PCL computeCovariances with k_correspondences = 20, gicp_epsilon = 0.001), once
+ *     per stored cloud in its own frame.  Neighbours: the k points with the smallest (dx dx + dy
+ *     dy) + dz dz in f32, d = own - other, ties to the lower index, the point itself included,
+ *     ranked ascending.  In f64 in rank order: s = sum p, S = sum p p^T, m = s / k, cov = S / k -
+ *     m m^T (entry by entry: S_ab / k - m_a m_b).  n = the unit eigenvector of cov's smallest
+ *     eigenvalue by cyclic Jacobi: V = I, UZL_CLOUD_JACOBI_SWEEPS sweeps over the planes (0,1),
+ *     (0,2), (1,2); a plane with a_pq == 0 is skipped, else theta = (a_qq - a_pp) / (2 a_pq),
+ *     t = (theta >= 0 ? 1 : -1) / (|theta| + sqrt(theta theta + 1)), c = 1 / sqrt(t t + 1),
+ *     s = t c; a_pp -= t a_pq, a_qq += t a_pq, a_pq = 0, (a_rp, a_rq) = (c a_rp - s a_rq, s a_rp
+ *     + c a_rq), the columns p, q of V likewise.  n = the column of V at the smallest diagonal
+ *     entry (ties to the lower index), divided by its norm.  C = I - ((1 - gicp_epsilon) n) n^T
+ *     (upper triangle stored), which is PCL's U diag(1, 1, eps) U^T.  A cloud with fewer than
+ *     k_neighbours points is refused at add time.  Divergence: the reference recomputes the
+ *     target's covariances after moving it by the first guess; here the moved target's covariance
+ *     is R0 C R0^T (step 6), the same up to the rounding of near-tied neighbours.
+ *  5. Pair set-up (:54-64, :142-147).  The caller composes T_diff (the first guess, 3x4), as for
+ *     uzl_laser_pair.  Target = the `to` cloud moved by G = T_diff cast to f32, per row ((g0 x +
+ *     g1 y) + g2 z) + g3 in f32, its colour unchanged; source = the `from` cloud; PCL's own guess
+ *     is the identity, so T starts as I.
+ *  6. Correspondences, once per outer iteration.  T = the current estimate in f64, Tf its
+ *     rounding to f32 (the reference's transformation_ is a Matrix4f).  Query i = Tf p_i per row
+ *     as in step 5.  j = the target point with the smallest 6-D squared distance ((((dx dx + dy
+ *     dy) + dz dz) + dL dL) + da da) + db db in f32, d = query - target, the last three on the
+ *     scaled colours; ties to the lowest j.  Kept iff that distance widened to f64 is <
+ *     max_correspondence_dist max_correspondence_dist in f64 (gicp6d.cpp:203, 239).  For a kept i
+ *     (:245-254): S = (R C1_i) R^T + (R0 C2_j) R0^T in f64, R the rotation of T, R0 that of T_diff
+ *     in f64, each product as ((a b) + (c d)) + (e f), the upper triangle only; M_i = adj(S) /
+ *     det(S) with det = (s00 c00 + s01 c01) + s02 c02.  num_corr = the number kept; none kept:
+ *     UZL_CLOUD_NO_CORR, the pair stops.
+ *  7. Inner step: minimise f(T) = sum d_i^T M_i d_i, d_i = (R p_i + t) - q_i in f64, the M_i held
+ *     fixed, from the current T, by damped Gauss-Newton on T <- [dR(w) | v] T (R <- dR R, t <- t +
+ *     v): with a = R p_i, J_i = [-[a]x | I], H = sum J^T M J, g = sum J^T M d.  At most
+ *     inner_iterations (10) trials: (H + mu diag H) delta = -g by a 6x6 Cholesky (a pivot that is
+ *     not positive: mu <- 10 mu, next trial); the trial pose is accepted iff its f <= the current
+ *     f, then mu <- max(mu / 10, UZL_CLOUD_MU_MIN), else mu <- 10 mu; mu starts at UZL_CLOUD_MU0
+ *     in every outer iteration; the loop stops after a trial whose largest |delta| entry is below
+ *     UZL_CLOUD_INNER_EPS.  dR is the rotation matrix of the unit quaternion (1, w / 2) / |.|.  The
+ *     28 sums (H 21, g 6, f) are reduced in a fixed order: index order within a lane's strip (lane
+ *     t of 256 owns points t, t + 256, ...), a butterfly over the 64 lanes of a wave, then (w0 +
+ *     w1) + (w2 + w3), so a result depends neither on the schedule nor on the other pairs of the
+ *     call.  Divergence: PCL minimises the same f with a BFGS and a line search that are not in the
+ *     reference tree; both stop at a stationary point of f (tests/test_cloud_reference.py holds the
+ *     two together).
+ *  8. Convergence (gicp6d.cpp:273-300): delta = the largest |T_prev - T| / eps over the 3x4
+ *     entries in f64, eps = rotation_epsilon (2e-3) for the rotation entries and
+ *     transformation_epsilon (5e-4) for the translation (PCL's GICP defaults).  Stop when delta < 1
+ *     or after max_iterations (20) outer iterations; `iterations` counts them.
+ *  9. Result (:152-155): T_final = T rounded to f32; transform = T_final^-1 T_diff in f64, the
+ *     inverse as Eigen's Affine inverse (3x3 by the adjugate, -R^-1 t); match_score = num_corr of
+ *     the last outer iteration / max(n_from, n_to).
+ * 10. Edge and gates (:66-94), on the host from the returned numbers: match_score <= min_score
+ *     (0.3): UZL_CLOUD_LOW_SCORE.  T_change = T_diff transform^-1; |t| > max_translation (1.0) or
+ *     acos((trace - 1) / 2) above max_rotation_deg (30): UZL_CLOUD_TOO_FAR.  Otherwise information
+ *     = diag(1e4, 1e4, 1e4, 1e6, 1e6, 1e6), matching_score = 1.0 and the edge is a TYPE_3D_FULL
+ *     edge.  The loop over a node's depth sensors (:46-51) and the viewer calls stay with the
+ *     caller.
+ *
+ *  Device side: cloud_nn6_kernel (256 queries per workgroup x pairs; the moved target streams
+ *  through LDS in tiles of 1024 points of 32 bytes, every lane of a wave reads the same address,
+ *  each lane keeps the running (distance, index) minimum of its query in the direct difference
+ *  form) and cloud_step_kernel (one workgroup per pair: M_i, the inner steps, the convergence test,
+ *  a per-pair done flag); the blocks of a finished pair exit at once, so an estimate enqueues
+ *  max_iterations x 2 launches and waits once.  The 3-D search of step 4 uses the same tile
+ *  scheme with a sorted list of 20 per lane in registers.  Steps 1-2 run over all images of a call
+ *  in shared launches: bounding boxes by integer atomic min / max, keys, rocPRIM's (stable) radix
+ *  sort of (image, key) with the pixel index as value, one thread per voxel for the sums.
+ * ====================================================================================== */
+#define UZL_CLOUD_MAX_POINTS     32768   /* per stored cloud                                   */
+#define UZL_CLOUD_MAX_ITERATIONS 64      /* the most max_iterations may be                      */
+#define UZL_CLOUD_JACOBI_SWEEPS  8       /* step 4 */
+#define UZL_CLOUD_MU0            1e-6    /* step 7 */
+#define UZL_CLOUD_MU_MIN         1e-12   /* step 7 */
+#define UZL_CLOUD_INNER_EPS      1e-9    /* step 7 */
+typedef struct uzl_cloud uzl_cloud;
+typedef struct uzl_cloud_cfg {
+    float   leaf_size;                  /* 0.05   cloud_transformation_estimator.cpp:119                                    */
+    float   z_min, z_max;               /* 0, 5   :121                                                                      */
+    float   lab_weight;                 /* 0.024  :145                                                                      */
+    int32_t k_neighbours;               /* 20     PCL k_correspondences_; 3..20                                             */
+    int32_t max_iterations;             /* 20     :149; 1..UZL_CLOUD_MAX_ITERATIONS                                         */
+    int32_t inner_iterations;           /* 10     step 7                                                                    */
+    int32_t device;
+    double  gicp_epsilon;               /* 0.001  PCL gicp_epsilon_                                                         */
+    double  max_correspondence_dist;    /* 0.2    :148 [m, and scaled CIELAB units]                                         */
+    double  rotation_epsilon;           /* 2e-3   PCL rotation_epsilon_                                                     */
+    double  transformation_epsilon;     /* 5e-4   PCL transformation_epsilon_                                               */
+    double  min_score;                  /* 0.3    :66                                                                       */
+    double  max_translation;            /* 1.0    :70 [m]                                                                   */
+    double  max_rotation_deg;           /* 30     :70                                                                       */
+} uzl_cloud_cfg;
+#define UZL_COLOR_BGR8 0
+#define UZL_COLOR_RGB8 1   /* channels swapped when the image is uploaded */
+typedef struct uzl_color_image {
+    const void* data;                   /* 3 bytes per pixel, borrowed for the call                                         */
+    int32_t width, height, step;        /* step = bytes per row                                                             */
+    int32_t encoding;                   /* UZL_COLOR_*                                                                      */
+} uzl_color_image;
+typedef struct uzl_cloud_pair {
+    int32_t cloud_from, cloud_to;       /* indices into the handle's store                                                  */
+    double  first_guess[12];            /* T_diff of :54-58, composed by the caller, 3x4 row-major                          */
+} uzl_cloud_pair;
+#define UZL_CLOUD_OK        0
+#define UZL_CLOUD_NO_CORR   1   /* step 6  */
+#define UZL_CLOUD_LOW_SCORE 2   /* step 10 */
+#define UZL_CLOUD_TOO_FAR   3   /* step 10 */
+typedef struct uzl_cloud_edge {
+    int32_t status;                     /* UZL_CLOUD_*                                                                      */
+    int32_t iterations;                 /* outer iterations taken                                                           */
+    int32_t num_corr;                   /* of the last outer iteration                                                      */
+    int32_t n_from, n_to, _pad;
+    int32_t num_corr_iter[UZL_CLOUD_MAX_ITERATIONS];   /* of every outer iteration taken, 0 beyond                          */
+    double  match_score;                /* step 9                                                                           */
+    double  matching_score;             /* 1.0, or 0 when status != 0                                                       */
+    double  transform[12];              /* step 9, 3x4 row-major                                                            */
+    double  information[36];            /* step 10, row-major 6x6; zero when status != 0                                    */
+} uzl_cloud_edge;
+void uzl_cloud_cfg_default(uzl_cloud_cfg* cfg);
+/* UZL_ERR_BAD_ARG for a NaN, infinite or non-positive leaf_size, gicp_epsilon (also above 1), max_correspondence_dist or epsilon,
+ * a NaN, infinite or negative lab_weight, min_score or gate limit, z_min > z_max, k_neighbours outside 3..20, max_iterations
+ * outside 1..UZL_CLOUD_MAX_ITERATIONS or inner_iterations outside 1..100 (before the device is looked for); UZL_ERR_NO_DEVICE
+ * without a GPU (no CPU fallback) */
+int  uzl_cloud_create(const uzl_cloud_cfg* cfg, uzl_cloud** out);
+void uzl_cloud_destroy(uzl_cloud* h);
+const char* uzl_cloud_last_error(uzl_cloud* h);
+/* Same checks as create; takes effect at the next call (stored clouds keep the covariances they were added with). */
+int  uzl_cloud_set_config(uzl_cloud* h, const uzl_cloud_cfg* cfg);
+/* Steps 1-4 for n image pairs in shared launches; the clouds go to the handle's append-only device store, one per image, in
+ * order; *first_cloud (may be NULL) = index of the first.  UZL_ERR_BAD_ARG, nothing stored, for what uzl_laserline_extract
+ * refuses in its depth images (their camera_transform and group are checked and not used), a NULL colour array, a colour image
+ * whose width or height differs from its depth image's, whose data is NULL for a non-empty image, whose step is smaller than
+ * 3 * width, whose height * step is beyond 2^31 bytes or whose encoding is unknown, a voxel grid that overflows int32, or an
+ * image that gives more than UZL_CLOUD_MAX_POINTS points.  n = 0 and 0 x 0 images are valid. */
+int  uzl_cloud_add_images(uzl_cloud* h, int32_t n, const uzl_depth_image* images, const uzl_color_image* colors, int32_t* first_cloud);
+/* The cloud handle runs its steps 1-4 over the filter's resident (refined) depth images where they lie, with their intrinsics as
+ * given to refine and colors[i] the colour image of resident image i: the store then holds, bit for bit, what uzl_depthfilter_read
+ * -> uzl_cloud_add_images would have put there.  UZL_ERR_BAD_ARG for a NULL cloud handle, one on another device, or what
+ * uzl_cloud_add_images refuses in its colour images and clouds; UZL_ERR_STATE before any refine.  Locks the filter handle, then
+ * the cloud handle. */
+int  uzl_depthfilter_to_cloud(uzl_depthfilter* h, uzl_cloud* cloud, const uzl_color_image* colors, int32_t* first_cloud);
+/* Store an already-downsampled cloud (xyz: 3 f32 per point, bgr: 3 u8 per point) in the handle's append-only device store and run
+ * steps 3-4 on it; *cloud (may be NULL) = its index.  UZL_ERR_BAD_ARG (nothing stored) for NULL arrays, fewer than k_neighbours or
+ * more than UZL_CLOUD_MAX_POINTS points, or a non-finite coordinate. */
+int  uzl_cloud_add_points(uzl_cloud* h, int32_t n_points, const float* xyz, const uint8_t* bgr, int32_t* cloud);
+int  uzl_cloud_count(uzl_cloud* h);
+/* Stored cloud `cloud`: xyz (3 f32), bgr (3 u8), lab (3 f32: L, a, b unscaled) and cov (9 f64, the symmetric C of step 4 row-major)
+ * per point; any output may be NULL (all NULL only asks for the count).  Returns the point count; UZL_ERR_BAD_ARG for a cloud
+ * outside the store or a negative cap, UZL_ERR_TRUNCATED when an output is given and cap is smaller. */
+int  uzl_cloud_read(uzl_cloud* h, int32_t cloud, int32_t cap, float* xyz, uint8_t* bgr, float* lab, double* cov);
+/* Steps 5-10 for n_pairs pairs without a host round trip between outer iterations; results[i] belongs to pairs[i] and does not
+ * depend on the other pairs.  UZL_ERR_BAD_ARG, handle unchanged, for n_pairs < 0, NULL arrays with pairs to solve, a cloud index
+ * outside the store, a cloud without covariances or a non-finite first guess.  n_pairs = 0 is valid. */
+int  uzl_cloud_estimate(uzl_cloud* h, int32_t n_pairs, const uzl_cloud_pair* pairs, uzl_cloud_edge* results);
+/* Stage entry: steps 5-6 once for one pair at the estimate T (3x4 row-major f64; the pair's first_guess moves the target).  Per
+ * point of `from` (any output may be NULL): j and dist2 of step 6, kept = 1 iff the correspondence is kept.  Returns
+ * n_points(from); errors as estimate, and UZL_ERR_BAD_ARG for a NULL or non-finite T. */
+int  uzl_cloud_correspondences(uzl_cloud* h, const uzl_cloud_pair* pair, const double* T, int32_t* j, float* dist2, int32_t* kept);
+
+/* ======================================================================================
  *  Wire and disk formats  
  *
  *  The data formats either side of the path: graph_slam_msgs/{Edge,Node,SensorData,Features,
@@ -1544,6 +1747,11 @@ int  uzl_wire_sensor_depth(const uzl_wire_sensor* s, uzl_wire_depth* out);
 /* The decoded depth image as uzl_laserline_extract takes it (data borrowed from the message): encoding "32FC1" / "16UC1",
  * little-endian, data of at least height * step bytes; anything else: UZL_ERR_UNSUPPORTED.  camera_transform = 12 doubles. */
 int  uzl_wire_depth_image(const uzl_wire_depth* d, const double* camera_transform, int32_t group, uzl_depth_image* out);
+/* SensorData.depth_image.color of a decoded sensor (any type; re-parsed from s->raw) as uzl_cloud_add_images takes it (data
+ * borrowed from the message): encoding "bgr8", or "rgb8", whose channels are swapped when the image is uploaded; any other
+ * encoding: UZL_ERR_UNSUPPORTED.  Truncated input, a step smaller than a row or data shorter than height * step:
+ * UZL_ERR_TRUNCATED.  A 0 x 0 image (the default-constructed one) decodes to an empty image with NULL data. */
+int  uzl_wire_sensor_color(const uzl_wire_sensor* s, uzl_color_image* out);
 /* A SENSOR_TYPE_DEPTH_IMAGE SensorData as SensorData::toMsg + DepthImageData::toMsg write it (sensor_data.cpp:40-49, 194-203):
  * header (stamp, frame_id = sensor_frame), displacement, the depth image, the color image verbatim or default-constructed,
  * camera_info (raw sensor_msgs/CameraInfo bytes) verbatim or default-constructed; features, gist and scan empty. */

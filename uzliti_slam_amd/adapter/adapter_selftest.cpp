@@ -7,6 +7,10 @@
 #include <cstdlib>
 #include <cstring>
 
+#include <condition_variable>
+#include <mutex>
+
+#include "cloud_transformation_estimator.h"
 #include "graph_optimizer.h"
 #include "rosbag_storage.h"
 #include "transformation_estimator.h"
@@ -265,8 +269,68 @@ static int grow_mode(const char* in, int n1)
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// cloud mode: n nodes with one depth image each (tests/test_cloud_adapter_gpu.py writes them); every ordered pair (i, i + 1) and
+// back goes through estimateEdge() of the CloudTransformationEstimator mirror (worker thread, one callback per pair), the first
+// pair also through estimateEdgeImpl; the edges are written in pair order.
+static int cloud_mode(const char* in, const char* out)
+{
+    FILE* f = fopen(in, "rb");
+    if (!f) return 2;
+    int32_t n;
+    rd(f, &n, 4);
+    std::vector<SlamNode> nodes(n);
+    for (int i = 0; i < n; i++) {
+        auto d = std::make_shared<DepthImageData>();
+        int32_t wh[2];
+        rd(f, wh, 8); d->width = wh[0]; d->height = wh[1];
+        double k[4];
+        rd(f, k, 32); d->fx = k[0]; d->fy = k[1]; d->cx = k[2]; d->cy = k[3];
+        nodes[i].id_ = node_id(i);
+        rd(f, nodes[i].pose_.m.data(), 96);
+        d->depth_image_.resize((size_t)wh[0] * wh[1]);
+        d->color_image_.resize((size_t)wh[0] * wh[1] * 3);
+        rd(f, d->depth_image_.data(), d->depth_image_.size() * 4);
+        rd(f, d->color_image_.data(), d->color_image_.size());
+        d->sensor_frame_ = "camera";
+        nodes[i].sensor_data_.push_back(std::make_shared<FeatureData>());     // a sensor the estimator passes over (:47)
+        nodes[i].sensor_data_.push_back(d);
+    }
+    fclose(f);
+    std::mutex m; std::condition_variable cv;
+    std::map<std::string, SlamEdge> got;
+    Mi355xCloudTransformationEstimator est([&](SlamEdge e) { std::lock_guard<std::mutex> l(m); got[e.id_from_ + ">" + e.id_to_] = e; cv.notify_all(); });
+    if (est.lastStatus() != UZL_OK) { fprintf(stderr, "no cloud handle (no HIP device?)\n"); return 3; }
+    est.sensor_transforms_["camera"] = Isometry3d::Identity();
+    std::vector<std::pair<int, int>> pairs;
+    for (int i = 0; i + 1 < n; i++) { pairs.push_back({i, i + 1}); pairs.push_back({i + 1, i}); }
+    for (auto& p : pairs) est.estimateEdge(nodes[p.first], nodes[p.second]);
+    { std::unique_lock<std::mutex> l(m); cv.wait(l, [&] { return got.size() == pairs.size(); }); }
+    SlamEdge direct;
+    const bool ok = est.estimateEdgeImpl(nodes[0], nodes[1], direct);
+    const SlamEdge& queued = got[nodes[0].id_ + ">" + nodes[1].id_];
+    if (!ok || memcmp(direct.transform_.m.data(), queued.transform_.m.data(), 96) != 0) { fprintf(stderr, "estimateEdgeImpl differs from the queue\n"); return 4; }
+    FILE* o = fopen(out, "wb");
+    if (!o) return 2;
+    for (auto& p : pairs) {
+        const SlamEdge& e = got[nodes[p.first].id_ + ">" + nodes[p.second].id_];
+        const int32_t head[2] = {(int32_t)e.type_, (int32_t)(e.sensor_from_ == "camera" && e.sensor_to_ == "camera")};
+        fwrite(head, 4, 2, o);
+        fwrite(&e.matching_score_, 8, 1, o);
+        fwrite(e.transform_.m.data(), 8, 12, o);
+        fwrite(e.information_.data(), 8, 36, o);
+    }
+    const uzl_cloud_edge& last = est.lastEdge();
+    fwrite(&last.iterations, 4, 1, o);
+    fwrite(&last.num_corr, 4, 1, o);
+    fclose(o);
+    printf("CLOUD_OK %d pairs\n", (int)pairs.size());
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
+    if (argc == 4 && std::string(argv[1]) == "cloud") return cloud_mode(argv[2], argv[3]);
     if (argc == 4 && std::string(argv[1]) == "grow") return grow_mode(argv[2], atoi(argv[3]));
     if (argc == 4 && std::string(argv[1]) == "storage") return storage_mode(argv[2], argv[3]);
     if (argc == 4 && std::string(argv[1]) == "filter") return filter_mode(argv[2], argv[3]);

@@ -64,8 +64,19 @@ struct FeatureData : SensorData {
     std::vector<bool> valid_3d_;
 };
 
+// DepthImageData (sensor_data.h): sensor_msgs::Image depth_image_ (32FC1), color_image_ (bgr8 / rgb8), PinholeCameraModel camera_model_
+struct DepthImageData : SensorData {
+    DepthImageData() { type_ = SENSOR_TYPE_DEPTH_IMAGE; }
+    int width = 0, height = 0;
+    std::vector<float> depth_image_;         // width * height, row-major, metres
+    std::vector<uint8_t> color_image_;       // 3 * width * height
+    bool color_is_rgb = false;               // color_image_.encoding == "rgb8"
+    double fx = 0, fy = 0, cx = 0, cy = 0;   // camera_model_.fx() ...
+};
+
 typedef std::shared_ptr<SensorData> SensorDataPtr;
 typedef std::shared_ptr<FeatureData> FeatureDataPtr;
+typedef std::shared_ptr<DepthImageData> DepthImageDataPtr;
 
 struct SlamNode {
     std::string id_;

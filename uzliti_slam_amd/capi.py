@@ -262,6 +262,39 @@ LASER_EDGE_DTYPE = np.dtype([("status", "<i4"), ("nvalid", "<i4"), ("scan_valid"
                              ("_pad", "<i4"), ("matching_score", "<f8"), ("error", "<f8"), ("transform", "<f8", (12,)),
                              ("information", "<f8", (36,))])
 
+class CloudCfg(C.Structure):
+    _fields_ = [("leaf_size", C.c_float), ("z_min", C.c_float), ("z_max", C.c_float), ("lab_weight", C.c_float),
+                ("k_neighbours", C.c_int32), ("max_iterations", C.c_int32), ("inner_iterations", C.c_int32), ("device", C.c_int32),
+                ("gicp_epsilon", C.c_double), ("max_correspondence_dist", C.c_double), ("rotation_epsilon", C.c_double),
+                ("transformation_epsilon", C.c_double), ("min_score", C.c_double), ("max_translation", C.c_double),
+                ("max_rotation_deg", C.c_double)]
+
+
+COLOR_BGR8, COLOR_RGB8 = 0, 1
+
+
+class ColorImage(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("step", C.c_int32), ("encoding", C.c_int32)]
+
+
+class CloudPair(C.Structure):
+    _fields_ = [("cloud_from", C.c_int32), ("cloud_to", C.c_int32), ("first_guess", C.c_double * 12)]
+
+
+CLOUD_MAX_POINTS, CLOUD_MAX_ITERATIONS = 32768, 64
+
+
+class CloudEdge(C.Structure):
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("num_corr", C.c_int32), ("n_from", C.c_int32), ("n_to", C.c_int32),
+                ("_pad", C.c_int32), ("num_corr_iter", C.c_int32 * CLOUD_MAX_ITERATIONS), ("match_score", C.c_double),
+                ("matching_score", C.c_double), ("transform", C.c_double * 12), ("information", C.c_double * 36)]
+
+
+CLOUD_OK, CLOUD_NO_CORR, CLOUD_LOW_SCORE, CLOUD_TOO_FAR = range(4)
+CLOUD_EDGE_DTYPE = np.dtype([("status", "<i4"), ("iterations", "<i4"), ("num_corr", "<i4"), ("n_from", "<i4"), ("n_to", "<i4"),
+                             ("_pad", "<i4"), ("num_corr_iter", "<i4", (CLOUD_MAX_ITERATIONS,)), ("match_score", "<f8"),
+                             ("matching_score", "<f8"), ("transform", "<f8", (12,)), ("information", "<f8", (36,))])
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
 
 _lib = None
@@ -287,7 +320,7 @@ def lib():
 
 
 _HANDLES = ("uzl_match", "uzl_pgo", "uzl_pgo_batch", "uzl_filter", "uzl_gate", "uzl_radius", "uzl_places", "uzl_gist")
-_MORE_HANDLES = ("uzl_grid", "uzl_laserline", "uzl_gfr", "uzl_laser", "uzl_depthfilter")      # declared like _HANDLES; kept apart because tests pin _HANDLES to the first eight
+_MORE_HANDLES = ("uzl_grid", "uzl_laserline", "uzl_gfr", "uzl_laser", "uzl_depthfilter", "uzl_cloud")      # declared like _HANDLES; kept apart because tests pin _HANDLES to the first eight
 
 
 def _declare(L):
@@ -301,7 +334,8 @@ def _declare(L):
         if hasattr(L, p + "_cfg_default"):          # (a batch takes uzl_pgo_cfg)
             getattr(L, p + "_cfg_default").restype = None
     for f in ("uzl_places_count", "uzl_gist_count", "uzl_grid_scan_count", "uzl_gate_edge_count", "uzl_filter_cluster_count",
-              "uzl_gfr_count", "uzl_gfr_feature_count", "uzl_gfr_link_count", "uzl_laser_scan_count", "uzl_depthfilter_image_count"):
+              "uzl_gfr_count", "uzl_gfr_feature_count", "uzl_gfr_link_count", "uzl_laser_scan_count", "uzl_depthfilter_image_count",
+              "uzl_cloud_count"):
         getattr(L, f).argtypes = [C.c_void_p]
     L.uzl_pgo_batch_graph.restype = C.c_void_p
     L.uzl_pgo_batch_graph.argtypes = [C.c_void_p, C.c_int32]
@@ -1466,6 +1500,18 @@ class DepthFilter(_Handle):
         return laserline.read()
 
 
+def _depthfilter_to_cloud(self, cloud, colors, encoding=COLOR_BGR8):
+    """the cloud handle voxelises the resident images on the device with one (h, w, 3) uint8 colour image each -> index of the
+    first cloud added"""
+    carr, ckeep = Cloud.pack_colors(colors, encoding)
+    first = C.c_int32(-1)
+    self._check(lib().uzl_depthfilter_to_cloud(self._h, cloud._h, carr if len(ckeep) else None, C.byref(first)))
+    return first.value
+
+
+DepthFilter.to_cloud = _depthfilter_to_cloud
+
+
 class Laser(_Handle):
     """uzl_laser_* (LaserTransformationEstimator, transformation_estimation/src/laser_transformation_estimator.cpp:134-443): stored
     laser scans aligned pair by pair with point-to-line ICP into TYPE_2D_LASER edges, all pairs of a call in one launch."""
@@ -1525,3 +1571,93 @@ class Laser(_Handle):
         n = self._check(lib().uzl_laser_correspondences(self._h, pair, xx, _p(j1, c_i32p), _p(j2, c_i32p), _p(valid, c_i32p), _p(dist, c_f64p)))
         assert n == n_beams, (n, n_beams)
         return j1, j2, valid, dist
+
+
+class Cloud(_Handle):
+    """uzl_cloud_* (CloudTransformationEstimator, transformation_estimation/src/cloud_transformation_estimator.cpp:40-161, with
+    GeneralizedIterativeClosestPoint6D, external/gicp6d/gicp6d.cpp): stored colour point clouds registered pair by pair into
+    TYPE_3D_FULL edges, all pairs of a call without a host round trip between the outer iterations."""
+
+    _prefix, _cfg_type = "uzl_cloud", CloudCfg
+    set_config = _Handle._set_config
+
+    @staticmethod
+    def pack_colors(colors, encoding=COLOR_BGR8):
+        """colors: (h, w, 3) uint8 arrays (rows may be strided) -> (ColorImage array, the pixel arrays it points into)"""
+        arr = (ColorImage * max(len(colors), 1))()
+        keep = []
+        for i, c in enumerate(colors):
+            c = np.asarray(c)
+            if c.ndim != 3 or c.shape[2] != 3 or c.dtype != np.uint8:
+                raise ValueError("a colour image is an (h, w, 3) uint8 array")
+            if c.size and (c.strides[2] != 1 or c.strides[1] != 3 or c.strides[0] < 3 * c.shape[1]):
+                c = np.ascontiguousarray(c)
+            keep.append(c)
+            arr[i].encoding = encoding
+            if c.size:
+                arr[i].data = c.ctypes.data; arr[i].height, arr[i].width = c.shape[:2]; arr[i].step = c.strides[0]
+        return arr, keep
+
+    def add_images(self, images, colors, encoding=COLOR_BGR8):
+        """images: what Laserline.pack_images takes; colors: one (h, w, 3) uint8 array per image -> index of the first cloud added"""
+        arr, keep = Laserline.pack_images(images)
+        carr, ckeep = self.pack_colors(colors, encoding)
+        if len(keep) != len(ckeep):
+            raise ValueError("one colour image per depth image")
+        first = C.c_int32(-1)
+        self._check(lib().uzl_cloud_add_images(self._h, C.c_int32(len(keep)), arr, carr, C.byref(first)))
+        return first.value
+
+    def add_points(self, xyz, bgr):
+        """an already-downsampled cloud: xyz (n, 3) float32, bgr (n, 3) uint8 -> its index in the store"""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        bgr = np.ascontiguousarray(bgr, np.uint8).reshape(-1, 3)
+        if len(xyz) != len(bgr):
+            raise ValueError("one colour per point")
+        idx = C.c_int32(-1)
+        self._check(lib().uzl_cloud_add_points(self._h, C.c_int32(len(xyz)), _p(xyz, C.POINTER(C.c_float)), _p(bgr, c_u8p), C.byref(idx)))
+        return idx.value
+
+    def count(self):
+        return self._check(lib().uzl_cloud_count(self._h))
+
+    def point_count(self, cloud):
+        return self._check(lib().uzl_cloud_read(self._h, C.c_int32(cloud), C.c_int32(0), None, None, None, None))
+
+    def read(self, cloud):
+        """-> dict(xyz (n, 3) f32, bgr (n, 3) u8, lab (n, 3) f32, cov (n, 3, 3) f64)"""
+        n = self.point_count(cloud)
+        xyz = np.zeros((n, 3), np.float32); bgr = np.zeros((n, 3), np.uint8); lab = np.zeros((n, 3), np.float32)
+        cov = np.zeros((n, 3, 3), np.float64)
+        m = self._check(lib().uzl_cloud_read(self._h, C.c_int32(cloud), C.c_int32(n), _p(xyz, C.POINTER(C.c_float)), _p(bgr, c_u8p),
+                                             _p(lab, C.POINTER(C.c_float)), _p(cov, c_f64p)))
+        assert m == n, (m, n)
+        return dict(xyz=xyz, bgr=bgr, lab=lab, cov=cov)
+
+    @staticmethod
+    def pack_pairs(pairs):
+        """pairs: (cloud_from, cloud_to, first_guess as 12 or 3x4) -> CloudPair array"""
+        arr = (CloudPair * max(len(pairs), 1))()
+        for i, (f, t, guess) in enumerate(pairs):
+            arr[i].cloud_from = int(f); arr[i].cloud_to = int(t)
+            arr[i].first_guess[:] = np.asarray(guess, np.float64).reshape(12).tolist()
+        return arr
+
+    def estimate(self, pairs):
+        """-> one CLOUD_EDGE_DTYPE record per pair.  pairs: a list of (cloud_from, cloud_to, first_guess)"""
+        arr = self.pack_pairs(pairs)
+        n = len(pairs)
+        out = np.zeros(max(n, 1), CLOUD_EDGE_DTYPE)
+        self._check(lib().uzl_cloud_estimate(self._h, C.c_int32(n), arr, out.ctypes.data_as(C.POINTER(CloudEdge))))
+        return out[:n]
+
+    def correspondences(self, cloud_from, cloud_to, first_guess, T):
+        """step 6 once at the estimate T (3x4) with the target moved by first_guess -> (j int32, dist2 float32, kept int32), one
+        entry per point of cloud_from"""
+        n = self.point_count(cloud_from)
+        pair = self.pack_pairs([(cloud_from, cloud_to, first_guess)])
+        TT = (C.c_double * 12)(*np.asarray(T, np.float64).reshape(12).tolist())
+        j = np.zeros(n, np.int32); d = np.zeros(n, np.float32); kept = np.zeros(n, np.int32)
+        m = self._check(lib().uzl_cloud_correspondences(self._h, pair, TT, _p(j, c_i32p), _p(d, C.POINTER(C.c_float)), _p(kept, c_i32p)))
+        assert m == n, (m, n)
+        return j, d, kept

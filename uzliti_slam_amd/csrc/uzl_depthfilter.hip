@@ -6,6 +6,7 @@
 // packs one half while the other half's copy and kernel run), each chunk's image records in front of its pixels so that a chunk
 // is one copy; the refined images stay in HBM as compact f32, where uzl_depthfilter_lift gathers from them and
 // uzl_depthfilter_to_laserline lets a laser-line handle bin them without a copy.
+#include "cloud_types.hpp"
 #include "depthfilter_types.hpp"
 #include "laserline_types.hpp"
 #include "uzl_common.hpp"
@@ -336,6 +337,31 @@ int uzl_depthfilter_to_laserline(uzl_depthfilter* h, uzl_laserline* laserline, i
     const int rc = laserline_extract_device(laserline, h->cfg.device, n, recs.data(), groups.data(),
                                             reinterpret_cast<const uint8_t*>(h->d_images.p), n_scans, n_beams);
     if (rc != UZL_OK) return fail(h, rc, "the laser-line handle refused the images (see its last_error)");
+    return UZL_OK;
+    UZL_GUARD_END(h)
+}
+
+int uzl_depthfilter_to_cloud(uzl_depthfilter* h, uzl_cloud* cloud, const uzl_color_image* colors, int32_t* first_cloud)
+{
+    UZL_GUARD_BEGIN(h)
+    if (!cloud) return fail(h, UZL_ERR_BAD_ARG, "null cloud handle");
+    if (!h->have) return fail(h, UZL_ERR_STATE, "no refine yet");
+    const int32_t n = (int32_t)h->resident.size();
+    if (n > 0 && !colors) return fail(h, UZL_ERR_BAD_ARG, "null colour images");
+    std::vector<uzl_depth_image> geom((size_t)n);
+    std::vector<const float*> d_depth((size_t)n);
+    for (int32_t i = 0; i < n; i++) {
+        const DepthResident& r = h->resident[i];
+        uzl_depth_image& g = geom[i];
+        memset(&g, 0, sizeof(g));
+        g.encoding = UZL_DEPTH_F32_M; g.width = r.width; g.height = r.height; g.step = 4 * r.width;
+        g.fx = r.fx; g.fy = r.fy; g.cx = r.cx; g.cy = r.cy;
+        d_depth[i] = h->d_images.p + r.off;
+    }
+    // the images are complete (refine synchronises) and stay while this handle's lock is held; the cloud handle's lock is taken
+    // inside, after this handle's
+    const int rc = cloud_add_device_images(cloud, h->cfg.device, n, geom.data(), d_depth.data(), colors, first_cloud);
+    if (rc != UZL_OK) return fail(h, rc, "the cloud handle refused the images (see its last_error)");
     return UZL_OK;
     UZL_GUARD_END(h)
 }

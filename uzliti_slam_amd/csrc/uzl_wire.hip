@@ -855,6 +855,36 @@ int uzl_wire_depth_image(const uzl_wire_depth* d, const double* camera_transform
     return UZL_OK;
 }
 
+int uzl_wire_sensor_color(const uzl_wire_sensor* s, uzl_color_image* out)
+{
+    if (!s || !s->raw.p || !out) return UZL_ERR_BAD_ARG;
+    Reader r(reinterpret_cast<const uint8_t*>(s->raw.p), s->raw.n);
+    uzl_wire_depth d;
+    memset(&d, 0, sizeof(d));
+    get_sensor(r, nullptr, nullptr, nullptr, &d, nullptr);
+    if (!r.ok) return UZL_ERR_TRUNCATED;
+    Reader c(reinterpret_cast<const uint8_t*>(d.color.p), d.color.n);     // sensor_msgs/Image
+    get_header(c);
+    const uint32_t height = c.get<uint32_t>(), width = c.get<uint32_t>();
+    const uzl_span enc = c.str();
+    c.skip(1);                                                             // is_bigendian: the channels are bytes
+    const uint32_t step = c.get<uint32_t>();
+    const uzl_span data = c.bytes(c.get<uint32_t>());
+    if (!c.ok) return UZL_ERR_TRUNCATED;
+    int32_t e;
+    if (enc.n == 4 && memcmp(enc.p, "bgr8", 4) == 0) e = UZL_COLOR_BGR8;
+    else if (enc.n == 4 && memcmp(enc.p, "rgb8", 4) == 0) e = UZL_COLOR_RGB8;
+    else return UZL_ERR_UNSUPPORTED;
+    if (width > 0x7fffffffu / 3 || height > 0x7fffffffu || step > 0x7fffffffu) return UZL_ERR_UNSUPPORTED;
+    if ((uint64_t)step < (uint64_t)width * 3 || (uint64_t)height * step > data.n) return UZL_ERR_TRUNCATED;
+    memset(out, 0, sizeof(*out));
+    const bool any = width > 0 && height > 0;
+    out->data = any ? data.p : nullptr;
+    out->width = any ? (int32_t)width : 0; out->height = any ? (int32_t)height : 0; out->step = any ? (int32_t)step : 0;
+    out->encoding = e;
+    return UZL_OK;
+}
+
 static bool depth_ok(const uzl_wire_depth* d, const uzl_span& camera_info)
 {
     return d && !(d->frame_id.n && !d->frame_id.p) && !(d->encoding.n && !d->encoding.p) && !(d->data.n && !d->data.p) &&
