@@ -341,3 +341,21 @@ def test_bad_arguments_leave_the_resident_set_as_it_was(capi):
     assert L.uzl_depthfilter_lift(h._h, 0, 4, *args, C.c_double(0.0), *outs) == capi.UZL_ERR_BAD_ARG
     assert L.uzl_depthfilter_lift(h._h, 0, 0, None, None, C.c_double(0.0), None, None) == capi.UZL_OK
     h.close()
+
+
+def test_three_staging_chunks_by_the_image_count(capi):
+    """2 * 8192 + 5 small images cross the stager's image-count limit (image_stager.hpp: kStageChunkImages) twice, far below its
+    byte limit: three chunks, so the first staging half is packed again while its first chunk's copy and kernel may still run.
+    Four distinct scenes with holes, repeated; the images either side of both chunk boundaries and the last equal the restatement."""
+    per_chunk = 8192
+    n = 2 * per_chunk + 5
+    sizes = [(16, 12), (15, 13), (17, 11), (16, 12)]
+    scenes = [DS.scene(w, h, seed=70 + k, nans=0.2) for k, (w, h) in enumerate(sizes)]
+    want = [DR.refine(im["depth"], g) for im, g in scenes]
+    assert all((w != 0).any() and (w == 0).any() for w in want) and not np.array_equal(want[0], want[3])
+    h = capi.DepthFilter()
+    h.refine([scenes[k % 4][0] for k in range(n)], [scenes[k % 4][1] for k in range(n)])
+    assert h.image_count() == n
+    for k in (0, per_chunk - 1, per_chunk, 2 * per_chunk - 1, 2 * per_chunk, n - 1):
+        same_image(h.read(k), want[k % 4], "image %d" % k)
+    h.close()

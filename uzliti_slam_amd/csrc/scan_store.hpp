@@ -1,0 +1,72 @@
+// scan_store.hpp — the append-only store of laser scans in HBM that uzl_grid and uzl_laser keep: one arena of f32 readings, scan
+// after scan, and one arena of (cos, sin) tables shared by the scans of the same (angle_min, angle_increment, n).  The per-scan
+// record, the limits and their messages are each module's own.
+#pragma once
+#include "uzl_common.hpp"
+
+#include <algorithm>
+#include <map>
+#include <tuple>
+
+namespace uzl {
+
+struct ScanStore {
+    int64_t n_values = 0, n_trig = 0;
+    std::map<std::tuple<uint32_t, uint32_t, int32_t>, int64_t> tables;   // (angle_min bits, increment bits, n) -> trig_off
+    DevBuf<float> d_values;
+    DevBuf<double2> d_trig;
+
+    // An append under way: where each scan will lie and where the call's values go.  The store itself is as it was until commit().
+    struct Pending {
+        std::vector<int64_t> values_off, trig_off;   // per scan
+        float* dst = nullptr;                        // the arena's end: the call's `total` values go here, on the same stream
+        std::vector<double2> trig;                   // the new tables' entries: pageable, read by the copy until the stream is synchronised
+        std::map<std::tuple<uint32_t, uint32_t, int32_t>, int64_t> tables;
+        int64_t n_values = 0, n_trig = 0;
+    };
+
+    // First half of an append of the checked scans `in` (each with .n, .angle_min, .angle_increment; `total` values in all): new
+    // tables from the host's libm, both arenas grown, the new tables' copy queued on `st`.  The caller queues the values to
+    // p.dst and whatever else belongs to the append, synchronises `st` ONCE, enters its own records and then commits: a throw
+    // anywhere before that leaves offsets, table map and the caller's books as they were.
+    template <typename Scan>
+    Pending begin(hipStream_t st, const std::vector<Scan>& in, int64_t total)
+    {
+        Pending p;
+        p.tables = tables;
+        p.n_trig = n_trig;
+        p.n_values = n_values;
+        for (const Scan& s : in) {
+            uint32_t ka, ki;
+            memcpy(&ka, &s.angle_min, 4); memcpy(&ki, &s.angle_increment, 4);
+            const auto key = std::make_tuple(ka, ki, (int32_t)s.n);
+            auto it = p.tables.find(key);
+            if (it == p.tables.end()) {
+                it = p.tables.emplace(key, p.n_trig).first;
+                for (int32_t b = 0; b < s.n; b++) {
+                    const double th = (double)s.angle_min + (double)b * (double)s.angle_increment;
+                    p.trig.push_back(make_double2(std::cos(th), std::sin(th)));
+                }
+                p.n_trig += s.n;
+            }
+            p.values_off.push_back(p.n_values);
+            p.trig_off.push_back(it->second);
+            p.n_values += s.n;
+        }
+        d_values.reserve((size_t)std::max<int64_t>(n_values + total, 1), true, st);
+        d_trig.reserve((size_t)std::max<int64_t>(p.n_trig, 1), true, st);
+        if (!p.trig.empty())
+            UZL_HIP(hipMemcpyAsync(d_trig.p + n_trig, p.trig.data(), p.trig.size() * sizeof(double2), hipMemcpyHostToDevice, st));
+        p.dst = d_values.p + n_values;
+        return p;
+    }
+
+    void commit(Pending& p) noexcept
+    {
+        n_values = p.n_values;
+        n_trig = p.n_trig;
+        tables.swap(p.tables);
+    }
+};
+
+}  // namespace uzl

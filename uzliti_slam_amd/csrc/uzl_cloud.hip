@@ -13,13 +13,12 @@
 
 #include <algorithm>
 #include <cmath>
-#include <new>
 
 using namespace uzl;
 
 struct uzl_cloud : HandleBase {
     uzl_cloud_cfg cfg;
-    hipStream_t stream = nullptr;
+    HandleStream stream;
     std::vector<CloudRec> clouds;
     int64_t n_points = 0;
     DevBuf<float> d_xyz, d_lab;
@@ -62,7 +61,7 @@ int check_pair(uzl_cloud* h, const uzl_cloud_pair& p)
     const int32_t nc = (int32_t)h->clouds.size();
     if (p.cloud_from < 0 || p.cloud_from >= nc || p.cloud_to < 0 || p.cloud_to >= nc) return fail(h, UZL_ERR_BAD_ARG, "cloud index out of range");
     if (!h->clouds[p.cloud_from].k || !h->clouds[p.cloud_to].k) return fail(h, UZL_ERR_BAD_ARG, "a cloud with fewer points than k_neighbours has no covariances");
-    for (int k = 0; k < 12; k++) if (!std::isfinite(p.first_guess[k])) return fail(h, UZL_ERR_BAD_ARG, "non-finite first guess");
+    if (!finite12(p.first_guess)) return fail(h, UZL_ERR_BAD_ARG, "non-finite first guess");
     return UZL_OK;
 }
 
@@ -301,18 +300,7 @@ void uzl_cloud_cfg_default(uzl_cloud_cfg* c)
 
 int uzl_cloud_create(const uzl_cloud_cfg* cfg, uzl_cloud** out)
 {
-    if (!out) return UZL_ERR_BAD_ARG;
-    *out = nullptr;
-    uzl_cloud_cfg c;
-    if (cfg) c = *cfg; else uzl_cloud_cfg_default(&c);
-    if (check_cfg(c) != UZL_OK) return UZL_ERR_BAD_ARG;
-    if (check_device(c.device) != UZL_OK) return UZL_ERR_NO_DEVICE;
-    uzl_cloud* h = new (std::nothrow) uzl_cloud();
-    if (!h) return UZL_ERR_OOM;
-    h->cfg = c;
-    try {
-        open_handle_stream(c.device, false, &h->stream);
-        UZL_HIP(hipSetDevice(c.device));
+    return create_handle(cfg, uzl_cloud_cfg_default, out, check_cfg, [](uzl_cloud* h) {
         // step 3: the sRGB linearisation, from the host's libm
         double table[256];
         for (int v = 0; v < 256; v++) {
@@ -322,35 +310,14 @@ int uzl_cloud_create(const uzl_cloud_cfg* cfg, uzl_cloud** out)
         h->d_table.reserve(256);
         UZL_HIP(hipMemcpyAsync(h->d_table.p, table, sizeof(table), hipMemcpyHostToDevice, h->stream));
         UZL_HIP(hipStreamSynchronize(h->stream));
-    } catch (...) {
-        const int code = caught_status(h->last_error);
-        close_handle_stream(c.device, h->stream);
-        delete h;
-        return code;
-    }
-    *out = h;
-    return UZL_OK;
+    });
 }
 
-void uzl_cloud_destroy(uzl_cloud* h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->cfg.device);
-    close_handle_stream(h->cfg.device, h->stream);
-    delete h;
-}
+void uzl_cloud_destroy(uzl_cloud* h) { destroy_handle(h); }
 
 const char* uzl_cloud_last_error(uzl_cloud* h) { return last_error_of(h); }
 
-int uzl_cloud_set_config(uzl_cloud* h, const uzl_cloud_cfg* cfg)
-{
-    UZL_GUARD_BEGIN(h)
-    if (!cfg || check_cfg(*cfg) != UZL_OK) return fail(h, UZL_ERR_BAD_ARG, "bad config");
-    if (cfg->device != h->cfg.device) return fail(h, UZL_ERR_BAD_ARG, "the device of a handle cannot change");
-    h->cfg = *cfg;
-    return UZL_OK;
-    UZL_GUARD_END(h)
-}
+int uzl_cloud_set_config(uzl_cloud* h, const uzl_cloud_cfg* cfg) { return set_config_of(h, cfg, check_cfg); }
 
 int uzl_cloud_add_points(uzl_cloud* h, int32_t n_points, const float* xyz, const uint8_t* bgr, int32_t* cloud)
 {

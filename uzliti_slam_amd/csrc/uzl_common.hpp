@@ -1,6 +1,7 @@
 // uzl_common.hpp — shared host-side plumbing of libuzl_mi355x.so (HIP runtime only, no torch).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -109,6 +110,26 @@ inline int caught_status(std::string& last_error)
     } catch (const ::uzl::HipError& e) { return ::uzl::report((h)->last_error, e); } \
     catch (const std::bad_alloc&) { (h)->last_error = "host out of memory"; return UZL_ERR_OOM; } \
     catch (...) { (h)->last_error = "unexpected exception"; return UZL_ERR_HIP; }
+
+// An event that destroys itself; made on first need (the device is current), without timing unless `flags` say otherwise.
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(const Event&) = delete;
+    Event& operator=(const Event&) = delete;
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    void create(unsigned flags = hipEventDisableTiming) { UZL_HIP(hipEventCreateWithFlags(&e, flags)); }
+    operator hipEvent_t() const { return e; }
+};
+
+inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
+
+// a 3 x 4 transform (pose, displacement, first guess) without NaN or infinity
+inline bool finite12(const double* v)
+{
+    for (int i = 0; i < 12; i++) if (!std::isfinite(v[i])) return false;
+    return true;
+}
 
 // Growable device buffer (never shrinks).  Plain hipMalloc: 288 GB of HBM, nothing is paged.
 template <typename T>

@@ -8,18 +8,16 @@
 // uzl_depthfilter_to_laserline lets a laser-line handle bin them without a copy.
 #include "cloud_types.hpp"
 #include "depthfilter_types.hpp"
+#include "image_stager.hpp"
 #include "laserline_types.hpp"
 #include "uzl_common.hpp"
 #include "uzl_streams.hpp"
 
 #include <algorithm>
 #include <cmath>
-#include <new>
 
 namespace uzl {
 
-constexpr size_t kDepthChunkBytes = (size_t)64 << 20;   // pixels of one staging half (an image larger than this gets a half of its own size)
-constexpr int kDepthChunkImages = 8192;                 // images of one chunk (gridDim.z)
 constexpr size_t kDepthAlign = 64;                      // floats: every resident image starts on a 256-byte boundary
 
 // A resident image: where it lies and what its depth image came with
@@ -36,8 +34,7 @@ using namespace uzl;
 
 struct uzl_depthfilter : HandleBase {
     uzl_depthfilter_cfg cfg;
-    hipStream_t stream = nullptr;
-    hipEvent_t copied[2] = {nullptr, nullptr};   // the copy out of staging half i has finished
+    HandleStream stream;
     // the tables last uploaded (contract step 2)
     bool have_tables = false;
     int32_t table_radius = 0;
@@ -48,8 +45,7 @@ struct uzl_depthfilter : HandleBase {
     std::vector<DepthResident> resident;
     DevBuf<float> d_images;
     // work
-    PinBuf<uint8_t> h_chunk[2];
-    DevBuf<uint8_t> d_chunk[2];
+    ImageStager stage;
     PinBuf<uint8_t> h_lift;
     DevBuf<uint8_t> d_lift;
 };
@@ -62,8 +58,6 @@ int check_cfg(const uzl_depthfilter_cfg& c)
     if (std::isnan(c.sigma_space) || std::isnan(c.sigma_color) || std::isnan(c.depth_scale) || !(c.depth_scale > 0.)) return UZL_ERR_BAD_ARG;
     return UZL_OK;
 }
-
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
 size_t guide_bytes(const uzl_guide_image& g) { return g.height <= 0 ? 0 : (size_t)(g.height - 1) * (size_t)g.step + (size_t)g.width; }
 
@@ -109,10 +103,7 @@ void run_chunk(uzl_depthfilter* h, const uzl_depth_image* images, const uzl_guid
     const size_t recs_bytes = align256((size_t)(i1 - i0) * sizeof(DepthImageRec));
     size_t total = recs_bytes;
     for (int32_t i = i0; i < i1; i++) total += align256(depth_image_bytes(images[i])) + (filter ? align256(guide_bytes(guides[i])) : 0);
-    UZL_HIP(hipEventSynchronize(h->copied[half]));         // the previous copy out of this half
-    h->h_chunk[half].reserve(total);
-    h->d_chunk[half].reserve(total);
-    uint8_t* w = h->h_chunk[half].p;
+    uint8_t* w = h->stage.open(half, total);
     DepthImageRec* recs = reinterpret_cast<DepthImageRec*>(w);
     size_t off = 0;
     int32_t max_width = 0, max_height = 0;
@@ -136,11 +127,10 @@ void run_chunk(uzl_depthfilter* h, const uzl_depth_image* images, const uzl_guid
         max_width = std::max(max_width, im.width);
         max_height = std::max(max_height, im.height);
     }
-    UZL_HIP(hipMemcpyAsync(h->d_chunk[half].p, w, total, hipMemcpyHostToDevice, s));
-    UZL_HIP(hipEventRecord(h->copied[half], s));
+    const uint8_t* d = h->stage.send(half, total, s);
     DepthRefineArgs a;
-    a.pixels = h->d_chunk[half].p + recs_bytes;
-    a.images = reinterpret_cast<const DepthImageRec*>(h->d_chunk[half].p);
+    a.pixels = d + recs_bytes;
+    a.images = reinterpret_cast<const DepthImageRec*>(d);
     a.tables = h->d_tables.p;
     a.out = h->d_images.p;
     a.depth_scale = h->cfg.depth_scale;
@@ -163,49 +153,14 @@ void uzl_depthfilter_cfg_default(uzl_depthfilter_cfg* c)
 
 int uzl_depthfilter_create(const uzl_depthfilter_cfg* cfg, uzl_depthfilter** out)
 {
-    if (!out) return UZL_ERR_BAD_ARG;
-    *out = nullptr;
-    uzl_depthfilter_cfg c;
-    if (cfg) c = *cfg; else uzl_depthfilter_cfg_default(&c);
-    if (check_cfg(c) != UZL_OK) return UZL_ERR_BAD_ARG;
-    if (check_device(c.device) != UZL_OK) return UZL_ERR_NO_DEVICE;
-    uzl_depthfilter* h = new (std::nothrow) uzl_depthfilter();
-    if (!h) return UZL_ERR_OOM;
-    h->cfg = c;
-    try {
-        open_handle_stream(c.device, false, &h->stream);
-        for (int i = 0; i < 2; i++) UZL_HIP(hipEventCreateWithFlags(&h->copied[i], hipEventDisableTiming));
-    } catch (...) {
-        const int code = caught_status(h->last_error);
-        for (int i = 0; i < 2; i++) if (h->copied[i]) (void)hipEventDestroy(h->copied[i]);
-        close_handle_stream(c.device, h->stream);
-        delete h;
-        return code;
-    }
-    *out = h;
-    return UZL_OK;
+    return create_handle(cfg, uzl_depthfilter_cfg_default, out, check_cfg, [](uzl_depthfilter* h) { h->stage.create(); });
 }
 
-void uzl_depthfilter_destroy(uzl_depthfilter* h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->cfg.device);
-    for (int i = 0; i < 2; i++) if (h->copied[i]) (void)hipEventDestroy(h->copied[i]);
-    close_handle_stream(h->cfg.device, h->stream);
-    delete h;
-}
+void uzl_depthfilter_destroy(uzl_depthfilter* h) { destroy_handle(h); }
 
 const char* uzl_depthfilter_last_error(uzl_depthfilter* h) { return last_error_of(h); }
 
-int uzl_depthfilter_set_config(uzl_depthfilter* h, const uzl_depthfilter_cfg* cfg)
-{
-    UZL_GUARD_BEGIN(h)
-    if (!cfg || check_cfg(*cfg) != UZL_OK) return fail(h, UZL_ERR_BAD_ARG, "bad config");
-    if (cfg->device != h->cfg.device) return fail(h, UZL_ERR_BAD_ARG, "the device of a handle cannot change");
-    h->cfg = *cfg;
-    return UZL_OK;
-    UZL_GUARD_END(h)
-}
+int uzl_depthfilter_set_config(uzl_depthfilter* h, const uzl_depthfilter_cfg* cfg) { return set_config_of(h, cfg, check_cfg); }
 
 int uzl_depthfilter_refine(uzl_depthfilter* h, int32_t n_images, const uzl_depth_image* images, const uzl_guide_image* guides)
 {
@@ -228,20 +183,10 @@ int uzl_depthfilter_refine(uzl_depthfilter* h, int32_t n_images, const uzl_depth
     h->resident.swap(set);
     if (h->cfg.use_bilateral_filter) upload_tables(h);
     h->d_images.reserve(std::max<size_t>(floats, 1));
-    int half = 0;
-    for (int32_t i0 = 0; i0 < n_images;) {
-        int32_t i1 = i0;
-        size_t bytes = 0;
-        while (i1 < n_images && i1 - i0 < kDepthChunkImages) {
-            const size_t nb = align256(depth_image_bytes(images[i1])) + (h->cfg.use_bilateral_filter ? align256(guide_bytes(guides[i1])) : 0);
-            if (i1 > i0 && bytes + nb > kDepthChunkBytes) break;
-            bytes += nb;
-            i1++;
-        }
-        run_chunk(h, images, guides, i0, i1, half);
-        half ^= 1;
-        i0 = i1;
-    }
+    const std::vector<int32_t> first = plan_chunks([&](int32_t i) {
+        return align256(depth_image_bytes(images[i])) + (h->cfg.use_bilateral_filter ? align256(guide_bytes(guides[i])) : 0);
+    }, n_images, kStageChunkBytes, kStageChunkImages);
+    for (size_t k = 0; k + 1 < first.size(); k++) run_chunk(h, images, guides, first[k], first[k + 1], (int)(k & 1));
     UZL_HIP(hipStreamSynchronize(h->stream));              // the caller's images are free again, the set is complete
     h->have = true;
     return UZL_OK;

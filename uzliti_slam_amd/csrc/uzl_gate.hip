@@ -27,7 +27,7 @@ using namespace uzl;
 
 struct uzl_gate : HandleBase {
     uzl_gate_cfg cfg;
-    hipStream_t stream = nullptr;
+    HandleStream stream;
     int32_t n = 0;
     std::vector<double> poses;
     std::vector<uint8_t> merged;
@@ -125,34 +125,11 @@ void uzl_gate_cfg_default(uzl_gate_cfg* c)
 
 int uzl_gate_create(const uzl_gate_cfg* cfg, uzl_gate** out)
 {
-    if (!out) return UZL_ERR_BAD_ARG;
-    *out = nullptr;
-    uzl_gate_cfg c;
-    if (cfg) c = *cfg; else uzl_gate_cfg_default(&c);
-    if (check_device(c.device) != UZL_OK) return UZL_ERR_NO_DEVICE;
-    uzl_gate* h = new (std::nothrow) uzl_gate();
-    if (!h) return UZL_ERR_OOM;
-    h->cfg = c;
-    h->dbg_on = diag_flag("UZL_GATE_DBG");
-    try {
-        open_handle_stream(c.device, false, &h->stream);
-    } catch (...) {
-        const int code = caught_status(h->last_error);
-        close_handle_stream(c.device, h->stream);
-        delete h;
-        return code;
-    }
-    *out = h;
-    return UZL_OK;
+    return create_handle(cfg, uzl_gate_cfg_default, out, [](const uzl_gate_cfg&) { return UZL_OK; },
+                         [](uzl_gate* h) { h->dbg_on = diag_flag("UZL_GATE_DBG"); });
 }
 
-void uzl_gate_destroy(uzl_gate* h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->cfg.device);
-    close_handle_stream(h->cfg.device, h->stream);
-    delete h;
-}
+void uzl_gate_destroy(uzl_gate* h) { destroy_handle(h); }
 
 const char* uzl_gate_last_error(uzl_gate* h) { return last_error_of(h); }
 

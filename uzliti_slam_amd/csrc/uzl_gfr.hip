@@ -30,7 +30,7 @@ using namespace uzl;
 
 struct uzl_gfr : HandleBase {
     uzl_gfr_cfg cfg;
-    hipStream_t stream = nullptr;
+    HandleStream stream;
     int32_t type = -1;                              // GlobalFeatureRepository::descriptor_
     int32_t bytes = 0, chunks = 0;                  // of the stored features (free again while F == 0)
     int32_t F = 0, L = 0;                           // features, link entries
@@ -186,38 +186,17 @@ void uzl_gfr_cfg_default(uzl_gfr_cfg* c)
 
 int uzl_gfr_create(const uzl_gfr_cfg* cfg, uzl_gfr** out)
 {
-    if (!out) return UZL_ERR_BAD_ARG;
-    *out = nullptr;
-    uzl_gfr_cfg c;
-    if (cfg) c = *cfg; else uzl_gfr_cfg_default(&c);
-    if (std::isnan(c.T) || std::isnan(c.min_time_gap) || c.k_nearest_neighbors < 0 || c.k_nearest_neighbors > kGfrMaxK ||
-        c.max_distance < 1 || c.max_distance > kGfrMaxDistance || c.initial_features < 1 || c.initial_features > kGfrMaxInitial)
-        return UZL_ERR_BAD_ARG;
-    if (check_device(c.device) != UZL_OK) return UZL_ERR_NO_DEVICE;
-    uzl_gfr* h = new (std::nothrow) uzl_gfr();
-    if (!h) return UZL_ERR_OOM;
-    h->cfg = c;
-    h->cap_f = h->cap_l = (size_t)c.initial_features;
-    try {
-        open_handle_stream(c.device, false, &h->stream);
+    return create_handle(cfg, uzl_gfr_cfg_default, out, [](const uzl_gfr_cfg& c) {
+        return std::isnan(c.T) || std::isnan(c.min_time_gap) || c.k_nearest_neighbors < 0 || c.k_nearest_neighbors > kGfrMaxK ||
+                       c.max_distance < 1 || c.max_distance > kGfrMaxDistance || c.initial_features < 1 || c.initial_features > kGfrMaxInitial
+                   ? UZL_ERR_BAD_ARG : UZL_OK;
+    }, [](uzl_gfr* h) {
+        h->cap_f = h->cap_l = (size_t)h->cfg.initial_features;
         h->d_res.reserve(2); h->h_res.reserve(2);
-    } catch (...) {
-        const int code = caught_status(h->last_error);
-        close_handle_stream(c.device, h->stream);
-        delete h;
-        return code;
-    }
-    *out = h;
-    return UZL_OK;
+    });
 }
 
-void uzl_gfr_destroy(uzl_gfr* h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->cfg.device);
-    close_handle_stream(h->cfg.device, h->stream);
-    delete h;
-}
+void uzl_gfr_destroy(uzl_gfr* h) { destroy_handle(h); }
 
 const char* uzl_gfr_last_error(uzl_gfr* h) { return last_error_of(h); }
 

@@ -27,7 +27,7 @@ using namespace uzl;
 
 struct uzl_gist : HandleBase {
     uzl_gist_cfg cfg;
-    hipStream_t stream = nullptr;
+    HandleStream stream;
     int32_t bytes = 0, stride = 0;                 // fixed by the first indexed descriptor
     DevBuf<uint8_t> d_store, d_live, d_query;
     DevBuf<int2> d_out; DevBuf<int32_t> d_out_n;
@@ -172,35 +172,12 @@ void uzl_gist_cfg_default(uzl_gist_cfg* c)
 
 int uzl_gist_create(const uzl_gist_cfg* cfg, uzl_gist** out)
 {
-    if (!out) return UZL_ERR_BAD_ARG;
-    *out = nullptr;
-    uzl_gist_cfg c;
-    if (cfg) c = *cfg; else uzl_gist_cfg_default(&c);
-    if (std::isnan(c.T) || c.k_nearest_neighbors < 0 || c.k_nearest_neighbors > kGistMaxK) return UZL_ERR_BAD_ARG;
-    if (check_device(c.device) != UZL_OK) return UZL_ERR_NO_DEVICE;
-    uzl_gist* h = new (std::nothrow) uzl_gist();
-    if (!h) return UZL_ERR_OOM;
-    h->cfg = c;
-    try {
-        open_handle_stream(c.device, false, &h->stream);
-        h->d_query.reserve(kGistMaxBytes);
-    } catch (...) {
-        const int code = caught_status(h->last_error);
-        close_handle_stream(c.device, h->stream);
-        delete h;
-        return code;
-    }
-    *out = h;
-    return UZL_OK;
+    return create_handle(cfg, uzl_gist_cfg_default, out, [](const uzl_gist_cfg& c) {
+        return std::isnan(c.T) || c.k_nearest_neighbors < 0 || c.k_nearest_neighbors > kGistMaxK ? UZL_ERR_BAD_ARG : UZL_OK;
+    }, [](uzl_gist* h) { h->d_query.reserve(kGistMaxBytes); });
 }
 
-void uzl_gist_destroy(uzl_gist* h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->cfg.device);
-    close_handle_stream(h->cfg.device, h->stream);
-    delete h;
-}
+void uzl_gist_destroy(uzl_gist* h) { destroy_handle(h); }
 
 const char* uzl_gist_last_error(uzl_gist* h) { return last_error_of(h); }
 

@@ -6,14 +6,12 @@
 // Host work per build: geometry, S = P * D per scan, each scan's conservative cell box, and the bins (scans and known-free squares
 // per tile, by count + prefix sum), uploaded in one copy; the device does every beam (grid_kernels.hip).
 #include "grid_types.hpp"
+#include "scan_store.hpp"
 #include "uzl_common.hpp"
 #include "uzl_streams.hpp"
 
 #include <algorithm>
 #include <cmath>
-#include <map>
-#include <new>
-#include <tuple>
 
 namespace uzl {
 
@@ -38,15 +36,12 @@ using namespace uzl;
 struct uzl_grid : HandleBase {
     uzl_grid_cfg cfg;            // as set
     uzl_grid_cfg gcfg;           // of the last full build (extend keeps it)
-    hipStream_t stream = nullptr;
+    HandleStream stream;
     bool built = false;
     GridGeom geom;
     uzl_grid_info info{};
     std::vector<GridScanHost> scans;
-    int64_t n_ranges = 0, n_trig = 0;
-    std::map<std::tuple<uint32_t, uint32_t, int32_t>, int64_t> tables;   // (angle_min bits, increment bits, n) -> trig_off
-    DevBuf<float> d_ranges;
-    DevBuf<double2> d_trig;
+    ScanStore store;             // the ranges and their (cos, sin) tables
     DevBuf<uint32_t> d_hits, d_passes;
     DevBuf<int8_t> d_grid;
     DevBuf<uint8_t> d_work;
@@ -76,12 +71,6 @@ void compose(const double* P, const double* D, double* S)
         for (int j = 0; j < 3; j++) S[4 * i + j] = (P[4 * i] * D[j] + P[4 * i + 1] * D[4 + j]) + P[4 * i + 2] * D[8 + j];
         S[4 * i + 3] = ((P[4 * i] * D[3] + P[4 * i + 1] * D[7]) + P[4 * i + 2] * D[11]) + P[4 * i + 3];
     }
-}
-
-bool finite12(const double* v)
-{
-    for (int i = 0; i < 12; i++) if (!std::isfinite(v[i])) return false;
-    return true;
 }
 
 // the nodes a call adds: present, < n_nodes, >= first
@@ -222,56 +211,28 @@ struct ScanIn {
     float angle_min, angle_increment, range_min;
 };
 
-// Append checked scans to the store: new (cos, sin) tables from the host's libm (contract step 3), the arenas grown, the `total`
-// ranges put at the arena's end by copy(dst, stream) - from the host (uzl_grid_add_scans) or from device memory
-// (grid_append_device) - and the bookkeeping, which changes only when everything before it succeeded.
+// Append checked scans to the store (scan_store.hpp; the tables are contract step 3): the `total` ranges are put at the arena's
+// end by copy(dst, stream) - from the host (uzl_grid_add_scans) or from device memory (grid_append_device) - and the bookkeeping
+// changes only when everything before it succeeded.
 template <typename Copy>
 void append(uzl_grid* h, const std::vector<ScanIn>& in, int64_t total, int32_t* first_scan, Copy&& copy)
 {
-    const int32_t n = (int32_t)in.size();
     UZL_HIP(hipSetDevice(h->cfg.device));
     hipStream_t st = h->stream;
-    std::vector<double2> trig;
-    std::vector<int64_t> toff(n);
-    auto tables = h->tables;
-    int64_t n_trig = h->n_trig;
-    for (int32_t i = 0; i < n; i++) {
-        const ScanIn& s = in[i];
-        uint32_t ka, ki;
-        memcpy(&ka, &s.angle_min, 4); memcpy(&ki, &s.angle_increment, 4);
-        const auto key = std::make_tuple(ka, ki, s.n);
-        auto it = tables.find(key);
-        if (it == tables.end()) {
-            it = tables.emplace(key, n_trig).first;
-            for (int32_t b = 0; b < s.n; b++) {
-                const double th = (double)s.angle_min + (double)b * (double)s.angle_increment;
-                trig.push_back(make_double2(std::cos(th), std::sin(th)));
-            }
-            n_trig += s.n;
-        }
-        toff[i] = it->second;
-    }
-    h->d_ranges.reserve((size_t)std::max<int64_t>(h->n_ranges + total, 1), true, st);
-    h->d_trig.reserve((size_t)std::max<int64_t>(n_trig, 1), true, st);
-    if (!trig.empty())
-        UZL_HIP(hipMemcpyAsync(h->d_trig.p + h->n_trig, trig.data(), trig.size() * sizeof(double2), hipMemcpyHostToDevice, st));
-    if (total) copy(h->d_ranges.p + h->n_ranges, st);
+    ScanStore::Pending p = h->store.begin(st, in, total);
+    if (total) copy(p.dst, st);
     UZL_HIP(hipStreamSynchronize(st));
-    if (first_scan) *first_scan = (int32_t)h->scans.size();
-    int64_t o = h->n_ranges;
-    for (int32_t i = 0; i < n; i++) {
-        GridScanHost g;
+    std::vector<GridScanHost> recs(in.size());
+    for (size_t i = 0; i < in.size(); i++) {
+        GridScanHost& g = recs[i];
         g.node = in[i].node; g.n = in[i].n; memcpy(g.D, in[i].D, sizeof(g.D));
-        g.range_min = in[i].range_min; g.ranges_off = o; g.trig_off = toff[i];
-        o += g.n;
-        h->scans.push_back(g);
+        g.range_min = in[i].range_min; g.ranges_off = p.values_off[i]; g.trig_off = p.trig_off[i];
     }
-    h->n_ranges = o;
-    h->tables.swap(tables);
-    h->n_trig = n_trig;
+    const size_t have = h->scans.size();
+    h->scans.insert(h->scans.end(), recs.begin(), recs.end());
+    h->store.commit(p);
+    if (first_scan) *first_scan = (int32_t)have;
 }
-
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
 // Upload the plan in one copy and run it; fills the call's totals into h->info.
 void run(uzl_grid* h, const Plan& p, bool fresh)
@@ -318,12 +279,12 @@ void run(uzl_grid* h, const Plan& p, bool fresh)
     const GridScanRec* recs = reinterpret_cast<const GridScanRec*>(d + off[0]);
 
     GridStatsArgs sa;
-    sa.ranges = h->d_ranges.p; sa.scans = recs; sa.range_max = c.range_max; sa.valid_total = h->d_totals.p;
+    sa.ranges = h->store.d_values.p; sa.scans = recs; sa.range_max = c.range_max; sa.valid_total = h->d_totals.p;
     launch_grid_stats(sa, (int)p.recs.size(), s);
     UZL_HIP(hipGetLastError());
 
     GridTileArgs a;
-    a.ranges = h->d_ranges.p; a.trig = h->d_trig.p; a.scans = recs;
+    a.ranges = h->store.d_values.p; a.trig = h->store.d_trig.p; a.scans = recs;
     a.tiles = reinterpret_cast<const int32_t*>(d + off[1]);
     a.ent_start = reinterpret_cast<const int32_t*>(d + off[2]);
     a.ent_scan = reinterpret_cast<const int32_t*>(d + off[3]);
@@ -383,46 +344,14 @@ void uzl_grid_cfg_default(uzl_grid_cfg* c)
 
 int uzl_grid_create(const uzl_grid_cfg* cfg, uzl_grid** out)
 {
-    if (!out) return UZL_ERR_BAD_ARG;
-    *out = nullptr;
-    uzl_grid_cfg c;
-    if (cfg) c = *cfg; else uzl_grid_cfg_default(&c);
-    if (check_cfg(c) != UZL_OK) return UZL_ERR_BAD_ARG;
-    if (check_device(c.device) != UZL_OK) return UZL_ERR_NO_DEVICE;
-    uzl_grid* h = new (std::nothrow) uzl_grid();
-    if (!h) return UZL_ERR_OOM;
-    h->cfg = h->gcfg = c;
-    try {
-        open_handle_stream(c.device, false, &h->stream);
-    } catch (...) {
-        const int code = caught_status(h->last_error);
-        close_handle_stream(c.device, h->stream);
-        delete h;
-        return code;
-    }
-    *out = h;
-    return UZL_OK;
+    return create_handle(cfg, uzl_grid_cfg_default, out, check_cfg, [](uzl_grid* h) { h->gcfg = h->cfg; });
 }
 
-void uzl_grid_destroy(uzl_grid* h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->cfg.device);
-    close_handle_stream(h->cfg.device, h->stream);
-    delete h;
-}
+void uzl_grid_destroy(uzl_grid* h) { destroy_handle(h); }
 
 const char* uzl_grid_last_error(uzl_grid* h) { return last_error_of(h); }
 
-int uzl_grid_set_config(uzl_grid* h, const uzl_grid_cfg* cfg)
-{
-    UZL_GUARD_BEGIN(h)
-    if (!cfg || check_cfg(*cfg) != UZL_OK) return fail(h, UZL_ERR_BAD_ARG, "bad config");
-    if (cfg->device != h->cfg.device) return fail(h, UZL_ERR_BAD_ARG, "the device of a handle cannot change");
-    h->cfg = *cfg;
-    return UZL_OK;
-    UZL_GUARD_END(h)
-}
+int uzl_grid_set_config(uzl_grid* h, const uzl_grid_cfg* cfg) { return set_config_of(h, cfg, check_cfg); }
 
 int uzl_grid_add_scans(uzl_grid* h, int32_t n, const uzl_grid_scan* scans, int32_t* first_scan)
 {
@@ -439,7 +368,7 @@ int uzl_grid_add_scans(uzl_grid* h, int32_t n, const uzl_grid_scan* scans, int32
         in[i] = ScanIn{s.node, s.n_ranges, s.displacement, s.angle_min, s.angle_increment, s.range_min};
         total += s.n_ranges;
     }
-    if (h->n_ranges + total >= ((int64_t)1 << 40)) return fail(h, UZL_ERR_BAD_ARG, "too many ranges");
+    if (h->store.n_values + total >= ((int64_t)1 << 40)) return fail(h, UZL_ERR_BAD_ARG, "too many ranges");
     append(h, in, total, first_scan, [&](float* dst, hipStream_t st) {
         h->h_work.reserve((size_t)total * 4);
         float* w = reinterpret_cast<float*>(h->h_work.p);
@@ -553,7 +482,7 @@ int uzl::grid_append_device(uzl_grid* h, int device, int32_t n_scans, int32_t n_
     if (!std::isfinite(angle_min) || !std::isfinite(angle_increment)) return fail(h, UZL_ERR_BAD_ARG, "non-finite scan angle or displacement");
     if (!(range_min >= 0.f)) return fail(h, UZL_ERR_BAD_ARG, "range_min negative or NaN");
     const int64_t total = (int64_t)n_scans * n_beams;
-    if (h->n_ranges + total >= ((int64_t)1 << 40)) return fail(h, UZL_ERR_BAD_ARG, "too many ranges");
+    if (h->store.n_values + total >= ((int64_t)1 << 40)) return fail(h, UZL_ERR_BAD_ARG, "too many ranges");
     append(h, in, total, first_scan, [&](float* dst, hipStream_t st) {
         UZL_HIP(hipMemcpyAsync(dst, d_ranges, (size_t)total * 4, hipMemcpyDeviceToDevice, st));
     });

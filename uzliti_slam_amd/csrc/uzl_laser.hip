@@ -7,25 +7,20 @@
 // rotation as (cos, sin) of the host's libm), runs one workgroup per pair (laser_kernels.hip) and finishes each result on the host:
 // theta by atan2, the information block, the plausibility test.
 #include "laser_types.hpp"
+#include "scan_store.hpp"
 #include "uzl_common.hpp"
 #include "uzl_streams.hpp"
 
 #include <algorithm>
 #include <cmath>
-#include <map>
-#include <new>
-#include <tuple>
 
 using namespace uzl;
 
 struct uzl_laser : HandleBase {
     uzl_laser_cfg cfg;
-    hipStream_t stream = nullptr;
+    HandleStream stream;
     std::vector<LaserScanRec> scans;
-    int64_t n_values = 0, n_trig = 0;
-    std::map<std::tuple<uint32_t, uint32_t, int32_t>, int64_t> tables;   // (angle_min bits, increment bits, n) -> trig_off
-    DevBuf<float> d_values;
-    DevBuf<double2> d_trig;
+    ScanStore store;             // the readings and their (cos, sin) tables
     DevBuf<LaserScanRec> d_scans;
     // work, reused between calls
     PinBuf<uint8_t> h_work;
@@ -62,56 +57,32 @@ int check_scan(uzl_laser* h, const ScanIn& s)
     return UZL_OK;
 }
 
-// Append checked scans: new tables from the host's libm (contract step 1), the arenas grown, the `total` values put at the arena's
-// end by copy(dst, stream), the records, and the bookkeeping, which changes only when everything before it succeeded.
+// Append checked scans to the store (scan_store.hpp; the tables are contract step 1): the `total` values are put at the arena's
+// end by copy(dst, stream), the records go up on the same stream, and the bookkeeping changes only when everything before it
+// succeeded.
 template <typename Copy>
 void append(uzl_laser* h, const std::vector<ScanIn>& in, int64_t total, int32_t* first_scan, Copy&& copy)
 {
-    const int32_t n = (int32_t)in.size();
+    const size_t n = in.size(), have = h->scans.size();
     UZL_HIP(hipSetDevice(h->cfg.device));
     hipStream_t st = h->stream;
-    std::vector<double2> trig;
+    ScanStore::Pending p = h->store.begin(st, in, total);
     std::vector<LaserScanRec> recs(n);
-    auto tables = h->tables;
-    int64_t n_trig = h->n_trig, o = h->n_values;
-    for (int32_t i = 0; i < n; i++) {
-        const ScanIn& s = in[i];
-        uint32_t ka, ki;
-        memcpy(&ka, &s.angle_min, 4); memcpy(&ki, &s.angle_increment, 4);
-        const auto key = std::make_tuple(ka, ki, s.n);
-        auto it = tables.find(key);
-        if (it == tables.end()) {
-            it = tables.emplace(key, n_trig).first;
-            for (int32_t b = 0; b < s.n; b++) {
-                const double th = (double)s.angle_min + (double)b * (double)s.angle_increment;
-                trig.push_back(make_double2(std::cos(th), std::sin(th)));
-            }
-            n_trig += s.n;
-        }
-        recs[i] = LaserScanRec{o, it->second, s.n, s.range_min, s.range_max, 0};
-        o += s.n;
-    }
-    const size_t have = h->scans.size();
-    h->d_values.reserve((size_t)std::max<int64_t>(h->n_values + total, 1), true, st);
-    h->d_trig.reserve((size_t)std::max<int64_t>(n_trig, 1), true, st);
+    for (size_t i = 0; i < n; i++) recs[i] = LaserScanRec{p.values_off[i], p.trig_off[i], in[i].n, in[i].range_min, in[i].range_max, 0};
     h->d_scans.reserve(std::max<size_t>(have + n, 1), true, st);
-    if (!trig.empty())
-        UZL_HIP(hipMemcpyAsync(h->d_trig.p + h->n_trig, trig.data(), trig.size() * sizeof(double2), hipMemcpyHostToDevice, st));
-    if (n) UZL_HIP(hipMemcpyAsync(h->d_scans.p + have, recs.data(), (size_t)n * sizeof(LaserScanRec), hipMemcpyHostToDevice, st));
-    if (total) copy(h->d_values.p + h->n_values, st);
+    if (n) UZL_HIP(hipMemcpyAsync(h->d_scans.p + have, recs.data(), n * sizeof(LaserScanRec), hipMemcpyHostToDevice, st));
+    if (total) copy(p.dst, st);
     UZL_HIP(hipStreamSynchronize(st));
-    if (first_scan) *first_scan = (int32_t)have;
     h->scans.insert(h->scans.end(), recs.begin(), recs.end());
-    h->n_values = o;
-    h->tables.swap(tables);
-    h->n_trig = n_trig;
+    h->store.commit(p);
+    if (first_scan) *first_scan = (int32_t)have;
 }
 
 int check_pair(uzl_laser* h, const uzl_laser_pair& p)
 {
     const int32_t ns = (int32_t)h->scans.size();
     if (p.scan_from < 0 || p.scan_from >= ns || p.scan_to < 0 || p.scan_to >= ns) return fail(h, UZL_ERR_BAD_ARG, "scan index out of range");
-    for (int k = 0; k < 12; k++) if (!std::isfinite(p.first_guess[k])) return fail(h, UZL_ERR_BAD_ARG, "non-finite first guess");
+    if (!finite12(p.first_guess)) return fail(h, UZL_ERR_BAD_ARG, "non-finite first guess");
     return UZL_OK;
 }
 
@@ -119,7 +90,7 @@ LaserIcpArgs icp_args(const uzl_laser* h)
 {
     const uzl_laser_cfg& c = h->cfg;
     LaserIcpArgs a{};
-    a.values = h->d_values.p; a.trig = h->d_trig.p; a.scans = h->d_scans.p;
+    a.values = h->store.d_values.p; a.trig = h->store.d_trig.p; a.scans = h->d_scans.p;
     a.max_corr_sq = c.max_correspondence_dist * c.max_correspondence_dist;
     a.max_perc = c.outliers_max_perc; a.adaptive_order = c.outliers_adaptive_order; a.adaptive_mult = c.outliers_adaptive_mult;
     a.fail_fraction = c.fail_fraction;
@@ -174,48 +145,14 @@ void uzl_laser_cfg_default(uzl_laser_cfg* c)
 
 int uzl_laser_create(const uzl_laser_cfg* cfg, uzl_laser** out)
 {
-    if (!out) return UZL_ERR_BAD_ARG;
-    *out = nullptr;
-    uzl_laser_cfg c;
-    if (cfg) c = *cfg; else uzl_laser_cfg_default(&c);
-    if (check_cfg(c) != UZL_OK) return UZL_ERR_BAD_ARG;
-    if (check_device(c.device) != UZL_OK) return UZL_ERR_NO_DEVICE;
-    uzl_laser* h = new (std::nothrow) uzl_laser();
-    if (!h) return UZL_ERR_OOM;
-    h->cfg = c;
-    try {
-        open_handle_stream(c.device, false, &h->stream);
-        UZL_HIP(hipSetDevice(c.device));
-        laser_icp_prepare();
-    } catch (...) {
-        const int code = caught_status(h->last_error);
-        close_handle_stream(c.device, h->stream);
-        delete h;
-        return code;
-    }
-    *out = h;
-    return UZL_OK;
+    return create_handle(cfg, uzl_laser_cfg_default, out, check_cfg, [](uzl_laser*) { laser_icp_prepare(); });
 }
 
-void uzl_laser_destroy(uzl_laser* h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->cfg.device);
-    close_handle_stream(h->cfg.device, h->stream);
-    delete h;
-}
+void uzl_laser_destroy(uzl_laser* h) { destroy_handle(h); }
 
 const char* uzl_laser_last_error(uzl_laser* h) { return last_error_of(h); }
 
-int uzl_laser_set_config(uzl_laser* h, const uzl_laser_cfg* cfg)
-{
-    UZL_GUARD_BEGIN(h)
-    if (!cfg || check_cfg(*cfg) != UZL_OK) return fail(h, UZL_ERR_BAD_ARG, "bad config");
-    if (cfg->device != h->cfg.device) return fail(h, UZL_ERR_BAD_ARG, "the device of a handle cannot change");
-    h->cfg = *cfg;
-    return UZL_OK;
-    UZL_GUARD_END(h)
-}
+int uzl_laser_set_config(uzl_laser* h, const uzl_laser_cfg* cfg) { return set_config_of(h, cfg, check_cfg); }
 
 int uzl_laser_add_scans(uzl_laser* h, int32_t n, const uzl_laser_scan* scans, int32_t* first_scan)
 {
@@ -230,7 +167,7 @@ int uzl_laser_add_scans(uzl_laser* h, int32_t n, const uzl_laser_scan* scans, in
         if (!s.values) return fail(h, UZL_ERR_BAD_ARG, "null values");
         total += s.n_beams;
     }
-    if ((int64_t)h->scans.size() + n > INT32_MAX || h->n_values + total >= ((int64_t)1 << 40)) return fail(h, UZL_ERR_BAD_ARG, "too many scans");
+    if ((int64_t)h->scans.size() + n > INT32_MAX || h->store.n_values + total >= ((int64_t)1 << 40)) return fail(h, UZL_ERR_BAD_ARG, "too many scans");
     append(h, in, total, first_scan, [&](float* dst, hipStream_t st) {
         h->h_work.reserve((size_t)total * 4);
         float* w = reinterpret_cast<float*>(h->h_work.p);
@@ -329,7 +266,7 @@ int uzl::laser_append_device(uzl_laser* h, int device, int32_t n_scans, int32_t 
     if (n_scans > 0)
         if (int rc = check_scan(h, one)) return rc;
     const int64_t total = (int64_t)n_scans * n_beams;
-    if ((int64_t)h->scans.size() + n_scans > INT32_MAX || h->n_values + total >= ((int64_t)1 << 40)) return fail(h, UZL_ERR_BAD_ARG, "too many scans");
+    if ((int64_t)h->scans.size() + n_scans > INT32_MAX || h->store.n_values + total >= ((int64_t)1 << 40)) return fail(h, UZL_ERR_BAD_ARG, "too many scans");
     append(h, std::vector<ScanIn>(n_scans, one), total, first_scan, [&](float* dst, hipStream_t st) {
         UZL_HIP(hipMemcpyAsync(dst, d_values, (size_t)total * 4, hipMemcpyDeviceToDevice, st));
     });

@@ -6,6 +6,7 @@
 // chunk's image records in front of its pixels so that a chunk is one copy; the per-image bins (min s / max s, u32) and the scans
 // stay in HBM, and uzl_laserline_to_grid hands the scans to a grid handle's store without leaving the device.
 #include "grid_types.hpp"
+#include "image_stager.hpp"
 #include "laser_types.hpp"
 #include "laserline_types.hpp"
 #include "uzl_common.hpp"
@@ -13,12 +14,8 @@
 
 #include <algorithm>
 #include <cmath>
-#include <new>
 
 namespace uzl {
-
-constexpr size_t kLaserChunkBytes = (size_t)64 << 20;   // pixels of one staging half (an image larger than this gets a half of its own size)
-constexpr int kLaserChunkImages = 8192;                 // images of one chunk (gridDim.y)
 
 // contract step 1
 struct LaserGrid {
@@ -32,8 +29,7 @@ using namespace uzl;
 
 struct uzl_laserline : HandleBase {
     uzl_laserline_cfg cfg;
-    hipStream_t stream = nullptr;
-    hipEvent_t copied[2] = {nullptr, nullptr};   // the copy out of staging half i has finished
+    HandleStream stream;
     // the table of the angular grid last used
     bool have_table = false;
     LaserGrid table_grid{};
@@ -46,8 +42,7 @@ struct uzl_laserline : HandleBase {
     DevBuf<float> d_ranges, d_intensities;
     DevBuf<double> d_centers;
     // work
-    PinBuf<uint8_t> h_chunk[2];
-    DevBuf<uint8_t> d_chunk[2];
+    ImageStager stage;
     DevBuf<uint32_t> d_smin, d_smax;
     DevBuf<int32_t> d_first;
 };
@@ -75,8 +70,6 @@ int check_cfg(const uzl_laserline_cfg& c)
     return angular_grid(c, &g) ? UZL_OK : UZL_ERR_BAD_ARG;
 }
 
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-
 int bytes_per_pixel(int32_t encoding) { return encoding == UZL_DEPTH_F32_M ? 4 : 2; }
 
 }  // namespace
@@ -99,8 +92,7 @@ int uzl::depth_images_check(HandleBase* h, int32_t n, const uzl_depth_image* ima
             return fail(h, UZL_ERR_BAD_ARG, "step smaller than a row, or height * step beyond 2^31");
         if (!std::isfinite(im.fx) || !std::isfinite(im.fy) || im.fx == 0. || im.fy == 0. || !std::isfinite(im.cx) || !std::isfinite(im.cy))
             return fail(h, UZL_ERR_BAD_ARG, "fx / fy zero or non-finite, or cx / cy non-finite");
-        for (int k = 0; k < 12; k++)
-            if (!std::isfinite(im.camera_transform[k])) return fail(h, UZL_ERR_BAD_ARG, "non-finite camera_transform entry");
+        if (!finite12(im.camera_transform)) return fail(h, UZL_ERR_BAD_ARG, "non-finite camera_transform entry");
         if (i > 0 && im.group != images[i - 1].group && im.group != images[i - 1].group + 1)
             return fail(h, UZL_ERR_BAD_ARG, "groups are not ascending and contiguous");
     }
@@ -160,15 +152,11 @@ void launch_bin(uzl_laserline* h, const LaserImageRec* d_recs, const uint8_t* d_
 // Images [i0, i1) through staging half `half`: records and pixels packed, one copy, one launch of the bin kernel.
 void run_chunk(uzl_laserline* h, const uzl_depth_image* images, int32_t i0, int32_t i1, int half, const LaserGrid& g)
 {
-    hipStream_t s = h->stream;
     const size_t recs_bytes = align256((size_t)(i1 - i0) * sizeof(LaserImageRec));
     size_t total = recs_bytes;
     int64_t rows = 0;
     for (int32_t i = i0; i < i1; i++) { total += align256(depth_image_bytes(images[i])); rows += images[i].height; }
-    UZL_HIP(hipEventSynchronize(h->copied[half]));         // the previous copy out of this half
-    h->h_chunk[half].reserve(total);
-    h->d_chunk[half].reserve(total);
-    uint8_t* w = h->h_chunk[half].p;
+    uint8_t* w = h->stage.open(half, total);
     LaserImageRec* recs = reinterpret_cast<LaserImageRec*>(w);
     size_t off = 0;
     int32_t max_height = 0;
@@ -186,9 +174,8 @@ void run_chunk(uzl_laserline* h, const uzl_depth_image* images, int32_t i0, int3
         off += align256(nb);
         max_height = std::max(max_height, im.height);
     }
-    UZL_HIP(hipMemcpyAsync(h->d_chunk[half].p, w, total, hipMemcpyHostToDevice, s));
-    UZL_HIP(hipEventRecord(h->copied[half], s));
-    launch_bin(h, reinterpret_cast<const LaserImageRec*>(h->d_chunk[half].p), h->d_chunk[half].p + recs_bytes, i1 - i0, rows, max_height, g);
+    const uint8_t* d = h->stage.send(half, total, h->stream);
+    launch_bin(h, reinterpret_cast<const LaserImageRec*>(d), d + recs_bytes, i1 - i0, rows, max_height, g);
 }
 
 // Steps 1-9 over n_images images, image i in group group_of(i): feed(grid) queues the bin launches of every image on the handle's
@@ -250,71 +237,23 @@ void uzl_laserline_cfg_default(uzl_laserline_cfg* c)
 
 int uzl_laserline_create(const uzl_laserline_cfg* cfg, uzl_laserline** out)
 {
-    if (!out) return UZL_ERR_BAD_ARG;
-    *out = nullptr;
-    uzl_laserline_cfg c;
-    if (cfg) c = *cfg; else uzl_laserline_cfg_default(&c);
-    if (check_cfg(c) != UZL_OK) return UZL_ERR_BAD_ARG;
-    if (check_device(c.device) != UZL_OK) return UZL_ERR_NO_DEVICE;
-    uzl_laserline* h = new (std::nothrow) uzl_laserline();
-    if (!h) return UZL_ERR_OOM;
-    h->cfg = c;
-    try {
-        open_handle_stream(c.device, false, &h->stream);
-        for (int i = 0; i < 2; i++) UZL_HIP(hipEventCreateWithFlags(&h->copied[i], hipEventDisableTiming));
-        UZL_HIP(hipSetDevice(c.device));
-        laser_prepare();
-    } catch (...) {
-        const int code = caught_status(h->last_error);
-        for (int i = 0; i < 2; i++) if (h->copied[i]) (void)hipEventDestroy(h->copied[i]);
-        close_handle_stream(c.device, h->stream);
-        delete h;
-        return code;
-    }
-    *out = h;
-    return UZL_OK;
+    return create_handle(cfg, uzl_laserline_cfg_default, out, check_cfg, [](uzl_laserline* h) { h->stage.create(); laser_prepare(); });
 }
 
-void uzl_laserline_destroy(uzl_laserline* h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->cfg.device);
-    for (int i = 0; i < 2; i++) if (h->copied[i]) (void)hipEventDestroy(h->copied[i]);
-    close_handle_stream(h->cfg.device, h->stream);
-    delete h;
-}
+void uzl_laserline_destroy(uzl_laserline* h) { destroy_handle(h); }
 
 const char* uzl_laserline_last_error(uzl_laserline* h) { return last_error_of(h); }
 
-int uzl_laserline_set_config(uzl_laserline* h, const uzl_laserline_cfg* cfg)
-{
-    UZL_GUARD_BEGIN(h)
-    if (!cfg || check_cfg(*cfg) != UZL_OK) return fail(h, UZL_ERR_BAD_ARG, "bad config");
-    if (cfg->device != h->cfg.device) return fail(h, UZL_ERR_BAD_ARG, "the device of a handle cannot change");
-    h->cfg = *cfg;
-    return UZL_OK;
-    UZL_GUARD_END(h)
-}
+int uzl_laserline_set_config(uzl_laserline* h, const uzl_laserline_cfg* cfg) { return set_config_of(h, cfg, check_cfg); }
 
 int uzl_laserline_extract(uzl_laserline* h, int32_t n_images, const uzl_depth_image* images, int32_t* n_scans, int32_t* n_beams)
 {
     UZL_GUARD_BEGIN(h)
     if (int rc = depth_images_check(h, n_images, images)) return rc;
     extract_with(h, n_images, [&](int32_t i) { return images[i].group; }, [&](const LaserGrid& g) {
-        int half = 0;
-        for (int32_t i0 = 0; i0 < n_images;) {
-            int32_t i1 = i0;
-            size_t bytes = 0;
-            while (i1 < n_images && i1 - i0 < kLaserChunkImages) {
-                const size_t nb = align256(depth_image_bytes(images[i1]));
-                if (i1 > i0 && bytes + nb > kLaserChunkBytes) break;
-                bytes += nb;
-                i1++;
-            }
-            run_chunk(h, images, i0, i1, half, g);
-            half ^= 1;
-            i0 = i1;
-        }
+        const std::vector<int32_t> first = plan_chunks([&](int32_t i) { return align256(depth_image_bytes(images[i])); }, n_images,
+                                                       kStageChunkBytes, kStageChunkImages);
+        for (size_t k = 0; k + 1 < first.size(); k++) run_chunk(h, images, first[k], first[k + 1], (int)(k & 1), g);
     }, n_scans, n_beams);
     return UZL_OK;
     UZL_GUARD_END(h)
@@ -374,26 +313,36 @@ int uzl::laserline_extract_device(uzl_laserline* h, int device, int32_t n_images
     if (n_images < 0 || (n_images > 0 && (!recs || !groups || !d_pixels))) return fail(h, UZL_ERR_BAD_ARG, "bad image count or null images");
     extract_with(h, n_images, [&](int32_t i) { return groups[i]; }, [&](const LaserGrid& g) {
         if (n_images == 0) return;
-        // all records in one copy through staging half 0, then one launch per kLaserChunkImages of them
+        // all records in one copy through staging half 0, then one launch per kStageChunkImages of them
         const size_t bytes = (size_t)n_images * sizeof(LaserImageRec);
-        UZL_HIP(hipEventSynchronize(h->copied[0]));
-        h->h_chunk[0].reserve(bytes);
-        h->d_chunk[0].reserve(bytes);
+        uint8_t* w = h->stage.open(0, bytes);
         for (int32_t i = 0; i < n_images; i++) {
             recs[i].lanes = lanes_for((recs[i].width + kLaserVec - 1) / kLaserVec);
             recs[i].out = i;
         }
-        memcpy(h->h_chunk[0].p, recs, bytes);
-        UZL_HIP(hipMemcpyAsync(h->d_chunk[0].p, h->h_chunk[0].p, bytes, hipMemcpyHostToDevice, h->stream));
-        UZL_HIP(hipEventRecord(h->copied[0], h->stream));
-        for (int32_t i0 = 0; i0 < n_images; i0 += kLaserChunkImages) {
-            const int32_t i1 = std::min(n_images, i0 + kLaserChunkImages);
+        memcpy(w, recs, bytes);
+        const LaserImageRec* d_recs = reinterpret_cast<const LaserImageRec*>(h->stage.send(0, bytes, h->stream));
+        for (int32_t i0 = 0; i0 < n_images; i0 += kStageChunkImages) {
+            const int32_t i1 = std::min(n_images, i0 + kStageChunkImages);
             int64_t rows = 0;
             int32_t max_height = 0;
             for (int32_t i = i0; i < i1; i++) { rows += recs[i].height; max_height = std::max(max_height, recs[i].height); }
-            launch_bin(h, reinterpret_cast<const LaserImageRec*>(h->d_chunk[0].p) + i0, d_pixels, i1 - i0, rows, max_height, g);
+            launch_bin(h, d_recs + i0, d_pixels, i1 - i0, rows, max_height, g);
         }
     }, n_scans, n_beams);
     return UZL_OK;
     UZL_GUARD_END(h)
 }
+
+#ifdef UZL_DIAG
+// Test hook (tests/test_stage_chunks_cpu.py): plan_chunks over n items of bytes[i] bytes each.  first_out, with room for n + 1
+// entries, takes the boundaries; returns the number of chunks, or -1 for arguments plan_chunks does not take.
+extern "C" UZL_DIAG_EXPORT int uzl_debug_plan_chunks(int32_t n, const int64_t* bytes, int64_t max_bytes, int32_t max_items, int32_t* first_out)
+{
+    if (n < 0 || (n > 0 && !bytes) || max_bytes < 0 || max_items < 1 || !first_out) return -1;
+    for (int32_t i = 0; i < n; i++) if (bytes[i] < 0) return -1;
+    const std::vector<int32_t> first = uzl::plan_chunks([&](int32_t i) { return (size_t)bytes[i]; }, n, (size_t)max_bytes, max_items);
+    std::copy(first.begin(), first.end(), first_out);
+    return (int)first.size() - 1;
+}
+#endif

@@ -36,7 +36,7 @@ using namespace uzl;
 
 struct uzl_match : HandleBase {
     uzl_match_cfg cfg;
-    hipStream_t stream = nullptr;
+    HandleStream stream;
     // frame arena: one HBM allocation, frames addressed by offset so it can grow
     DevBuf<uint8_t> arena;
     size_t arena_used = 0;               // high-water mark: [0, arena_used) is handed out or on the free list
@@ -62,9 +62,9 @@ struct uzl_match : HandleBase {
     PinBuf<uint8_t> h_up;
     // uzl_match_add_frames staging: two larger halves, packed by several host threads while the other half's copy is in flight
     PinBuf<uint8_t> h_bulk;
-    hipEvent_t bulk_ev[2] = {nullptr, nullptr};
+    Event bulk_ev[2];
     bool bulk_pending[2] = {false, false};
-    hipEvent_t up_ev[2] = {nullptr, nullptr};
+    Event up_ev[2];
     bool up_pending[2] = {false, false};
     int up_half = 0;
     size_t up_used = 0;
@@ -388,36 +388,12 @@ void uzl_match_cfg_default(uzl_match_cfg* cfg)
 
 int uzl_match_create(const uzl_match_cfg* cfg, uzl_match** out)
 {
-    if (!out) return UZL_ERR_BAD_ARG;
-    *out = nullptr;
-    uzl_match_cfg c;
-    if (cfg) c = *cfg; else uzl_match_cfg_default(&c);
-    if (check_device(c.device) != UZL_OK) return UZL_ERR_NO_DEVICE;
-    uzl_match* h = new (std::nothrow) uzl_match();
-    if (!h) return UZL_ERR_OOM;
-    h->cfg = c;
-    try {
-        open_handle_stream(c.device, true, &h->stream);              // (its launch sequences run beside a solve: config 5)
-        h->arena.reserve((size_t)64 << 20);
-    } catch (...) {
-        const int code = caught_status(h->last_error);
-        close_handle_stream(c.device, h->stream);
-        delete h;
-        return code;
-    }
-    *out = h;
-    return UZL_OK;
+    // (its launch sequences run beside a solve: config 5)
+    return create_handle(cfg, uzl_match_cfg_default, out, [](const uzl_match_cfg&) { return UZL_OK; },
+                         [](uzl_match* h) { h->arena.reserve((size_t)64 << 20); }, /*beside_solver=*/true);
 }
 
-void uzl_match_destroy(uzl_match* h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->cfg.device);
-    close_handle_stream(h->cfg.device, h->stream);
-    for (auto& e : h->up_ev) if (e) (void)hipEventDestroy(e);
-    for (auto& e : h->bulk_ev) if (e) (void)hipEventDestroy(e);
-    delete h;
-}
+void uzl_match_destroy(uzl_match* h) { destroy_handle(h); }
 
 int uzl_match_set_config(uzl_match* h, const uzl_match_cfg* cfg)
 {
@@ -459,7 +435,7 @@ int uzl_match_add_frame(uzl_match* h, const uzl_frame* f, int32_t* frame_id)
         if (span <= kUpHalf) {
             if (!h->h_up.p) {
                 h->h_up.reserve(2 * kUpHalf);
-                for (auto& e : h->up_ev) UZL_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+                for (Event& e : h->up_ev) e.create();
             }
             if (h->up_used + span > kUpHalf) {                       // this half is full: close it, move to the other one once it is free
                 UZL_HIP(hipEventRecord(h->up_ev[h->up_half], h->stream));
@@ -532,7 +508,7 @@ int uzl_match_add_frames(uzl_match* h, int32_t n_frames, const uzl_frame* f, int
     }
     if (!h->h_bulk.p) {
         h->h_bulk.reserve(2 * kBulkHalf);
-        for (auto& e : h->bulk_ev) UZL_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        for (Event& e : h->bulk_ev) e.create();
     }
     const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
     std::vector<size_t> soff((size_t)n_frames);

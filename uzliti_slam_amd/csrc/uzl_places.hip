@@ -146,7 +146,7 @@ using namespace uzl;
 
 struct uzl_places : HandleBase {
     uzl_places_cfg cfg;
-    hipStream_t stream = nullptr;
+    HandleStream stream;
     int nt = 0;
     struct Tab { DevBuf<unsigned long long> keys; DevBuf<int32_t> head; uint32_t cap = 0; int32_t used = 0; };
     Tab tab[kPlMaxTables];
@@ -281,42 +281,21 @@ void uzl_places_cfg_default(uzl_places_cfg* c)
 
 int uzl_places_create(const uzl_places_cfg* cfg, uzl_places** out)
 {
-    if (!out) return UZL_ERR_BAD_ARG;
-    *out = nullptr;
-    uzl_places_cfg c;
-    if (cfg) c = *cfg; else uzl_places_cfg_default(&c);
-    if (c.key_width < 1 || c.key_width > 8) return UZL_ERR_BAD_ARG;
-    if (!(c.min_time_gap >= 0.)) return UZL_ERR_BAD_ARG;       // a place is 0 s from itself: only a gap >= 0 keeps the own slot out
-    if (check_device(c.device) != UZL_OK) return UZL_ERR_NO_DEVICE;
-    uzl_places* h = new (std::nothrow) uzl_places();
-    if (!h) return UZL_ERR_OOM;
-    h->cfg = c;
-    for (int i = 0; i < 32 - c.key_width + 1; i += c.key_width) h->nt++;                     // FastLshSet::clear :253-259: 32 .. 4 tables
-    try {
-        open_handle_stream(c.device, false, &h->stream);
+    return create_handle(cfg, uzl_places_cfg_default, out, [](const uzl_places_cfg& c) {
+        // (a place is 0 s from itself: only a gap >= 0 keeps the own slot out)
+        return c.key_width < 1 || c.key_width > 8 || !(c.min_time_gap >= 0.) ? UZL_ERR_BAD_ARG : UZL_OK;
+    }, [](uzl_places* h) {
+        for (int i = 0; i < 32 - h->cfg.key_width + 1; i += h->cfg.key_width) h->nt++;           // FastLshSet::clear :253-259: 32 .. 4 tables
         for (int t = 0; t < h->nt; t++) alloc_table(h, h->tab[t], 1u << 16);
         h->d_n_entries.reserve(1); h->d_used.reserve(kPlMaxTables); h->h_small.reserve(kPlMaxTables + 1);
         UZL_HIP(hipMemsetAsync(h->d_n_entries.p, 0, 4, h->stream));
         UZL_HIP(hipMemsetAsync(h->d_used.p, 0, kPlMaxTables * 4, h->stream));
         h->entries.reserve(1 << 16); h->entry_cap = 1 << 16;
         UZL_HIP(hipStreamSynchronize(h->stream));
-    } catch (...) {
-        const int code = caught_status(h->last_error);
-        close_handle_stream(c.device, h->stream);
-        delete h;
-        return code;
-    }
-    *out = h;
-    return UZL_OK;
+    });
 }
 
-void uzl_places_destroy(uzl_places* h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->cfg.device);
-    close_handle_stream(h->cfg.device, h->stream);
-    delete h;
-}
+void uzl_places_destroy(uzl_places* h) { destroy_handle(h); }
 
 const char* uzl_places_last_error(uzl_places* h) { return last_error_of(h); }
 

@@ -126,7 +126,7 @@ using namespace uzl;
 
 struct uzl_radius : HandleBase {
     uzl_radius_cfg cfg;
-    hipStream_t stream = nullptr;
+    HandleStream stream;
     int32_t n = 0;
     DevBuf<double> d_x, d_y, d_z, d_rot;
     DevBuf<int64_t> d_stamp, d_off;
@@ -146,33 +146,10 @@ void uzl_radius_cfg_default(uzl_radius_cfg* c)
 
 int uzl_radius_create(const uzl_radius_cfg* cfg, uzl_radius** out)
 {
-    if (!out) return UZL_ERR_BAD_ARG;
-    *out = nullptr;
-    uzl_radius_cfg c;
-    if (cfg) c = *cfg; else uzl_radius_cfg_default(&c);
-    if (check_device(c.device) != UZL_OK) return UZL_ERR_NO_DEVICE;
-    uzl_radius* h = new (std::nothrow) uzl_radius();
-    if (!h) return UZL_ERR_OOM;
-    h->cfg = c;
-    try {
-        open_handle_stream(c.device, false, &h->stream);
-    } catch (...) {
-        const int code = caught_status(h->last_error);
-        close_handle_stream(c.device, h->stream);
-        delete h;
-        return code;
-    }
-    *out = h;
-    return UZL_OK;
+    return create_handle(cfg, uzl_radius_cfg_default, out, [](const uzl_radius_cfg&) { return UZL_OK; }, [](uzl_radius*) {});
 }
 
-void uzl_radius_destroy(uzl_radius* h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->cfg.device);
-    close_handle_stream(h->cfg.device, h->stream);
-    delete h;
-}
+void uzl_radius_destroy(uzl_radius* h) { destroy_handle(h); }
 
 const char* uzl_radius_last_error(uzl_radius* h) { return last_error_of(h); }
 

@@ -314,16 +314,17 @@ void stream_release(int device, hipStream_t s)
     P.pooled[at].leased = false;
 }
 
-void open_handle_stream(int device, bool beside_solver, hipStream_t* s)
+void HandleStream::open(int dev, bool beside_solver)
 {
+    device = dev;
     UZL_HIP(hipSetDevice(device));
-    UZL_HIP(hipStreamCreateWithFlags(s, hipStreamNonBlocking));
+    UZL_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     Pool& P = pool_of(device);
     std::lock_guard<std::mutex> lock(P.mu);
-    P.registered.push_back({*s, beside_solver});
+    P.registered.push_back({s, beside_solver});
 }
 
-void close_handle_stream(int device, hipStream_t& s)
+void HandleStream::close()
 {
     if (!s) return;
     (void)hipStreamSynchronize(s);
