@@ -1580,6 +1580,153 @@ int  uzl_cloud_estimate(uzl_cloud* h, int32_t n_pairs, const uzl_cloud_pair* pai
 int  uzl_cloud_correspondences(uzl_cloud* h, const uzl_cloud_pair* pair, const double* T, int32_t* j, float* dist2, int32_t* kept);
 
 /* ======================================================================================
+ *  ORB keypoints, descriptors and binary GIST from grey images
+ *
+ *  The deployed front end (feature_extraction/launch/feature_extraction_service.launch:6-7:
+ *  descriptor_type 2 = ORB, 300 features) detects with cv::GridAdaptedFeatureDetector over
+ *  cv::AORB(2 * number_of_features, 1.2f, 2, 31, 0, 2, FAST_SCORE, 31, 5) and describes with
+ *  cv::AORB() (feature_extraction_core.cpp:65-66, 84, 93-102; feature_extraction/external/aorb/
+ *  aorb.cpp); extractBinaryGist (:119-162) describes the image shrunk to 63 x 63 with the same
+ *  descriptor code.  The call sites are feature_extraction_service_node.cpp:183-189, 238-243.
+ *  first_level 0, WTA_K 2 and FAST_SCORE are fixed.  BRISK and FREAK are not in the reference tree
+ *  and stay out of scope.
+ *
+ *  Provenance.  Steps marked [EXT] restate OpenCV 2.4 routines that are not in the reference tree
+ *  (FAST, resize, GaussianBlur, fastAtan2, KeyPointsFilter, GridAdaptedFeatureDetector), from
+ *  knowledge of that library; they are not pinned against it.  The rule as written here is the
+ *  contract, and the results equal a NumPy restatement (tests/orb_reference.py) bit for bit.
+ *  Arithmetic.  Integer, or f32 / f64 where stated, every operation rounded on its own (no fused
+ *  multiply-add), / correctly rounded.  No libm call on the device.  The two values taken from the
+ *  host's libm - pow in steps 2 and 6 - are rounded to f32 at once (the table rule of step 2 of the
+ *  depth filter).  rnd(x) is cvRound: the f32 value widened to f64, then rounded half to even.
+ *  The pattern: 512 points int8 (x, y), every coordinate in [-15, 15]; points 2k, 2k + 1 give bit
+ *  k.  The library ships no pattern table: the reference keeps its table as program text
+ *  (aorb.cpp:280-538) and the reference-side caller passes it.
+ *
+ *  1. Cells (GridAdaptedFeatureDetector) [EXT].  Cell (i, j) spans rows [i H / gr, (i+1) H / gr)
+ *     and columns [j W / gc, (j+1) W / gc) in integer division; the mask is cut the same way.  Each
+ *     cell goes through steps 2-7 as an image of its own with nfeatures = 2 * number_of_features
+ *     (feature_extraction_core.cpp:65).
+ *  2. Pyramid (aorb.cpp:764-814).  Level 0 is the cell.  Level l has size (rnd(w s), rnd(h s)), s =
+ *     1.0f / (float)pow((double)scale_factor, l), the products in f32, and is resized from level
+ *     l - 1 by step 3; the mask likewise.
+ *  3. Resize (cv::resize, INTER_LINEAR, 8-bit) [EXT].  For a destination column dx, scale_x = 1.0 /
+ *     ((double)dw / sw): fx = (float)((dx + 0.5) * scale_x - 0.5); sx = floor(fx); fx -= sx; sx < 0
+ *     gives sx = 0, fx = 0; sx >= sw - 1 gives sx = sw - 1, fx = 0.  a0 = sat_s16(rnd((1 - fx) *
+ *     2048)), a1 = sat_s16(rnd(fx * 2048)) in f32, the right-hand tap index clamped to sw - 1.  Rows
+ *     likewise give sy, b0, b1.  h(y, x) = S[y][sx] a0 + S[y][sx+1] a1 as int32; dst = (((b0 *
+ *     (h(sy, x) >> 4)) >> 16) + ((b1 * (h(sy+1, x) >> 4)) >> 16) + 2) >> 2.
+ *  4. FAST-9/16 (FastFeatureDetector(fast_threshold, true)) [EXT].  Circle offsets (dx, dy), k =
+ *     0..15: (0,3) (1,3) (2,2) (3,1) (3,0) (3,-1) (2,-2) (1,-3) (0,-3) (-1,-3) (-2,-2) (-3,-1) (-3,0)
+ *     (-3,1) (-2,2) (-1,3).  p is a corner at t if 9 cyclically contiguous circle pixels are all >
+ *     Ip + t or all < Ip - t.  score(p) = the largest t >= 0 at which p is a corner, 0 if none;
+ *     defined for rows and columns in [3, n - 3), 0 everywhere else.  p is a keypoint iff score >=
+ *     fast_threshold and score > the score of each of its 8 neighbours; response = (float)score.
+ *     With a mask p is dropped if mask(y, x) == 0 at that level.
+ *  5. Border (runByImageBorder, aorb.cpp:670) [EXT].  Keep edge <= x < w - edge and edge <= y < h -
+ *     edge; a level with w <= 2 edge or h <= 2 edge keeps nothing.
+ *  6. Per-level cut (retainBest, aorb.cpp:620-633, 682) [EXT].  With nf = nfeatures of step 1:
+ *     factor = (float)(1.0 / (double)scale_factor); d = (float)nf * (1 - factor) / (1 - (float)pow(
+ *     (double)factor, (double)n_levels)) in f32; for l < n_levels - 1: n_l = rnd(d), d = d * factor;
+ *     the last level gets max(nf - sum, 0).  600 features on two levels: 327 and 273.  If more than
+ *     n_l keypoints remain, c = the n_l-th largest response and every keypoint with response >= c is
+ *     kept: ties are all kept, so a level may exceed n_l (n_l = 0 keeps nothing).  Nothing is ever
+ *     truncated: the device buffers hold the most a level can give.
+ *  7. Orientation (IC_Angle, aorb.cpp:101-129; umax from :639-654, for patch 31: 15 15 15 15 14 14
+ *     14 13 13 12 11 10 9 8 6 3).  On the unblurred level image of the cell: m10 = sum dx I, m01 =
+ *     sum dy I over |dy| <= 15, |dx| <= umax[|dy|], integers.  angle = fastAtan2((float)m01,
+ *     (float)m10).  fastAtan2(y, x) [EXT], all f32, ax = |x|, ay = |y|: if ax >= ay: c = ay / (ax +
+ *     (float)DBL_EPSILON), a = (((p7 c2 + p5) c2 + p3) c2 + p1) c with c2 = c c; else c = ax / (ay +
+ *     (float)DBL_EPSILON), a = 90 - that polynomial in c; x < 0: a = 180 - a; y < 0: a = 360 - a.  p1
+ *     = 0.9997878412794807f * (float)(180 / pi), p3 = -0.3258083974640975f * ..., p5 =
+ *     0.1555786518463281f * ..., p7 = -0.04432655554792128f * ...
+ *  8. Per-cell cut and order.  A level-l keypoint becomes pt = pt * (float)pow((double)
+ *     scale_factor, l) in f32 (l > 0; aorb.cpp:929-935); the cell's union gets the cut of step 6
+ *     with n = number_of_features / (grid_rows grid_cols); then the cell's corner is added in f32.
+ *     The image's list is ordered by (octave ascending, response descending, v ascending, u
+ *     ascending).  The reference's own tie order is unspecified (std::sort at
+ *     feature_extraction_core.cpp:99 is unstable, the level grouping comes from aorb.cpp:846-850):
+ *     this order is the project's rule.
+ *  9. Descriptors (AORB().compute, aorb.cpp:747-763, 843-864, 903-926), on the pyramid of the WHOLE
+ *     image (step 2 on the image), each level blurred by step 10.  A keypoint is kept iff edge <=
+ *     rnd(u) < W - edge and likewise v ([EXT]: the float point becomes an integer point before the
+ *     test).  Level position (rnd(u s), rnd(v s)), s = 1.0f / (float)pow(...) of its octave.
+ *     a = (float)cos, b = (float)sin of angle * (float)(pi / 180) (f32 product), cos and sin from one
+ *     arithmetic-only f64 recipe: k = rint(x * (2 / pi)); r = (x - k * P1) - k * P2 with P1 =
+ *     1.57079632673412561417, P2 = 6.07710050650619224932e-11; the degree-13 / degree-14 polynomials
+ *     of csrc/orb_types.hpp in r; the quadrant k mod 4 selects and signs.  Bit k of byte i is
+ *     I(P[16 i + 2 k]) < I(P[16 i + 2 k + 1]); a pattern point (x, y) is read at row rnd(x b + y a),
+ *     column rnd(x a - y b) from the level position, products and sum in f32 (aorb.cpp:146-148).  A
+ *     read outside the level image returns the UNBLURRED level image at the reflect-101 index (the
+ *     reference blurs the ROI in place inside a bordered buffer, :788-799, 922-924).
+ * 10. Blur (GaussianBlur 7 x 7, sigma 2, 8-bit) [EXT].  Separable, integer weights rnd(k * 256) of
+ *     the f32 Gaussian kernel: 18 34 49 55 49 34 18 (sum 257, not renormalised), borders
+ *     reflect-101 (-1 -> 1, n -> n - 2, repeated while outside); out = sat_u8((sum_y ky (sum_x kx
+ *     p) + 32768) >> 16).
+ * 11. GIST (feature_extraction_core.cpp:139-154).  The whole image resized to 63 x 63 by step 3,
+ *     blurred by step 10, one descriptor by step 9 at (31, 31) with the caller's angle, level 0.
+ *     Undistortion (:123-131) stays with the caller.  A 0 x 0 image gives 32 zero bytes.
+ *
+ *  Device side: a fixed sequence of launches per staging chunk, whatever the number of images
+ *  (unit = cell or whole image, level and tile index the grids; no host round trip between stages;
+ *  counts stay on the device until a read): resize per level, FAST with the tile and a 4-pixel halo
+ *  in LDS and one global atomic per workgroup, both cuts from 256-bin histograms, orientation one
+ *  wave per kept candidate, the order by counting smaller keys, blur, descriptors one wave per
+ *  keypoint.  Integer atomics only: the result does not depend on arrival order or batching.
+ * ====================================================================================== */
+typedef struct uzl_orb uzl_orb;
+typedef struct uzl_orb_cfg {
+    int32_t number_of_features;   /* 300   feature_extraction_service.launch:7                                       */
+    int32_t grid_rows;            /* 2     feature_extraction_core.cpp:84                                            */
+    int32_t grid_cols;            /* 2     :84                                                                       */
+    int32_t n_levels;             /* 2     :65                                                                       */
+    float   scale_factor;         /* 1.2f  :65                                                                       */
+    int32_t edge_threshold;       /* 31    :65                                                                       */
+    int32_t patch_size;           /* 31    :65 (the only value admitted)                                             */
+    int32_t fast_threshold;       /* 5     :65                                                                       */
+    int32_t gist_size;            /* 63    :141-142 (the only value admitted)                                        */
+    int32_t device;
+} uzl_orb_cfg;
+void uzl_orb_cfg_default(uzl_orb_cfg* cfg);
+/* pattern: 512 points as int8_t[512][2] (x, y), copied.  UZL_ERR_BAD_ARG, before the device is looked for, for a NULL pattern, a
+ * coordinate outside [-15, 15], patch_size other than 31, edge_threshold below 19 (the orientation patch and the FAST halo stay
+ * inside the level), n_levels outside [1, 8], scale_factor not in (1, 2], fast_threshold outside [1, 254], number_of_features < 1,
+ * grid_rows or grid_cols outside [1, 8], gist_size other than 63; UZL_ERR_NO_DEVICE without a GPU (no CPU fallback) */
+int  uzl_orb_create(const uzl_orb_cfg* cfg, const int8_t* pattern, uzl_orb** out);
+void uzl_orb_destroy(uzl_orb* h);
+const char* uzl_orb_last_error(uzl_orb* h);
+/* Same checks as create; takes effect at the next extract (the resident results stay as they are). */
+int  uzl_orb_set_config(uzl_orb* h, const uzl_orb_cfg* cfg);
+/* Steps 1-11 over n_images mono8 images (borrowed for the call); replaces the handle's resident results.  masks may be NULL (no
+ * mask), else one per image of its image's size.  gist_angle_deg may be NULL (no GIST), else one f32 per image: the caller's
+ * 180 * roll / pi of feature_extraction_core.cpp:149.  UZL_ERR_BAD_ARG, resident results unchanged, for n_images < 0, a NULL image
+ * array, an image or mask that is neither width, height > 0 with data nor 0 x 0, whose step is smaller than its width or whose
+ * height * step is beyond 2^31 bytes, a mask whose size differs from its image's, a gist angle that is NaN or beyond 1e6 degrees
+ * in magnitude.  n_images = 0 and 0 x 0 images are valid. */
+int  uzl_orb_extract(uzl_orb* h, int32_t n_images, const uzl_guide_image* images, const uzl_guide_image* masks, const float* gist_angle_deg);
+/* Number of resident images; UZL_ERR_STATE before any extract. */
+int  uzl_orb_image_count(uzl_orb* h);
+/* Number of keypoints of resident image `image`; UZL_ERR_BAD_ARG for an image outside the set, UZL_ERR_STATE before any extract. */
+int  uzl_orb_count(uzl_orb* h, int32_t image);
+/* The keypoints of resident image `image` in the order of step 8: u, v (Feature.u / .v), response, angle in degrees as f32, octave
+ * as i32, desc as n x 32 u8, the layout uzl_frame.desc takes.  Any output may be NULL (all NULL only asks for the count).  Returns
+ * the count; UZL_ERR_BAD_ARG for an image outside the set or a negative cap, UZL_ERR_TRUNCATED when an output is given and cap is
+ * smaller, UZL_ERR_STATE before any extract. */
+int  uzl_orb_read(uzl_orb* h, int32_t image, int32_t cap, float* u, float* v, float* response, float* angle, int32_t* octave, uint8_t* desc);
+/* The 32 bytes of step 11 for resident image `image`, as uzl_gist_search_and_add and uzl_wire_gist_sensor_encode take them.
+ * UZL_ERR_STATE before any extract or when the last extract had no angles; UZL_ERR_BAD_ARG for an image outside the set or a NULL
+ * output. */
+int  uzl_orb_gist(uzl_orb* h, int32_t image, uint8_t* out32);
+/* The keypoints of `image`, in read order, through step 7 of the depth filter's contract on resident image df_image of
+ * `depthfilter`, without leaving the device: u = (int)round(Feature.u), half away from zero, v likewise
+ * (feature_extraction_core.cpp:264, 270); the result equals uzl_depthfilter_lift on those values.  pos_xyz: 3 f64 per keypoint,
+ * valid3d: one u8, as uzl_frame takes them.  Returns the number of keypoints.  UZL_ERR_BAD_ARG for a NULL filter handle, one on
+ * another device, an image outside either set, or what uzl_depthfilter_lift refuses; UZL_ERR_STATE before any extract or refine.
+ * Locks the orb handle, then the filter handle. */
+int  uzl_orb_lift(uzl_orb* h, int32_t image, uzl_depthfilter* depthfilter, int32_t df_image, double max_depth, double* pos_xyz,
+                  uint8_t* valid3d);
+
+/* ======================================================================================
  *  Wire and disk formats  
  *
  *  The data formats either side of the path: graph_slam_msgs/{Edge,Node,SensorData,Features,

@@ -28,6 +28,7 @@ UZL_ERR_BUSY = -5
 UZL_ERR_OOM = -6
 UZL_ERR_NOT_FOUND = -7
 UZL_ERR_STATE = -8
+UZL_ERR_TRUNCATED = -9
 
 
 class UzlError(RuntimeError):
@@ -234,6 +235,12 @@ class GuideImage(C.Structure):
     _fields_ = [("data", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("step", C.c_int32), ("_pad", C.c_int32)]
 
 
+class OrbCfg(C.Structure):
+    _fields_ = [("number_of_features", C.c_int32), ("grid_rows", C.c_int32), ("grid_cols", C.c_int32), ("n_levels", C.c_int32),
+                ("scale_factor", C.c_float), ("edge_threshold", C.c_int32), ("patch_size", C.c_int32), ("fast_threshold", C.c_int32),
+                ("gist_size", C.c_int32), ("device", C.c_int32)]
+
+
 class LaserCfg(C.Structure):
     _fields_ = [("max_iterations", C.c_int32), ("device", C.c_int32), ("epsilon_xy", C.c_double), ("epsilon_theta", C.c_double),
                 ("max_correspondence_dist", C.c_double), ("outliers_max_perc", C.c_double), ("outliers_adaptive_order", C.c_double),
@@ -320,7 +327,7 @@ def lib():
 
 
 _HANDLES = ("uzl_match", "uzl_pgo", "uzl_pgo_batch", "uzl_filter", "uzl_gate", "uzl_radius", "uzl_places", "uzl_gist")
-_MORE_HANDLES = ("uzl_grid", "uzl_laserline", "uzl_gfr", "uzl_laser", "uzl_depthfilter", "uzl_cloud")      # declared like _HANDLES; kept apart because tests pin _HANDLES to the first eight
+_MORE_HANDLES = ("uzl_grid", "uzl_laserline", "uzl_gfr", "uzl_laser", "uzl_depthfilter", "uzl_cloud", "uzl_orb")      # declared like _HANDLES; kept apart because tests pin _HANDLES to the first eight
 
 
 def _declare(L):
@@ -335,7 +342,7 @@ def _declare(L):
             getattr(L, p + "_cfg_default").restype = None
     for f in ("uzl_places_count", "uzl_gist_count", "uzl_grid_scan_count", "uzl_gate_edge_count", "uzl_filter_cluster_count",
               "uzl_gfr_count", "uzl_gfr_feature_count", "uzl_gfr_link_count", "uzl_laser_scan_count", "uzl_depthfilter_image_count",
-              "uzl_cloud_count"):
+              "uzl_cloud_count", "uzl_orb_image_count"):
         getattr(L, f).argtypes = [C.c_void_p]
     L.uzl_pgo_batch_graph.restype = C.c_void_p
     L.uzl_pgo_batch_graph.argtypes = [C.c_void_p, C.c_int32]
@@ -1510,6 +1517,71 @@ def _depthfilter_to_cloud(self, cloud, colors, encoding=COLOR_BGR8):
 
 
 DepthFilter.to_cloud = _depthfilter_to_cloud
+
+
+class Orb(_Handle):
+    """uzl_orb_* (FeatureExtractionCore::extractFeatures and ::extractBinaryGist, feature_extraction_core.cpp:93-102, 119-162, over
+    cv::AORB, feature_extraction/external/aorb/aorb.cpp): ORB keypoints, descriptors and the binary GIST of many mono8 images per
+    call; they stay on the device.  The pattern (512 x (x, y) int8) is the caller's: the library ships none."""
+
+    _prefix, _cfg_type = "uzl_orb", OrbCfg
+    set_config = _Handle._set_config
+
+    def __init__(self, pattern, **cfg):
+        pat = None
+        if pattern is not None:
+            pat = np.ascontiguousarray(pattern, np.int8)
+            if pat.shape != (512, 2):
+                raise ValueError("the pattern is 512 points (x, y)")
+        super().__init__(_p(pat, C.POINTER(C.c_int8)), **cfg)
+
+    def extract(self, images, masks=None, gist_angles=None):
+        """images, masks: 2-D uint8 arrays (rows may be strided), one mask per image or None; gist_angles: one angle in degrees per
+        image, or None for no GIST.  Replaces the resident results."""
+        arr, keep = DepthFilter.pack_guides(images)
+        marr, mkeep = DepthFilter.pack_guides(masks) if masks is not None else (None, None)
+        if masks is not None and len(mkeep) != len(keep):
+            raise ValueError("one mask per image")
+        ang = None
+        if gist_angles is not None:
+            ang = np.ascontiguousarray(gist_angles, np.float32).reshape(-1)
+            if len(ang) != len(keep):
+                raise ValueError("one gist angle per image")
+            ang = np.concatenate([ang, np.zeros(1, np.float32)])          # never an empty array: NULL means no GIST
+        self._check(lib().uzl_orb_extract(self._h, C.c_int32(len(keep)), arr, marr, _p(ang, C.POINTER(C.c_float))))
+
+    def image_count(self):
+        return self._check(lib().uzl_orb_image_count(self._h))
+
+    def count(self, image):
+        return self._check(lib().uzl_orb_count(self._h, C.c_int32(image)))
+
+    def read(self, image):
+        """-> dict(u, v, response, angle: float32 (n); octave: int32 (n); desc: uint8 (n, 32)) in the contract's order"""
+        n = self.count(image)
+        f32p = C.POINTER(C.c_float)
+        o = dict(u=np.zeros(n, np.float32), v=np.zeros(n, np.float32), response=np.zeros(n, np.float32), angle=np.zeros(n, np.float32),
+                 octave=np.zeros(n, np.int32), desc=np.zeros((n, 32), np.uint8))
+        m = self._check(lib().uzl_orb_read(self._h, C.c_int32(image), C.c_int32(n), _p(o["u"], f32p), _p(o["v"], f32p), _p(o["response"], f32p),
+                                           _p(o["angle"], f32p), _p(o["octave"], c_i32p), _p(o["desc"], c_u8p)))
+        assert m == n, (m, n)
+        return o
+
+    def gist(self, image):
+        """-> uint8 (32), as Gist.search_and_add takes it"""
+        out = np.zeros(32, np.uint8)
+        self._check(lib().uzl_orb_gist(self._h, C.c_int32(image), _p(out, c_u8p)))
+        return out
+
+    def lift(self, image, depthfilter, df_image, max_depth=0.0):
+        """the keypoints of `image` lifted on the device with resident image df_image of a DepthFilter
+        -> (pos (3, n) float64, valid (n) uint8), as Match.add_frame takes them"""
+        n = self.count(image)
+        pos = np.zeros((n, 3), np.float64); valid = np.zeros(n, np.uint8)
+        m = self._check(lib().uzl_orb_lift(self._h, C.c_int32(image), depthfilter._h, C.c_int32(df_image), C.c_double(max_depth),
+                                           _p(pos, c_f64p), _p(valid, c_u8p)))
+        assert m == n, (m, n)
+        return pos.T, valid
 
 
 class Laser(_Handle):

@@ -58,4 +58,9 @@ inline size_t depth_refine_lds(int radius, int nearest)
 void launch_depth_refine(const DepthRefineArgs& a, int tiles_x, int tiles_y, int n_images, hipStream_t s);
 void launch_depth_lift(const DepthLiftArgs& a, hipStream_t s);
 
+// uzl_depthfilter_lift for keypoints that lie on `device` already (uzl_orb_lift): n int32 each, complete when the call is made.
+// Takes the filter handle's lock; UZL_ERR_BAD_ARG for another device, else as uzl_depthfilter_lift.
+int depthfilter_lift_device(uzl_depthfilter* h, int device, int32_t image, int32_t n, const int32_t* d_u, const int32_t* d_v,
+                            double max_depth, double* pos_xyz, uint8_t* valid3d);
+
 }  // namespace uzl

@@ -218,13 +218,18 @@ int uzl_depthfilter_read(uzl_depthfilter* h, int32_t image, float* out, int64_t 
     UZL_GUARD_END(h)
 }
 
-int uzl_depthfilter_lift(uzl_depthfilter* h, int32_t image, int32_t n, const int32_t* u, const int32_t* v, double max_depth,
-                         double* pos_xyz, uint8_t* valid3d)
+}  // extern "C"
+
+namespace {
+
+// uzl_depthfilter_lift under the handle's lock.  The keypoints come from the host (u, v) or, with d_u, lie on the handle's device
+// already (complete: the caller has synchronised the stream that made them).
+int lift_locked(uzl_depthfilter* h, int32_t image, int32_t n, const int32_t* u, const int32_t* v, const int32_t* d_u, const int32_t* d_v,
+                double max_depth, double* pos_xyz, uint8_t* valid3d)
 {
-    UZL_GUARD_BEGIN(h)
     if (!h->have) return fail(h, UZL_ERR_STATE, "no refine yet");
     if (image < 0 || (size_t)image >= h->resident.size()) return fail(h, UZL_ERR_BAD_ARG, "no such image");
-    if (n < 0 || (n > 0 && (!u || !v || !pos_xyz || !valid3d))) return fail(h, UZL_ERR_BAD_ARG, "bad keypoint count or null arrays");
+    if (n < 0 || (n > 0 && ((!d_u && (!u || !v)) || !pos_xyz || !valid3d))) return fail(h, UZL_ERR_BAD_ARG, "bad keypoint count or null arrays");
     if (std::isnan(max_depth) || max_depth < 0.) return fail(h, UZL_ERR_BAD_ARG, "max_depth is NaN or negative");
     const DepthResident& r = h->resident[image];
     if (n > 0 && r.width == 0) return fail(h, UZL_ERR_BAD_ARG, "keypoints on a 0 x 0 image");
@@ -236,15 +241,17 @@ int uzl_depthfilter_lift(uzl_depthfilter* h, int32_t image, int32_t n, const int
     h->h_lift.reserve(all);
     h->d_lift.reserve(all);
     uint8_t* w = h->h_lift.p;
-    memcpy(w + pos_bytes, u, (size_t)n * 4);
-    memcpy(w + pos_bytes + (size_t)n * 4, v, (size_t)n * 4);
     uint8_t* d = h->d_lift.p;
-    UZL_HIP(hipMemcpyAsync(d + pos_bytes, w + pos_bytes, in_bytes, hipMemcpyHostToDevice, s));
+    if (!d_u) {
+        memcpy(w + pos_bytes, u, (size_t)n * 4);
+        memcpy(w + pos_bytes + (size_t)n * 4, v, (size_t)n * 4);
+        UZL_HIP(hipMemcpyAsync(d + pos_bytes, w + pos_bytes, in_bytes, hipMemcpyHostToDevice, s));
+    }
     DepthLiftArgs a;
     a.image = h->d_images.p + r.off;
     a.pos = reinterpret_cast<double*>(d);
-    a.u = reinterpret_cast<const int32_t*>(d + pos_bytes);
-    a.v = a.u + n;
+    a.u = d_u ? d_u : reinterpret_cast<const int32_t*>(d + pos_bytes);
+    a.v = d_u ? d_v : a.u + n;
     a.valid = d + pos_bytes + in_bytes;
     a.fx = r.fx; a.fy = r.fy; a.cx = r.cx; a.cy = r.cy; a.max_depth = max_depth;
     a.width = r.width; a.height = r.height; a.n = n;
@@ -256,6 +263,31 @@ int uzl_depthfilter_lift(uzl_depthfilter* h, int32_t image, int32_t n, const int
     memcpy(pos_xyz, w, pos_bytes);
     memcpy(valid3d, w + pos_bytes + in_bytes, (size_t)n);
     return UZL_OK;
+}
+
+}  // namespace
+
+namespace uzl {
+
+int depthfilter_lift_device(uzl_depthfilter* h, int device, int32_t image, int32_t n, const int32_t* d_u, const int32_t* d_v,
+                            double max_depth, double* pos_xyz, uint8_t* valid3d)
+{
+    UZL_GUARD_BEGIN(h)
+    if (device != h->cfg.device) return fail(h, UZL_ERR_BAD_ARG, "the keypoints lie on another device");
+    if (n > 0 && (!d_u || !d_v)) return fail(h, UZL_ERR_BAD_ARG, "null device keypoints");
+    return lift_locked(h, image, n, nullptr, nullptr, d_u, d_v, max_depth, pos_xyz, valid3d);
+    UZL_GUARD_END(h)
+}
+
+}  // namespace uzl
+
+extern "C" {
+
+int uzl_depthfilter_lift(uzl_depthfilter* h, int32_t image, int32_t n, const int32_t* u, const int32_t* v, double max_depth,
+                         double* pos_xyz, uint8_t* valid3d)
+{
+    UZL_GUARD_BEGIN(h)
+    return lift_locked(h, image, n, u, v, nullptr, nullptr, max_depth, pos_xyz, valid3d);
     UZL_GUARD_END(h)
 }
 
