@@ -1504,7 +1504,7 @@ typedef struct uzl_cloud_cfg {
     int32_t max_iterations;             /* 20     :149; 1..UZL_CLOUD_MAX_ITERATIONS                                         */
     int32_t inner_iterations;           /* 10     step 7                                                                    */
     int32_t device;
-    double  gicp_epsilon;               /* 0.001  PCL gicp_epsilon_                                                         */
+    double  gicp_epsilon;               /* 0.001  PCL gicp_epsilon_; <= 1, and 1.0 - gicp_epsilon < 1.0 in f64 (see create) */
     double  max_correspondence_dist;    /* 0.2    :148 [m, and scaled CIELAB units]                                         */
     double  rotation_epsilon;           /* 2e-3   PCL rotation_epsilon_                                                     */
     double  transformation_epsilon;     /* 5e-4   PCL transformation_epsilon_                                               */
@@ -1539,10 +1539,11 @@ typedef struct uzl_cloud_edge {
     double  information[36];            /* step 10, row-major 6x6; zero when status != 0                                    */
 } uzl_cloud_edge;
 void uzl_cloud_cfg_default(uzl_cloud_cfg* cfg);
-/* UZL_ERR_BAD_ARG for a NaN, infinite or non-positive leaf_size, gicp_epsilon (also above 1), max_correspondence_dist or epsilon,
- * a NaN, infinite or negative lab_weight, min_score or gate limit, z_min > z_max, k_neighbours outside 3..20, max_iterations
- * outside 1..UZL_CLOUD_MAX_ITERATIONS or inner_iterations outside 1..100 (before the device is looked for); UZL_ERR_NO_DEVICE
- * without a GPU (no CPU fallback) */
+/* UZL_ERR_BAD_ARG for a NaN, infinite or non-positive leaf_size, gicp_epsilon (also above 1, and so small that 1.0 - gicp_epsilon
+ * < 1.0 is false in f64: 2^-53 is admitted, 2^-54 and below are not; there step 4's C of an exact plane would be singular and step
+ * 6's M not finite), max_correspondence_dist or epsilon, a NaN, infinite or negative lab_weight, min_score or gate limit,
+ * z_min > z_max, k_neighbours outside 3..20, max_iterations outside 1..UZL_CLOUD_MAX_ITERATIONS or inner_iterations outside 1..100
+ * (before the device is looked for); UZL_ERR_NO_DEVICE without a GPU (no CPU fallback) */
 int  uzl_cloud_create(const uzl_cloud_cfg* cfg, uzl_cloud** out);
 void uzl_cloud_destroy(uzl_cloud* h);
 const char* uzl_cloud_last_error(uzl_cloud* h);

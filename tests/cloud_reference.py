@@ -2,7 +2,9 @@
 the pin of uzl_cloud_*.  Steps 1-2 (cloud from images, voxel grid) make the test clouds; steps 3-10 are what the device runs.
 Every formula is written in the order the header gives; f32 values are numpy.float32 arrays (NumPy neither fuses nor widens),
 the sums of steps 4 and 7 are the only place where the order differs from the device's (rank order is kept; the 28 sums of
-step 7 go through numpy.sum).  tests/test_cloud_reference.py checks this file by independent means."""
+step 7 go through numpy.sum unless order="device" asks for the kernel's strip -> butterfly -> four-wave order, which the stage
+tests of tests/test_cloud_step_gpu.py compare bit for bit).  tests/test_cloud_reference.py and tests/test_cloud_step_reference.py
+check this file by independent means."""
 import math
 
 import numpy as np
@@ -231,16 +233,16 @@ def correspondences(src, tgt, G, T, cfg=DEFAULTS):
 
 def _rcr(R, c6):
     """upper triangle of (R C) R^T, each product as ((a b) + (c d)) + (e f)"""
-    C = full(c6)
+    C = full(np.asarray(c6, R.dtype))
     A = [[(R[r, 0] * C[:, 0, c] + R[r, 1] * C[:, 1, c]) + R[r, 2] * C[:, 2, c] for c in range(3)] for r in range(3)]
     return [(A[r][0] * R[c, 0] + A[r][1] * R[c, 1]) + A[r][2] * R[c, 2] for r in range(3) for c in range(r, 3)]
 
 
-def mahalanobis(T, G, c1, c2):
+def mahalanobis(T, G, c1, c2, dtype=np.float64):
     """M_i of step 6 -> (n, 6)"""
-    T, G = np.asarray(T, np.float64).reshape(3, 4), np.asarray(G, np.float64).reshape(3, 4)
+    T, G = np.asarray(T, np.float64).reshape(3, 4).astype(dtype), np.asarray(G, np.float64).reshape(3, 4).astype(dtype)
     a, b = _rcr(T[:, :3], c1), _rcr(G[:, :3], c2)
-    s00, s01, s02, s11, s12, s22 = [(0.0 + x) + y for x, y in zip(a, b)]
+    s00, s01, s02, s11, s12, s22 = [(dtype(0.0) + x) + y for x, y in zip(a, b)]
     c00, c01, c02 = s11 * s22 - s12 * s12, s02 * s12 - s01 * s22, s01 * s12 - s02 * s11
     c11, c12, c22 = s00 * s22 - s02 * s02, s01 * s02 - s00 * s12, s00 * s11 - s01 * s01
     det = (s00 * c00 + s01 * c01) + s02 * c02
@@ -248,9 +250,13 @@ def mahalanobis(T, G, c1, c2):
 
 
 # ------------------------------------------------------------------------------------------------ step 7
-def evaluate(T, p, q, M):
-    """the 28 sums at the pose T: H (ww 6, wv 9, vv 6), g (6), f.  p, q: (n, 3) f64; M: (n, 6)"""
-    T = np.asarray(T, np.float64).reshape(3, 4)
+BLOCK, WAVE = 256, 64                 # the step kernel's workgroup and its waves
+
+
+def terms(T, p, q, M, dtype=np.float64):
+    """the terms of step 7's 28 sums, one column per kept row -> (28, n)"""
+    T = np.asarray(T, np.float64).reshape(3, 4).astype(dtype)
+    p, q, M = np.asarray(p, dtype), np.asarray(q, dtype), np.asarray(M, dtype)
     x, y, z = p[:, 0], p[:, 1], p[:, 2]
     ax, ay, az = [(T[r, 0] * x + T[r, 1] * y) + T[r, 2] * z for r in range(3)]
     dx, dy, dz = (ax + T[0, 3]) - q[:, 0], (ay + T[1, 3]) - q[:, 1], (az + T[2, 3]) - q[:, 2]
@@ -259,10 +265,41 @@ def evaluate(T, p, q, M):
     A00, A01, A02 = ay * m02 - az * m01, ay * m12 - az * m11, ay * m22 - az * m12
     A10, A11, A12 = az * m00 - ax * m02, az * m01 - ax * m12, az * m02 - ax * m22
     A20, A21, A22 = ax * m01 - ay * m00, ax * m11 - ay * m01, ax * m12 - ay * m02
-    terms = [ay * A02 - az * A01, az * A00 - ax * A02, ax * A01 - ay * A00, az * A10 - ax * A12, ax * A11 - ay * A10, ax * A21 - ay * A20,
-             A00, A01, A02, A10, A11, A12, A20, A21, A22, m00, m01, m02, m11, m12, m22,
-             ay * ez - az * ey, az * ex - ax * ez, ax * ey - ay * ex, ex, ey, ez, (dx * ex + dy * ey) + dz * ez]
-    return np.array([float(np.sum(t)) for t in terms])
+    return np.stack([ay * A02 - az * A01, az * A00 - ax * A02, ax * A01 - ay * A00, az * A10 - ax * A12, ax * A11 - ay * A10, ax * A21 - ay * A20,
+                     A00, A01, A02, A10, A11, A12, A20, A21, A22, m00, m01, m02, m11, m12, m22,
+                     ay * ez - az * ey, az * ex - ax * ez, ax * ey - ay * ex, ex, ey, ez, (dx * ex + dy * ey) + dz * ez]).reshape(28, len(p))
+
+
+def device_sum(t, rows):
+    """(k, n) terms of the kept rows `rows` (their indices in the source cloud, ascending) summed as cloud_eval sums them: lane l
+    of 256 adds its rows l, l + 256, ... in increasing order from 0.0 (a row that is not kept adds nothing), an xor butterfly with
+    offsets 32, 16, ..., 1 inside each wave of 64 lanes, then (w0 + w1) + (w2 + w3) -> (k,)"""
+    rows = np.asarray(rows, np.int64)
+    strips = int(rows.max()) // BLOCK + 1 if len(rows) else 0
+    grid = np.zeros((t.shape[0], max(strips, 1), BLOCK), t.dtype)
+    grid[:, rows // BLOCK, rows % BLOCK] = t
+    acc = np.zeros((t.shape[0], BLOCK), t.dtype)
+    for s in range(strips):                                   # one addition per strip; 0.0 for a row that is not kept changes nothing
+        acc = acc + grid[:, s]
+    acc = acc.reshape(t.shape[0], BLOCK // WAVE, WAVE)
+    lane = np.arange(WAVE)
+    off = WAVE // 2
+    while off >= 1:
+        acc = acc + acc[:, :, lane ^ off]
+        off //= 2
+    w = acc[:, :, 0]
+    return (w[:, 0] + w[:, 1]) + (w[:, 2] + w[:, 3])
+
+
+def evaluate(T, p, q, M, order="numpy", rows=None, dtype=np.float64):
+    """the 28 sums at the pose T: H (ww 6, wv 9, vv 6), g (6), f.  p, q: (n, 3) f64; M: (n, 6), the kept rows only.  order "numpy":
+    numpy.sum of every term; "device": the kernel's order, with rows = the kept rows' indices in the source cloud (all of
+    0 .. n - 1 when None)"""
+    t = terms(T, p, q, M, dtype)
+    if order == "device":
+        return device_sum(t, np.arange(t.shape[1]) if rows is None else rows)
+    assert order == "numpy", order
+    return np.array([np.sum(row) for row in t], dtype)
 
 
 def solve(S, mu):
@@ -318,17 +355,25 @@ def apply(T, delta):
     return Tn
 
 
-def inner(T, p, q, M, cfg=DEFAULTS):
-    """step 7 from T -> the pose after the damped Gauss-Newton trials"""
-    S = evaluate(T, p, q, M)
+REFUSED, ACCEPTED, REJECTED = range(3)
+
+
+def inner(T, p, q, M, cfg=DEFAULTS, log=None, order="numpy", rows=None):
+    """step 7 from T -> the pose after the damped Gauss-Newton trials.  log: a list that receives one dict(mu, outcome, delta, f)
+    per trial: mu as used, REFUSED (delta and f left zero) / ACCEPTED / REJECTED, the step and the trial pose's f"""
+    S = evaluate(T, p, q, M, order, rows)
     mu = MU0
     for _ in range(cfg["inner_iterations"]):
         delta = solve(S, mu)
         if delta is None:
+            if log is not None:
+                log.append(dict(mu=mu, outcome=REFUSED, delta=np.zeros(6), f=0.0))
             mu = mu * 10.0
             continue
         Tn = apply(T, delta)
-        Sn = evaluate(Tn, p, q, M)
+        Sn = evaluate(Tn, p, q, M, order, rows)
+        if log is not None:
+            log.append(dict(mu=mu, outcome=ACCEPTED if Sn[27] <= S[27] else REJECTED, delta=delta.copy(), f=float(Sn[27])))
         if Sn[27] <= S[27]:
             T, S = Tn, Sn
             mu = max(mu / 10.0, MU_MIN)
@@ -337,6 +382,22 @@ def inner(T, p, q, M, cfg=DEFAULTS):
         if np.abs(delta).max() < INNER_EPS:
             break
     return T
+
+
+def branches(log, cfg=DEFAULTS):
+    """which ways through step 7's loop one trial log shows -> a set of "accepted", "rejected", "refused" (a Cholesky pivot that is
+    not positive), "mu_floor" (an accepted trial whose mu / 10 lies below MU_MIN), "inner_eps" (stopped by a step below INNER_EPS),
+    "ran_out" (stopped by inner_iterations)"""
+    out = set()
+    for e in log:
+        out.add(("refused", "accepted", "rejected")[e["outcome"]])
+        if e["outcome"] == ACCEPTED and e["mu"] / 10.0 < MU_MIN:
+            out.add("mu_floor")
+    if log:
+        small = log[-1]["outcome"] != REFUSED and float(np.abs(log[-1]["delta"]).max()) < INNER_EPS
+        assert small or len(log) == cfg["inner_iterations"], "a loop that stopped for no reason"
+        out.add("inner_eps" if small else "ran_out")
+    return out
 
 
 def problem(src, tgt, G, T, cfg=DEFAULTS):
@@ -375,30 +436,46 @@ def mul34(A, B):
     return C
 
 
-def estimate(src, tgt, G, cfg=DEFAULTS):
-    """steps 5-10 -> dict(status, iterations, num_corr, num_corr_iter, T, transform, match_score, matching_score, information)"""
+def converged(T, Tn, cfg=DEFAULTS):
+    """step 8"""
+    eps = np.array([[cfg["rotation_epsilon"]] * 3 + [cfg["transformation_epsilon"]]] * 3)
+    return float((np.abs(np.asarray(T).reshape(3, 4) - np.asarray(Tn).reshape(3, 4)) / eps).max()) < 1.0
+
+
+def step(src, tgt, G, T, cfg=DEFAULTS, order="device", j=None, kept=None):
+    """one outer iteration (steps 6-8) at T with the state a fresh pair has, as the diagnostic hook uzl_debug_cloud_step returns it ->
+    dict(M (n_from, 6) with zero rows where not kept, sums (28), T, status, done, num_corr, log).  src, tgt: dicts with xyz and cov
+    (n, 6); j, kept: the correspondences to use instead of the restatement's own search"""
     G = np.asarray(G, np.float64).reshape(3, 4)
-    T = np.eye(3, 4)
-    status, its, hist = OK, 0, []
-    for it in range(cfg["max_iterations"]):
-        p, q, M, cnt = problem(src, tgt, G, T, cfg)
-        hist.append(cnt)
-        if cnt == 0:
-            status = NO_CORR
-            break
-        Tn = inner(T, p, q, M, cfg)
-        eps = np.array([[cfg["rotation_epsilon"]] * 3 + [cfg["transformation_epsilon"]]] * 3)
-        delta = float((np.abs(T - Tn) / eps).max())
-        T = Tn
-        its = it + 1
-        if delta < 1.0:
-            break
-    out = dict(status=status, iterations=its, num_corr=hist[-1], num_corr_iter=hist, T=T, n_from=src["n"], n_to=tgt["n"],
+    T = np.asarray(T, np.float64).reshape(3, 4)
+    if j is None:
+        j, _, kept = correspondences(src, tgt, G, T, cfg)
+    rows = np.flatnonzero(kept)
+    M = np.zeros((len(src["xyz"]), 6))
+    if len(rows) == 0:
+        return dict(M=M, sums=np.zeros(28), T=T, status=NO_CORR, done=1, num_corr=0, log=[])
+    p = src["xyz"][rows].astype(np.float64)
+    q = move32(tgt["xyz"], G)[j[rows]].astype(np.float64)
+    with np.errstate(all="ignore"):
+        M[rows] = mahalanobis(T, G, src["cov"][rows], tgt["cov"][j[rows]])
+        log = []
+        Tn = inner(T, p, q, M[rows], cfg, log, order, rows)
+        sums = evaluate(T, p, q, M[rows], order, rows)
+    return dict(M=M, sums=sums, T=Tn, status=OK, done=int(converged(T, Tn, cfg) or cfg["max_iterations"] <= 1), num_corr=len(rows),
+                log=log)
+
+
+def finish(T, G, status, hist, n_from, n_to, cfg=DEFAULTS):
+    """steps 9-10 from the final pose, the status and num_corr of every outer iteration taken"""
+    G = np.asarray(G, np.float64).reshape(3, 4)
+    T = np.asarray(T, np.float64).reshape(3, 4)
+    its = len(hist) - (1 if status == NO_CORR else 0)
+    out = dict(status=status, iterations=its, num_corr=hist[-1], num_corr_iter=hist, T=T, n_from=n_from, n_to=n_to,
                matching_score=0.0, information=np.zeros((6, 6)))
     Tf = T.astype(f32).astype(np.float64)
     X = mul34(inv34(Tf), G)
     out["transform"] = X
-    out["match_score"] = hist[-1] / max(src["n"], tgt["n"])
+    out["match_score"] = hist[-1] / max(n_from, n_to)
     if status != OK:
         return out
     if not out["match_score"] > cfg["min_score"]:
@@ -413,3 +490,22 @@ def estimate(src, tgt, G, cfg=DEFAULTS):
     out["information"] = np.diag([1e4, 1e4, 1e4, 1e6, 1e6, 1e6])
     out["matching_score"] = 1.0
     return out
+
+
+def estimate(src, tgt, G, cfg=DEFAULTS):
+    """steps 5-10 -> dict(status, iterations, num_corr, num_corr_iter, T, transform, match_score, matching_score, information)"""
+    G = np.asarray(G, np.float64).reshape(3, 4)
+    T = np.eye(3, 4)
+    status, hist = OK, []
+    for it in range(cfg["max_iterations"]):
+        p, q, M, cnt = problem(src, tgt, G, T, cfg)
+        hist.append(cnt)
+        if cnt == 0:
+            status = NO_CORR
+            break
+        Tn = inner(T, p, q, M, cfg)
+        stop = converged(T, Tn, cfg)
+        T = Tn
+        if stop:
+            break
+    return finish(T, G, status, hist, src["n"], tgt["n"], cfg)

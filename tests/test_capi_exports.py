@@ -47,6 +47,8 @@ def test_stage_hooks_live_in_the_diagnostic_library_only(capi):
 
     assert hooks <= exported(capi.DIAG_LIB_PATH)
     assert not [n for n in exported(capi.LIB_PATH) if n.startswith("uzl_debug_pgo")]
+    # and the hook of one outer iteration of the cloud registration (test_cloud_step_gpu.py)
+    assert "uzl_debug_cloud_step" in exported(capi.DIAG_LIB_PATH) and "uzl_debug_cloud_step" not in exported(capi.LIB_PATH)
 
 def test_struct_layouts_match_header(capi):
     assert ctypes.sizeof(capi.EdgeResult) == capi.EDGE_RESULT_DTYPE.itemsize == 432

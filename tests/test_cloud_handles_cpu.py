@@ -67,7 +67,7 @@ POSITIVE = ["leaf_size", "gicp_epsilon", "max_correspondence_dist", "rotation_ep
 NONNEG = ["lab_weight", "min_score", "max_translation", "max_rotation_deg"]
 BAD = ([{k: math.nan} for k in POSITIVE + NONNEG] + [{k: -0.5} for k in POSITIVE + NONNEG] + [{k: 0.0} for k in POSITIVE] +
        [{k: math.inf} for k in POSITIVE + NONNEG] +
-       [dict(gicp_epsilon=1.5), dict(z_min=2.0, z_max=1.0), dict(z_min=math.nan), dict(k_neighbours=2), dict(k_neighbours=21),
+       [dict(gicp_epsilon=1.5), dict(gicp_epsilon=2.0 ** -54), dict(gicp_epsilon=5e-324), dict(z_min=2.0, z_max=1.0), dict(z_min=math.nan), dict(k_neighbours=2), dict(k_neighbours=21),
         dict(max_iterations=0), dict(max_iterations=65), dict(inner_iterations=0), dict(inner_iterations=101)])
 
 
@@ -80,9 +80,9 @@ def test_argument_errors_come_before_the_device_check(capi, bad):
 
 
 def test_the_edges_of_the_ranges_are_allowed(capi):
-    """zero weights and limits, gicp_epsilon 1, k 3 and 20, 1 and 64 iterations: not BAD_ARG (without a GPU they fail at the device
+    """zero weights and limits, gicp_epsilon 1 and 2^-53 (the least for which 1.0 - gicp_epsilon < 1.0), k 3 and 20, 1 and 64 iterations: not BAD_ARG (without a GPU they fail at the device
     check)"""
-    for ok in ({k: 0.0 for k in NONNEG}, dict(gicp_epsilon=1.0), dict(k_neighbours=3), dict(k_neighbours=20), dict(max_iterations=1),
+    for ok in ({k: 0.0 for k in NONNEG}, dict(gicp_epsilon=1.0), dict(gicp_epsilon=2.0 ** -53), dict(gicp_epsilon=1.5 * 2.0 ** -54), dict(k_neighbours=3), dict(k_neighbours=20), dict(max_iterations=1),
                dict(max_iterations=64), dict(inner_iterations=1), dict(inner_iterations=100), dict(z_min=1.0, z_max=1.0)):
         try:
             capi.Cloud(**ok).close()

@@ -1677,7 +1677,7 @@ class Cloud(_Handle):
         if len(keep) != len(ckeep):
             raise ValueError("one colour image per depth image")
         first = C.c_int32(-1)
-        self._check(lib().uzl_cloud_add_images(self._h, C.c_int32(len(keep)), arr, carr, C.byref(first)))
+        self._check(self._lib().uzl_cloud_add_images(self._h, C.c_int32(len(keep)), arr, carr, C.byref(first)))
         return first.value
 
     def add_points(self, xyz, bgr):
@@ -1687,21 +1687,21 @@ class Cloud(_Handle):
         if len(xyz) != len(bgr):
             raise ValueError("one colour per point")
         idx = C.c_int32(-1)
-        self._check(lib().uzl_cloud_add_points(self._h, C.c_int32(len(xyz)), _p(xyz, C.POINTER(C.c_float)), _p(bgr, c_u8p), C.byref(idx)))
+        self._check(self._lib().uzl_cloud_add_points(self._h, C.c_int32(len(xyz)), _p(xyz, C.POINTER(C.c_float)), _p(bgr, c_u8p), C.byref(idx)))
         return idx.value
 
     def count(self):
-        return self._check(lib().uzl_cloud_count(self._h))
+        return self._check(self._lib().uzl_cloud_count(self._h))
 
     def point_count(self, cloud):
-        return self._check(lib().uzl_cloud_read(self._h, C.c_int32(cloud), C.c_int32(0), None, None, None, None))
+        return self._check(self._lib().uzl_cloud_read(self._h, C.c_int32(cloud), C.c_int32(0), None, None, None, None))
 
     def read(self, cloud):
         """-> dict(xyz (n, 3) f32, bgr (n, 3) u8, lab (n, 3) f32, cov (n, 3, 3) f64)"""
         n = self.point_count(cloud)
         xyz = np.zeros((n, 3), np.float32); bgr = np.zeros((n, 3), np.uint8); lab = np.zeros((n, 3), np.float32)
         cov = np.zeros((n, 3, 3), np.float64)
-        m = self._check(lib().uzl_cloud_read(self._h, C.c_int32(cloud), C.c_int32(n), _p(xyz, C.POINTER(C.c_float)), _p(bgr, c_u8p),
+        m = self._check(self._lib().uzl_cloud_read(self._h, C.c_int32(cloud), C.c_int32(n), _p(xyz, C.POINTER(C.c_float)), _p(bgr, c_u8p),
                                              _p(lab, C.POINTER(C.c_float)), _p(cov, c_f64p)))
         assert m == n, (m, n)
         return dict(xyz=xyz, bgr=bgr, lab=lab, cov=cov)
@@ -1720,7 +1720,7 @@ class Cloud(_Handle):
         arr = self.pack_pairs(pairs)
         n = len(pairs)
         out = np.zeros(max(n, 1), CLOUD_EDGE_DTYPE)
-        self._check(lib().uzl_cloud_estimate(self._h, C.c_int32(n), arr, out.ctypes.data_as(C.POINTER(CloudEdge))))
+        self._check(self._lib().uzl_cloud_estimate(self._h, C.c_int32(n), arr, out.ctypes.data_as(C.POINTER(CloudEdge))))
         return out[:n]
 
     def correspondences(self, cloud_from, cloud_to, first_guess, T):
@@ -1730,6 +1730,31 @@ class Cloud(_Handle):
         pair = self.pack_pairs([(cloud_from, cloud_to, first_guess)])
         TT = (C.c_double * 12)(*np.asarray(T, np.float64).reshape(12).tolist())
         j = np.zeros(n, np.int32); d = np.zeros(n, np.float32); kept = np.zeros(n, np.int32)
-        m = self._check(lib().uzl_cloud_correspondences(self._h, pair, TT, _p(j, c_i32p), _p(d, C.POINTER(C.c_float)), _p(kept, c_i32p)))
+        m = self._check(self._lib().uzl_cloud_correspondences(self._h, pair, TT, _p(j, c_i32p), _p(d, C.POINTER(C.c_float)), _p(kept, c_i32p)))
         assert m == n, (m, n)
         return j, d, kept
+
+    def debug_step(self, cloud_from, cloud_to, first_guess, T):
+        """uzl_debug_cloud_step (the diagnostic library only: call it on a DiagCloud): one outer iteration at the estimate T through
+        the kernels estimate runs -> dict(M (n, 6) f64, zero rows where not kept; sums (28): H, g, f at T; T (3, 4) after the inner
+        loop; status, done, num_corr; log: one dict(mu, outcome 0 refused / 1 accepted / 2 rejected, delta (6), f) per trial)"""
+        L = self._lib()
+        if not hasattr(L, "uzl_debug_cloud_step"):
+            raise UzlError(UZL_ERR_STATE, "uzl_debug_cloud_step exists in the diagnostic library only: use DiagCloud")
+        n = self.point_count(cloud_from)
+        pair = self.pack_pairs([(cloud_from, cloud_to, first_guess)])
+        TT = (C.c_double * 12)(*np.asarray(T, np.float64).reshape(12).tolist())
+        M = np.zeros((n, 6)); sums = np.zeros(28); Tn = np.zeros((3, 4)); state = np.zeros(4, np.int32); trials = np.zeros((100, 9))
+        m = self._check(L.uzl_debug_cloud_step(self._h, pair, TT, _p(M, c_f64p), _p(sums, c_f64p), _p(Tn, c_f64p), _p(state, c_i32p),
+                                               _p(trials, c_f64p)))
+        assert m == n, (m, n)
+        log = [dict(mu=float(t[0]), outcome=int(t[1]), delta=t[2:8].copy(), f=float(t[8])) for t in trials[:int(state[3])]]
+        assert not trials[int(state[3]):].any()
+        return dict(M=M, sums=sums, T=Tn, status=int(state[0]), done=int(state[1]), num_corr=int(state[2]), log=log)
+
+
+class DiagCloud(Cloud):
+    """A Cloud handle of the diagnostic library (diag_lib), the only one debug_step works on: created and fed by that library's own
+    uzl_cloud_* - a handle of the product library must never reach a uzl_debug_* hook."""
+
+    _lib = staticmethod(lambda: diag_lib())

@@ -325,6 +325,19 @@ __device__ inline void cloud_apply(const double* T, const double* delta, double*
     }
 }
 
+#ifdef UZL_DIAG
+// Trial s of the launch into the diagnostic log: thread 0 writes (every thread holds the same values); delta == NULL: a refused trial.
+__device__ inline void cloud_log_trial(const CloudIcpArgs& a, int s, double mu, int outcome, const double* delta, double f)
+{
+    if (!a.log || threadIdx.x != 0 || s >= kCloudLogTrials) return;
+    double* e = a.log->trial[s];
+    e[0] = mu; e[1] = (double)outcome;
+    for (int k = 0; k < 6; k++) e[2 + k] = delta ? delta[k] : 0.0;
+    e[8] = f;
+    a.log->n_trials = s + 1;
+}
+#endif
+
 __global__ __launch_bounds__(kCloudBlock) void cloud_step_kernel(CloudIcpArgs a)
 {
     __shared__ StepLds l;
@@ -379,11 +392,23 @@ __global__ __launch_bounds__(kCloudBlock) void cloud_step_kernel(CloudIcpArgs a)
     }
     double S[kCloudSums], Sn[kCloudSums], Tn[12], delta[6];
     cloud_eval(a, P, from, T, l, S);
+#ifdef UZL_DIAG
+    if (a.log && tid == 0) for (int k = 0; k < kCloudSums; k++) a.log->sums[k] = S[k];
+#endif
     double mu = UZL_CLOUD_MU0;
     for (int s = 0; s < a.inner_iterations; s++) {
-        if (!cloud_solve(S, mu, delta)) { mu = mu * 10.0; continue; }
+        if (!cloud_solve(S, mu, delta)) {
+#ifdef UZL_DIAG
+            cloud_log_trial(a, s, mu, 0, nullptr, 0.0);
+#endif
+            mu = mu * 10.0;
+            continue;
+        }
         cloud_apply(T, delta, Tn);
         cloud_eval(a, P, from, Tn, l, Sn);
+#ifdef UZL_DIAG
+        cloud_log_trial(a, s, mu, Sn[27] <= S[27] ? 1 : 2, delta, Sn[27]);
+#endif
         if (Sn[27] <= S[27]) {
 #pragma unroll
             for (int k = 0; k < 12; k++) T[k] = Tn[k];

@@ -36,6 +36,16 @@ struct CloudPairState {
     int32_t num_corr_iter[UZL_CLOUD_MAX_ITERATIONS];
 };
 
+#ifdef UZL_DIAG
+// What cloud_step_kernel's thread 0 records of one launch for uzl_debug_cloud_step (the diagnostic library only).
+constexpr int kCloudLogTrials = 100;      // the most inner_iterations may be
+struct CloudStepLog {
+    double sums[kCloudSums];              // H, g and f at the pose the launch starts from
+    double trial[kCloudLogTrials][9];     // mu as used, outcome (0 refused, 1 accepted, 2 rejected), delta (6), the trial pose's f
+    int32_t n_trials, _pad;
+};
+#endif
+
 struct CloudIcpArgs {
     const CloudRec* clouds;
     const float* xyz;
@@ -50,6 +60,9 @@ struct CloudIcpArgs {
     double max_corr_sq, rot_eps, trans_eps;
     float lab_weight;
     int32_t max_iterations, inner_iterations;
+#ifdef UZL_DIAG
+    CloudStepLog* log;                    // NULL in every launch but uzl_debug_cloud_step's (one pair)
+#endif
 };
 
 // One image pair of an add: depth and colour pixels already on the device.

@@ -33,6 +33,9 @@ struct uzl_cloud : HandleBase {
     DevBuf<float> d_tgt, d_nn_d;
     DevBuf<int32_t> d_nn_j;
     DevBuf<double> d_M;
+#ifdef UZL_DIAG
+    DevBuf<CloudStepLog> d_log;
+#endif
     // work of an add from images
     DevBuf<uint8_t> d_chunk, d_sort_temp;
     DevBuf<uint32_t> d_bbox, d_vals[2], d_flag, d_rank;
@@ -50,6 +53,8 @@ int check_cfg(const uzl_cloud_cfg& c)
     for (double v : nonneg) if (!(v >= 0.) || !std::isfinite(v)) return UZL_ERR_BAD_ARG;
     if (!(c.z_min <= c.z_max)) return UZL_ERR_BAD_ARG;
     if (!(c.gicp_epsilon <= 1.)) return UZL_ERR_BAD_ARG;
+    // step 4 scales n n^T by 1 - gicp_epsilon: where that rounds to 1 (below 2^-53), C of an exact plane is singular and M not finite
+    if (!(1.0 - c.gicp_epsilon < 1.0)) return UZL_ERR_BAD_ARG;
     if (c.k_neighbours < kCloudMinPoints || c.k_neighbours > kCloudK) return UZL_ERR_BAD_ARG;
     if (c.max_iterations < 1 || c.max_iterations > UZL_CLOUD_MAX_ITERATIONS) return UZL_ERR_BAD_ARG;
     if (c.inner_iterations < 1 || c.inner_iterations > 100) return UZL_ERR_BAD_ARG;
@@ -439,6 +444,56 @@ int uzl_cloud_correspondences(uzl_cloud* h, const uzl_cloud_pair* pair, const do
 }
 
 }  // extern "C"
+
+#ifdef UZL_DIAG
+// Stage hook of the diagnostic library (tests/test_cloud_step_gpu.py): one outer iteration of one pair from the estimate T, through
+// the kernels an estimate runs - the pair uploaded with T0 = T, then cloud_prepare, cloud_nn6 and cloud_step_kernel once each.  Any
+// output may be NULL.  M: 6 f64 per point of `from`, zero rows where the correspondence is not kept; sums: the 28 sums at T; T_next:
+// the pose after the inner loop; state: status, done, num_corr, n_trials; trials: 100 x 9 f64, per trial mu as used, the outcome
+// (0 refused, 1 accepted, 2 rejected), delta and the trial pose's f (delta and f zero for a refused trial), zero beyond n_trials.
+// Returns n_points(from); errors as uzl_cloud_correspondences.
+extern "C" UZL_DIAG_EXPORT int uzl_debug_cloud_step(uzl_cloud* h, const uzl_cloud_pair* pair, const double* T, double* M, double* sums,
+                                                    double* T_next, int32_t* state, double* trials)
+{
+    UZL_GUARD_BEGIN(h)
+    if (!pair || !T) return fail(h, UZL_ERR_BAD_ARG, "null pair or estimate");
+    if (int rc = check_pair(h, *pair)) return rc;
+    if (!finite12(T)) return fail(h, UZL_ERR_BAD_ARG, "non-finite estimate");
+    UZL_HIP(hipSetDevice(h->cfg.device));
+    hipStream_t s = h->stream;
+    CloudIcpArgs a = icp_args(h);
+    int32_t max_from, max_to;
+    upload_pairs(h, 1, pair, T, a, &max_from, &max_to);
+    h->d_log.reserve(1);
+    UZL_HIP(hipMemsetAsync(h->d_log.p, 0, sizeof(CloudStepLog), s));
+    a.log = h->d_log.p;
+    launch_cloud_prepare(a, 1, max_to, s);
+    launch_cloud_nn6(a, 1, max_from, s);
+    launch_cloud_step(a, 1, s);
+    UZL_HIP(hipGetLastError());
+    const int32_t nf = max_from;
+    std::vector<float> d(nf);
+    std::vector<double> m(6 * (size_t)nf);
+    std::vector<CloudStepLog> log(1);
+    CloudPairState st;
+    UZL_HIP(hipMemcpyAsync(d.data(), a.nn_d, (size_t)nf * 4, hipMemcpyDeviceToHost, s));
+    UZL_HIP(hipMemcpyAsync(m.data(), a.M, (size_t)nf * 48, hipMemcpyDeviceToHost, s));
+    UZL_HIP(hipMemcpyAsync(log.data(), a.log, sizeof(CloudStepLog), hipMemcpyDeviceToHost, s));
+    UZL_HIP(hipMemcpyAsync(&st, a.state, sizeof(st), hipMemcpyDeviceToHost, s));
+    UZL_HIP(hipStreamSynchronize(s));
+    if (M)
+        for (int32_t i = 0; i < nf; i++) {
+            const bool kept = (double)d[i] < a.max_corr_sq;
+            for (int k = 0; k < 6; k++) M[6 * (size_t)i + k] = kept ? m[6 * (size_t)i + k] : 0.0;
+        }
+    if (sums) memcpy(sums, log[0].sums, sizeof(log[0].sums));
+    if (T_next) memcpy(T_next, st.T, sizeof(st.T));
+    if (state) { state[0] = st.status; state[1] = st.done; state[2] = st.num_corr; state[3] = log[0].n_trials; }
+    if (trials) memcpy(trials, log[0].trial, sizeof(log[0].trial));
+    return nf;
+    UZL_GUARD_END(h)
+}
+#endif  // UZL_DIAG
 
 int uzl::cloud_add_device_images(uzl_cloud* h, int device, int32_t n, const uzl_depth_image* geom, const float* const* d_depth,
                                  const uzl_color_image* colors, int32_t* first_cloud)
