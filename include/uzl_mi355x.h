@@ -1726,6 +1726,30 @@ int  uzl_orb_gist(uzl_orb* h, int32_t image, uint8_t* out32);
  * Locks the orb handle, then the filter handle. */
 int  uzl_orb_lift(uzl_orb* h, int32_t image, uzl_depthfilter* depthfilter, int32_t df_image, double max_depth, double* pos_xyz,
                   uint8_t* valid3d);
+#define UZL_ORB_STAGE_LEVEL     0   /* step 2: level `level` >= 1 of cell `cell`, or of the whole image (cell = -1) */
+#define UZL_ORB_STAGE_MASK      1   /* step 2: level `level` >= 1 of the mask of cell `cell` >= 0                   */
+#define UZL_ORB_STAGE_BLUR      2   /* step 10: blurred level `level` >= 0 of the whole image (cell = -1)           */
+#define UZL_ORB_STAGE_GIST      3   /* step 11: the 63 x 63 image (cell and level are ignored)                      */
+#define UZL_ORB_STAGE_GIST_BLUR 4   /* step 11: its blur                                                            */
+/* Stage entry: one intermediate image of resident image `image` as the last extract left it in the handle's work buffers, read
+ * back without a launch.  `what` is one of UZL_ORB_STAGE_*; cells are numbered row by row, 0 .. grid_rows grid_cols - 1, with the
+ * grid and the level count the extract ran with.  out: width * height u8, rows compact; width and height (either may be NULL) are
+ * set whenever the call succeeds or ends with UZL_ERR_TRUNCATED, and out = NULL only asks for them.  A 0 x 0 image gives 0 x 0.  The work buffers hold the last
+ * staging chunk of the extract only (every image, unless the call had more than 8192 / (cells + 1) images or 64 MiB of pixels):
+ * an image of an earlier chunk is UZL_ERR_STATE, and last_error says so.  UZL_ERR_STATE also before any extract, for a GIST image
+ * when the last extract had no angles and for a mask level when it had no masks; UZL_ERR_BAD_ARG for an unknown `what`, an image,
+ * cell or level out of range, level 0 of UZL_ORB_STAGE_LEVEL or _MASK (that is the caller's own input), a mask level of the whole
+ * image, a blurred level of a cell, a negative cap; UZL_ERR_TRUNCATED when out is given and cap < width * height. */
+int  uzl_orb_stage_image(uzl_orb* h, int32_t image, int32_t what, int32_t cell, int32_t level, int64_t cap, uint8_t* out, int32_t* width,
+                         int32_t* height);
+/* Stage entry: the candidates of level `level` of cell `cell` after steps 4-5 (FAST, mask, border), before the cuts: x, y at the
+ * level as i32 and the score as u8, in the order the device found them, which is not defined (sort before comparing); thr (may be
+ * NULL) is the smallest response steps 6 and 8 keep on that level: the larger of the level's cut and the cell's, a cut being the
+ * n-th largest response when more than n remain, 256 when n = 0 and something remains, else 0.  Any output may be NULL (x, y and
+ * score all NULL only ask for the count and thr).  Returns the count.  Errors as uzl_orb_stage_image; cell = -1 is
+ * UZL_ERR_BAD_ARG; UZL_ERR_TRUNCATED when an array is given and cap is smaller than the count.  Launches nothing. */
+int  uzl_orb_stage_candidates(uzl_orb* h, int32_t image, int32_t cell, int32_t level, int32_t cap, int32_t* x, int32_t* y, uint8_t* score,
+                              int32_t* thr);
 
 /* ======================================================================================
  *  Wire and disk formats  

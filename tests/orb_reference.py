@@ -219,16 +219,27 @@ def blur(img):
     return np.minimum((vs + 32768) >> 16, 255).astype(np.uint8)
 
 
-def describe(blurred, raw, cx, cy, angle, pattern):
-    """one descriptor at level position (cx, cy): 32 bytes"""
-    H, W = raw.shape
+def pattern_reads(cx, cy, angle, pattern):
+    """step 9: the row and the column at which each of the 512 pattern points is read from level position (cx, cy)"""
     rad = F32(angle) * F32(math.pi / 180.0)
     c, s = cos_sin(float(rad))
     a, b = F32(c), F32(s)
     P = np.asarray(pattern, np.int8).reshape(512, 2)
     px, py = P[:, 0].astype(F32), P[:, 1].astype(F32)
-    row = cy + rnd(px * b + py * a)
-    col = cx + rnd(px * a - py * b)
+    return cy + rnd(px * b + py * a), cx + rnd(px * a - py * b)
+
+
+def reads_outside(shape, cx, cy, angle, pattern):
+    """how many of a descriptor's 512 reads fall outside its level image (and so take the unblurred, reflected branch of step 9)"""
+    H, W = shape
+    row, col = pattern_reads(cx, cy, angle, pattern)
+    return int(((row < 0) | (row >= H) | (col < 0) | (col >= W)).sum())
+
+
+def describe(blurred, raw, cx, cy, angle, pattern):
+    """one descriptor at level position (cx, cy): 32 bytes"""
+    H, W = raw.shape
+    row, col = pattern_reads(cx, cy, angle, pattern)
     inside = (row >= 0) & (row < H) & (col >= 0) & (col < W)
     val = np.where(inside, blurred[np.clip(row, 0, H - 1), np.clip(col, 0, W - 1)], raw[reflect101(row, H), reflect101(col, W)]).astype(np.int64)
     bits = (val[0::2] < val[1::2]).astype(np.uint8)                      # bit k of the descriptor: points 2k, 2k + 1
@@ -236,13 +247,27 @@ def describe(blurred, raw, cx, cy, angle, pattern):
 
 
 # ---------------------------------------------------------------------------------------------- the whole
+def cut(response, n):
+    """steps 6 and 8 as a number: the smallest response a cut to n keeps - the n-th largest when more than n remain, 256 (above every
+    response) when n is 0 and something remains, 0 (below every response) when nothing is cut"""
+    response = np.asarray(response)
+    if len(response) <= n:
+        return 0
+    if n <= 0:
+        return 256
+    return int(np.sort(response)[::-1][n - 1])
+
+
 def detect_cell(cell, mask, cfg, info=None):
-    """steps 2-8 for one cell -> list of (u, v, response, angle, octave) in cell coordinates (f32), after the cell's cut"""
+    """steps 2-8 for one cell -> list of (u, v, response, angle, octave) in cell coordinates (f32), after the cell's cut.  With info,
+    info["stages"] gets one dict for the cell: levels and masks (the pyramids of step 2), candidates (per level x, y, score after
+    steps 4-5) and cut (per level the smallest response steps 6 and 8 keep: the larger of the level's cut and the cell's)"""
     L, sf, edge = cfg["n_levels"], cfg["scale_factor"], cfg["edge_threshold"]
     n_l = n_per_level(2 * cfg["number_of_features"], sf, L)
     levels = pyramid(cell, L, sf)
     masks = pyramid(mask, L, sf) if mask is not None else [None] * L
     found = []
+    stage = dict(levels=levels, masks=masks, candidates=[], cut=[])
     for l in range(L):
         img = levels[l]
         h, w = img.shape
@@ -254,6 +279,8 @@ def detect_cell(cell, mask, cfg, info=None):
         x, y, s = x[keep], y[keep], s[keep]
         if info is not None:
             info.setdefault("level_candidates", []).append((l, len(x), n_l[l]))
+        stage["candidates"].append((x.astype(np.int64), y.astype(np.int64), s.astype(np.int64)))
+        stage["cut"].append(cut(s, n_l[l]))
         keep = retain_best(s, n_l[l])
         scale = level_scale(sf, l)
         for xx, yy, ss in zip(x[keep], y[keep], s[keep]):
@@ -264,12 +291,17 @@ def detect_cell(cell, mask, cfg, info=None):
     n_cell = cfg["number_of_features"] // (cfg["grid_rows"] * cfg["grid_cols"])
     if info is not None:
         info.setdefault("cell_candidates", []).append((len(found), n_cell))
+        cell_cut = cut([f[2] for f in found], n_cell)
+        stage["cut"] = [max(c, cell_cut) for c in stage["cut"]]
+        info.setdefault("stages", []).append(stage)
     keep = retain_best([f[2] for f in found], n_cell)
     return [f for f, k in zip(found, keep) if k]
 
 
 def extract(img, pattern, mask=None, **cfg):
-    """steps 1-10 for one image -> dict(u, v, response, angle: f32; octave: i32; desc: u8 (n, 32)) in the contract's order"""
+    """steps 1-10 for one image -> dict(u, v, response, angle: f32; octave: i32; desc: u8 (n, 32)) in the contract's order.  A dict
+    passed as info=... comes back with the stages: per cell, row by row, what detect_cell reports; pyramid and blurred, the levels of
+    the whole image of steps 9-10; outside, per keypoint the number of pattern points its descriptor read outside its level image"""
     cfg = dict(DEFAULTS, **cfg)
     info = cfg.pop("info", None)
     img = np.asarray(img, np.uint8)
@@ -288,13 +320,18 @@ def extract(img, pattern, mask=None, **cfg):
     n = len(kps)
     out = dict(u=np.array([k[4] for k in kps], F32), v=np.array([k[5] for k in kps], F32), response=np.array([k[6] for k in kps], F32),
                angle=np.array([k[7] for k in kps], F32), octave=np.array([k[0] for k in kps], np.int32), desc=np.zeros((n, 32), np.uint8))
-    if n:
+    if n or (info is not None and H and W):
         raw = pyramid(img, cfg["n_levels"], cfg["scale_factor"])
         blurred = [blur(r) for r in raw]
+        if info is not None:
+            info.update(pyramid=raw, blurred=blurred, outside=[])
         for i, k in enumerate(kps):
             o = k[0]
             s = F32(1.0) / level_scale(cfg["scale_factor"], o)
-            out["desc"][i] = describe(blurred[o], raw[o], int(rnd(k[4] * s)), int(rnd(k[5] * s)), k[7], pattern)
+            cx, cy = int(rnd(k[4] * s)), int(rnd(k[5] * s))
+            out["desc"][i] = describe(blurred[o], raw[o], cx, cy, k[7], pattern)
+            if info is not None:
+                info["outside"].append(reads_outside(raw[o].shape, cx, cy, k[7], pattern))
     return out
 
 

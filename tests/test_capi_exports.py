@@ -50,6 +50,17 @@ def test_stage_hooks_live_in_the_diagnostic_library_only(capi):
     # and the hook of one outer iteration of the cloud registration (test_cloud_step_gpu.py)
     assert "uzl_debug_cloud_step" in exported(capi.DIAG_LIB_PATH) and "uzl_debug_cloud_step" not in exported(capi.LIB_PATH)
 
+
+def test_stage_entries_of_the_header_are_in_the_product_library(capi):
+    """Stage entries that only read back what a call left behind are part of the header (uzl_cloud_correspondences, uzl_orb_stage_*):
+    declared, documented as "Stage entry:" and exported by the product library."""
+    src = open(os.path.join(ROOT, "include", "uzl_mi355x.h")).read()
+    L = ctypes.CDLL(capi.LIB_PATH)
+    for name in ("uzl_cloud_correspondences", "uzl_orb_stage_image", "uzl_orb_stage_candidates"):
+        assert name in _declared() and hasattr(L, name), name
+        comment = src[:src.index("int  " + name + "(")].rsplit("/*", 1)[1]
+        assert comment.lstrip().startswith("Stage entry:"), name
+
 def test_struct_layouts_match_header(capi):
     assert ctypes.sizeof(capi.EdgeResult) == capi.EDGE_RESULT_DTYPE.itemsize == 432
     assert ctypes.sizeof(capi.PairJob) == capi.PAIR_JOB_DTYPE.itemsize == 24

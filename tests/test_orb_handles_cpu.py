@@ -2,6 +2,8 @@
 tests/test_depthfilter_handles_cpu.py.  Nothing here needs a handle on a device, so the tests pass with or without one."""
 import ctypes as C
 import math
+import os
+import re
 
 import numpy as np
 import pytest
@@ -22,6 +24,19 @@ def test_null_handle(capi):
     assert L.uzl_orb_gist(None, 0, None) == capi.UZL_ERR_BAD_ARG
     assert L.uzl_orb_lift(None, 0, None, 0, C.c_double(0.0), None, None) == capi.UZL_ERR_BAD_ARG
     assert L.uzl_orb_create(None, None, None) == capi.UZL_ERR_BAD_ARG
+
+
+def test_null_handle_at_the_stage_entry(capi):
+    L = capi.lib()
+    w, h = C.c_int32(-7), C.c_int32(-7)
+    for what in (capi.ORB_STAGE_LEVEL, capi.ORB_STAGE_MASK, capi.ORB_STAGE_BLUR, capi.ORB_STAGE_GIST, capi.ORB_STAGE_GIST_BLUR):
+        assert L.uzl_orb_stage_image(None, 0, what, 0, 1, C.c_int64(0), None, C.byref(w), C.byref(h)) == capi.UZL_ERR_BAD_ARG
+    assert (w.value, h.value) == (-7, -7)                                  # a refused call writes nothing
+    assert L.uzl_orb_stage_candidates(None, 0, 0, 0, 0, None, None, None, None) == capi.UZL_ERR_BAD_ARG
+    assert (capi.ORB_STAGE_LEVEL, capi.ORB_STAGE_MASK, capi.ORB_STAGE_BLUR, capi.ORB_STAGE_GIST, capi.ORB_STAGE_GIST_BLUR) == (0, 1, 2, 3, 4)
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "uzl_mi355x.h")).read()
+    for k, name in enumerate(("LEVEL", "MASK", "BLUR", "GIST", "GIST_BLUR")):
+        assert re.search(r"#define UZL_ORB_STAGE_%s\s+%d\b" % (name, k), src), name
 
 
 def test_the_prefix_is_registered_apart_from_the_first_eight(capi):

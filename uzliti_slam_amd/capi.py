@@ -241,6 +241,9 @@ class OrbCfg(C.Structure):
                 ("gist_size", C.c_int32), ("device", C.c_int32)]
 
 
+ORB_STAGE_LEVEL, ORB_STAGE_MASK, ORB_STAGE_BLUR, ORB_STAGE_GIST, ORB_STAGE_GIST_BLUR = range(5)
+
+
 class LaserCfg(C.Structure):
     _fields_ = [("max_iterations", C.c_int32), ("device", C.c_int32), ("epsilon_xy", C.c_double), ("epsilon_theta", C.c_double),
                 ("max_correspondence_dist", C.c_double), ("outliers_max_perc", C.c_double), ("outliers_adaptive_order", C.c_double),
@@ -1582,6 +1585,26 @@ class Orb(_Handle):
                                            _p(pos, c_f64p), _p(valid, c_u8p)))
         assert m == n, (m, n)
         return pos.T, valid
+
+    def stage_image(self, image, what, cell=-1, level=0):
+        """Stage entry: one intermediate image of the last extract (what: ORB_STAGE_*; cell -1 = the whole image) -> uint8 (h, w)"""
+        w, h = C.c_int32(0), C.c_int32(0)
+        args = (self._h, C.c_int32(image), C.c_int32(what), C.c_int32(cell), C.c_int32(level))
+        self._check(lib().uzl_orb_stage_image(*args, C.c_int64(0), None, C.byref(w), C.byref(h)))
+        out = np.zeros((h.value, w.value), np.uint8)
+        self._check(lib().uzl_orb_stage_image(*args, C.c_int64(out.size), _p(out, c_u8p), C.byref(w), C.byref(h)))
+        assert (h.value, w.value) == out.shape
+        return out
+
+    def stage_candidates(self, image, cell, level):
+        """Stage entry: the candidates of one (cell, level) before the cuts -> (x, y: int32 (n); score: uint8 (n); thr) in the
+        device's arrival order"""
+        args = (self._h, C.c_int32(image), C.c_int32(cell), C.c_int32(level))
+        n = self._check(lib().uzl_orb_stage_candidates(*args, C.c_int32(0), None, None, None, None))
+        x, y, s, thr = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.uint8), C.c_int32(-1)
+        m = self._check(lib().uzl_orb_stage_candidates(*args, C.c_int32(n), _p(x, c_i32p), _p(y, c_i32p), _p(s, c_u8p), C.byref(thr)))
+        assert m == n, (m, n)
+        return x, y, s, thr.value
 
 
 class Laser(_Handle):

@@ -46,6 +46,10 @@ struct uzl_orb : HandleBase {
     DevBuf<OrbKp> d_kp_tmp;
     PinBuf<uint8_t> h_read;
     DevBuf<int32_t> d_uv;
+    // the last staging chunk as its launches saw it (the stage entry): its records, its first image, its grid and level count
+    std::vector<OrbImage> chunk_images;
+    std::vector<OrbUnit> chunk_units;
+    int32_t chunk_first = 0, chunk_cells = 0, chunk_levels = 0;
 };
 
 namespace {
@@ -200,6 +204,9 @@ void run_chunk(uzl_orb* h, const OrbPlan& plan, const uzl_guide_image* images, c
     h->d_cand_score.reserve(std::max<size_t>((size_t)cand, 1));
     h->d_kp_tmp.reserve(std::max<size_t>((size_t)tmp, 1));
     h->d_counters.reserve(std::max<size_t>(n_counters, 1));
+    h->chunk_images.assign(ims, ims + ni);                 // the work buffers belong to this chunk until the next one
+    h->chunk_units.assign(units, units + n_units);
+    h->chunk_first = i0; h->chunk_cells = cells; h->chunk_levels = L;
     const uint8_t* d = h->stage.send(half, total, s);
     if (n_counters) UZL_HIP(hipMemsetAsync(h->d_counters.p, 0, n_counters * sizeof(uint32_t), s));
     OrbArgs a{};
@@ -239,6 +246,32 @@ void fetch_counts(uzl_orb* h)
         for (size_t i = 0; i < n; i++) h->counts[i] = std::min<uint32_t>(h->counts[i], (uint32_t)h->resident[i].kp_cap);
     }
     h->have_counts = true;
+}
+
+// The stage entry's way to a unit of the last chunk: the checks every stage read shares.  cell = -1 is the whole image.
+int stage_unit(uzl_orb* h, int32_t image, int32_t cell, int32_t level, const OrbImage** im, const OrbUnit** un)
+{
+    if (!h->have) return fail(h, UZL_ERR_STATE, "no extract yet");
+    if (image < 0 || (size_t)image >= h->resident.size()) return fail(h, UZL_ERR_BAD_ARG, "no such image");
+    if (cell < -1 || cell >= h->chunk_cells) return fail(h, UZL_ERR_BAD_ARG, "no such cell");
+    if (level < 0 || level >= h->chunk_levels) return fail(h, UZL_ERR_BAD_ARG, "no such level");
+    const int64_t k = (int64_t)image - h->chunk_first;
+    if (k < 0 || k >= (int64_t)h->chunk_images.size())
+        return fail(h, UZL_ERR_STATE, "the image is outside the last staging chunk: the work buffers hold that chunk only");
+    *im = &h->chunk_images[(size_t)k];
+    *un = &h->chunk_units[cell < 0 ? (size_t)(*im)->whole : (size_t)k * (size_t)h->chunk_cells + (size_t)cell];
+    return UZL_OK;
+}
+
+// n bytes of a work buffer through the pinned read buffer
+void stage_fetch(uzl_orb* h, const void* src, size_t n, void* out)
+{
+    if (!n) return;
+    UZL_HIP(hipSetDevice(h->cfg.device));
+    h->h_read.reserve(n);
+    UZL_HIP(hipMemcpyAsync(h->h_read.p, src, n, hipMemcpyDeviceToHost, h->stream));
+    UZL_HIP(hipStreamSynchronize(h->stream));
+    memcpy(out, h->h_read.p, n);
 }
 
 }  // namespace
@@ -397,6 +430,73 @@ int uzl_orb_lift(uzl_orb* h, int32_t image, uzl_depthfilter* depthfilter, int32_
     // this handle's
     const int rc = depthfilter_lift_device(depthfilter, h->cfg.device, df_image, n, a.u, a.v, max_depth, pos_xyz, valid3d);
     if (rc != UZL_OK) return fail(h, rc, "the filter handle refused the keypoints (see its last_error)");
+    return n;
+    UZL_GUARD_END(h)
+}
+
+int uzl_orb_stage_image(uzl_orb* h, int32_t image, int32_t what, int32_t cell, int32_t level, int64_t cap, uint8_t* out, int32_t* width,
+                        int32_t* height)
+{
+    UZL_GUARD_BEGIN(h)
+    if (what < UZL_ORB_STAGE_LEVEL || what > UZL_ORB_STAGE_GIST_BLUR) return fail(h, UZL_ERR_BAD_ARG, "no such stage image");
+    const bool gist = what == UZL_ORB_STAGE_GIST || what == UZL_ORB_STAGE_GIST_BLUR;
+    if (gist) { cell = -1; level = 0; }
+    const OrbImage* im = nullptr;
+    const OrbUnit* un = nullptr;
+    const int rc = stage_unit(h, image, cell, level, &im, &un);
+    if (rc != UZL_OK) return rc;
+    if (cap < 0) return fail(h, UZL_ERR_BAD_ARG, "negative capacity");
+    if ((what == UZL_ORB_STAGE_LEVEL || what == UZL_ORB_STAGE_MASK) && level == 0)
+        return fail(h, UZL_ERR_BAD_ARG, "level 0 of an image or a mask is the caller's own input");
+    if (what == UZL_ORB_STAGE_MASK && cell < 0) return fail(h, UZL_ERR_BAD_ARG, "masks are cut per cell: the whole image has no mask levels");
+    if (what == UZL_ORB_STAGE_BLUR && cell >= 0) return fail(h, UZL_ERR_BAD_ARG, "only the whole image's levels are blurred");
+    if (gist && !h->have_gist) return fail(h, UZL_ERR_STATE, "the last extract had no gist angles");
+    if (what == UZL_ORB_STAGE_MASK && im->width > 0 && !un->has_mask) return fail(h, UZL_ERR_STATE, "the last extract had no masks");
+    const OrbLevel& lv = un->lev[level];
+    const int32_t w = im->width == 0 ? 0 : gist ? kOrbGist : lv.w, ht = im->width == 0 ? 0 : gist ? kOrbGist : lv.h;
+    if (width) *width = w;
+    if (height) *height = ht;
+    const int64_t n = (int64_t)w * ht;
+    if (!out) return UZL_OK;
+    if (cap < n) return fail(h, UZL_ERR_TRUNCATED, "capacity below the image's width * height");
+    const uint8_t* src = what == UZL_ORB_STAGE_LEVEL ? h->d_pyr.p + lv.img_off : what == UZL_ORB_STAGE_MASK ? h->d_pyr.p + lv.mask_off
+                         : what == UZL_ORB_STAGE_BLUR ? h->d_blur.p + lv.blur_off : what == UZL_ORB_STAGE_GIST ? h->d_pyr.p + im->gist_off
+                         : h->d_blur.p + im->gist_blur_off;
+    stage_fetch(h, src, (size_t)n, out);                   // every one of these is compact: its pitch is its width
+    return UZL_OK;
+    UZL_GUARD_END(h)
+}
+
+int uzl_orb_stage_candidates(uzl_orb* h, int32_t image, int32_t cell, int32_t level, int32_t cap, int32_t* x, int32_t* y, uint8_t* score,
+                             int32_t* thr)
+{
+    UZL_GUARD_BEGIN(h)
+    const OrbImage* im = nullptr;
+    const OrbUnit* un = nullptr;
+    const int rc = stage_unit(h, image, cell, level, &im, &un);
+    if (rc != UZL_OK) return rc;
+    if (cell < 0) return fail(h, UZL_ERR_BAD_ARG, "candidates belong to a cell");
+    if (cap < 0) return fail(h, UZL_ERR_BAD_ARG, "negative capacity");
+    const OrbLevel& lv = un->lev[level];
+    // the chunk's counters: hist, n_cand, thr, one entry per (cell unit, level)
+    const size_t jobs = (size_t)h->chunk_images.size() * (size_t)h->chunk_cells * (size_t)h->chunk_levels;
+    const size_t job = ((size_t)(image - h->chunk_first) * (size_t)h->chunk_cells + (size_t)cell) * (size_t)h->chunk_levels + (size_t)level;
+    uint32_t nc = 0, t = 0;
+    stage_fetch(h, h->d_counters.p + jobs * kOrbBins + job, sizeof(uint32_t), &nc);
+    stage_fetch(h, h->d_counters.p + jobs * kOrbBins + jobs + job, sizeof(uint32_t), &t);
+    const int32_t n = (int32_t)std::min<uint32_t>(nc, (uint32_t)lv.cand_cap);
+    if ((x || y || score) && cap < n) return fail(h, UZL_ERR_TRUNCATED, "capacity below the number of candidates");
+    if (thr) *thr = (int32_t)t;
+    if (n == 0 || (!x && !y && !score)) return n;
+    if (x || y) {
+        std::vector<uint2> xy((size_t)n);
+        stage_fetch(h, h->d_cand_xy.p + lv.cand_off, (size_t)n * sizeof(uint2), xy.data());
+        for (int32_t i = 0; i < n; i++) {
+            if (x) x[i] = (int32_t)xy[i].x;
+            if (y) y[i] = (int32_t)xy[i].y;
+        }
+    }
+    if (score) stage_fetch(h, h->d_cand_score.p + lv.cand_off, (size_t)n, score);
     return n;
     UZL_GUARD_END(h)
 }
