@@ -39,7 +39,7 @@ def test_stage_hooks_live_in_the_diagnostic_library_only(capi):
     the product library."""
     import subprocess
     hooks = {"uzl_debug_pgo_linearize", "uzl_debug_pgo_solve", "uzl_debug_pgo_reduced", "uzl_debug_pgo_apply", "uzl_debug_pgo_hierarchy",
-             "uzl_debug_pgo_pcg_state", "uzl_debug_pgo_ban_mult", "uzl_debug_pgo_trial"}
+             "uzl_debug_pgo_pcg_state", "uzl_debug_pgo_ban_mult", "uzl_debug_pgo_trial", "uzl_debug_gate_stages"}
 
     def exported(path):
         out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
@@ -49,6 +49,8 @@ def test_stage_hooks_live_in_the_diagnostic_library_only(capi):
     assert not [n for n in exported(capi.LIB_PATH) if n.startswith("uzl_debug_pgo")]
     # and the hook of one outer iteration of the cloud registration (test_cloud_step_gpu.py)
     assert "uzl_debug_cloud_step" in exported(capi.DIAG_LIB_PATH) and "uzl_debug_cloud_step" not in exported(capi.LIB_PATH)
+    # and the read-back of which launch settled each candidate of the edge gate (test_gate_stages_gpu.py)
+    assert "uzl_debug_gate_stages" in exported(capi.DIAG_LIB_PATH) and "uzl_debug_gate_stages" not in exported(capi.LIB_PATH)
 
 
 def test_stage_entries_of_the_header_are_in_the_product_library(capi):

@@ -11,15 +11,20 @@ pytestmark = pytest.mark.gpu
 DMAX = np.finfo(np.float64).max
 
 
-def scenario(capi, n, e, seed, n_cand, valid_frac=0.5):
+def scenario(capi, n, e, seed, n_cand, valid_frac=0.5, draws=4, cut_every=0):
+    """draws: random node pairs drawn per wanted candidate (those within 2 m are kept); cut_every = k > 0: every k-th odometry edge is
+    not valid and no loop closure is, so the graph falls into chains of k nodes and most candidates are unreachable."""
     g = synth.make_pose_graph(n, e, seed=seed)
     ed = g["edges"]
     rng = np.random.default_rng(seed + 100)
     valid = np.where(ed["type"] == synth.EDGE_TYPE_ODOM, 1, (rng.random(len(ed["type"])) < valid_frac).astype(int))
+    if cut_every:
+        odom = ed["type"] == synth.EDGE_TYPE_ODOM
+        valid = np.where(odom, (np.cumsum(odom) % cut_every != 0).astype(int), 0)
     graph_edges = capi.gate_edges(ed["from"], ed["to"], ed["type"], valid=valid)
     gt = g["gt_pose"].reshape(n, 3, 4)
     # candidates: pairs of nodes within 2 m (some far apart in the graph), transform = noisy relative pose, mixed scores / types
-    a = rng.integers(0, n, 4 * n_cand); b = rng.integers(0, n, 4 * n_cand)
+    a = rng.integers(0, n, draws * n_cand); b = rng.integers(0, n, draws * n_cand)
     close = np.linalg.norm(gt[a][:, :, 3] - gt[b][:, :, 3], axis=1) < 2.0
     a, b = a[close & (a != b)][:n_cand], b[close & (a != b)][:n_cand]
     rel = synth.se3_mul(synth.se3_inv(gt[a]), gt[b])
@@ -33,14 +38,22 @@ def scenario(capi, n, e, seed, n_cand, valid_frac=0.5):
     return g["nodes_pose"], graph_edges, merged, c
 
 
+def _split(cfg):
+    """a row's dict: the handle's cfg and, under scene_*, what the row asks of scenario()"""
+    return ({k: v for k, v in cfg.items() if not k.startswith("scene_")}, {k[6:]: v for k, v in cfg.items() if k.startswith("scene_")})
+
+
 @pytest.mark.parametrize("n,e,seed,n_cand,cfg", [
     (300, 1200, 5, 400, dict()),
-    (1000, 5000, 6, 700, dict()),                                              # more candidates than one launch chunk
+    (1000, 5000, 6, 700, dict(scene_draws=12)),                                # more candidates than one launch chunk
     (400, 1500, 7, 300, dict(min_accept_valid=60.0)),                          # accepted edges become valid: re-search path
     (200, 700, 8, 200, dict(min_matching_score=40.0, max_edge_distance_T=1.5, max_edge_distance_R=35.0, scope_size_factor=0.3)),
+    (300, 1200, 10, 400, dict(max_edge_distance_T=100.0, max_edge_distance_R=360.0, scene_cut_every=25)),   # chains of 25 nodes: half the candidates are unreachable
 ])
 def test_gate_equals_oracle(capi, oracle, n, e, seed, n_cand, cfg):
-    P, E, merged, c = scenario(capi, n, e, seed, n_cand)
+    cfg, scene = _split(cfg)
+    P, E, merged, c = scenario(capi, n, e, seed, n_cand, **scene)
+    assert len(c) > 256 or "draws" not in scene
     g = capi.Gate(**cfg); o = oracle.Gate(**cfg)
     g.set_graph(P, E, merged); o.set_graph(P, E, merged)
     ag, vg, dg = g.check(c)
@@ -49,7 +62,9 @@ def test_gate_equals_oracle(capi, oracle, n, e, seed, n_cand, cfg):
     assert dg.tobytes() == do.tobytes()                                       # search distances bit-identical
     assert g.edge_count() == o.edge_count()
     assert 0.05 * len(c) < ag.sum() < 0.95 * len(c)                            # the scenario exercises both verdicts
-    assert (dg == DMAX).sum() >= 0 and (dg > 0).sum() > 10
+    unreachable = int((do == DMAX).sum())                                      # by the oracle: none in a connected graph, most in a cut one
+    assert (unreachable >= 10 if "cut_every" in scene else unreachable == 0) and (dg == DMAX).sum() == unreachable
+    assert ((dg > 0) & (dg < DMAX)).sum() > 10
     # a second call sees the edges accepted by the first one (existsEdge)
     ag2, _, _ = g.check(c)
     ao2, _, _ = o.check(c)
@@ -59,7 +74,7 @@ def test_gate_equals_oracle(capi, oracle, n, e, seed, n_cand, cfg):
 
 @pytest.mark.parametrize("n,e,seed,n_cand,cfg", [
     (300, 1200, 5, 400, dict()),
-    (1000, 5000, 6, 700, dict()),
+    (1000, 5000, 6, 700, dict(scene_draws=12)),
     (400, 1500, 7, 300, dict(min_accept_valid=60.0)),
     (200, 700, 8, 200, dict(min_matching_score=40.0, max_edge_distance_T=1.5, max_edge_distance_R=35.0, scope_size_factor=0.3)),
     (300, 1200, 9, 300, dict(scope_size_factor=0.0)),                          # the tests do not depend on the path length at all
@@ -68,7 +83,9 @@ def test_verdicts_without_path_lengths(capi, oracle, n, e, seed, n_cand, cfg):
     """astar_dist = NULL: uzl_gate_check may skip every search whose verdict the straight-line distance between the two nodes decides
     (checkEdgeHeuristic is monotone in the path length, and no path is shorter than the straight line).  The verdicts - and the graph
     the later candidates of the call see - must be the reference's all the same."""
-    P, E, merged, c = scenario(capi, n, e, seed, n_cand)
+    cfg, scene = _split(cfg)
+    P, E, merged, c = scenario(capi, n, e, seed, n_cand, **scene)
+    assert len(c) > 256 or "draws" not in scene
     g = capi.Gate(**cfg); o = oracle.Gate(**cfg)
     g.set_graph(P, E, merged); o.set_graph(P, E, merged)
     ag, vg, dg = g.check(c, want_dist=False)
@@ -122,10 +139,11 @@ def _verdicts_only(capi, P, E, c, accept_ref, cfg, oracle=None):
 
 
 def test_wave_search_on_long_chains_multi_edges_and_overflow(capi, oracle):
-    """The wave-per-candidate search (open list in LDS, neighbours in parallel lanes) against the CPU checker where it differs from
-    the lane kernel structurally: paths of thousands of hops along the odometry chain (an online run's shape), a node with more
-    neighbours than a node record holds, multi-edges (the same neighbour listed twice), and a graph dense enough that an open
-    list outgrows LDS and the search is redone by the lane kernel."""
+    """The wave-per-candidate search as these sizes run it - gate_reg_kernel: open list in registers, closed / open bitmaps in LDS,
+    neighbours in parallel lanes - against the CPU checker where it differs from the lane kernel structurally: paths of thousands of
+    hops along the odometry chain (an online run's shape), a node with more neighbours than a node record holds, multi-edges (the
+    same neighbour listed twice), and a graph dense enough that an open list outgrows the registers and the search is redone by the
+    lane kernel.  (gate_wave_kernel, with the list in LDS, only runs on graphs of more than 384 512 nodes: test_gate_stages_gpu.py.)"""
     rng = np.random.default_rng(3)
     # (a) chain-like: 6000 nodes, few valid loop closures; candidates between nodes thousands of hops apart
     g = synth.make_pose_graph(6000, 6300, seed=11)
@@ -143,7 +161,7 @@ def test_wave_search_on_long_chains_multi_edges_and_overflow(capi, oracle):
     assert np.array_equal(ag, ao) and dg.tobytes() == do.tobytes()
     assert (dg[dg < DMAX] > 100.0).sum() > 50                                 # paths of hundreds of hops (0.3 m each) were walked
     w, l = _counts(capi, G)
-    assert w > 0 and l == 0                                                  # all of them by the wave kernel
+    assert w > 0 and l == 0                                                  # none of them by the lane kernel (w counts gate_reg_kernel's searches too)
     G.close(); O.close()
     _verdicts_only(capi, g["nodes_pose"], E, c, ao, dict(max_edge_distance_R=360.0))
     # (b) a hub with 40 neighbours + every edge of the graph listed twice (two edge types between the same nodes)
@@ -161,7 +179,7 @@ def test_wave_search_on_long_chains_multi_edges_and_overflow(capi, oracle):
     assert np.array_equal(ag, ao) and dg.tobytes() == do.tobytes()
     G.close(); O.close()
     _verdicts_only(capi, g["nodes_pose"], E, c, ao, dict(max_edge_distance_T=100.0, max_edge_distance_R=360.0))
-    # (c) dense random graph: frontiers of thousands of nodes -> some open lists overflow LDS and fall back to the lane kernel
+    # (c) dense random graph: frontiers of thousands of nodes -> some open lists outgrow gate_reg_kernel<4>'s 256 entries and fall back to the lane kernel
     n = 6000
     P = np.tile(np.eye(3, 4).reshape(1, 12), (n, 1)); P[:, [3, 7, 11]] = rng.uniform(-30, 30, (n, 3))
     fr = rng.integers(0, n, 60000); to = rng.integers(0, n, 60000); keep = fr != to
@@ -172,6 +190,8 @@ def test_wave_search_on_long_chains_multi_edges_and_overflow(capi, oracle):
     G.set_graph(P, E); O.set_graph(P, E)
     ag, vg, dg = G.check(c); ao, vo, do = O.check(c)
     assert np.array_equal(ag, ao) and dg.tobytes() == do.tobytes()
+    w, l = _counts(capi, G)
+    assert l > 0                                                             # some of them by the lane kernel
     G.close(); O.close()
     _verdicts_only(capi, P, E, c, ao, dict(max_edge_distance_T=100.0, max_edge_distance_R=360.0))      # (the deciding search's list overflows its registers here)
     _verdicts_only(capi, P, E, c, None, dict(max_edge_distance_T=100.0, max_edge_distance_R=360.0, scope_size_factor=0.004), oracle)   # most need the greedy search

@@ -1,9 +1,9 @@
 """CPU tests of the edge-gate oracle (oracle/uzl_oracle_gate.c): GraphSlamNode::newEdgeCallback / checkEdgeHeuristic
 (graph_slam_node.cpp:779-829,1064-1085) and SlamGraph::astar (slam_graph.cpp:843-890), against hand-made known answers
 and a pure-Python restatement of the search."""
-import heapq
-
 import numpy as np
+
+import gate_reference
 
 from uzliti_slam_amd import capi, synth
 
@@ -26,22 +26,8 @@ def cand(frm, to, score=50.0, t=(0.1, 0.0, 0.0), yaw_deg=0.0, typ=1):
 
 
 def py_astar(pos, adj, s, t):
-    """the reference's loop, literally (priority = straight-line distance to the target only)"""
-    h = lambda a: float(np.sqrt(((pos[a] - pos[t]) ** 2)[[0, 1]].sum() + (pos[a][2] - pos[t][2]) ** 2))
-    d = lambda a, b: float(np.sqrt(((pos[a] - pos[b]) ** 2)[[0, 1]].sum() + (pos[a][2] - pos[b][2]) ** 2))
-    g = {s: 0.0}; open_ = {s}; closed = set(); heap = [(h(s), s)]
-    while open_:
-        w, v = heap[0]
-        if v == t:
-            return g[t]
-        heapq.heappop(heap); open_.discard(v); closed.add(v)
-        for u in adj[v]:
-            if u in closed:
-                continue
-            tent = g[v] + d(v, u)
-            if u not in open_ or tent < g[u]:
-                g[u] = tent; heapq.heappush(heap, (h(u), u)); open_.add(u)
-    return DMAX
+    """the reference's loop, literally (priority = straight-line distance to the target only): gate_reference.astar"""
+    return gate_reference.astar(pos, adj, s, t)[0]
 
 
 def test_astar_is_greedy_best_first(oracle):

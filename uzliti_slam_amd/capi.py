@@ -996,7 +996,7 @@ class Gate(_Handle):
         P = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
         E = np.ascontiguousarray(edges, GATE_EDGE_DTYPE)
         m = None if merged is None else np.ascontiguousarray(merged, np.uint8)
-        self._check(lib().uzl_gate_set_graph(self._h, C.c_int32(len(P)), _p(P, c_f64p), _p(m, c_u8p), C.c_int32(len(E)),
+        self._check(self._lib().uzl_gate_set_graph(self._h, C.c_int32(len(P)), _p(P, c_f64p), _p(m, c_u8p), C.c_int32(len(E)),
                                              _p(E, C.c_void_p) if len(E) else None))
 
     def check(self, cand, want_dist=True):
@@ -1005,12 +1005,33 @@ class Gate(_Handle):
         Cn = np.ascontiguousarray(cand, GATE_EDGE_DTYPE)
         n = len(Cn)
         acc = np.zeros(max(n, 1), np.uint8); val = np.zeros(max(n, 1), np.uint8); dist = np.zeros(max(n, 1)) if want_dist else None
-        self._check(lib().uzl_gate_check(self._h, C.c_int32(n), _p(Cn, C.c_void_p) if n else None, _p(acc, c_u8p), _p(val, c_u8p),
+        self._check(self._lib().uzl_gate_check(self._h, C.c_int32(n), _p(Cn, C.c_void_p) if n else None, _p(acc, c_u8p), _p(val, c_u8p),
                                          _p(dist, c_f64p) if want_dist else None))
         return acc[:n], val[:n], (dist[:n] if want_dist else None)
 
     def edge_count(self):
-        return self._check(lib().uzl_gate_edge_count(self._h))
+        return self._check(self._lib().uzl_gate_edge_count(self._h))
+
+
+class DiagGate(Gate):
+    """A Gate handle of the diagnostic library (diag_lib), the only one stages() works on: created and fed by that library's own
+    uzl_gate_* - a handle of the product library must never reach a uzl_debug_* hook."""
+
+    _lib = staticmethod(lambda: diag_lib())
+
+    def stages(self):
+        """uzl_debug_gate_stages: per candidate of the last check(), the launch that wrote its final outputs - 0 none (refused by the
+        host's index checks), 1 settled without the reference's search (straight line or ball), 2 gate_reg_kernel<2>,
+        3 gate_reg_kernel<4>, 4 gate_wave_kernel, 5 gate_kernel."""
+        L = self._lib()
+        L.uzl_debug_gate_stages.argtypes = [C.c_void_p, c_u8p, C.c_int32]
+        cap = 1 << 16
+        while True:
+            out = np.zeros(cap, np.uint8)
+            n = self._check(L.uzl_debug_gate_stages(self._h, _p(out, c_u8p), C.c_int32(cap)))
+            if n < cap:
+                return out[:n].copy()
+            cap *= 4
 
 
 def schur_plan(row_ptr, col, cap=24):

@@ -179,7 +179,8 @@ __global__ __launch_bounds__(kGateBlock) void gate_kernel(GateArgs a)
 // entries, so any implementation returns the reference's sequence), a node's position + degree + first neighbours come
 // in one 64-byte record, and the neighbours of the popped node are handled by one lane each (state + g-score in one
 // 16-byte record): two dependent round trips per step.  Same arithmetic as gate_kernel (node_dist operand order,
-// -ffp-contract=off): distances and verdicts are bit-identical (tests/test_gate_gpu.py runs both).
+// -ffp-contract=off): distances and verdicts are bit-identical.  The host launches this kernel only for graphs whose bitmaps do not fit
+// gate_reg_kernel's LDS (tests/test_gate_stages_gpu.py: the first such size, beside the last one that fits).
 __device__ __forceinline__ double rec_dist(double ax, double ay, double az, double bx, double by, double bz)
 {
     const double dx = ax - bx, dy = ay - by, dz = az - bz;

@@ -50,6 +50,9 @@ struct uzl_gate : HandleBase {
     DevBuf<uint8_t> d_redo;
     DevBuf<long long> d_dbg;         // diagnostic build (UZL_GATE_DBG=1): per-search counters of gate_reg_kernel
     std::vector<long long> dbg_last;
+#ifdef UZL_DIAG
+    std::vector<uint8_t> stage_last; // per candidate of the last uzl_gate_check: the launch that wrote its final outputs (uzl_debug_gate_stages)
+#endif
     bool dbg_on = false;
     int reg_slots = 2;               // open-list entries per lane gate_reg_kernel starts with (4 once a search of this handle outgrew 2)
     PinBuf<uint8_t> h_redo;
@@ -207,6 +210,10 @@ int uzl_gate_check(uzl_gate* h, int32_t nc, const uzl_gate_edge* cand, uint8_t* 
     h->h_pre.reserve((size_t)nc); h->h_heur.reserve((size_t)nc); h->h_dist.reserve((size_t)nc); h->h_over.reserve(1);
     UZL_HIP(hipMemcpyAsync(h->d_cand.p, cand, sizeof(uzl_gate_edge) * (size_t)nc, hipMemcpyHostToDevice, s));
     std::vector<uint8_t> run((size_t)nc), srch((size_t)nc);
+#ifdef UZL_DIAG
+    h->stage_last.assign((size_t)nc, 0);
+    std::vector<uint8_t> esc((size_t)nc);                    // searched again by gate_reg_kernel<4> in the current pass
+#endif
     int32_t first = 0;                                        // candidates before `first` are decided
     constexpr int kChunk = 256;                               // searches per launch (scratch = chunk x (9 n + 16 heap_cap) bytes)
     while (first < nc) {
@@ -240,6 +247,11 @@ int uzl_gate_check(uzl_gate* h, int32_t nc, const uzl_gate_edge* cand, uint8_t* 
         }
         bool any_left = true;
         for (int32_t k = first; k < last; k++) srch[k] = run[k];            // which candidates the search stages still have to run
+#ifdef UZL_DIAG
+        bool reg_ran = false;
+        const int slots0 = h->reg_slots;
+        for (int32_t k = first; k < last; k++) esc[k] = 0;
+#endif
         GateWaveArgs wa;
         memset(&wa, 0, sizeof(wa));
         wa.n = n; wa.n_query = m; wa.poses = h->d_poses.p; wa.rec = h->d_rec.p; wa.adj_nbr = h->d_adj_nbr.p;
@@ -268,6 +280,9 @@ int uzl_gate_check(uzl_gate* h, int32_t nc, const uzl_gate_edge* cand, uint8_t* 
         }
         if (any_left) {
             bool reg_ok = lds_path && launch_gate_reg(wa, h->reg_slots, s);
+#ifdef UZL_DIAG
+            reg_ran = reg_ok;
+#endif
             if (!reg_ok) {
                 if (lds_path) {                                                                // the attribute could not be raised: the HBM-state kernel
                     h->d_gst.reserve((size_t)m * std::max(n, 1));
@@ -288,6 +303,9 @@ int uzl_gate_check(uzl_gate* h, int32_t nc, const uzl_gate_edge* cand, uint8_t* 
                 std::vector<uint8_t> run4((size_t)m);
                 for (int32_t k = 0; k < m; k++) run4[k] = (srch[first + k] && h->h_redo.p[first + k]) ? 1 : 0;
                 UZL_HIP(hipMemcpyAsync(h->d_run.p + first, run4.data(), (size_t)m, hipMemcpyHostToDevice, s));
+#ifdef UZL_DIAG
+                for (int32_t k = 0; k < m; k++) esc[first + k] = run4[k];
+#endif
                 wa.keep_unrun = 1;
                 launch_gate_reg(wa, 4, s);
                 UZL_HIP(hipGetLastError());
@@ -335,6 +353,21 @@ int uzl_gate_check(uzl_gate* h, int32_t nc, const uzl_gate_edge* cand, uint8_t* 
         UZL_HIP(hipMemcpyAsync(h->h_over.p, h->d_over.p, 4, hipMemcpyDeviceToHost, s));
         UZL_HIP(hipStreamSynchronize(s));
         if (h->h_over.p[0]) return fail(h, UZL_ERR_STATE, "graph search ran out of heap space");
+#ifdef UZL_DIAG
+        // which launch wrote each candidate's outputs: 0 none, 1 settled without the reference's search (dist = -2: straight line or ball;
+        // or refused by gate_bound_kernel's thresholds), 2 / 3 gate_reg_kernel<2> / <4>, 4 gate_wave_kernel, 5 gate_kernel.  Candidates
+        // behind a valid accept are searched again by the next pass, which overwrites theirs.
+        for (int32_t q = first; q < last; q++) {
+            uint8_t st = 0;
+            if (run[q]) {
+                if (!srch[q] || h->h_dist.p[q] == -2.) st = 1;
+                else if (h->h_redo.p[q]) st = 5;
+                else if (!reg_ran) st = 4;
+                else st = (slots0 > 2 || esc[q]) ? 3 : 2;
+            }
+            h->stage_last[q] = st;
+        }
+#endif
         // replay newEdgeCallback in candidate order over the search results
         int32_t k = first;
         for (; k < last; k++) {
@@ -377,6 +410,18 @@ UZL_DIAG_EXPORT int uzl_debug_gate_profile(uzl_gate* h, long long* out, int32_t 
     std::lock_guard<std::mutex> lock(h->mu);
     const int32_t nq = (int32_t)std::min<size_t>(h->dbg_last.size() / 8, (size_t)std::max(cap, 0));
     for (int32_t i = 0; i < 8 * nq; i++) out[i] = h->dbg_last[i];
+    return nq;
+}
+
+// per candidate of the last uzl_gate_check, the launch that wrote its final outputs: 0 none (refused by the host's index checks),
+// 1 settled without the reference's search (straight line or ball), 2 gate_reg_kernel<2>, 3 gate_reg_kernel<4>, 4 gate_wave_kernel,
+// 5 gate_kernel.  Host bookkeeping only.  Returns the number of entries written.
+UZL_DIAG_EXPORT int uzl_debug_gate_stages(uzl_gate* h, uint8_t* out, int32_t cap)
+{
+    if (!h || !out) return UZL_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    const int32_t nq = (int32_t)std::min<size_t>(h->stage_last.size(), (size_t)std::max(cap, 0));
+    for (int32_t i = 0; i < nq; i++) out[i] = h->stage_last[i];
     return nq;
 }
 
