@@ -50,15 +50,15 @@ def cell(v, origin, res):
     return np.floor((np.asarray(v, np.float64) - origin) / res).astype(np.int64)
 
 
-def bresenham(x0, y0, x1, y1):
-    """step 5, literally: the visited cells of one ray, both ends included"""
+def bresenham_iter(x0, y0, x1, y1):
+    """step 5, literally: the visited cells of one ray in walk order, both ends included (lazily: a ray of 2^24 cells can be cut short)"""
     dx, dy = abs(x1 - x0), -abs(y1 - y0)
     sx, sy = (1 if x0 < x1 else -1), (1 if y0 < y1 else -1)
-    err, x, y, out = dx + dy, x0, y0, []
+    err, x, y = dx + dy, x0, y0
     while True:
-        out.append((x, y))
+        yield (x, y)
         if x == x1 and y == y1:
-            return out
+            return
         e2 = 2 * err
         if e2 >= dy:
             err += dy
@@ -66,6 +66,11 @@ def bresenham(x0, y0, x1, y1):
         if e2 <= dx:
             err += dx
             y += sy
+
+
+def bresenham(x0, y0, x1, y1):
+    """the visited cells of one ray as a list"""
+    return list(bresenham_iter(x0, y0, x1, y1))
 
 
 def beams(cfg, scan, S):
@@ -86,28 +91,35 @@ def beams(cfg, scan, S):
     return int(valid.sum()), ex, ey, hit
 
 
-def walk_lockstep(x0, y0, x1, y1, W, H, passes):
-    """step 5 for many rays at once: passes (flat, W*H) += 1 on every visited in-bounds cell"""
+def steps(x0, y0, x1, y1):
+    """step 5 for many rays at once: yields (ray indices, x, y) of the cells visited at step 0, 1, 2, ... (finished rays dropped)"""
     x, y = np.array(x0, np.int64), np.array(y0, np.int64)
     x1, y1 = np.array(x1, np.int64), np.array(y1, np.int64)
+    idx = np.arange(len(x))
     dx, dy = np.abs(x1 - x), -np.abs(y1 - y)
     sx, sy = np.where(x < x1, 1, -1), np.where(y < y1, 1, -1)
     err = dx + dy
-    buf, nbuf = [], 0
     while len(x):
+        yield idx, x, y
+        act = ~((x == x1) & (y == y1))
+        idx, x, y, x1, y1, dx, dy, sx, sy, err = (a[act] for a in (idx, x, y, x1, y1, dx, dy, sx, sy, err))
+        e2 = 2 * err
+        mx, my = e2 >= dy, e2 <= dx
+        err = err + np.where(mx, dy, 0) + np.where(my, dx, 0)
+        x = x + np.where(mx, sx, 0)
+        y = y + np.where(my, sy, 0)
+
+
+def walk_lockstep(x0, y0, x1, y1, W, H, passes):
+    """step 5 for many rays at once: passes (flat, W*H) += 1 on every visited in-bounds cell"""
+    buf, nbuf = [], 0
+    for _, x, y in steps(x0, y0, x1, y1):
         inb = (x >= 0) & (x < W) & (y >= 0) & (y < H)
         buf.append(y[inb] * W + x[inb])
         nbuf += int(inb.sum())
         if nbuf > 20_000_000:
             passes += np.bincount(np.concatenate(buf), minlength=W * H).astype(passes.dtype)
             buf, nbuf = [], 0
-        act = ~((x == x1) & (y == y1))
-        x, y, x1, y1, dx, dy, sx, sy, err = (a[act] for a in (x, y, x1, y1, dx, dy, sx, sy, err))
-        e2 = 2 * err
-        mx, my = e2 >= dy, e2 <= dx
-        err = err + np.where(mx, dy, 0) + np.where(my, dx, 0)
-        x = x + np.where(mx, sx, 0)
-        y = y + np.where(my, sy, 0)
     if buf:
         passes += np.bincount(np.concatenate(buf), minlength=W * H).astype(passes.dtype)
 

@@ -51,6 +51,9 @@ def test_stage_hooks_live_in_the_diagnostic_library_only(capi):
     assert "uzl_debug_cloud_step" in exported(capi.DIAG_LIB_PATH) and "uzl_debug_cloud_step" not in exported(capi.LIB_PATH)
     # and the read-back of which launch settled each candidate of the edge gate (test_gate_stages_gpu.py)
     assert "uzl_debug_gate_stages" in exported(capi.DIAG_LIB_PATH) and "uzl_debug_gate_stages" not in exported(capi.LIB_PATH)
+    # and the host side of the occupancy grid: the tile clip and the plan of a build (test_grid_plan_cpu.py)
+    for name in ("uzl_debug_grid_ray_clip", "uzl_debug_grid_plan"):
+        assert name in exported(capi.DIAG_LIB_PATH) and name not in exported(capi.LIB_PATH), name
 
 
 def test_stage_entries_of_the_header_are_in_the_product_library(capi):

@@ -1403,6 +1403,60 @@ class Grid(_Handle):
         return hits.reshape(i["height"], i["width"]), passes.reshape(i["height"], i["width"])
 
 
+def grid_ray_clip(rays, cap):
+    """uzl_debug_grid_ray_clip (diagnostic library, host only): rays [n, 8] = x0, y0, x1, y1, ux0, uy0, ux1, uy1 ->
+    (count [n] int64, cells [n, cap, 2] int32: the first min(count, cap) cells of each ray inside its rectangle, in walk order)"""
+    q = np.ascontiguousarray(rays, np.int32).reshape(-1, 8)
+    count = np.zeros(len(q), np.int64)
+    cells = np.zeros((len(q), cap, 2), np.int32)
+    L = diag_lib()
+    L.uzl_debug_grid_ray_clip.argtypes = [C.c_int32, c_i32p, C.c_int32, C.POINTER(C.c_int64), c_i32p]
+    rc = L.uzl_debug_grid_ray_clip(len(q), _p(q, c_i32p), cap, _p(count, C.POINTER(C.c_int64)), _p(cells, c_i32p))
+    if rc != UZL_OK:
+        raise UzlError(rc, "uzl_debug_grid_ray_clip")
+    return count, cells
+
+
+def grid_plan(cfg, geom, poses, scans, present=None, first_node=0):
+    """uzl_debug_grid_plan (diagnostic library, host only): the bins of a build (first_node = 0) or an extend on the geometry
+    geom = (origin_x, origin_y, width, height) for cfg (keywords of GridCfg over the defaults), poses [n, 12] and scans (dicts with
+    node, n or ranges, range_min and optionally displacement) -> dict of tiles, ent_start, ent_scan, ent_beam, kf_start,
+    kf_rect [rects, 4], ocx, ocy (per projected scan).  A refusal raises UzlError with plan()'s reason."""
+    L = diag_lib()
+    c = GridCfg()
+    L.uzl_grid_cfg_default(C.byref(c))
+    for k, v in cfg.items():
+        setattr(c, k, v)
+    P, pr = Grid._poses(poses, present)
+    node = np.array([int(s["node"]) for s in scans], np.int32)
+    n = np.array([int(s["n"]) if "n" in s else len(s["ranges"]) for s in scans], np.int32)
+    rmin = np.array([float(s["range_min"]) for s in scans], np.float32)
+    D = np.array([np.asarray(s.get("displacement", np.eye(3, 4)), np.float64).reshape(12) for s in scans], np.float64).reshape(-1, 12)
+    origin = np.array([geom[0], geom[1]], np.float64)
+    sizes = np.zeros(4, np.int64)
+    err = C.create_string_buffer(256)
+    c_i64p, c_f32p = C.POINTER(C.c_int64), C.POINTER(C.c_float)
+    L.uzl_debug_grid_plan.argtypes = [C.POINTER(GridCfg), c_f64p, C.c_uint32, C.c_uint32, C.c_int32, c_f64p, c_u8p, C.c_int32, C.c_int32, c_i32p,
+                                      c_f64p, c_i32p, c_f32p, c_i64p, c_i32p, c_i32p, c_i32p, c_i64p, c_i32p, c_i32p, c_i32p, c_i32p,
+                                      C.c_char_p, C.c_int32]
+
+    def call(*out):
+        rc = L.uzl_debug_grid_plan(C.byref(c), _p(origin, c_f64p), int(geom[2]), int(geom[3]), len(P), _p(P, c_f64p), _p(pr, c_u8p),
+                                   int(first_node), len(scans), _p(node, c_i32p), _p(D, c_f64p), _p(n, c_i32p), _p(rmin, c_f32p),
+                                   _p(sizes, c_i64p), *out, err, len(err))
+        if rc != UZL_OK:
+            raise UzlError(rc, err.value.decode() or "uzl_debug_grid_plan")
+
+    call(*([None] * 8))
+    nr, nt, ne, nk = (int(v) for v in sizes)
+    o = dict(tiles=np.zeros(nt, np.int32), ent_start=np.zeros(nt + 1, np.int32), ent_scan=np.zeros(ne, np.int32),
+             ent_beam=np.zeros(ne, np.int64), kf_start=np.zeros(nt + 1, np.int32), kf_rect=np.zeros((nk, 4), np.int32),
+             ocx=np.zeros(nr, np.int32), ocy=np.zeros(nr, np.int32))
+    call(*[_p(o[k], c_i64p if k == "ent_beam" else c_i32p) for k in ("tiles", "ent_start", "ent_scan", "ent_beam", "kf_start", "kf_rect",
+                                                                     "ocx", "ocy")])
+    return o
+
+
 class Laserline(_Handle):
     """uzl_laserline_* (GraphGridMapper::extractImageLaserLine + mergeLaserScans + scanMean, map_projection/src/graph_grid_mapper.cpp:
     420-468, 135-212, 605-621): depth images binned by bearing into the laser scans the occupancy grid ray-traces."""

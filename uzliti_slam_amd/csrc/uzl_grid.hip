@@ -114,9 +114,11 @@ struct Plan {
     std::vector<int4> kf_rect;
 };
 
-// Steps 2-5 of the nodes >= first: the scans' records and cell boxes, the known-free rectangles, and their tiles.
-int plan(uzl_grid* h, const uzl_grid_cfg& c, const GridGeom& g, int32_t n_nodes, const double* poses, const uint8_t* present,
-         int32_t first, Plan& p)
+// Steps 2-5 of the nodes >= first: the scans' records and cell boxes, the known-free rectangles, and their tiles.  Host arithmetic
+// on the stored scans' descriptions alone (tests/test_grid_plan_cpu.py holds its invariants through uzl_debug_grid_plan); a refusal
+// leaves its reason in err.
+int plan(const std::vector<GridScanHost>& scans, const uzl_grid_cfg& c, const GridGeom& g, int32_t n_nodes, const double* poses,
+         const uint8_t* present, int32_t first, Plan& p, std::string& err)
 {
     const int32_t W = (int32_t)g.width, H = (int32_t)g.height;
     const int32_t tiles_x = (W + kGridTile - 1) / kGridTile, tiles_y = (H + kGridTile - 1) / kGridTile;
@@ -126,7 +128,7 @@ int plan(uzl_grid* h, const uzl_grid_cfg& c, const GridGeom& g, int32_t n_nodes,
     const double reff = std::max(0., std::min(c.range_max, c.max_distance));
     struct Box { int32_t x0, y0, x1, y1; };
     std::vector<Box> sbox;                     // per record: tile box (x0 > x1: off the grid)
-    for (const GridScanHost& s : h->scans) {
+    for (const GridScanHost& s : scans) {
         if (s.node >= n_nodes || !adds(present, s.node, first)) continue;
         double S[12];
         compose(poses + 12 * (size_t)s.node, s.D, S);
@@ -134,8 +136,10 @@ int plan(uzl_grid* h, const uzl_grid_cfg& c, const GridGeom& g, int32_t n_nodes,
         r.r00 = S[0]; r.r01 = S[1]; r.r10 = S[4]; r.r11 = S[5]; r.tx = S[3]; r.ty = S[7];
         r.ranges_off = s.ranges_off; r.trig_off = s.trig_off; r.n = s.n; r.range_min = s.range_min;
         const double bx = std::sqrt(S[0] * S[0] + S[1] * S[1]) * reff, by = std::sqrt(S[4] * S[4] + S[5] * S[5]) * reff;
-        if (!std::isfinite(bx) || !std::isfinite(by) || bx / res > kGridMaxRayCells || by / res > kGridMaxRayCells)
-            return fail(h, UZL_ERR_BAD_ARG, "a scan's pose scales its rays beyond 2^24 cells");
+        if (!std::isfinite(bx) || !std::isfinite(by) || bx / res > kGridMaxRayCells || by / res > kGridMaxRayCells) {
+            err = "a scan's pose scales its rays beyond 2^24 cells";
+            return UZL_ERR_BAD_ARG;
+        }
         // conservative world box (relative slack for the roundings of p, q, e), one cell of margin for the floor
         const double sx = bx * (1 + 1e-6) + 1e-9 * (std::fabs(r.tx) + 1.), sy = by * (1 + 1e-6) + 1e-9 * (std::fabs(r.ty) + 1.);
         const double cx0 = std::floor((r.tx - sx - g.origin_x) / res) - 1, cx1 = std::floor((r.tx + sx - g.origin_x) / res) + 1;
@@ -395,7 +399,8 @@ int uzl_grid_build(uzl_grid* h, int32_t n_nodes, const double* poses, const uint
     GridGeom g;
     if (int rc = geometry(h, c, n_nodes, poses, present, &g)) return rc;
     Plan p;
-    if (int rc = plan(h, c, g, n_nodes, poses, present, 0, p)) return rc;
+    std::string err;
+    if (int rc = plan(h->scans, c, g, n_nodes, poses, present, 0, p, err)) return fail(h, rc, err.c_str());
     UZL_HIP(hipSetDevice(h->cfg.device));
     h->built = false;                        // a failure below leaves no half-built grid behind
     h->gcfg = c;
@@ -415,7 +420,8 @@ int uzl_grid_extend(uzl_grid* h, int32_t n_nodes, const double* poses, const uin
     if (first_node < 0) return fail(h, UZL_ERR_BAD_ARG, "negative first_node");
     if (int rc = check_poses(h, n_nodes, poses, present)) return rc;
     Plan p;
-    if (int rc = plan(h, h->gcfg, h->geom, n_nodes, poses, present, first_node, p)) return rc;
+    std::string err;
+    if (int rc = plan(h->scans, h->gcfg, h->geom, n_nodes, poses, present, first_node, p, err)) return fail(h, rc, err.c_str());
     UZL_HIP(hipSetDevice(h->cfg.device));
     const int32_t og = off_grid(h->gcfg, h->geom, n_nodes, poses, present, first_node);
     run(h, p, false);
@@ -462,6 +468,80 @@ int uzl_grid_counts(uzl_grid* h, int64_t cap, uint32_t* hits, uint32_t* passes)
 }
 
 }  // extern "C"
+
+#ifdef UZL_DIAG
+// grid_ray_clip on the host (tests/test_grid_plan_cpu.py): case i is rays[8 i ..] = x0, y0, x1, y1 and the rectangle ux0, uy0, ux1, uy1
+// (inclusive); count[i] = the cells it visits, cells[2 cap i ..] = the first min(count, cap) of them as (x, y) in walk order.
+extern "C" UZL_DIAG_EXPORT int uzl_debug_grid_ray_clip(int32_t n, const int32_t* rays, int32_t cap, int64_t* count, int32_t* cells)
+{
+    if (n < 0 || cap < 0 || (n > 0 && (!rays || !count || (cap > 0 && !cells)))) return UZL_ERR_BAD_ARG;
+    for (int32_t i = 0; i < n; i++) {
+        const int32_t* q = rays + 8 * (size_t)i;
+        int32_t* out = cells + 2 * (size_t)cap * (size_t)i;
+        int64_t m = 0;
+        grid_ray_clip(q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], [&](int32_t x, int32_t y) {
+            if (m < cap) { out[2 * m] = x; out[2 * m + 1] = y; }
+            m++;
+        });
+        count[i] = m;
+    }
+    return UZL_OK;
+}
+
+// plan() without a handle or a device (tests/test_grid_plan_cpu.py): the bins a build (first_node = 0) or an extend would upload for
+// the config, the geometry (origin_x, origin_y, width, height), the poses and the scans' descriptions (node, displacement [12], n,
+// range_min each).  sizes[4] = records, tiles, entries, known-free rectangles: with every output NULL the call only counts; otherwise
+// sizes holds the room on entry (in those units) and the outputs are tiles [tiles], ent_start / kf_start [tiles + 1], ent_scan /
+// ent_beam [entries], kf_rect [4 rects] and the records' ocx / ocy [records].  A refusal of plan() is returned with its reason in err.
+extern "C" UZL_DIAG_EXPORT int uzl_debug_grid_plan(const uzl_grid_cfg* cfg, const double* origin, uint32_t width, uint32_t height, int32_t n_nodes,
+                                                   const double* poses, const uint8_t* present, int32_t first_node, int32_t n_scans,
+                                                   const int32_t* scan_node, const double* scan_D, const int32_t* scan_n,
+                                                   const float* scan_range_min, int64_t* sizes, int32_t* tiles, int32_t* ent_start,
+                                                   int32_t* ent_scan, int64_t* ent_beam, int32_t* kf_start, int32_t* kf_rect, int32_t* ocx,
+                                                   int32_t* ocy, char* err, int32_t err_cap)
+{
+    if (!cfg || !origin || !sizes || n_nodes < 0 || (n_nodes > 0 && !poses) || first_node < 0 || n_scans < 0 ||
+        (n_scans > 0 && (!scan_node || !scan_D || !scan_n || !scan_range_min)) || check_cfg(*cfg) != UZL_OK)
+        return UZL_ERR_BAD_ARG;
+    try {
+        std::vector<GridScanHost> scans((size_t)n_scans);
+        for (int32_t i = 0; i < n_scans; i++) {
+            GridScanHost& s = scans[i];
+            if (scan_node[i] < 0 || scan_n[i] < 0) return UZL_ERR_BAD_ARG;
+            s.node = scan_node[i]; s.n = scan_n[i]; memcpy(s.D, scan_D + 12 * (size_t)i, sizeof(s.D));
+            s.range_min = scan_range_min[i]; s.ranges_off = 0; s.trig_off = 0;
+        }
+        GridGeom g;
+        g.origin_x = origin[0]; g.origin_y = origin[1]; g.width = width; g.height = height;
+        Plan p;
+        std::string why;
+        if (int rc = plan(scans, *cfg, g, n_nodes, poses, present, first_node, p, why)) {
+            if (err && err_cap > 0) { strncpy(err, why.c_str(), (size_t)err_cap - 1); err[err_cap - 1] = 0; }
+            return rc;
+        }
+        const int64_t need[4] = {(int64_t)p.recs.size(), (int64_t)p.tiles.size(), (int64_t)p.ent_scan.size(), (int64_t)p.kf_rect.size()};
+        const bool fill = tiles || ent_start || ent_scan || ent_beam || kf_start || kf_rect || ocx || ocy;
+        if (fill) {
+            for (int i = 0; i < 4; i++)
+                if (sizes[i] < need[i]) return UZL_ERR_TRUNCATED;
+            if (!tiles || !ent_start || !ent_scan || !ent_beam || !kf_start || !kf_rect || !ocx || !ocy) return UZL_ERR_BAD_ARG;
+            std::copy(p.tiles.begin(), p.tiles.end(), tiles);
+            std::copy(p.ent_start.begin(), p.ent_start.end(), ent_start);
+            std::copy(p.ent_scan.begin(), p.ent_scan.end(), ent_scan);
+            std::copy(p.ent_beam.begin(), p.ent_beam.end(), ent_beam);
+            std::copy(p.kf_start.begin(), p.kf_start.end(), kf_start);
+            for (size_t i = 0; i < p.kf_rect.size(); i++) {
+                kf_rect[4 * i] = p.kf_rect[i].x; kf_rect[4 * i + 1] = p.kf_rect[i].y; kf_rect[4 * i + 2] = p.kf_rect[i].z; kf_rect[4 * i + 3] = p.kf_rect[i].w;
+            }
+            for (size_t i = 0; i < p.recs.size(); i++) { ocx[i] = p.recs[i].ocx; ocy[i] = p.recs[i].ocy; }
+        }
+        for (int i = 0; i < 4; i++) sizes[i] = need[i];
+        return UZL_OK;
+    } catch (const std::bad_alloc&) {
+        return UZL_ERR_OOM;
+    }
+}
+#endif  // UZL_DIAG
 
 // uzl_laserline_to_grid's way into the store (declared in grid_types.hpp): n_scans scans of n_beams ranges each, contiguous in the
 // memory of `device` and complete (the caller has synchronised their producer), appended as uzl_grid_add_scans appends scans
