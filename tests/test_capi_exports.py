@@ -39,7 +39,7 @@ def test_stage_hooks_live_in_the_diagnostic_library_only(capi):
     the product library."""
     import subprocess
     hooks = {"uzl_debug_pgo_linearize", "uzl_debug_pgo_solve", "uzl_debug_pgo_reduced", "uzl_debug_pgo_apply", "uzl_debug_pgo_hierarchy",
-             "uzl_debug_pgo_pcg_state", "uzl_debug_pgo_ban_mult", "uzl_debug_pgo_trial", "uzl_debug_gate_stages"}
+             "uzl_debug_pgo_pcg_state", "uzl_debug_pgo_ban_mult", "uzl_debug_pgo_trial", "uzl_debug_pgo_structure_plan", "uzl_debug_gate_stages"}
 
     def exported(path):
         out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout

@@ -480,7 +480,7 @@ def test_near_tree_graph_without_odometry(capi, oracle):
 
 def test_vertex_order_does_not_matter(capi, oracle):
     """The aggregates of the preconditioner are 8 consecutive blocks of an order derived from the graph (heaviest-edge chains,
-    uzl_pgo.hip aggregation_order), not of the node index: renumbered nodes, two sessions with interleaved ids (merged / global-scope
+    pgo_structure.hip aggregation_order), not of the node index: renumbered nodes, two sessions with interleaved ids (merged / global-scope
     graphs, graph_slam_node.cpp:401-576) and graphs without an odometry chain must solve to the oracle's result with iteration
     counts close to the time-ordered case (with index-order aggregates they were 7x / 4-6x higher)."""
     n, e, its = 1000, 5000, 10

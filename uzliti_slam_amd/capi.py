@@ -710,7 +710,7 @@ class Pgo(_Handle):
 
 
 class DiagPgo(Pgo):
-    """A Pgo handle of the diagnostic library (diag_lib), with its stage-level hooks of the linear system (uzl_pgo.hip, UZL_DIAG): the
+    """A Pgo handle of the diagnostic library (diag_lib), with its stage-level hooks of the linear system (uzl_pgo_debug.hip, UZL_DIAG): the
     handle is created and fed by that library's own uzl_pgo_* - a handle of the product library must never reach a uzl_debug_* hook."""
 
     _lib = staticmethod(lambda: diag_lib())
@@ -1101,6 +1101,90 @@ def ml_plan(row_ptr, col, precond_on=True, strong_blocks=False, mult_banned=Fals
             lv["col"] = cl if l == 0 else array(l, 1)
         out["lv"].append(lv)
     return out
+
+
+_STRUCTURE_STAGES = dict(flatten=0, gauge=1, order=2, system=3, row_blocks=4, numbering=5, admission=6, shard=7, exchange=8, grown=9)
+
+
+def pgo_structure_plan(stage, **kw):
+    """uzl_debug_pgo_structure_plan (diagnostic library, host only): one stage of the structure of a pose graph (csrc/pgo_structure.hpp)
+    -> dict of everything the stage decides.  Stages and their keyword arguments:
+      flatten    n, fixed [n], in_edges [e_in, 4] = (from, to, odom, valid), in_w [e_in]            -> ij [e, 2], src, robust, edge_w
+      gauge      n, fixed, ij                                                                       -> fixed_eff, n_gauge
+      order      n, fixed (effective), ij, edge_w (None: every edge weighs 1)                       -> b2v
+      system     n, ij, robust, b2v                      -> nb, nslots, n_rb, v2b, row_ptr, col, slot_edge, smeta [nslots, 4], rb_ptr, rowhdr [rows, 24]
+      row_blocks row_ptr                                                                            -> rb_ptr, cap_slots, cap_rows, max_partials
+      numbering  cfg_numbering, preconditioner, may_shard, num_its (2)                              -> strong_min, max_contig
+      admission  nb, n_int                                                                          -> min_int, admitted
+      shard      e, rank, world                                                                     -> e_begin, e_end, diag_owner
+      exchange   row_ptr, col of the system the PCG solves (+ ml_plan's flags)                      -> sg, part_a, iter_span, gather_level, n_gather
+      grown      old = (n, fixed, ij), new = (n, fixed, ij), window                                 -> survive, grown"""
+    L = diag_lib()
+    i32 = lambda a: np.ascontiguousarray(a if a is not None else [], np.int32).reshape(-1)
+    u8 = lambda a: np.ascontiguousarray(a if a is not None else [], np.uint8).reshape(-1)
+
+    def run(iv, what, dtype, dv=None, fixed=None, ij=None, robust=None, edge_w=None, aux=None):
+        iv = i32(iv); dv = None if dv is None else np.ascontiguousarray(dv, np.float64)
+        arrs = [None if a is None or len(a) == 0 else a for a in (fixed, ij, robust, edge_w, aux)]
+
+        def call(out, nbytes):
+            rc = L.uzl_debug_pgo_structure_plan(C.c_int32(_STRUCTURE_STAGES[stage]), _p(iv, c_i32p), _p(dv, c_f64p), _p(arrs[0], c_u8p), _p(arrs[1], c_i32p),
+                                                _p(arrs[2], c_u8p), _p(arrs[3], c_f64p), _p(arrs[4], c_i32p), C.c_int32(what),
+                                                out.ctypes.data_as(C.c_void_p) if out is not None else None, C.byref(nbytes))
+            if rc != UZL_OK:
+                raise UzlError(rc, "uzl_debug_pgo_structure_plan(%s, %d)" % (stage, what))
+
+        nbytes = C.c_int64(0)
+        call(None, nbytes)
+        out = np.zeros(nbytes.value // np.dtype(dtype).itemsize, dtype)
+        if nbytes.value:
+            call(out, nbytes)
+        return out
+
+    if stage == "flatten":
+        ie = i32(kw["in_edges"]); a = dict(iv=[kw["n"], len(ie) // 4], fixed=u8(kw["fixed"]), aux=ie, edge_w=np.ascontiguousarray(kw["in_w"], np.float64))
+        return dict(ij=run(what=0, dtype=np.int32, **a).reshape(-1, 2), src=run(what=1, dtype=np.int32, **a), robust=run(what=2, dtype=np.uint8, **a),
+                    edge_w=run(what=3, dtype=np.float64, **a))
+    if stage in ("gauge", "order"):
+        ij = i32(kw["ij"]); a = dict(iv=[kw["n"], len(ij) // 2], fixed=u8(kw["fixed"]), ij=ij)
+        if stage == "gauge":
+            return dict(fixed_eff=run(what=0, dtype=np.uint8, **a), n_gauge=int(run(what=1, dtype=np.int32, **a)[0]))
+        w = kw.get("edge_w")
+        return dict(b2v=run(what=0, dtype=np.int32, edge_w=None if w is None else np.ascontiguousarray(w, np.float64), **a))
+    if stage == "system":
+        ij = i32(kw["ij"]); b2v = i32(kw["b2v"]); a = dict(iv=[kw["n"], len(ij) // 2, len(b2v)], ij=ij, robust=u8(kw["robust"]), aux=b2v)
+        sz = run(what=0, dtype=np.int32, **a)
+        out = dict(nb=int(sz[0]), nslots=int(sz[1]), n_rb=int(sz[2]))
+        for what, k in enumerate(("v2b", "row_ptr", "col", "slot_edge", "smeta", "rb_ptr", "rowhdr"), 1):
+            out[k] = run(what=what, dtype=np.int32, **a)
+        out["smeta"] = out["smeta"].reshape(-1, 4); out["rowhdr"] = out["rowhdr"].reshape(-1, 24)
+        return out
+    if stage == "row_blocks":
+        rp = i32(kw["row_ptr"]); a = dict(iv=[len(rp) - 1], aux=rp)
+        caps = run(what=1, dtype=np.int32, **a)
+        return dict(rb_ptr=run(what=0, dtype=np.int32, **a), cap_slots=int(caps[0]), cap_rows=int(caps[1]), max_partials=int(caps[2]))
+    if stage == "numbering":
+        r = run(iv=[kw["cfg_numbering"], kw["preconditioner"], 1 if kw["may_shard"] else 0], dv=kw["num_its"], what=0, dtype=np.float64)
+        return dict(strong_min=int(r[0]), max_contig=float(r[1]))
+    if stage == "admission":
+        r = run(iv=[kw["nb"], kw["n_int"]], what=0, dtype=np.int32)
+        return dict(min_int=int(r[0]), admitted=bool(r[1]))
+    if stage == "shard":
+        r = run(iv=[kw["e"], kw["rank"], kw["world"]], what=0, dtype=np.int32)
+        return dict(e_begin=int(r[0]), e_end=int(r[1]), diag_owner=int(r[2]))
+    if stage == "exchange":
+        rp = i32(kw["row_ptr"])
+        flags = ((1 if kw.get("precond_on", True) else 0) | (2 if kw.get("strong_blocks") else 0) | (4 if kw.get("mult_banned") else 0) |
+                 (8 if kw.get("comp4_off") else 0))
+        r = run(iv=[len(rp) - 1, flags], aux=rp, ij=i32(kw["col"]), what=0, dtype=np.int64)
+        return dict(zip(("sg", "part_a", "iter_span", "gather_level", "n_gather"), (int(v) for v in r)))
+    if stage == "grown":
+        (n0, f0, ij0), (n1, f1, ij1) = kw["old"], kw["new"]
+        ij0, ij1 = i32(ij0), i32(ij1)
+        r = run(iv=[n0, n1, len(ij0) // 2, len(ij1) // 2, kw.get("window", 4096)], fixed=np.concatenate([u8(f0)[:n0], u8(f1)[:n1]]), aux=ij0, ij=ij1, what=0,
+                dtype=np.int32)
+        return dict(survive=bool(r[0]), grown=bool(r[1]))
+    raise ValueError(stage)
 
 
 # --------------------------------------------------------------------------------------- distance loop-closure candidates

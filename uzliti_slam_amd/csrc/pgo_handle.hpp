@@ -1,11 +1,12 @@
 // pgo_handle.hpp — the pose-graph handle (struct uzl_pgo), the kernel launchers and the host-side pieces shared by the translation
-// units behind uzl_pgo_*: uzl_pgo.hip (C ABI, structure, the host-driven Levenberg-Marquardt loop), uzl_pgo_lm.hip (the device-resident
-// loop: captured passes over slot twins).  Private to csrc/: the product surface is include/uzl_mi355x.h.
+// units behind uzl_pgo_*: uzl_pgo.hip (C ABI, structure uploads, the host-driven Levenberg-Marquardt loop), uzl_pgo_lm.hip (the device-resident
+// loop: captured passes over slot twins), uzl_pgo_debug.hip (the stage hooks of the diagnostic library).  Private to csrc/: the product surface is include/uzl_mi355x.h.
 #pragma once
 #include "uzl_common.hpp"
 #include "pgo_types.hpp"
 #include "pgo_schur.hpp"
 #include "pgo_ml_plan.hpp"
+#include "pgo_structure.hpp"
 #include "pgo_lm.hpp"
 
 #include <algorithm>
@@ -84,9 +85,10 @@ using namespace uzl;      // (private header of the uzl_pgo_* translation units;
 struct SysBufs {
     DevBuf<int32_t> row_ptr, col, rowhdr, b2v;
     DevBuf<double> blk, hdiag, minv, x, xs, r, z, p, p2, ap;
-    // sizes for nb rows, then the index arrays and the row headers made of them; returns the headers' staging vector: keep it (and the
-    // arguments) until the stream has been synchronised
-    std::vector<int32_t> upload(int nb, const std::vector<int32_t>& h_row_ptr, const std::vector<int32_t>& h_col, const std::vector<int32_t>& h_b2v, hipStream_t s)
+    // sizes for nb rows, then copies the index arrays and the row headers (row_headers, pgo_structure.hpp): keep the arguments until the
+    // stream has been synchronised
+    void upload(int nb, const std::vector<int32_t>& h_row_ptr, const std::vector<int32_t>& h_col, const std::vector<int32_t>& h_b2v, const std::vector<int32_t>& h_rowhdr,
+                hipStream_t s)
     {
         const int nslots = h_row_ptr[nb];
         const size_t nbz = std::max(nb, 1), nsz = std::max(nslots, 1);
@@ -95,16 +97,10 @@ struct SysBufs {
         hdiag.reserve(nbz * 42); minv.reserve(nbz * 36);               // [H_aa | b] contiguous: one all-reduce when sharded
         x.reserve(nbz * 6); xs.reserve(nbz * 6); r.reserve(nbz * 6); z.reserve(nbz * 6); p.reserve(nbz * 6); p2.reserve(nbz * 6);
         ap.reserve(nbz * 12 + kMaxPartials);                           // [A p | restricted A p | partials]
-        std::vector<int32_t> hdr(nbz * kRowHdr, -1);
-        for (int a = 0; a < nb; a++) {
-            hdr[(size_t)a * kRowHdr] = h_row_ptr[a]; hdr[(size_t)a * kRowHdr + 1] = h_row_ptr[a + 1];
-            for (int k = 0; k < 20 && h_row_ptr[a] + k < h_row_ptr[a + 1]; k++) hdr[(size_t)a * kRowHdr + 2 + k] = h_col[h_row_ptr[a] + k];
-        }
         if (nb > 0) UZL_HIP(hipMemcpyAsync(b2v.p, h_b2v.data(), sizeof(int32_t) * nb, hipMemcpyHostToDevice, s));
         UZL_HIP(hipMemcpyAsync(row_ptr.p, h_row_ptr.data(), sizeof(int32_t) * (nb + 1), hipMemcpyHostToDevice, s));
         if (nslots > 0) UZL_HIP(hipMemcpyAsync(col.p, h_col.data(), sizeof(int32_t) * nslots, hipMemcpyHostToDevice, s));
-        UZL_HIP(hipMemcpyAsync(rowhdr.p, hdr.data(), sizeof(int32_t) * hdr.size(), hipMemcpyHostToDevice, s));
-        return hdr;
+        UZL_HIP(hipMemcpyAsync(rowhdr.p, h_rowhdr.data(), sizeof(int32_t) * h_rowhdr.size(), hipMemcpyHostToDevice, s));
     }
     void bind(PgoDev& D, int nb, int nslots) const
     {
@@ -123,9 +119,7 @@ struct uzl_pgo : uzl::HandleBase {
     std::vector<uint8_t> fixed_in, fixed_eff;
     std::vector<int32_t> ij;       // system edges, 2 per edge
     std::vector<int32_t> src;      // system edge -> input edge
-    // what the skip rules need of every INPUT edge of uzl_pgo_add_graph (kept so that uzl_pgo_append_graph can grow the graph in place)
-    struct InEdge { int32_t from, to; uint8_t odom, valid; double w; };
-    std::vector<InEdge> in_edges;
+    std::vector<InEdge> in_edges;  // the input edges of uzl_pgo_add_graph (pgo_structure.hpp), kept so that uzl_pgo_append_graph can grow the graph in place
     bool in_ready = false;         // in_edges / d_edges describe the current graph (add_graph or append_graph, not set_graph)
     int32_t n_sensors_in = 0;
     std::vector<uint8_t> robust;
@@ -166,7 +160,7 @@ struct uzl_pgo : uzl::HandleBase {
     } red;
     int prev_pcg_iters = 0;
     double num_its[2] = {-1., -1.};            // PCG iterations per LM trial of the last solve with the reduced system in row order / by strong aggregates
-    int num_last = -1;                         // numbering of that solve (-1: none yet); see build_structure
+    int num_last = -1;                         // numbering of that solve (-1: none yet); see reduced_numbering (pgo_structure.hpp)
     // multilevel preconditioner: the class and per-level sizes of this structure's hierarchy as ml_plan decided them (its index arrays
     // released once uploaded); levels = 0: block-Jacobi
     MlPlan mlp;
@@ -233,8 +227,8 @@ inline double pgo_tol_f2(const uzl_pgo_cfg& c) { return c.pcg_stop == 1 ? 1. : k
 inline double pgo_eps_t(const uzl_pgo_cfg& c) { return c.pcg_stop == 1 ? 0. : kStepT * c.pcg_tol; }
 inline double pgo_eps_r(const uzl_pgo_cfg& c) { return c.pcg_stop == 1 ? 0. : kStepR * c.pcg_tol; }
 // ---- shared host-side pieces (uzl_pgo.hip)
-int32_t gauge_fix(uzl_pgo* h);                        // G2: setFixedNodes (g2o_optimizer.cpp:301-349)
-void build_structure(uzl_pgo* h);                     // block-CSR, Schur plan, hierarchy plan, uploads; bumps structure_gen
+void build_structure(uzl_pgo* h);                     // system plan, Schur plan, hierarchy plan (pgo_structure.hpp), each uploaded and bound; bumps structure_gen
+void ensure_structure(uzl_pgo* h);                    // gauge + build_structure, unless the structure is ready
 void destroy_pcg_graph(uzl_pgo* h);
 bool ml_async_level(const uzl_pgo* h);
 double ml_rate_drop(const uzl_pgo* h);
@@ -243,6 +237,12 @@ void prepare_optimize(uzl_pgo* h);                    // optimizeImpl's front pa
 void own_streams(uzl_pgo* h, bool drain_borrowed);               // a batch's handle takes streams of its own (uzl_pgo.hip)
 int do_optimize_host(uzl_pgo* h, int32_t iterations, uzl_pgo_stats* st);      // the host-driven loop (sharded / block-Jacobi / profiled solves, anomaly fallback)
 int do_optimize(uzl_pgo* h, int32_t iterations, uzl_pgo_stats* st);           // picks the loop
+// ---- pieces of the host-driven loop the stage hooks drive one by one (uzl_pgo.hip; uzl_pgo_debug.hip)
+HostSlot host_slot(uzl_pgo* h);                       // the slot twins' slot for this handle, the hierarchy copy in use, the current pose buffer
+void set_lambda(uzl_pgo* h, double lambda, double tol_f2);
+void ml_setup_numeric(uzl_pgo* h, const HostSlot& hs, hipStream_t s, KernelTimer* timer);
+int pcg_solve(uzl_pgo* h, int it, bool* converged);   // one (H + lambda I) dx = b solve in LM iteration `it`; returns PCG iterations used
+inline double tol_factor2(const uzl_pgo_cfg& c) { return pgo_tol_f2(c); }
 // ---- the device-resident loop (uzl_pgo_lm.hip)
 struct LmRun;                                          // captured passes + slot table of one handle (or one batch)
 void lm_run_destroy(LmRun* r);
@@ -254,7 +254,6 @@ LmShape make_shape(const std::vector<uzl_pgo*>& hs, int nslots, bool batch_geome
 int batch_optimize_lm(LmRun*& R, const std::vector<uzl_pgo*>& hs, int resident, hipStream_t s, hipStream_t s2, int32_t iterations, bool eager, bool verbose, KernelTimer* timer,
                       uzl_pgo_stats* stats, int* rc_all);
 constexpr int kSchurStrongOneMax = 256;                // strong aggregates: up to this many groups as ONE level (level-1 path), beyond in blocks of 4 (pgo_schur.hpp)
-constexpr int kSchurStrongMin = 32;                   // separators from which on the reduced system is numbered by strong aggregates
 extern const int kUpperNs;                            // Newton-Schulz steps of the dense levels above the composite level
 // lazy refresh of the multilevel preconditioner (lm_refresh): rebuilt when the last step moved chi2 by more than kRefreshRel ... and,
 // where the rebuild is synchronous (large loopy graphs: its GEMMs are 1.4 ms at 10k / 50k, 7 ms at 20k / 100k, in front of the solve),

@@ -1,7 +1,8 @@
 // pgo_ml_plan.hpp — the symbolic aggregation hierarchy of the multilevel preconditioner as a host-side value: which class a block system
 // gets (aggregates per PCG workgroup, levels, fan-outs, dense level, gather level, multiplicative or additive, Newton-Schulz steps, LDS
 // demand - or block-Jacobi) and every level's index arrays.  Pure integer work: no handle, no HIP call, no environment.  A structure is
-// made in three steps (uzl_pgo.hip: build_structure): schur_plan (pgo_schur.hpp) -> ml_plan -> upload_ml (arena layout and descriptors).
+// made in three steps, each plan -> upload -> bind (uzl_pgo.hip: build_structure): system_plan (pgo_structure.hpp) -> schur_plan
+// (pgo_schur.hpp) -> ml_plan, uploaded by upload_ml (arena layout and descriptors).
 // tests/test_ml_plan.py holds the class boundaries on the CPU through uzl_debug_ml_plan.
 #pragma once
 #include "pgo_types.hpp"

@@ -29,7 +29,8 @@
 // group becomes one aggregate of the level-1 path (blocks of 8 rows); beyond, the groups are matched once more (<= 4 to a block) and laid
 // out in blocks of 4 x 8 rows - the AGG = 4 geometry of the PCG kernels.  Either way groups and blocks are padded with EMPTY rows
 // (sep_rows = -1: identity diagonal block, zero right-hand side and prolongation block; x stays 0).  Same linear system, same solution;
-// which numbering a handle takes: uzl_pgo_cfg::reduced_numbering, build_structure (uzl_pgo.hip), DESIGN.md section 6.
+// which numbering a handle takes: uzl_pgo_cfg::reduced_numbering, reduced_numbering (pgo_structure.hpp); whether the
+// plan is adopted: schur_admitted (pgo_structure.hpp).
 #pragma once
 #include <cstdint>
 #include <vector>

@@ -1,5 +1,5 @@
-// uzl_pgo.hip — host side of the pose-graph half: graph flattening bookkeeping (skip rules), gauge
-// fixing, block-CSR structure, the Levenberg-Marquardt driver and the C ABI (uzl_pgo_*).
+// uzl_pgo.hip — host side of the pose-graph half: the graph-entry calls, the structure's uploads (its plans are host-side values:
+// pgo_structure.hpp, pgo_schur.hpp, pgo_ml_plan.hpp), the Levenberg-Marquardt driver and the C ABI (uzl_pgo_*, uzl_pgo_batch_*).
 // Mirrors G2oOptimizer (graph_optimization/src/g2o_optimizer.cpp:55-349): add_graph = addGraphImpl,
 // optimize = optimizeImpl (initializeOptimization + setFixedNodes + optimize(iterations)),
 // store = storeImpl.  All arithmetic on poses, measurements and the normal equations runs in the HIP
@@ -96,19 +96,20 @@ void fetch_scal(uzl_pgo* h)
 // (kStepT, kStepR, kTolFloor2: pgo_lm.hpp)
 constexpr int kProgressEveryBJ = 8;           // block-Jacobi path: PCG iterations between two looks (a launch of their own; the multilevel path looks every
                                               // kProgressEvery iterations inside its kernels, pgo_types.hpp)
-inline double tol_factor2(const uzl_pgo_cfg& c) { return pgo_tol_f2(c); }
 // How stale is a kept preconditioner?  Not the iteration count of the last solve (with an absolute stop test that follows the size of
 // the LM step and lambda, not the operator): the CONTRACTION it delivers, nats of r.M^-1 r per PCG iteration.  rz_stop = scal[1] is
 // pcg_tol^2 * tol_f2 * (r_0.M^-1 r_0).  A rebuild is due when the rate has fallen below kRateDrop of what the operator delivered when fresh.
 // (kRateDrop, lm_pcg_rate: pgo_lm.hpp - shared with the device-resident loop)
 inline double pcg_rate(double rz_stop, double rz_end, int its, double tol2, double tol_f2) { return lm_pcg_rate(rz_stop, rz_end, its, tol2, tol_f2); }
+}  // namespace
 
-void set_lambda(uzl_pgo* h, double lambda, double tol_f2)
+void uzl::set_lambda(uzl_pgo* h, double lambda, double tol_f2)
 {
     k_set_trial(h->D.scal, lambda, tol_f2, pgo_eps_t(h->cfg), pgo_eps_r(h->cfg), h->stream);
     h->lambda_now = lambda;
 }
 
+namespace {
 // exchange step of the sharded solve: sum `count` doubles at dev_ptr over all ranks (caller-supplied RCCL all-reduce)
 void shard_allreduce(uzl_pgo* h, double* ptr, int64_t count)
 {
@@ -148,32 +149,14 @@ void alloc_problem(uzl_pgo* h, bool keep_poses = false)
     h->cur = cur_b ? h->pose_b.p : h->pose_a.p; h->trial = cur_b ? h->pose_a.p : h->pose_b.p;
 }
 
-// the skip rules of addGraphImpl over uzl_pgo::in_edges: odometry edges are added while iterating (:78-79), filtered feature edges after (:100-103)
+// the system edges of uzl_pgo::in_edges (flatten_edges, pgo_structure.hpp: the skip rules of addGraphImpl)
 void flatten_edges(uzl_pgo* h)
 {
-    h->ij.clear(); h->src.clear(); h->robust.clear(); h->edge_w.clear();
-    const int n_nodes = h->n, n_edges = (int)h->in_edges.size();
-    for (int pass = 0; pass < 2; pass++) {
-        for (int k = 0; k < n_edges; k++) {
-            const uzl_pgo::InEdge& ed = h->in_edges[k];
-            if (ed.from < 0 || ed.to < 0 || ed.from >= n_nodes || ed.to >= n_nodes) continue;     // :77, :194-201, :263-268
-            if (ed.from == ed.to) continue;                                                        // degenerate self edge
-            if ((pass == 0) != (ed.odom != 0)) continue;
-            if (ed.odom) {
-                if (h->fixed_in[ed.from] && !h->fixed_in[ed.to]) continue;                         // :203-206
-            } else {
-                if (!ed.valid) continue;                                                           // not in validEdges() (:98)
-                if (h->fixed_in[ed.from] && h->fixed_in[ed.to]) continue;                          // :270-274
-            }
-            h->ij.push_back(ed.from); h->ij.push_back(ed.to);
-            h->src.push_back(k);
-            h->edge_w.push_back(ed.w);
-            h->robust.push_back(ed.odom ? 0 : 1);                                                  // Huber on feature edges (:292-294)
-        }
-    }
+    FlatEdges F = uzl::flatten_edges(h->n, h->in_edges, h->fixed_in);
+    h->ij.swap(F.ij); h->src.swap(F.src); h->robust.swap(F.robust); h->edge_w.swap(F.edge_w);
     h->e = (int32_t)h->src.size();
 }
-uzl_pgo::InEdge in_edge_of(const uzl_edge& ed)
+InEdge in_edge_of(const uzl_edge& ed)
 {
     double tr = 0.; for (int r = 0; r < 6; r++) tr += ed.information[r * 7];
     return {ed.from, ed.to, (uint8_t)(ed.type == UZL_EDGE_TYPE_2D_WHEEL_ODOMETRY ? 1 : 0), (uint8_t)(ed.valid ? 1 : 0), tr};
@@ -192,13 +175,6 @@ void upload_edges_common(uzl_pgo* h)
         UZL_HIP(hipMemcpyAsync(h->d_robust.p, h->robust.data(), (size_t)e, hipMemcpyHostToDevice, s));
         UZL_HIP(hipStreamSynchronize(s));   // ei/ej are stack vectors
     }
-}
-
-// union-find root with path halving (gauge_fix)
-int32_t uf_find(std::vector<int32_t>& p, int32_t x)
-{
-    while (p[x] != x) { p[x] = p[p[x]]; x = p[x]; }
-    return x;
 }
 
 // The hierarchy a plan describes (pgo_ml_plan.hpp), on the device: one arena holding both hierarchy copies, the two MlDev / MlHot
@@ -321,64 +297,12 @@ void upload_ml(uzl_pgo* h, const MlPlan& P, const int32_t* d_row_ptr, const int3
     UZL_HIP(hipStreamSynchronize(s));      // stage / Mh are locals
 }
 
-// Order of the free vertices in the block system.  The multilevel preconditioner aggregates 8 CONSECUTIVE blocks, which is only a
-// good coarse space when consecutive blocks are strongly coupled.  In a single session the node ids are time-ordered (std::map
-// order = trajectory order, graph_slam_node.cpp:294) and the index order is already that; in merged / global-scope graphs
-// (graph_slam_node.cpp:401-576, 665-777: ids of several sessions interleave) or graphs without an odometry chain it is not, and
-// the PCG iteration count grows 4-7x (tests/diag/vertex_order.py).  So the order is computed from the graph: starting at the
-// lowest-index unvisited free vertex, follow the heaviest edge (trace of the information matrix; odometry edges are the stiff
-// ones) to an unvisited free vertex until stuck, then extend the same chain backwards from the start; repeat.  Ties go to the lower
-// index.  A time-ordered single-session graph comes out in index order (nothing changes for it); O(N + E), deterministic.
-std::vector<int32_t> aggregation_order(const uzl_pgo* h)
-{
-    const int n = h->n, e = h->e;
-    std::vector<int32_t> ptr((size_t)n + 1, 0);
-    auto is_free = [&](int v) { return !h->fixed_eff[v]; };
-    for (int k = 0; k < e; k++) {
-        const int a = h->ij[2 * k], b = h->ij[2 * k + 1];
-        if (is_free(a) && is_free(b)) { ptr[a + 1]++; ptr[b + 1]++; }
-    }
-    for (int v = 0; v < n; v++) ptr[v + 1] += ptr[v];
-    std::vector<int32_t> nbr((size_t)std::max(ptr[n], 1));
-    std::vector<double> wgt((size_t)std::max(ptr[n], 1));
-    std::vector<int32_t> fill(ptr.begin(), ptr.end() - 1);
-    const bool have_w = h->edge_w.size() == (size_t)e;
-    for (int k = 0; k < e; k++) {
-        const int a = h->ij[2 * k], b = h->ij[2 * k + 1];
-        if (!(is_free(a) && is_free(b))) continue;
-        const double w = have_w ? h->edge_w[k] : 1.;
-        nbr[fill[a]] = b; wgt[fill[a]++] = w;
-        nbr[fill[b]] = a; wgt[fill[b]++] = w;
-    }
-    std::vector<uint8_t> seen((size_t)std::max(n, 1), 0);
-    std::vector<int32_t> order, back;
-    order.reserve((size_t)n);
-    auto next_of = [&](int v) {
-        int best = -1; double bw = -1.;
-        for (int q = ptr[v]; q < ptr[v + 1]; q++) {
-            const int u = nbr[q];
-            if (seen[u]) continue;
-            if (wgt[q] > bw || (wgt[q] == bw && u < best)) { bw = wgt[q]; best = u; }
-        }
-        return best;
-    };
-    for (int start = 0; start < n; start++) {
-        if (!is_free(start) || seen[start]) continue;
-        const size_t first = order.size();
-        for (int v = start; v >= 0; v = next_of(v)) { seen[v] = 1; order.push_back(v); }
-        back.clear();
-        for (int v = next_of(start); v >= 0; v = next_of(v)) { seen[v] = 1; back.push_back(v); }
-        if (!back.empty()) {                                     // chain = reverse(back) + forward part
-            order.insert(order.begin() + (std::ptrdiff_t)first, back.rbegin(), back.rend());
-        }
-    }
-    return order;
-}
+}  // namespace
 
 // the slot twins' slot for this handle: its slot (the handle's own flags; rebuilt with the structure - the additive fallback bumps
 // structure_gen when it swaps hot.Cmat), the hierarchy copy in use, the pose buffer of the current estimate and pcg_tol^2.  Launch
 // geometry: h->ml_shape
-HostSlot host_slot(uzl_pgo* h)
+HostSlot uzl::host_slot(uzl_pgo* h)
 {
     if (h->ml_slot_gen != h->structure_gen) {
         h->ml_slot = make_slot(h, nullptr, nullptr);
@@ -390,11 +314,12 @@ HostSlot host_slot(uzl_pgo* h)
     return hs;
 }
 // numeric part of the set-up of hierarchy copy hs.ix; a sharded solve all-reduces level 1 on the way (levels >= 2 need no exchange)
-void ml_setup_numeric(uzl_pgo* h, const HostSlot& hs, hipStream_t s, KernelTimer* timer)
+void uzl::ml_setup_numeric(uzl_pgo* h, const HostSlot& hs, hipStream_t s, KernelTimer* timer)
 {
     kl_ml_numeric(hs, h->ml_shape, s, timer, [&] { shard_allreduce(h, h->mlb[hs.ix].l1_span_ptr, h->l1_span); });
 }
 
+namespace {
 // enqueue `pairs` x 2 PCG iterations (p0 -> p1 -> p0); kernels no-op once the device `done` flag is set
 void enqueue_pcg_pairs(uzl_pgo* h, int pairs, bool timed)
 {
@@ -460,8 +385,10 @@ void ensure_pcg_graph(uzl_pgo* h)
     h->structure_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
+}  // namespace
+
 // one (H + lambda I) dx = b solve in LM iteration `it`; returns PCG iterations used, sets *converged
-int pcg_solve(uzl_pgo* h, int it, bool* converged)
+int uzl::pcg_solve(uzl_pgo* h, int it, bool* converged)
 {
     hipStream_t s = h->stream;
     const PgoDev& D = h->Dp;
@@ -516,7 +443,7 @@ int pcg_solve(uzl_pgo* h, int it, bool* converged)
     h->prev_pcg_iters = iters;
     return iters;
 }
-}  // namespace
+
 
 namespace uzl {
 const int kUpperNs = 4;                   // Newton-Schulz steps of the dense levels above the composite level (even: the result ends in Ydense[l])
@@ -534,27 +461,6 @@ int ml_ns_steps_at(int structure_steps, int it)
 }
 double ml_rate_drop(const uzl_pgo* h) { return (!ml_async_level(h) && h->mlp.cl > 0) ? kRateDropSyncDense : kRateDrop; }
 
-// G2: setFixedNodes (g2o_optimizer.cpp:301-349): per connected component (over the system edges) without a
-// fixed vertex, fix the vertex with the smallest index (= lexicographically smallest node id, :338).
-int32_t gauge_fix(uzl_pgo* h)
-{
-    const int n = h->n;
-    std::vector<int32_t> p((size_t)n);
-    std::iota(p.begin(), p.end(), 0);
-    for (int k = 0; k < h->e; k++) {
-        int32_t a = uf_find(p, h->ij[2 * k]), b = uf_find(p, h->ij[2 * k + 1]);
-        if (a != b) { if (a < b) p[b] = a; else p[a] = b; }
-    }
-    std::vector<uint8_t> has((size_t)n, 0);
-    for (int v = 0; v < n; v++) if (h->fixed_eff[v]) has[uf_find(p, v)] = 1;
-    int32_t cnt = 0;
-    for (int v = 0; v < n; v++) {
-        const int32_t r = uf_find(p, v);
-        if (!has[r]) { h->fixed_eff[r] = 1; has[r] = 1; cnt++; }
-    }
-    return cnt;
-}
-
 // Asynchronous rebuild (second stream, second copy of the hierarchy) pays on the composite level-1 path, and for the reduced system of a
 // chain-like graph on the level-2 path: there a rebuild (0.8 ms) is as long as the LM iteration it would otherwise hold up.  (Other
 // level-2 graphs - config 4 - measured +9 % PCG iterations for no net gain.)
@@ -563,8 +469,73 @@ bool ml_async_level(const uzl_pgo* h)
     return h->mlp.cl == 1 || (h->mlp.cl == 2 && h->red.on && h->red.strong);
 }
 
-// block-CSR structure over the free vertices (one slot per (free endpoint, system edge)), then the three steps of DESIGN.md section 6:
-// Schur plan -> hierarchy plan -> upload
+namespace {
+void upload_i32(DevBuf<int32_t>& b, const std::vector<int32_t>& v, size_t n, hipStream_t s)      // the first n of v; the buffer holds at least one
+{
+    b.reserve(std::max<size_t>(n, 1));
+    if (n > 0) UZL_HIP(hipMemcpyAsync(b.p, v.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
+}
+// step 1 of build_structure: the block system of a SystemPlan on the device (Y stays alive until the stream is synchronised), bound to h->D
+void upload_system(uzl_pgo* h, const SystemPlan& Y)
+{
+    hipStream_t s = h->stream;
+    const int n = h->n, nb = Y.nb, nslots = Y.nslots;
+    const size_t nsz = std::max(nslots, 1);
+    h->nb = nb; h->nslots = nslots;
+    h->d_srec.reserve(nsz * 44); h->d_smeta.reserve(nsz);
+    h->srec_stale = true;
+    static_assert(sizeof(int4) == 4 * sizeof(int32_t), "SystemPlan::smeta is the kernels' int4 per slot");
+    if (nslots > 0) UZL_HIP(hipMemcpyAsync(h->d_smeta.p, Y.smeta.data(), sizeof(int4) * nslots, hipMemcpyHostToDevice, s));
+    if (n > 0) UZL_HIP(hipMemcpyAsync(h->d_v2b.p, Y.v2b.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
+    h->sys.upload(nb, Y.row_ptr, Y.col, Y.b2v, Y.rowhdr, s);
+    upload_i32(h->d_slot_edge, Y.slot_edge, (size_t)nslots, s);
+    upload_i32(h->d_rb_ptr, Y.rb_ptr, Y.rb_ptr.size(), s);
+    // blocks of slots whose neighbour is fixed are never written: keep them defined
+    if (nslots > 0) UZL_HIP(hipMemsetAsync(h->sys.blk.p, 0, sizeof(double) * 36 * (size_t)nslots, s));      // (and slots of edges other ranks own stay 0)
+    UZL_HIP(hipStreamSynchronize(s));
+    PgoDev& D = h->D;
+    D.n = n; D.e = h->e;
+    h->sys.bind(D, nb, nslots);
+    D.pose = h->cur; D.pose_trial = h->trial;
+    D.v2b = h->d_v2b.p; D.ei = h->d_ei.p; D.ej = h->d_ej.p;
+    D.zinv = h->d_zinv.p; D.info = h->d_info.p; D.robust = h->d_robust.p;
+    D.rb_ptr = h->d_rb_ptr.p; D.n_rb = (int32_t)Y.rb_ptr.size() - 1; D.pad_rb = 0; D.srec = h->d_srec.p; D.smeta = h->d_smeta.p;
+    D.part_b = h->d_part_b.p; D.part_c = h->d_part_c.p;
+    D.scal = h->d_scal.p; D.flags = h->d_flags.p;
+    D.e_begin = 0; D.e_end = h->e; D.diag_owner = 1; D.sibling0 = 1;      // sibling0 finalised once the hierarchy is planned
+}
+// step 2: an adopted SchurPlan on the device, the reduced system bound to h->Dp (rb2v: its rows as vertices)
+void upload_schur(uzl_pgo* h, const SchurPlan& P, const std::vector<int32_t>& rb2v, bool may_shard)
+{
+    hipStream_t s = h->stream;
+    uzl_pgo::Reduced& Rd = h->red;
+    Rd.on = true; Rd.n_int = P.n_int; Rd.n_runs = P.n_runs; Rd.longest_run = P.longest_run; Rd.strong = P.strong; Rd.strong_blocks = P.strong && P.n_strong2 > 0; Rd.n_sep = P.n_sep;
+    const size_t ni = (size_t)P.n_int, nru = (size_t)P.n_runs;
+    const std::pair<DevBuf<int32_t>*, const std::vector<int32_t>*> idx[] = {{&Rd.run_ptr, &P.run_ptr}, {&Rd.run_rows, &P.run_rows}, {&Rd.slotP, &P.slotP}, {&Rd.slotN, &P.slotN},
+                                                                             {&Rd.endL, &P.endL}, {&Rd.endR, &P.endR}, {&Rd.sep_rows, &P.sep_rows}, {&Rd.rsrc, &P.rsrc},
+                                                                             {&Rd.inc_ptr, &P.inc_ptr}, {&Rd.inc, &P.inc}};
+    for (const auto& bv : idx) upload_i32(*bv.first, *bv.second, bv.second->size(), s);
+    const std::vector<int32_t> rhdr = row_headers(P.nbr, P.row_ptr, P.col);
+    Rd.sys.upload(P.nbr, P.row_ptr, P.col, rb2v, rhdr, s);
+    Rd.elim.reserve(std::max<size_t>(ni, 1) * kSchurElim); Rd.runout.reserve(std::max<size_t>(nru, 1) * kSchurRunOut);
+    UZL_HIP(hipStreamSynchronize(s));                                  // rhdr is a local
+    SchurDev& S = Rd.S;
+    S.n_runs = P.n_runs; S.n_int = P.n_int; S.nbr = P.nbr; S.nslots_r = P.nslots_r;
+    S.run_ptr = Rd.run_ptr.p; S.run_rows = Rd.run_rows.p; S.slotP = Rd.slotP.p; S.slotN = Rd.slotN.p; S.endL = Rd.endL.p; S.endR = Rd.endR.p;
+    S.sep_rows = Rd.sep_rows.p; S.rsrc = Rd.rsrc.p; S.inc_ptr = Rd.inc_ptr.p; S.inc = Rd.inc.p; S.elim = Rd.elim.p; S.runout = Rd.runout.p;
+    // Sharded solve: a run is eliminated by EVERY rank (the reduced system's diagonal blocks and right-hand side are then complete
+    // everywhere, like H_aa | b after its all-reduce), so each needs the run's chain blocks whole - one more all-reduce per
+    // linearisation, [E_m per eliminated vertex | C_1 per run] gathered into a contiguous buffer.  Fill blocks enter A p on rank 0 only.
+    S.runblk = nullptr;
+    if (may_shard) { Rd.runblk.reserve((ni + nru) * 36); S.runblk = Rd.runblk.p; }
+    h->Dp = h->D;
+    Rd.sys.bind(h->Dp, P.nbr, P.nslots_r);
+    h->Dp.smeta = nullptr; h->Dp.srec = nullptr;                      // the reduced system is assembled by schur_assemble_kernel
+}
+}  // namespace
+
+// The structure of a graph in the three steps of DESIGN.md section 6, each "plan (a host-side value: pgo_structure.hpp, pgo_schur.hpp,
+// pgo_ml_plan.hpp) -> upload -> bind": the block system over the free vertices, the Schur reduction of the chain interiors, the hierarchy
 void build_structure(uzl_pgo* h)
 {
     auto t_prev = std::chrono::steady_clock::now();
@@ -576,160 +547,43 @@ void build_structure(uzl_pgo* h)
     };
     destroy_pcg_graph(h);
     tick("drop the captured graphs");
-    const int n = h->n, e = h->e;
-    std::vector<int32_t> v2b((size_t)std::max(n, 1), -1), b2v = aggregation_order(h);
+    // ---- 1. the block system over the free vertices
+    std::vector<int32_t> order = aggregation_order(h->n, h->ij, h->fixed_eff, h->edge_w);
     tick("aggregation order");
-    const int nb = (int)b2v.size();
-    for (int b = 0; b < nb; b++) v2b[b2v[b]] = b;
-    h->nb = nb;
-    std::vector<int32_t> row_ptr((size_t)nb + 1, 0);
-    for (int k = 0; k < e; k++) {
-        const int a = v2b[h->ij[2 * k]], b = v2b[h->ij[2 * k + 1]];
-        if (a >= 0) row_ptr[a + 1]++;
-        if (b >= 0) row_ptr[b + 1]++;
-    }
-    for (int a = 0; a < nb; a++) row_ptr[a + 1] += row_ptr[a];
-    const int nslots = row_ptr[nb];
-    h->nslots = nslots;
-    std::vector<int32_t> fill(row_ptr.begin(), row_ptr.end() - 1);
-    std::vector<int32_t> col((size_t)std::max(nslots, 1)), slot_i((size_t)std::max(e, 1)), slot_j((size_t)std::max(e, 1)), slot_edge((size_t)std::max(nslots, 1));
-    for (int k = 0; k < e; k++) {
-        const int a = v2b[h->ij[2 * k]], b = v2b[h->ij[2 * k + 1]];
-        slot_i[k] = -1; slot_j[k] = -1;
-        if (a >= 0) { const int s = fill[a]++; slot_i[k] = s; col[s] = b; slot_edge[s] = 2 * k; }
-        if (b >= 0) { const int s = fill[b]++; slot_j[k] = s; col[s] = a; slot_edge[s] = 2 * k + 1; }
-    }
-    hipStream_t s = h->stream;
-    const size_t nsz = std::max(nslots, 1);
-    h->d_slot_edge.reserve(nsz); h->d_srec.reserve(nsz * 44); h->d_smeta.reserve(nsz);
-    h->srec_stale = true;
-    std::vector<int4> smeta(nsz);
-    for (int q = 0; q < nslots; q++) {
-        const int k = slot_edge[q] >> 1, other = (slot_edge[q] & 1) ? slot_i[k] : slot_j[k];
-        smeta[q] = make_int4(slot_edge[q], h->ij[2 * k], h->ij[2 * k + 1], (other + 1) | (h->robust[k] ? 1 << 30 : 0));
-    }
-    if (nslots > 0) UZL_HIP(hipMemcpyAsync(h->d_smeta.p, smeta.data(), sizeof(int4) * nslots, hipMemcpyHostToDevice, s));
-    if (n > 0) UZL_HIP(hipMemcpyAsync(h->d_v2b.p, v2b.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
-    const std::vector<int32_t> rowhdr = h->sys.upload(nb, row_ptr, col, b2v, s);
-    if (nslots > 0) UZL_HIP(hipMemcpyAsync(h->d_slot_edge.p, slot_edge.data(), sizeof(int32_t) * nslots, hipMemcpyHostToDevice, s));
-    // row blocks of the Hessian build: consecutive rows with <= 256 slots and <= 42 rows, so that a workgroup makes one pass (a row with
-    // more slots is a block of its own and loops); beyond kMaxPartials blocks (> ~1M slots) blocks hold more and loop as well
-    std::vector<int32_t> rb_ptr(1, 0);
-    {
-        const int cap_slots = std::max(256, (int)(((int64_t)nslots + kMaxPartials / 2 - 1) / (kMaxPartials / 2) + 255) / 256 * 256);
-        const int cap_rows = std::max(42, (nb + kMaxPartials / 2 - 1) / (kMaxPartials / 2));
-        int rows = 0, slots = 0;
-        for (int a = 0; a < nb; a++) {
-            const int d = row_ptr[a + 1] - row_ptr[a];
-            if (rows > 0 && (rows >= cap_rows || slots + d > cap_slots)) { rb_ptr.push_back(a); rows = 0; slots = 0; }
-            rows++; slots += d;
-        }
-        rb_ptr.push_back(nb);
-    }
-    h->d_rb_ptr.reserve(rb_ptr.size());
-    UZL_HIP(hipMemcpyAsync(h->d_rb_ptr.p, rb_ptr.data(), sizeof(int32_t) * rb_ptr.size(), hipMemcpyHostToDevice, s));
-    // blocks of slots whose neighbour is fixed are never written: keep them defined
-    if (nslots > 0) UZL_HIP(hipMemsetAsync(h->sys.blk.p, 0, sizeof(double) * 36 * (size_t)nslots, s));      // (and slots of edges other ranks own stay 0)
-    UZL_HIP(hipStreamSynchronize(s));       // host vectors go out of scope
+    const SystemPlan Y = system_plan(h->n, h->ij, h->robust, std::move(order));
+    upload_system(h, Y);
     PgoDev& D = h->D;
-    D.n = n; D.e = e;
-    h->sys.bind(D, nb, nslots);
-    D.pose = h->cur; D.pose_trial = h->trial;
-    D.v2b = h->d_v2b.p; D.ei = h->d_ei.p; D.ej = h->d_ej.p;
-    D.zinv = h->d_zinv.p; D.info = h->d_info.p; D.robust = h->d_robust.p;
-    D.rb_ptr = h->d_rb_ptr.p; D.n_rb = (int32_t)rb_ptr.size() - 1; D.pad_rb = 0; D.srec = h->d_srec.p; D.smeta = h->d_smeta.p;
-    D.part_b = h->d_part_b.p; D.part_c = h->d_part_c.p;
-    D.scal = h->d_scal.p; D.flags = h->d_flags.p;
-    D.e_begin = 0; D.e_end = e; D.diag_owner = 1; D.sibling0 = 1;      // sibling0 finalised once the hierarchy is planned
-    // ---- Schur reduction of the chain interiors (pgo_schur.hpp): when a third or more of the free vertices carry nothing but their two
+    PgoDev& Dp = h->Dp;
+    // ---- 2. Schur reduction of the chain interiors (pgo_schur.hpp): when a third or more of the free vertices carry nothing but their two
     //      chain edges, the PCG runs on the Schur complement over the others (sharded solves included: see SchurDev::runblk).
     uzl_pgo::Reduced& Rd = h->red;
     Rd.on = false; Rd.n_int = 0; Rd.n_runs = 0; Rd.longest_run = 0; Rd.strong = false; Rd.strong_blocks = false; Rd.n_sep = 0;
-    PgoDev& Dp = h->Dp;
     // longest run: 24.  (Twelve for small graphs paid 3 - 8 % while one wave walked a whole run; with a run eliminated from both ends the
     // chain is twelve steps anyway, and stars of 20-vertex arms keep being eliminated completely: tests/test_schur_gpu.py.)
     constexpr int kSchurCap = 24;
-    constexpr int kSchurMinPct = 33;                                        // reduced when at least this share of the free vertices goes
+    constexpr int kStrongThetaPct = 25;                                      // groups hang together by edges >= 0.25 x the stiffest at either end
     const bool may_shard = h->allreduce != nullptr || h->rccl_comm != nullptr;
-    std::vector<int32_t> rrow_ptr, rcol;
-    if (h->cfg.schur_reduce >= 0 && nb > 0) {
+    SchurPlan P;
+    if (h->cfg.schur_reduce >= 0 && Y.nb > 0) {
         tick("block-CSR + uploads");
-        // The reduced system of a large chain-like graph is numbered by strong aggregates (pgo_schur.hpp) and takes the AGG = 4 hierarchy: the
-        // separators an aggregate holds then move (nearly) rigidly together, which is what its six coarse modes can represent.  In row order
-        // "8 consecutive separators" put loop-closure partners into different aggregates and the two ends of a long soft run into the same
-        // one: config 5's last re-optimisation took 70 - 140 PCG iterations per LM iteration (tests/diag/reduced_proto.py: 70 -> 23).
-        constexpr int kStrongThetaPct = 25;                                   // groups hang together by edges >= 0.25 x the stiffest at either end
-        int strong_min = (may_shard || h->cfg.preconditioner == 0) ? 0 : kSchurStrongMin;
-        // Which numbering (uzl_pgo_cfg::reduced_numbering)?  Strong aggregates pay where loop closures are stiffer than the runs between
-        // separators (config 5: 71 -> 31 PCG iterations per LM iteration); where the runs are the stiff part the matching follows the chain,
-        // the groups are runs of consecutive separators anyway, and the row order with its level-1 path is better (tests/diag/strong_ab.py).
-        // A handle's first structure goes by that shape; afterwards by what its own solves measured - PCG iterations per LM trial of the last
-        // solve in either numbering, an iteration on the padded AGG = 4 layout counted as 1.3 (the measured 1.5x per iteration less the rebuilds it saves; up to 256 groups
-        // the strong layout runs on the level-1 path, at the row order's cost per iteration) - so an online session that
-        // started on the wrong foot corrects itself.  Iteration counts only: deterministic.
-        double max_contig = 2.;
-        const double cost_strong = 1.;                                       // (the weight of the layout is in the figure: do_optimize)
-        if (h->cfg.reduced_numbering == 1) strong_min = 0;
-        else if (h->cfg.reduced_numbering != 2 && strong_min > 0) {
-            const double ir = h->num_its[0], is = h->num_its[1];
-            bool strong;
-            if (ir >= 0. && is >= 0.) strong = cost_strong * is < ir;        // both known: the cheaper (the figures are of different solves: a hard
-                                                                              // interval can send it the wrong way for one solve - whose own figure sets it right)
-            else if (ir >= 0.) strong = ir > 40.;                            // only the row order known: if it is doing badly, try
-            else if (is >= 0.) strong = !(is > 40.);                         // only strong aggregates known: likewise
-            else { strong = true; max_contig = 0.6; }                        // first structure: by the shape of the groups
-            if (!strong) strong_min = 0;
-        }
-        std::vector<double> slot_w;
-        if (strong_min > 0 && h->edge_w.size() == (size_t)e) {
-            slot_w.resize((size_t)std::max(nslots, 1));
-            for (int q = 0; q < nslots; q++) slot_w[q] = h->edge_w[slot_edge[q] >> 1];
-        }
-        // (reduced when >= 64 rows and >= kSchurMinPct of the rows go: the plan stops early otherwise)
-        const int min_int = std::max(64, (int)(((int64_t)kSchurMinPct * nb + 99) / 100));
-        SchurPlan P = schur_plan(nb, row_ptr, col, kSchurCap, slot_w.empty() ? nullptr : slot_w.data(), strong_min, 0.01 * kStrongThetaPct, max_contig, kSchurStrongOneMax, min_int);
+        const ReducedNumbering num = reduced_numbering(h->cfg.reduced_numbering, h->cfg.preconditioner, may_shard, h->num_its);
+        const std::vector<double> slot_w = (num.strong_min > 0 && h->edge_w.size() == (size_t)h->e) ? slot_weights(Y, h->edge_w) : std::vector<double>();
+        P = schur_plan(Y.nb, Y.row_ptr, Y.col, kSchurCap, slot_w.empty() ? nullptr : slot_w.data(), num.strong_min, 0.01 * kStrongThetaPct, num.max_contig, kSchurStrongOneMax,
+                       schur_min_interiors(Y.nb));
         tick("Schur plan");
-        if (P.n_int >= 64 && (int64_t)100 * P.n_int >= (int64_t)kSchurMinPct * nb) {
-            Rd.on = true; Rd.n_int = P.n_int; Rd.n_runs = P.n_runs; Rd.longest_run = P.longest_run; Rd.strong = P.strong; Rd.strong_blocks = P.strong && P.n_strong2 > 0; Rd.n_sep = P.n_sep;
-            const size_t ni = (size_t)P.n_int, nru = (size_t)P.n_runs;
-            auto up = [&](DevBuf<int32_t>& b, const std::vector<int32_t>& v, size_t min_n) {
-                b.reserve(std::max(v.size(), min_n));
-                if (!v.empty()) UZL_HIP(hipMemcpyAsync(b.p, v.data(), sizeof(int32_t) * v.size(), hipMemcpyHostToDevice, s));
-            };
-            up(Rd.run_ptr, P.run_ptr, 1); up(Rd.run_rows, P.run_rows, 1); up(Rd.slotP, P.slotP, 1); up(Rd.slotN, P.slotN, 1);
-            up(Rd.endL, P.endL, 1); up(Rd.endR, P.endR, 1); up(Rd.sep_rows, P.sep_rows, 1); up(Rd.rsrc, P.rsrc, 1);
-            up(Rd.inc_ptr, P.inc_ptr, 1); up(Rd.inc, P.inc, 1);
-            std::vector<int32_t> rb2v((size_t)P.nbr);
-            for (int i = 0; i < P.nbr; i++) rb2v[i] = P.sep_rows[i] >= 0 ? b2v[P.sep_rows[i]] : -1;
-            const std::vector<int32_t> rhdr = Rd.sys.upload(P.nbr, P.row_ptr, P.col, rb2v, s);
-            Rd.elim.reserve(std::max<size_t>(ni, 1) * kSchurElim); Rd.runout.reserve(std::max<size_t>(nru, 1) * kSchurRunOut);
-            UZL_HIP(hipStreamSynchronize(s));                                  // P's vectors and the two locals go out of scope
-            SchurDev& S = Rd.S;
-            S.n_runs = P.n_runs; S.n_int = P.n_int; S.nbr = P.nbr; S.nslots_r = P.nslots_r;
-            S.run_ptr = Rd.run_ptr.p; S.run_rows = Rd.run_rows.p; S.slotP = Rd.slotP.p; S.slotN = Rd.slotN.p; S.endL = Rd.endL.p; S.endR = Rd.endR.p;
-            S.sep_rows = Rd.sep_rows.p; S.rsrc = Rd.rsrc.p; S.inc_ptr = Rd.inc_ptr.p; S.inc = Rd.inc.p; S.elim = Rd.elim.p; S.runout = Rd.runout.p;
-            // Sharded solve: a run is eliminated by EVERY rank (the reduced system's diagonal blocks and right-hand side are then complete
-            // everywhere, like H_aa | b after its all-reduce), so each needs the run's chain blocks whole - one more all-reduce per
-            // linearisation, [E_m per eliminated vertex | C_1 per run] gathered into a contiguous buffer.  Fill blocks enter A p on rank 0 only.
-            S.runblk = nullptr;
-            if (may_shard) { Rd.runblk.reserve((ni + nru) * 36); S.runblk = Rd.runblk.p; }
-            Dp = D;
-            Rd.sys.bind(Dp, P.nbr, P.nslots_r);
-            Dp.smeta = nullptr; Dp.srec = nullptr;                            // the reduced system is assembled by schur_assemble_kernel
-            rrow_ptr.swap(P.row_ptr); rcol.swap(P.col);
-        }
+        if (schur_admitted(Y.nb, P.n_int)) upload_schur(h, P, reduced_b2v(P.sep_rows, Y.b2v), may_shard);
     }
     PgoDev& Dsys = Rd.on ? Dp : D;                                             // what the PCG kernels get
     const int nbp = Dsys.nb;
     const SysBufs& Bsys = Rd.on ? Rd.sys : h->sys;
-    double* apbuf = Bsys.ap.p;
     tick("reduced system uploads");
+    // ---- 3. the hierarchy of the system the PCG solves
     {
         static const bool comp4_off = diag_flag("UZL_ML_NO_COMP4");          // the walked hierarchy instead (tests/test_ab_paths_gpu.py)
         MlPlanIn in;
         in.nb = nbp; in.nslots = Dsys.nslots;
         in.precond_on = h->cfg.preconditioner != 0; in.strong_blocks = Rd.strong_blocks; in.mult_banned = h->mult_banned; in.comp4_off = comp4_off;
-        h->mlp = ml_plan(in, Rd.on ? rrow_ptr : row_ptr, Rd.on ? rcol : col);
+        h->mlp = ml_plan(in, Rd.on ? P.row_ptr : Y.row_ptr, Rd.on ? P.col : Y.col);
         tick("hierarchy plan (host index arrays)");
         upload_ml(h, h->mlp, Dsys.row_ptr, Dsys.col, Dsys.blk, Dsys.hdiag);
         h->mlp.release_indices();
@@ -738,11 +592,10 @@ void build_structure(uzl_pgo* h)
     }
     tick("hierarchy uploads");
     {   // per-iteration exchange buffer: [A p (6 nb) | restricted A p (6 n_g) | p.Ap partials]
-        const int gl = h->mlp.gather_level;
-        const size_t ng6 = gl ? (size_t)h->mlp.n[gl] * 6 * (gl == 2 ? 2 : 1) : 0;      // gather level 2: two half-aggregate parts per entity (sg_at)
-        if (gl) { h->mlb[0].hot.Sg = apbuf + (size_t)nbp * 6; h->mlb[1].hot.Sg = h->mlb[0].hot.Sg; }
-        Dsys.part_a = apbuf + (size_t)nbp * 6 + ng6;
-        h->iter_span = (int64_t)((size_t)nbp * 6 + ng6 + (gl ? (size_t)g_ml_spmv(nbp, h->mlp.agg) : 0));
+        const ExchangeLayout X = exchange_layout(nbp, h->mlp);
+        if (h->mlp.gather_level) { h->mlb[0].hot.Sg = Bsys.ap.p + X.sg; h->mlb[1].hot.Sg = h->mlb[0].hot.Sg; }
+        Dsys.part_a = Bsys.ap.p + X.part_a;
+        h->iter_span = X.iter_span;
     }
     Dsys.sibling0 = (h->mlp.levels > 0 && h->mlp.agg == 1) ? 1 : 0;     // large graphs keep the level-0 smoother block-diagonal
     D.sibling0 = Dsys.sibling0;
@@ -751,10 +604,8 @@ void build_structure(uzl_pgo* h)
     //  graphs too small for the multilevel path are simply solved redundantly by every rank)
     h->sharded = h->mlp.levels > 0 && may_shard;
     if (h->sharded) {
-        const int base = e / h->world, rem = e % h->world;
-        D.e_begin = h->rank * base + std::min(h->rank, rem);
-        D.e_end = D.e_begin + base + (h->rank < rem ? 1 : 0);
-        D.diag_owner = h->rank == 0 ? 1 : 0;
+        const ShardRange R = shard_range(h->e, h->rank, h->world);
+        D.e_begin = R.e_begin; D.e_end = R.e_end; D.diag_owner = R.diag_owner;
         D.sibling0 = 0;
     }
     if (Rd.on) {                                                              // (Dp was copied from D before the rank's share was known)
@@ -767,6 +618,7 @@ void build_structure(uzl_pgo* h)
     h->structure_gen++;
 }
 
+
 void destroy_pcg_graph(uzl_pgo* h)
 {
     for (auto& B : h->mlb) {
@@ -777,7 +629,15 @@ void destroy_pcg_graph(uzl_pgo* h)
     }
 }
 
-// optimizeImpl's front part (initializeOptimization :139, setFixedNodes :144-146): the structure, cached until the next add_graph / set_graph
+// initializeOptimization :139, setFixedNodes :144-146: the structure, cached until the next add_graph / set_graph
+void ensure_structure(uzl_pgo* h)
+{
+    if (h->structure_ready) return;
+    h->fixed_eff = h->fixed_in;
+    h->n_gauge = gauge_fix(h->n, h->ij, h->fixed_eff);
+    build_structure(h);
+}
+// optimizeImpl's front part
 void prepare_optimize(uzl_pgo* h)
 {
     h->t_start = std::chrono::steady_clock::now();
@@ -785,9 +645,7 @@ void prepare_optimize(uzl_pgo* h)
     h->last_structure_reused = h->structure_ready;
     if (!h->structure_ready) {
         const auto ts = std::chrono::steady_clock::now();
-        h->fixed_eff = h->fixed_in;
-        h->n_gauge = gauge_fix(h);
-        build_structure(h);
+        ensure_structure(h);
         h->structure_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ts).count();
     }
     if (h->srec_stale) {                // the edges' values in slot order (new values on a kept structure, or a new structure)
@@ -1053,46 +911,38 @@ struct StructureKey {
     std::vector<int32_t> ij;
     std::vector<double> edge_w;
 };
-static StructureKey take_structure_key(uzl_pgo* h)
+// Every graph-entry call (add_graph, append_graph, set_graph) begins here, with the node count of the graph it brings ...
+// clear() (:57): the reference rebuilds everything.  Here the structure of the previous graph (gauge, block-CSR, aggregation order,
+// hierarchy arrays, captured PCG graph) is kept when the new graph has the same vertices, fixed flags, system edges and edge
+// weights - a timer-driven re-optimisation of an unchanged graph, or one whose poses / measurements only moved - and rebuilt
+// otherwise; either way the solve is the one a fresh handle would run (same order, same operators).
+static StructureKey begin_graph(uzl_pgo* h, int32_t n_new)
 {
     StructureKey k;
     k.ready = h->structure_ready && h->have_graph;
-    if (!k.ready) return k;
-    k.n = h->n;
-    k.fixed_in.swap(h->fixed_in); k.robust.swap(h->robust); k.ij.swap(h->ij); k.edge_w.swap(h->edge_w);
+    if (k.ready) {
+        k.n = h->n;
+        k.fixed_in.swap(h->fixed_in); k.robust.swap(h->robust); k.ij.swap(h->ij); k.edge_w.swap(h->edge_w);
+    }
+    // what the handle learned about the numbering of ITS reduced systems (num_its, reduced_numbering) belongs to the session it came from: a
+    // graph that is not the previous one grown (fewer nodes than before) starts as on a fresh handle
+    if (n_new < h->n) { h->num_its[0] = h->num_its[1] = -1.; h->num_last = -1; }
+    h->have_graph = false; h->structure_ready = false;
     return k;
 }
-static bool same_structure(const uzl_pgo* h, const StructureKey& k)
+// ... and ends here, once n, fixed_in, ij, robust and edge_w describe the new graph and its values are enqueued: the start poses are
+// kept for uzl_pgo_reset, the system edges' index arrays go up, the structure is kept if it is the key's, and the numbering history if the graph is the key's grown (graph_grown)
+static void finish_graph(uzl_pgo* h, const StructureKey& k)
 {
-    return k.ready && k.n == h->n && k.fixed_in == h->fixed_in && k.ij == h->ij && k.robust == h->robust && k.edge_w == h->edge_w;
+    if (h->n) UZL_HIP(hipMemcpyAsync(h->pose_init.p, h->cur, sizeof(double) * 8 * (size_t)h->n, hipMemcpyDeviceToDevice, h->stream));
+    UZL_HIP(hipStreamSynchronize(h->stream));                  // inputs are borrowed for the duration of the call only
+    upload_edges_common(h);
+    h->have_graph = true;
+    h->structure_ready = k.ready && k.n == h->n && k.fixed_in == h->fixed_in && k.ij == h->ij && k.robust == h->robust && k.edge_w == h->edge_w;
+    if (!k.ready || h->structure_ready) return;                     // nothing learned yet / the same structure again
+    if (!graph_grown(k.n, k.fixed_in, k.ij, h->n, h->fixed_in, h->ij)) { h->num_its[0] = h->num_its[1] = -1.; h->num_last = -1; }
 }
 
-// What a handle learned about the numbering of its reduced systems (num_its, build_structure) belongs to the session it came from: it is
-// kept while the graph is the previous one, unchanged or GROWN - at least as many nodes, the old nodes' fixed flags in front, AND the old
-// system edges still there in their order (nine in ten of them found in order in the new list: an online session appends edges and
-// invalidates a few, graph_slam_node.cpp:1138-1150) - and dropped for anything else: an unrelated graph on a reused handle then solves
-// as on a fresh one (round 5 looked at the fixed flags only, which for most graphs is "node 0 is fixed").
-static bool edges_survive_in_order(const std::vector<int32_t>& old_ij, const std::vector<int32_t>& new_ij)
-{
-    const size_t n_old = old_ij.size() / 2, n_new = new_ij.size() / 2;
-    if (n_old == 0) return true;
-    constexpr size_t kWindow = 4096;                                 // how far ahead a surviving edge may have moved
-    size_t at = 0, found = 0;
-    for (size_t k = 0; k < n_old; k++) {
-        const int32_t a = old_ij[2 * k], c = old_ij[2 * k + 1];
-        const size_t end = std::min(n_new, at + kWindow);
-        for (size_t q = at; q < end; q++)
-            if (new_ij[2 * q] == a && new_ij[2 * q + 1] == c) { found++; at = q + 1; break; }
-    }
-    return 10 * found >= 9 * n_old;
-}
-static void keep_or_drop_numbering_history(uzl_pgo* h, const StructureKey& k)
-{
-    if (!k.ready || h->structure_ready) return;                     // nothing learned yet / the same structure again
-    const bool grown = h->n >= k.n && (size_t)k.n <= k.fixed_in.size() && std::equal(k.fixed_in.begin(), k.fixed_in.begin() + k.n, h->fixed_in.begin()) &&
-                       edges_survive_in_order(k.ij, h->ij);
-    if (!grown) { h->num_its[0] = h->num_its[1] = -1.; h->num_last = -1; }
-}
 
 // A handle with a stream pair of its own from the device's pool (uzl_pgo_create), or - the graphs of a batch - on the batch's streams: a
 // stream costs the runtime ~3.5 ms to make and ~2 ms to destroy (round 4's uzl_pgo_create 6.9 ms, measured: tests/diag/create_cost.py),
@@ -1219,15 +1069,7 @@ int uzl_pgo_add_graph(uzl_pgo* h, int32_t n_nodes, const uzl_node* nodes, int32_
         (n_sensors > 0 && !sensors))
         return fail(h, UZL_ERR_BAD_ARG, "null or negative-size input");
     UZL_HIP(hipSetDevice(h->cfg.device));
-    // clear() (:57): the reference rebuilds everything.  Here the structure of the previous graph (gauge, block-CSR, aggregation order,
-    // hierarchy arrays, captured PCG graph) is kept when the new graph has the same vertices, fixed flags, system edges and edge
-    // weights - a timer-driven re-optimisation of an unchanged graph, or one whose poses / measurements only moved - and rebuilt
-    // otherwise; either way the solve is the one a fresh handle would run (same order, same operators).
-    StructureKey old_key = take_structure_key(h);
-    // what the handle learned about the numbering of ITS reduced systems (num_its, build_structure) belongs to the session it came from: a
-    // graph that is not the previous one grown (fewer nodes than before) starts as on a fresh handle
-    if (n_nodes < h->n) { h->num_its[0] = h->num_its[1] = -1.; h->num_last = -1; }
-    h->have_graph = false; h->structure_ready = false;
+    const StructureKey old_key = begin_graph(h, n_nodes);
     h->n = n_nodes; h->e_in = n_edges;
     h->fixed_in.assign((size_t)n_nodes, 0);
     for (int v = 0; v < n_nodes; v++) h->fixed_in[v] = nodes[v].fixed ? 1 : 0;
@@ -1249,12 +1091,7 @@ int uzl_pgo_add_graph(uzl_pgo* h, int32_t n_nodes, const uzl_node* nodes, int32_
     k_prepare_edges(h->d_edges.p, h->d_src.p, h->e, h->d_stage.p, n_sensors, h->cfg.optimize_xy_only, h->cfg.use_odometry_parameters,
                     h->d_zinv.p, h->d_info.p, s);
     UZL_HIP(hipGetLastError());
-    if (n_nodes) UZL_HIP(hipMemcpyAsync(h->pose_init.p, h->cur, sizeof(double) * 8 * (size_t)n_nodes, hipMemcpyDeviceToDevice, s));
-    UZL_HIP(hipStreamSynchronize(s));                          // inputs are borrowed for the duration of the call only
-    upload_edges_common(h);
-    h->have_graph = true;
-    h->structure_ready = same_structure(h, old_key);
-    keep_or_drop_numbering_history(h, old_key);
+    finish_graph(h, old_key);
     return UZL_OK;
     UZL_GUARD_END(h)
 }
@@ -1270,8 +1107,7 @@ int uzl_pgo_append_graph(uzl_pgo* h, int32_t n_new_nodes, const uzl_node* new_no
     const int32_t n_old = h->n, e_old = h->e_in;
     for (int q = 0; q < n_flags; q++) if (edge_index[q] < 0 || edge_index[q] >= e_old) return fail(h, UZL_ERR_BAD_ARG, "edge index out of range");
     UZL_HIP(hipSetDevice(h->cfg.device));
-    StructureKey old_key = take_structure_key(h);
-    h->have_graph = false; h->structure_ready = false;
+    const StructureKey old_key = begin_graph(h, n_old + n_new_nodes);
     h->n = n_old + n_new_nodes; h->e_in = e_old + n_new_edges;
     if (old_key.ready) { h->fixed_in = old_key.fixed_in; }               // (the key took the vectors; the old flags are the first n_old of the new)
     for (int v = 0; v < n_new_nodes; v++) h->fixed_in.push_back(new_nodes[v].fixed ? 1 : 0);
@@ -1290,12 +1126,7 @@ int uzl_pgo_append_graph(uzl_pgo* h, int32_t n_new_nodes, const uzl_node* new_no
     k_prepare_edges(h->d_edges.p, h->d_src.p, h->e, h->d_stage.p, h->n_sensors_in, h->cfg.optimize_xy_only, h->cfg.use_odometry_parameters,
                     h->d_zinv.p, h->d_info.p, s);
     UZL_HIP(hipGetLastError());
-    if (h->n) UZL_HIP(hipMemcpyAsync(h->pose_init.p, h->cur, sizeof(double) * 8 * (size_t)h->n, hipMemcpyDeviceToDevice, s));
-    UZL_HIP(hipStreamSynchronize(s));                          // inputs are borrowed for the duration of the call only
-    upload_edges_common(h);
-    h->have_graph = true;
-    h->structure_ready = same_structure(h, old_key);
-    keep_or_drop_numbering_history(h, old_key);
+    finish_graph(h, old_key);
     return UZL_OK;
     UZL_GUARD_END(h)
 }
@@ -1310,9 +1141,7 @@ int uzl_pgo_set_graph(uzl_pgo* h, int32_t n, const double* poses, const uint8_t*
         if (ij[2 * k] < 0 || ij[2 * k] >= n || ij[2 * k + 1] < 0 || ij[2 * k + 1] >= n || ij[2 * k] == ij[2 * k + 1])
             return fail(h, UZL_ERR_BAD_ARG, "edge endpoint out of range");
     UZL_HIP(hipSetDevice(h->cfg.device));
-    StructureKey old_key = take_structure_key(h);
-    if (n < h->n) { h->num_its[0] = h->num_its[1] = -1.; h->num_last = -1; }      // (as uzl_pgo_add_graph)
-    h->have_graph = false; h->structure_ready = false;
+    const StructureKey old_key = begin_graph(h, n);
     h->n = n; h->e_in = e; h->e = e;
     h->in_ready = false; h->in_edges.clear();                            // (d_stage, the sensors' place, is this call's staging area)
     h->fixed_in.assign(fixed, fixed + n);
@@ -1338,15 +1167,11 @@ int uzl_pgo_set_graph(uzl_pgo* h, int32_t n, const double* poses, const uint8_t*
     k_prepare_flat_nodes(d_p, n, h->cur, s);
     k_prepare_flat_edges(d_m, d_i, e, h->d_zinv.p, h->d_info.p, s);
     UZL_HIP(hipGetLastError());
-    if (n) UZL_HIP(hipMemcpyAsync(h->pose_init.p, h->cur, sizeof(double) * 8 * (size_t)n, hipMemcpyDeviceToDevice, s));
-    UZL_HIP(hipStreamSynchronize(s));
-    upload_edges_common(h);
-    h->have_graph = true;
-    h->structure_ready = same_structure(h, old_key);
-    keep_or_drop_numbering_history(h, old_key);
+    finish_graph(h, old_key);
     return UZL_OK;
     UZL_GUARD_END(h)
 }
+
 
 int uzl_pgo_reset(uzl_pgo* h)
 {
@@ -1379,11 +1204,7 @@ int uzl_pgo_store(uzl_pgo* h, double* poses, double* edge_error, uint8_t* edge_i
     }
     std::vector<double> err;
     if (edge_error && h->e > 0) {
-        if (!h->structure_ready) {      // store without optimize: same structure optimize would build
-            h->fixed_eff = h->fixed_in;
-            h->n_gauge = gauge_fix(h);
-            build_structure(h);
-        }
+        ensure_structure(h);    // store without optimize: same structure optimize would build
         h->d_err.reserve((size_t)h->e);
         k_edge_error(h->D, h->cur, h->d_err.p, s);                                    // :124-131
         err.resize((size_t)h->e);
@@ -1489,456 +1310,6 @@ int uzl_pgo_rccl_ranks(uzl_pgo* h)
 
 }  // extern "C"
 
-#ifdef UZL_DIAG
-// ---- stage-level test hooks of the pose-graph linear system (tests/test_pgo_system_gpu.py).  Diagnostic build only; every hook takes a
-//      handle made by THIS library's uzl_pgo_create / uzl_pgo_add_graph, runs the production kernels and host steps (no arithmetic of its
-//      own), and leaves the handle as usable as it found it: the poses are not touched and every buffer it writes is rewritten by the
-//      next optimize.  Array outputs: a call with null arrays returns the sizes only.
-namespace {
-// gauge + structure + slot records (as optimize), then one linearisation at the current poses: H in D.blk / D.hdiag, b, chi2, max diag
-void debug_linearize(uzl_pgo* h)
-{
-    if (h->sharded) throw HipError{hipErrorNotSupported, "stage hooks: not on a sharded handle", __FILE__, __LINE__};
-    UZL_HIP(hipSetDevice(h->cfg.device));
-    prepare_optimize(h);
-    PgoDev& D = h->D;
-    D.pose = h->cur; D.pose_trial = h->trial;
-    h->Dp.pose = h->cur; h->Dp.pose_trial = h->trial;
-    if (h->nb == 0 || h->e == 0) return;
-    int gl = 0, ga = 0;
-    UZL_HIP(k_hessian(D, h->cur, h->cfg.huber_delta, &gl, &ga, h->stream, true));
-    k_finalize(D, gl, 0, ga, 2, h->stream);
-}
-// the Schur reduction for this lambda, as an LM trial makes it (do_optimize_host: schur_reduce)
-void debug_reduce(uzl_pgo* h, double lambda)
-{
-    if (!h->red.on) return;
-    k_set_scalar(h->D.scal + 3, lambda, h->stream);
-    kl_schur_reduce(host_slot(h), h->ml_shape, h->stream, nullptr);
-}
-double debug_lambda(uzl_pgo* h, double lambda)
-{
-    if (lambda >= 0.) return lambda;
-    double sc[16];
-    UZL_HIP(hipMemcpyAsync(sc, h->D.scal, sizeof(sc), hipMemcpyDeviceToHost, h->stream));
-    UZL_HIP(hipStreamSynchronize(h->stream));
-    return 1e-5 * sc[6];                                       // computeLambdaInit
-}
-}  // namespace
-
-// sizes[4] = {n, nb, nslots, e}.  v2b [n]: vertex -> block row (-1: fixed); row_ptr [nb+1]; col [nslots] (-1: the neighbour is fixed, the
-// block is zero); blk [nslots][36]: H_{a, col} row-major for row a, one slot per incident edge (multi-edges give several slots of one
-// block); haa [nb][36] (no lambda); b [nb][6] = -J^T Omega' e; scal[2] = {chi2, max |H_jj|}; poses [n][12]: the poses linearised at, as
-// uzl_pgo_store writes them.  Structure (sizes) only when blk is null.
-extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_linearize(uzl_pgo* h, int32_t* sizes, int32_t* v2b, int32_t* row_ptr, int32_t* col,
-                                                       double* blk, double* haa, double* b, double* scal, double* poses)
-{
-    UZL_GUARD_BEGIN(h)
-    if (!h->have_graph) return fail(h, UZL_ERR_STATE, "linearize before add_graph/set_graph");
-    if (!sizes) return fail(h, UZL_ERR_BAD_ARG, "sizes is required");
-    own_streams(h, true);
-    hipStream_t s = h->stream;
-    if (!blk) {
-        UZL_HIP(hipSetDevice(h->cfg.device));
-        prepare_optimize(h);
-    } else {
-        debug_linearize(h);
-    }
-    sizes[0] = h->n; sizes[1] = h->nb; sizes[2] = h->nslots; sizes[3] = h->e;
-    if (!blk) { UZL_HIP(hipStreamSynchronize(s)); return UZL_OK; }
-    const size_t nb = (size_t)h->nb, ns = (size_t)h->nslots;
-    if (v2b && h->n) UZL_HIP(hipMemcpyAsync(v2b, h->d_v2b.p, sizeof(int32_t) * (size_t)h->n, hipMemcpyDeviceToHost, s));
-    if (row_ptr) UZL_HIP(hipMemcpyAsync(row_ptr, h->sys.row_ptr.p, sizeof(int32_t) * (nb + 1), hipMemcpyDeviceToHost, s));
-    if (ns) {
-        if (col) UZL_HIP(hipMemcpyAsync(col, h->sys.col.p, sizeof(int32_t) * ns, hipMemcpyDeviceToHost, s));
-        UZL_HIP(hipMemcpyAsync(blk, h->D.blk, sizeof(double) * 36 * ns, hipMemcpyDeviceToHost, s));
-    }
-    if (nb) {
-        if (haa) UZL_HIP(hipMemcpyAsync(haa, h->D.hdiag, sizeof(double) * 36 * nb, hipMemcpyDeviceToHost, s));
-        if (b) UZL_HIP(hipMemcpyAsync(b, h->D.b, sizeof(double) * 6 * nb, hipMemcpyDeviceToHost, s));
-    }
-    double sc[16] = {};
-    if (nb && h->e) UZL_HIP(hipMemcpyAsync(sc, h->D.scal, sizeof(sc), hipMemcpyDeviceToHost, s));
-    if (poses && h->n) {
-        h->d_out12.reserve((size_t)h->n * 12);
-        k_poses_out(h->cur, h->n, h->d_out12.p, s);
-        UZL_HIP(hipMemcpyAsync(poses, h->d_out12.p, sizeof(double) * 12 * (size_t)h->n, hipMemcpyDeviceToHost, s));
-    }
-    UZL_HIP(hipGetLastError());
-    UZL_HIP(hipStreamSynchronize(s));
-    if (scal) { scal[0] = sc[4]; scal[1] = sc[6]; }
-    return UZL_OK;
-    UZL_GUARD_END(h)
-}
-
-// One linear solve (H + lambda I) dx = b at the current poses, done as the first trial of an LM iteration of the host-driven loop does it
-// (do_optimize_host): linearise, Schur reduction for this lambda (when the structure has one), the preconditioner's set-up (numeric part
-// and lambda-dependent part; the multiplicative operator and its Newton-Schulz steps where the structure selected them), pcg_solve under the
-// handle's cfg (pcg_tol, pcg_stop, pcg_max_iter), back-substitution.  lambda < 0: g2o's lambda_init = 1e-5 max |H_jj|.  No fallback to the
-// additive operator: a residual-guard trip is reported (info[3]) and leaves converged = 0.
-// dx [n][6]: the step per vertex, zero rows for fixed vertices.  info[8] = {pcg iterations, converged, 0, guard trips, lambda used, |r|^2 / |b|^2 (scal[7]),
-// r.M^-1 r at the end (scal[0]), the stop threshold on it (scal[1])}.
-extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_solve(uzl_pgo* h, double lambda, double* dx, double* info)
-{
-    UZL_GUARD_BEGIN(h)
-    if (!h->have_graph) return fail(h, UZL_ERR_STATE, "solve before add_graph/set_graph");
-    if (!dx || !info) return fail(h, UZL_ERR_BAD_ARG, "dx and info are required");
-    own_streams(h, true);
-    debug_linearize(h);
-    hipStream_t s = h->stream;
-    const int n = h->n;
-    for (int i = 0; i < 8; i++) info[i] = 0.;
-    memset(dx, 0, sizeof(double) * 6 * (size_t)n);
-    if (h->nb == 0 || h->e == 0) { info[1] = 1.; return UZL_OK; }
-    PgoDev& D = h->D;
-    if (lambda < 0.) {
-        double sc[16];
-        UZL_HIP(hipMemcpyAsync(sc, D.scal, sizeof(sc), hipMemcpyDeviceToHost, s));
-        UZL_HIP(hipStreamSynchronize(s));
-        lambda = 1e-5 * sc[6];
-    }
-    h->ml_ix = 0; h->ml_pending = false;
-    debug_reduce(h, lambda);
-    if (h->mlp.levels > 0) { ml_setup_numeric(h, host_slot(h), s, nullptr); h->ml_trial_setup = true; }
-    set_lambda(h, lambda, tol_factor2(h->cfg));
-    h->prev_pcg_iters = 0;
-    const int trips0 = h->guard_trips;
-    bool conv = false;
-    const int its = pcg_solve(h, 0, &conv);
-    h->prev_pcg_iters = 0;
-    if (h->red.on) kl_schur_backsub(host_slot(h), h->ml_shape, s, nullptr);
-    const size_t nb = (size_t)h->nb;
-    std::vector<double> x(nb * 6);
-    std::vector<int32_t> v2b((size_t)n);
-    UZL_HIP(hipMemcpyAsync(x.data(), D.x, sizeof(double) * 6 * nb, hipMemcpyDeviceToHost, s));
-    UZL_HIP(hipMemcpyAsync(v2b.data(), h->d_v2b.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
-    UZL_HIP(hipGetLastError());
-    UZL_HIP(hipStreamSynchronize(s));
-    for (int v = 0; v < n; v++) {
-        const int32_t a = v2b[(size_t)v];
-        if (a < 0 || (size_t)a >= nb) continue;
-        for (int c = 0; c < 6; c++) dx[(size_t)v * 6 + c] = x[(size_t)a * 6 + c];
-    }
-    info[0] = its; info[1] = conv ? 1. : 0.; info[3] = h->guard_trips - trips0; info[4] = lambda;
-    info[5] = h->h_scal.p->scal[7]; info[6] = h->h_scal.p->scal[0]; info[7] = h->h_scal.p->scal[1];
-    h->guard_trips = trips0;
-    return UZL_OK;
-    UZL_GUARD_END(h)
-}
-
-// The system the PCG sees when the structure Schur-eliminates chain interiors, for this lambda (< 0: lambda_init): linearisation, then
-// the Schur reduction (kl_schur_reduce).  sizes[3] = {reduced rows nbr, reduced slots, 1 if the structure has a reduction (0: nothing
-// else is written)}.  sep_rows [nbr]: full-system block row of every reduced row (-1: an empty row of the strong-aggregate numbering);
-// row_ptr [nbr+1], col [slots] (-1: none), blk [slots][36]: off-diagonal blocks (kept and fill); hdiag [nbr][36] and b [nbr][6]: the
-// diagonal blocks and the right-hand side.  lambda is NOT in hdiag: the separators' own lambda I is added by the SpMV (as for the full
-// system), while the eliminated interiors' lambda is inside the Schur terms.  An empty row has hdiag = I, b = 0 and no slots.
-// Structure (sizes) only when blk is null.
-extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_reduced(uzl_pgo* h, double lambda, int32_t* sizes, int32_t* sep_rows, int32_t* row_ptr,
-                                                     int32_t* col, double* blk, double* hdiag, double* b)
-{
-    UZL_GUARD_BEGIN(h)
-    if (!h->have_graph) return fail(h, UZL_ERR_STATE, "reduced before add_graph/set_graph");
-    if (!sizes) return fail(h, UZL_ERR_BAD_ARG, "sizes is required");
-    own_streams(h, true);
-    hipStream_t s = h->stream;
-    if (!blk) { UZL_HIP(hipSetDevice(h->cfg.device)); prepare_optimize(h); }
-    else debug_linearize(h);
-    const bool on = h->red.on && h->nb > 0 && h->e > 0;
-    sizes[0] = on ? h->Dp.nb : 0; sizes[1] = on ? h->Dp.nslots : 0; sizes[2] = on ? 1 : 0;
-    if (!blk || !on) { UZL_HIP(hipStreamSynchronize(s)); return UZL_OK; }
-    debug_reduce(h, debug_lambda(h, lambda));
-    const PgoDev& R = h->Dp;
-    const size_t nr = (size_t)R.nb, ns = (size_t)R.nslots;
-    if (sep_rows && nr) UZL_HIP(hipMemcpyAsync(sep_rows, h->red.sep_rows.p, sizeof(int32_t) * nr, hipMemcpyDeviceToHost, s));
-    if (row_ptr) UZL_HIP(hipMemcpyAsync(row_ptr, R.row_ptr, sizeof(int32_t) * (nr + 1), hipMemcpyDeviceToHost, s));
-    if (ns) {
-        if (col) UZL_HIP(hipMemcpyAsync(col, R.col, sizeof(int32_t) * ns, hipMemcpyDeviceToHost, s));
-        UZL_HIP(hipMemcpyAsync(blk, R.blk, sizeof(double) * 36 * ns, hipMemcpyDeviceToHost, s));
-    }
-    if (nr) {
-        if (hdiag) UZL_HIP(hipMemcpyAsync(hdiag, R.hdiag, sizeof(double) * 36 * nr, hipMemcpyDeviceToHost, s));
-        if (b) UZL_HIP(hipMemcpyAsync(b, R.b, sizeof(double) * 6 * nr, hipMemcpyDeviceToHost, s));
-    }
-    UZL_HIP(hipGetLastError());
-    UZL_HIP(hipStreamSynchronize(s));
-    return UZL_OK;
-    UZL_GUARD_END(h)
-}
-
-// One application of the PCG's operators to x, on the system the PCG iterates on (the full one, or the reduced one in its numbering: x, y
-// [nb_sys][6]) for this lambda (< 0: lambda_init), after the set-up an LM trial makes (linearisation, Schur reduction, preconditioner
-// numeric and lambda-dependent parts, set_lambda).  The fused kernels are driven in a state where their fused part is exact:
-//   op 0, y = (A + lambda I) x: the PCG's init kernel (kl_ml_pcg_init / k_precond + k_pcg_init: flags and iteration count cleared, so beta = 0),
-//         then x written into z and the iteration kernel run with the zero previous direction the init left: it forms p = z + 0 p_old = x
-//         and y = A p (ml_spmv / pcg_spmv, D.ap);
-//   op 1, y = M^-1 x: the right-hand side replaced by x (and restored afterwards), then the PCG's first step - kl_ml_pcg_init + kl_ml_cg with
-//         init = 1 (block-Jacobi: k_precond + k_pcg_init) - which forms z = M^-1 r0 = M^-1 x.
-// info[4] = {operator: 0 block-Jacobi, 1 additive multilevel, 2 multiplicative cycle / Newton-Schulz; aggregates per PCG workgroup (AGG);
-// level of the dense operator (0: none); rows of the system}.  x = null: info only (after the set-up).
-extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_apply(uzl_pgo* h, double lambda, int32_t op, const double* x, double* y, double* info)
-{
-    UZL_GUARD_BEGIN(h)
-    if (!h->have_graph) return fail(h, UZL_ERR_STATE, "apply before add_graph/set_graph");
-    if (!info || (op != 0 && op != 1) || (x && !y)) return fail(h, UZL_ERR_BAD_ARG, "apply: op 0 / 1, info, and y with x");
-    own_streams(h, true);
-    debug_linearize(h);
-    hipStream_t s = h->stream;
-    PgoDev& Dp = h->Dp;
-    const bool ml = h->mlp.levels > 0;
-    info[0] = ml ? ((h->ml_mult || h->ml_ns_steps > 0) ? 2. : 1.) : 0.; info[1] = ml ? h->mlp.agg : 0; info[2] = ml ? h->mlp.cl : 0;
-    info[3] = (h->nb > 0 && h->e > 0) ? Dp.nb : 0;
-    if (!x || info[3] == 0) { UZL_HIP(hipStreamSynchronize(s)); return UZL_OK; }
-    const double lam = debug_lambda(h, lambda);
-    h->ml_ix = 0; h->ml_pending = false;
-    debug_reduce(h, lam);
-    set_lambda(h, lam, tol_factor2(h->cfg));                   // (before the lambda-dependent set-up, as in pcg_solve)
-    const HostSlot hs = ml ? host_slot(h) : HostSlot{};
-    if (ml) {
-        ml_setup_numeric(h, hs, s, nullptr);
-        kl_ml_trial(hs, h->ml_shape, ml_ns_steps_at(h->ml_ns_steps, 0), s, nullptr);
-        h->ml_trial_setup = true;                              // (the next solve takes its own inverses)
-    }
-    const size_t n6 = (size_t)Dp.nb * 6;
-    const double tol2 = h->cfg.pcg_tol * h->cfg.pcg_tol;
-    DevBuf<double> saved;
-    if (op == 0) {
-        if (ml) kl_ml_pcg_init(hs, h->ml_shape, s);
-        else { k_precond(Dp, s); k_pcg_init(Dp, h->pbuf[0], h->pbuf[1], s); }
-        UZL_HIP(hipMemcpyAsync(Dp.z, x, sizeof(double) * n6, hipMemcpyHostToDevice, s));
-        if (ml) kl_ml_spmv(hs, h->ml_shape, 0, s);
-        else k_pcg_spmv(Dp, h->pbuf[0], h->pbuf[1], g_pcg_update(Dp.nb), tol2, s);
-        UZL_HIP(hipMemcpyAsync(y, Dp.ap, sizeof(double) * n6, hipMemcpyDeviceToHost, s));
-    } else {
-        saved.reserve(n6);
-        UZL_HIP(hipMemcpyAsync(saved.p, Dp.b, sizeof(double) * n6, hipMemcpyDeviceToDevice, s));
-        UZL_HIP(hipMemcpyAsync(Dp.b, x, sizeof(double) * n6, hipMemcpyHostToDevice, s));
-        if (ml) {
-            kl_ml_pcg_init(hs, h->ml_shape, s);
-            UZL_HIP(kl_ml_cg(hs, h->ml_shape, 0, 1, s));
-        } else {
-            k_precond(Dp, s);
-            k_pcg_init(Dp, h->pbuf[0], h->pbuf[1], s);
-        }
-        UZL_HIP(hipMemcpyAsync(y, Dp.z, sizeof(double) * n6, hipMemcpyDeviceToHost, s));
-        UZL_HIP(hipMemcpyAsync(Dp.b, saved.p, sizeof(double) * n6, hipMemcpyDeviceToDevice, s));
-    }
-    UZL_HIP(hipGetLastError());
-    UZL_HIP(hipStreamSynchronize(s));
-    return UZL_OK;
-    UZL_GUARD_END(h)
-}
-
-// The multilevel hierarchy as its set-up kernels leave it (tests/test_pgo_hierarchy_gpu.py), array by array.  Two kinds of call:
-//   what < 0:  the set-up an LM trial of the host-driven loop makes, exactly as uzl_debug_pgo_apply does it (linearisation, Schur reduction,
-//              set_lambda, numeric part, lambda-dependent part) into hierarchy copy 0, for this lambda (< 0: lambda_init) and with ns_steps
-//              Newton-Schulz steps at the composite level (< 0: what the first trial takes, ml_ns_steps_at(.., 0); otherwise even: the
-//              steps ping-pong and an even count ends where MlHot::Cmat points; 0 = the cycle's X_0 as it comes).  Fills
-//              info[64] = {levels, cl, agg, mult, steps taken at cl, upper_ns, sibling0, rows of the system, c32_stride, Schur-reduced,
-//              strong numbering, strong blocks of 4, the structure's own step count, the ml_cg variant (LmCgVariant), 0..; [16 + l] n_l; [32 + l] fan_l; [48 + l] nslots_l}
-//              and *lam_used.  levels = 0 (block-Jacobi): nothing else happens.
-//   what >= 0: copies one array of level `level` of that copy, as the last what < 0 call left it (no kernel runs): 0 row_ptr [n_l + 1],
-//              1 col [nslots_l] (both i32), 2 blk [nslots_l][36], 3 G [n_l][36] (lambda = 0), 4 M [n_l][36] (levels >= 1), 5 geo (level 0:
-//              [n_0][12] = R^T | d, above [n_l][3]), 6 cen [n_l][4] (levels >= 1), 7 Winv [n_{l+1}][(6 fan_{l+1})^2] (levels < L),
-//              8 Ydense [(6 n_l)^2] (cl <= l < L), 9 top_inv [(6 n_L)^2], 10 Cmat32 [6 n_cl][c32_stride] (f32), 11 b2v of the system's rows
-//              [n_0] (i32, -1: EMPTY row).  *nbytes: in = the room at `out` (ignored when out is null), out = the array's size in bytes
-//              (0: that level has no such array).
-// The hook only reads what the production kernels wrote.
-extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_hierarchy(uzl_pgo* h, double lambda, int32_t ns_steps, int32_t level, int32_t what, int32_t* info,
-                                                       double* lam_used, void* out, int64_t* nbytes)
-{
-    UZL_GUARD_BEGIN(h)
-    if (!h->have_graph) return fail(h, UZL_ERR_STATE, "hierarchy before add_graph/set_graph");
-    own_streams(h, true);
-    hipStream_t s = h->stream;
-    if (what < 0) {
-        if (!info || (ns_steps > 0 && (ns_steps & 1))) return fail(h, UZL_ERR_BAD_ARG, "hierarchy: info, and an even step count");
-        debug_linearize(h);
-        for (int i = 0; i < 64; i++) info[i] = 0;
-        if (h->mlp.levels == 0 || h->nb == 0 || h->e == 0) { UZL_HIP(hipStreamSynchronize(s)); return UZL_OK; }
-        const double lam = debug_lambda(h, lambda);
-        h->ml_ix = 0; h->ml_pending = false;
-        debug_reduce(h, lam);
-        set_lambda(h, lam, tol_factor2(h->cfg));
-        const HostSlot hs = host_slot(h);
-        const int steps = !h->ml_mult ? 0 : (ns_steps < 0 ? ml_ns_steps_at(h->ml_ns_steps, 0) : ns_steps);
-        ml_setup_numeric(h, hs, s, nullptr);
-        kl_ml_trial(hs, h->ml_shape, steps, s, nullptr);
-        h->ml_trial_setup = true;                              // (the next solve takes its own inverses)
-        UZL_HIP(hipGetLastError());
-        UZL_HIP(hipStreamSynchronize(s));
-        info[0] = h->mlp.levels; info[1] = h->mlp.cl; info[2] = h->mlp.agg; info[3] = h->ml_mult ? 1 : 0; info[4] = steps;
-        info[5] = kUpperNs; info[6] = h->Dp.sibling0; info[7] = h->Dp.nb; info[8] = h->mlb[0].hot.c32_stride;
-        info[9] = h->red.on ? 1 : 0; info[10] = h->red.strong ? 1 : 0; info[11] = h->red.strong_blocks ? 1 : 0; info[12] = h->ml_ns_steps;
-        info[13] = h->ml_shape.cg_variant;
-        for (int l = 0; l <= h->mlp.levels; l++) { info[16 + l] = h->mlp.n[l]; info[32 + l] = h->mlp.fan[l]; info[48 + l] = h->mlp.nslots[l]; }
-        if (lam_used) *lam_used = lam;
-        return UZL_OK;
-    }
-    const int L = h->mlp.levels, cl = h->mlp.cl;
-    if (!nbytes || !h->structure_ready || L == 0 || level < 0 || level > L) return fail(h, UZL_ERR_BAD_ARG, "hierarchy: no such level (or no set-up yet)");
-    MlDev M;
-    UZL_HIP(hipMemcpyAsync(&M, h->mlb[0].dml, sizeof(MlDev), hipMemcpyDeviceToHost, s));
-    UZL_HIP(hipStreamSynchronize(s));
-    const MlLevel& X = M.lv[level];
-    const size_t n = (size_t)X.n, ns = (size_t)X.nslots;
-    const void* src = nullptr;
-    size_t bytes = 0;
-    switch (what) {
-    case 0: src = X.row_ptr; bytes = (n + 1) * 4; break;
-    case 1: src = X.col; bytes = ns * 4; break;
-    case 2: src = X.blk; bytes = ns * 36 * 8; break;
-    case 3: src = X.G; bytes = n * 36 * 8; break;
-    case 4: if (level >= 1) { src = X.M; bytes = n * 36 * 8; } break;
-    case 5: src = X.geo; bytes = n * (level == 0 ? 12 : 3) * 8; break;
-    case 6: if (level >= 1) { src = X.cen; bytes = n * 4 * 8; } break;
-    case 7: if (level < L) { const size_t m = (size_t)6 * M.lv[level + 1].fan; src = X.Winv; bytes = (size_t)M.lv[level + 1].n * m * m * 8; } break;
-    case 8: if (cl > 0 && level >= cl && level < L) { src = M.Ydense[level]; bytes = 36 * n * n * 8; } break;
-    case 9: if (level == L) { src = M.top_inv; bytes = 36 * n * n * 8; } break;
-    case 10: if (cl > 0 && level == cl) { src = h->mlb[0].hot.Cmat32; bytes = 6 * n * (size_t)h->mlb[0].hot.c32_stride * 4; } break;
-    case 11: if (level == 0) { src = h->Dp.b2v; bytes = n * 4; } break;
-    default: return fail(h, UZL_ERR_BAD_ARG, "hierarchy: no such array");
-    }
-    if (out && bytes) {
-        if (*nbytes < (int64_t)bytes || !src) return fail(h, UZL_ERR_BAD_ARG, "hierarchy: the buffer is too small");
-        UZL_HIP(hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, s));
-        UZL_HIP(hipStreamSynchronize(s));
-    }
-    *nbytes = (int64_t)bytes;
-    return UZL_OK;
-    UZL_GUARD_END(h)
-}
-
-// The PCG's state after k iterations on the system's own right-hand side, for this lambda (< 0: lambda_init): the set-up of
-// uzl_debug_pgo_apply, the PCG's init (kl_ml_pcg_init + kl_ml_cg with init = 1), then k times the two launches of an iteration
-// (kl_ml_spmv, kl_ml_cg) one by one as the eager solve enqueues them.  Copies x, r, z [rows][6], the direction p the last iteration
-// formed (k = 0: the init's), and rg [n_g][6]: the gather-level residual buffer the NEXT ml_cg would read.  The stop test runs as in any
-// solve: give the handle a pcg_tol it cannot reach in k iterations (info[3] tells).  Multilevel path only.
-// info[6] = {rows, gather level, n_g, done flag, iterations the kernels counted, lambda}.  x = null: info only (no kernel runs).
-extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_pcg_state(uzl_pgo* h, double lambda, int32_t k, double* x, double* r, double* z, double* p,
-                                                       double* rg, double* info)
-{
-    UZL_GUARD_BEGIN(h)
-    if (!h->have_graph) return fail(h, UZL_ERR_STATE, "pcg_state before add_graph/set_graph");
-    if (!info || k < 0 || (x && !(r && z && p && rg))) return fail(h, UZL_ERR_BAD_ARG, "pcg_state: info, k >= 0, and every array with x");
-    own_streams(h, true);
-    debug_linearize(h);
-    hipStream_t s = h->stream;
-    PgoDev& Dp = h->Dp;
-    const bool ml = h->mlp.levels > 0 && h->nb > 0 && h->e > 0;
-    const int gl = !ml ? 0 : h->mlp.gather_level;
-    for (int i = 0; i < 6; i++) info[i] = 0.;
-    info[0] = ml ? Dp.nb : 0; info[1] = gl; info[2] = ml ? h->mlp.n[gl] : 0;
-    if (!x || !ml) { UZL_HIP(hipStreamSynchronize(s)); return UZL_OK; }
-    const double lam = debug_lambda(h, lambda);
-    h->ml_ix = 0; h->ml_pending = false;
-    debug_reduce(h, lam);
-    set_lambda(h, lam, tol_factor2(h->cfg));
-    const HostSlot hs = host_slot(h);
-    ml_setup_numeric(h, hs, s, nullptr);
-    kl_ml_trial(hs, h->ml_shape, ml_ns_steps_at(h->ml_ns_steps, 0), s, nullptr);
-    h->ml_trial_setup = true;                                  // (the next solve takes its own inverses)
-    kl_ml_pcg_init(hs, h->ml_shape, s);
-    UZL_HIP(kl_ml_cg(hs, h->ml_shape, 0, 1, s));
-    for (int i = 0; i < k; i++) {
-        kl_ml_spmv(hs, h->ml_shape, i & 1, s);
-        UZL_HIP(kl_ml_cg(hs, h->ml_shape, i & 1, 0, s));
-    }
-    const size_t n6 = (size_t)Dp.nb * 6, g6 = (size_t)h->mlp.n[gl] * 6;
-    int32_t fl[4] = {0, 0, 0, 0};
-    UZL_HIP(hipMemcpyAsync(x, Dp.x, sizeof(double) * n6, hipMemcpyDeviceToHost, s));
-    UZL_HIP(hipMemcpyAsync(r, Dp.r, sizeof(double) * n6, hipMemcpyDeviceToHost, s));
-    UZL_HIP(hipMemcpyAsync(z, Dp.z, sizeof(double) * n6, hipMemcpyDeviceToHost, s));
-    UZL_HIP(hipMemcpyAsync(p, h->pbuf[k & 1], sizeof(double) * n6, hipMemcpyDeviceToHost, s));
-    UZL_HIP(hipMemcpyAsync(rg, h->mlb[0].rg[(k & 1) ^ 1], sizeof(double) * g6, hipMemcpyDeviceToHost, s));
-    UZL_HIP(hipMemcpyAsync(fl, Dp.flags, sizeof(fl), hipMemcpyDeviceToHost, s));
-    UZL_HIP(hipGetLastError());
-    UZL_HIP(hipStreamSynchronize(s));
-    info[3] = fl[0]; info[4] = fl[1]; info[5] = lam;
-    return UZL_OK;
-    UZL_GUARD_END(h)
-}
-
-// A handle whose later structures start with the additive dense operator: the state the host-driven loop leaves once the multiplicative
-// operator has broken down on one of its graphs (uzl_pgo::mult_banned).  Call before add_graph / set_graph.
-extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_ban_mult(uzl_pgo* h)
-{
-    UZL_GUARD_BEGIN(h)
-    if (h->have_graph) return fail(h, UZL_ERR_STATE, "ban_mult: before the first graph");
-    h->mult_banned = true;
-    return UZL_OK;
-    UZL_GUARD_END(h)
-}
-
-// One LM trial's retraction and evaluation for a step the caller gives (tests/test_pgo_geometry_gpu.py): linearise at the current poses,
-// write the free vertices' rows of dx [n][6] into D.x (rows of fixed vertices are ignored), scal[3] = lambda, then the launches of a
-// trial of the host-driven loop - oplus_kernel from the current poses into the trial buffer, chi2_trial_kernel on the current poses
-// (the in-lane retraction) - and chi2_kernel on the stored trial poses with the same grid.  poses [n][12]: the trial poses as
-// uzl_pgo_store would write them; part_inlane / part_stored [sizes[0]]: part_a after chi2_trial_kernel / after chi2_kernel;
-// info[4] = {computeScale (sum of part_b), chi2 of the in-lane launch, chi2 of the stored poses, 0}.  sizes[1] = {workgroups of the
-// two chi2 launches}; a call with null poses returns sizes only.  The current poses are not touched.
-extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_trial(uzl_pgo* h, const double* dx, double lambda, int32_t* sizes, double* poses,
-                                                   double* part_inlane, double* part_stored, double* info)
-{
-    UZL_GUARD_BEGIN(h)
-    if (!h->have_graph) return fail(h, UZL_ERR_STATE, "trial before add_graph/set_graph");
-    if (!sizes) return fail(h, UZL_ERR_BAD_ARG, "sizes is required");
-    own_streams(h, true);
-    hipStream_t s = h->stream;
-    if (!poses) {
-        UZL_HIP(hipSetDevice(h->cfg.device));
-        prepare_optimize(h);
-        sizes[0] = (h->nb && h->e) ? g_edges_for(h->D.e_end - h->D.e_begin) : 0;
-        UZL_HIP(hipStreamSynchronize(s));
-        return UZL_OK;
-    }
-    if (!dx || !part_inlane || !part_stored || !info) return fail(h, UZL_ERR_BAD_ARG, "dx, the partial arrays and info are required");
-    debug_linearize(h);
-    const int n = h->n;
-    const size_t nb = (size_t)h->nb;
-    for (int i = 0; i < 4; i++) info[i] = 0.;
-    sizes[0] = 0;
-    h->d_out12.reserve((size_t)n * 12);
-    if (h->nb == 0 || h->e == 0) {
-        k_poses_out(h->cur, n, h->d_out12.p, s);
-        UZL_HIP(hipMemcpyAsync(poses, h->d_out12.p, sizeof(double) * 12 * (size_t)n, hipMemcpyDeviceToHost, s));
-        UZL_HIP(hipGetLastError());
-        UZL_HIP(hipStreamSynchronize(s));
-        return UZL_OK;
-    }
-    PgoDev& D = h->D;
-    std::vector<int32_t> v2b((size_t)n);
-    UZL_HIP(hipMemcpyAsync(v2b.data(), h->d_v2b.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
-    UZL_HIP(hipStreamSynchronize(s));
-    std::vector<double> x(nb * 6, 0.);
-    for (int v = 0; v < n; v++) {
-        const int32_t a = v2b[(size_t)v];
-        if (a < 0 || (size_t)a >= nb) continue;
-        for (int c = 0; c < 6; c++) x[(size_t)a * 6 + c] = dx[(size_t)v * 6 + c];
-    }
-    UZL_HIP(hipMemcpyAsync(D.x, x.data(), sizeof(double) * 6 * nb, hipMemcpyHostToDevice, s));
-    k_set_scalar(D.scal + 3, lambda, s);
-    const double delta = h->cfg.huber_delta;
-    const int go = k_oplus(D, h->cur, h->trial, s);
-    const int gc = k_chi2_trial(D, h->cur, delta, s);
-    UZL_HIP(hipMemcpyAsync(part_inlane, D.part_a, sizeof(double) * (size_t)gc, hipMemcpyDeviceToHost, s));
-    k_finalize(D, gc, go, 0, 1, s);
-    double sc[16] = {}, sc2[16] = {};
-    UZL_HIP(hipMemcpyAsync(sc, D.scal, sizeof(sc), hipMemcpyDeviceToHost, s));
-    const int gs = k_chi2(D, h->trial, delta, s);
-    if (gs != gc) { UZL_HIP(hipStreamSynchronize(s)); return fail(h, UZL_ERR_STATE, "trial: the two chi2 launches differ in their grids"); }
-    UZL_HIP(hipMemcpyAsync(part_stored, D.part_a, sizeof(double) * (size_t)gs, hipMemcpyDeviceToHost, s));
-    k_finalize(D, gs, 0, 0, 0, s);
-    UZL_HIP(hipMemcpyAsync(sc2, D.scal, sizeof(sc2), hipMemcpyDeviceToHost, s));
-    k_poses_out(h->trial, n, h->d_out12.p, s);
-    UZL_HIP(hipMemcpyAsync(poses, h->d_out12.p, sizeof(double) * 12 * (size_t)n, hipMemcpyDeviceToHost, s));
-    UZL_HIP(hipGetLastError());
-    UZL_HIP(hipStreamSynchronize(s));
-    sizes[0] = gc;
-    info[0] = sc[5]; info[1] = sc[4]; info[2] = sc2[4];
-    return UZL_OK;
-    UZL_GUARD_END(h)
-}
-#endif  // UZL_DIAG
 
 // =====================================================================================================================
 //  Batched solve: B independent graphs through ONE launch sequence (uzl_pgo_batch_*)
