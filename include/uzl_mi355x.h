@@ -865,6 +865,101 @@ int  uzl_gfr_last_votes(uzl_gfr* h, int32_t cap, int32_t* votes);
 int  uzl_gfr_get_feature(uzl_gfr* h, int32_t feature, uint8_t* desc_out, int32_t cap, int32_t* places, int32_t* n_places);
 
 /* ======================================================================================
+ *  Node uncertainty and local scope  (the scope split)
+ *
+ *  The mechanism that keeps a long-running graph bounded.  It is driven by one number per node,
+ *  SlamNode::uncertainty_: the length of the shortest path over the graph's edges, at the current poses,
+ *  from the oldest node.  SlamGraph::reevaluateUncertainty() (graph_slam_common/src/slam_graph.cpp:506-517)
+ *  runs after every optimisation (graph_slam/src/graph_slam_node.cpp:1257), reevaluateUncertainty(id)
+ *  (slam_graph.cpp:519-556) for every new node of a sub-graph (graph_slam_node.cpp:360);
+ *  scopeRequestTimerCallback (:578-663) turns the current node's uncertainty into a radius and drops the
+ *  nodes outside it, scopeRequestCallback (:535-559) picks the nodes inside a radius that the requester
+ *  lacks.  Node and edge ids are indices, and INDEX ORDER IS THE REFERENCE'S std::map ID ORDER: node 0 is
+ *  nodes_.begin(), "oldest" means smallest index, id lists come out ascending like a std::set.
+ *
+ *  Contract (parity is against this repository's own restatement, tests/scope_reference.py):
+ *    1. Adjacency.  An edge takes part in dijkstra (slam_graph.cpp:765-797) iff valid != 0 and type !=
+ *       UZL_EDGE_TYPE_2D_LASER (getNeighbors(id, true), :558-578, :787), in both directions; parallel edges
+ *       and self-loops are harmless.  oldestReachableNode (:892-910) calls getNeighbors with its default
+ *       only_valid = false: the component whose smallest index becomes `start` is taken over ALL non-laser
+ *       edges, the distances run over the valid ones only, so a node joined to its start only by an invalid
+ *       edge is not reached.  The component minimum is integer work and done on the host (union-find).
+ *    2. Edge length: sqrt((dx*dx + dy*dy) + dz*dz) of the two current translations (:788, Eigen's norm()),
+ *       computed on the device at the start of every pass; symmetric in the two ends.
+ *    3. Distances.  distance_[source] = 0 and distance_[u] is the least fixed point of
+ *       d[u] = min over neighbours v of fl(d[v] + w(v,u)); nodes not reached hold DBL_MAX.  That is what the
+ *       reference's heap returns, its lazy duplicate entries included: addition is monotone in its first
+ *       operand and fl(d + w) >= d, so every label-correcting order ends in the same bits.
+ *    4. Write-back.  node < 0: uncertainty_ = distance_ where reached (:511-515), source = node 0.
+ *       node >= 0: uncertainty_ = uncertainty_[start] + distance_ where reached (:547-554); start itself gets
+ *       initial + 0, and initial is read before any write.  Nodes not reached keep their value.  A node index
+ *       >= the node count is existsNode == false (:539): nothing changes, the call succeeds, *start = -1.
+ *    5. Scope.  request: *radius = current_scope_ = max(scope_size_min, scope_size_factor *
+ *       uncertainty_[current]) (graph_slam_node.cpp:586; the reference leaves it unchanged while the graph has
+ *       a single node, here it is always computed); the nodes out of scope are those with
+ *       |t - t_current| > (double)(float)(current_scope_ + out_margin) (:623 passes the sum to
+ *       getOutOfScopeNodes(std::string, float), slam_graph.cpp:216-229), strict.  select: the nodes with
+ *       |t - center| < radius (graph_slam_node.cpp:551, strict, radius a double) that are not among have[]
+ *       (:553); an entry of have[] that names no node of the graph matches none, duplicates are harmless.
+ *
+ *  Device side: scope_sssp_kernel is one persistent workgroup per pass over a CSR of the participating
+ *  edges that the host rebuilds only when edges or flags change.  Distances are 64-bit patterns (a
+ *  non-negative double orders as its bits), a relaxation is one unsigned 64-bit atomic min: on LDS while the
+ *  graph has at most uzl_scope_lds_nodes() nodes, on global memory (L2-resident) above.  Frontier bitmaps are
+ *  double-buffered and served in distance buckets, the pass ends with the round that improves nothing, and a
+ *  lane that has strictly improved a node of degree 2 walks on through it, so the barrier rounds are bounded
+ *  by the nodes of degree != 2 (+ 2), not by the hop depth of a trajectory.  scope_scan_kernel streams the positions and appends hits in
+ *  index order (ballot + prefix, a count pass and a write pass).
+ * ====================================================================================== */
+typedef struct uzl_scope uzl_scope;
+typedef struct uzl_scope_cfg {
+    double  scope_size_min;       /* 8.0   GraphSlam.cfg:33                                              */
+    double  scope_size_factor;    /* 0.1   GraphSlam.cfg:34                                              */
+    double  out_margin;           /* 4.0   graph_slam_node.cpp:623                                       */
+    int32_t device;
+    int32_t _pad;
+} uzl_scope_cfg;
+void uzl_scope_cfg_default(uzl_scope_cfg* cfg);
+/* UZL_ERR_BAD_ARG for a NaN in the config; UZL_ERR_NO_DEVICE without a GPU (no CPU fallback) */
+int  uzl_scope_create(const uzl_scope_cfg* cfg, uzl_scope** out);
+void uzl_scope_destroy(uzl_scope* h);
+const char* uzl_scope_last_error(uzl_scope* h);
+/* nodes whose distances a pass keeps in LDS (the bound of the on-chip path) */
+int32_t uzl_scope_lds_nodes(void);
+/* poses n x 12, uncertainty n (SlamNode::uncertainty_, NULL = zeros), edges as handed to uzl_gate_set_graph (from, to, type,
+ * valid are read; the rest ignored).  UZL_ERR_BAD_ARG, and nothing changed, for an edge that names a node outside the graph. */
+int  uzl_scope_set_graph(uzl_scope* h, int32_t n_nodes, const double* poses, const double* uncertainty,
+                         int32_t n_edges, const uzl_gate_edge* edges);
+/* append nodes / edges (the graph grows in place, as in the gate and the solver); new edges may join old and new nodes */
+int  uzl_scope_add(uzl_scope* h, int32_t n_new_nodes, const double* poses, const double* uncertainty,
+                   int32_t n_new_edges, const uzl_gate_edge* edges);
+/* new poses after a solve, from host memory (n_nodes must be the graph's) ... */
+int  uzl_scope_set_poses(uzl_scope* h, int32_t n_nodes, const double* poses);
+/* ... or where they lie: straight from a uzl_pgo handle on the same device and of the same node count, no host copy.  Waits for
+ * the solver's stream; the solver is only read.  UZL_ERR_STATE for a solver without a graph. */
+int  uzl_scope_poses_from_pgo(uzl_scope* h, uzl_pgo* solver);
+/* the filter flips SlamEdge::valid_: edge_index[k] (an index into the edges in the order given) takes valid[k] */
+int  uzl_scope_set_valid(uzl_scope* h, int32_t n, const int32_t* edge_index, const uint8_t* valid);
+/* uncertainty_ of one node (graph_slam_node.cpp:339, :411, :481 are the caller's); UZL_ERR_NOT_FOUND outside the graph */
+int  uzl_scope_set_uncertainty(uzl_scope* h, int32_t node, double value);
+/* node < 0: reevaluateUncertainty() (:506-517), source = node 0.  node >= 0: reevaluateUncertainty(id) (:519-556); *start = the
+ * oldest reachable node (-1: no such node, or an empty graph).  *n_reached = nodes whose distance_ is finite.  Either may be NULL. */
+int  uzl_scope_reevaluate(uzl_scope* h, int32_t node, int32_t* start, int32_t* n_reached);
+/* uncertainty_ / the distance_ of the last pass (DBL_MAX = not reached) of every node; cap >= node count, returns the node count.
+ * distance: UZL_ERR_STATE before the first pass over the current nodes. */
+int  uzl_scope_uncertainty(uzl_scope* h, int32_t cap, double* out);
+int  uzl_scope_distance(uzl_scope* h, int32_t cap, double* out);
+/* scopeRequestTimerCallback :586 + :623: *radius (may be NULL) = current_scope_, out = getOutOfScopeNodes(current, radius +
+ * out_margin) in ascending index order (std::set), *n = total found (may exceed cap: then only the first cap are written).
+ * UZL_ERR_NOT_FOUND for a current node outside the graph. */
+int  uzl_scope_request(uzl_scope* h, int32_t current_node, double* radius, int32_t cap, int32_t* out, int32_t* n);
+/* scopeRequestCallback :549-559: nodes with |t - center| < radius that are not among have[], ascending; *n as above */
+int  uzl_scope_select(uzl_scope* h, const double center[3], double radius, int32_t n_have, const int32_t* have,
+                      int32_t cap, int32_t* out, int32_t* n);
+/* introspection for the tests: barrier rounds and strict improvements of the last pass, and whether its distances lived in LDS */
+int  uzl_scope_stats(uzl_scope* h, int64_t* rounds, int64_t* relaxations, int32_t* in_lds);
+
+/* ======================================================================================
  *  Occupancy-grid map from the stored laser scans at the solved poses
  *
  *  GraphGridMapper::convertLaserScans2Map (map_projection/src/graph_grid_mapper.cpp:295-400), which

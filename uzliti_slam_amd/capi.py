@@ -194,6 +194,14 @@ class GfrCfg(C.Structure):
                 ("min_time_gap", C.c_double), ("initial_features", C.c_int32)]
 
 
+class ScopeCfg(C.Structure):
+    _fields_ = [("scope_size_min", C.c_double), ("scope_size_factor", C.c_double), ("out_margin", C.c_double),
+                ("device", C.c_int32), ("_pad", C.c_int32)]
+
+
+SCOPE_LDS_NODES = 16384         # scope_types.hpp kScopeLdsNodes = uzl_scope_lds_nodes(): the on-chip bound of a pass
+
+
 class GridCfg(C.Structure):
     _fields_ = [("resolution", C.c_double), ("range_max", C.c_double), ("occupancy_threshold", C.c_double), ("max_distance", C.c_double),
                 ("known_free_radius", C.c_double), ("min_pass_through", C.c_int32), ("device", C.c_int32), ("max_cells", C.c_int64)]
@@ -330,7 +338,7 @@ def lib():
 
 
 _HANDLES = ("uzl_match", "uzl_pgo", "uzl_pgo_batch", "uzl_filter", "uzl_gate", "uzl_radius", "uzl_places", "uzl_gist")
-_MORE_HANDLES = ("uzl_grid", "uzl_laserline", "uzl_gfr", "uzl_laser", "uzl_depthfilter", "uzl_cloud", "uzl_orb")      # declared like _HANDLES; kept apart because tests pin _HANDLES to the first eight
+_MORE_HANDLES = ("uzl_grid", "uzl_laserline", "uzl_gfr", "uzl_laser", "uzl_depthfilter", "uzl_cloud", "uzl_orb", "uzl_scope")    # declared like _HANDLES; kept apart because tests pin _HANDLES to the first eight
 
 
 def _declare(L):
@@ -1412,6 +1420,97 @@ class Gfr(_Handle):
         pl = np.zeros(max(n.value, 1), np.int32)
         self._check(lib().uzl_gfr_get_feature(self._h, C.c_int32(feature), _p(d, c_u8p), C.c_int32(n.value), _p(pl, c_i32p), C.byref(n)))
         return d[:nbytes], pl[:n.value]
+
+
+class Scope(_Handle):
+    """uzl_scope_* (SlamGraph::reevaluateUncertainty / getOutOfScopeNodes, GraphSlamNode::scopeRequestTimerCallback /
+    scopeRequestCallback): uncertainty_ of every node as its shortest-path distance from the oldest node, and the scope lists drawn
+    from it.  Node and edge ids are indices in the reference's std::map id order."""
+
+    _prefix, _cfg_type = "uzl_scope", ScopeCfg
+
+    def __init__(self, **cfg):
+        super().__init__(**cfg)
+        self.n = 0
+
+    @staticmethod
+    def _graph(poses, uncertainty, edges):
+        P = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
+        u = None if uncertainty is None else np.ascontiguousarray(uncertainty, np.float64).reshape(len(P))
+        E = np.zeros(0, GATE_EDGE_DTYPE) if edges is None else np.ascontiguousarray(edges, GATE_EDGE_DTYPE)
+        return P, u, E
+
+    def set_graph(self, poses, uncertainty, edges):
+        """poses (n,12); uncertainty (n) or None; edges: GATE_EDGE_DTYPE array (from, to, type, valid)."""
+        P, u, E = self._graph(poses, uncertainty, edges)
+        self._check(self._lib().uzl_scope_set_graph(self._h, C.c_int32(len(P)), _p(P, c_f64p) if len(P) else None, _p(u, c_f64p),
+                                                    C.c_int32(len(E)), _p(E, C.c_void_p) if len(E) else None))
+        self.n = len(P)
+
+    def add(self, poses, uncertainty, edges):
+        """new nodes (k,12) with their uncertainty (k) or None, and new edges, appended"""
+        P, u, E = self._graph(poses, uncertainty, edges)
+        self._check(self._lib().uzl_scope_add(self._h, C.c_int32(len(P)), _p(P, c_f64p) if len(P) else None, _p(u, c_f64p),
+                                              C.c_int32(len(E)), _p(E, C.c_void_p) if len(E) else None))
+        self.n += len(P)
+
+    def set_poses(self, poses):
+        P = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
+        self._check(self._lib().uzl_scope_set_poses(self._h, C.c_int32(len(P)), _p(P, c_f64p) if len(P) else None))
+
+    def poses_from_pgo(self, pgo):
+        """the current estimates of a Pgo handle on the same device, read where they lie"""
+        self._check(self._lib().uzl_scope_poses_from_pgo(self._h, pgo._h))
+
+    def set_valid(self, edge_index, valid):
+        i = np.ascontiguousarray(edge_index, np.int32); v = np.ascontiguousarray(valid, np.uint8)
+        assert i.shape == v.shape
+        self._check(self._lib().uzl_scope_set_valid(self._h, C.c_int32(len(i)), _p(i, c_i32p), _p(v, c_u8p)))
+
+    def set_uncertainty(self, node, value):
+        self._check(self._lib().uzl_scope_set_uncertainty(self._h, C.c_int32(node), C.c_double(value)))
+
+    def reevaluate(self, node=-1):
+        """-> (start, n_reached): node < 0 is reevaluateUncertainty(), node >= 0 reevaluateUncertainty(id)"""
+        start = C.c_int32(); reached = C.c_int32()
+        self._check(self._lib().uzl_scope_reevaluate(self._h, C.c_int32(node), C.byref(start), C.byref(reached)))
+        return start.value, reached.value
+
+    def _doubles(self, fn):
+        out = np.zeros(max(self.n, 1))
+        n = self._check(fn(self._h, C.c_int32(self.n), _p(out, c_f64p)))
+        return out[:n]
+
+    def uncertainty(self):
+        return self._doubles(self._lib().uzl_scope_uncertainty)
+
+    def distance(self):
+        """distance_ of the last pass; DBL_MAX = not reached"""
+        return self._doubles(self._lib().uzl_scope_distance)
+
+    def request(self, current, cap=None):
+        """-> (current_scope_, ids out of scope, ascending); with a cap below their number only the first cap ids"""
+        cap = self.n if cap is None else cap
+        out = np.zeros(max(cap, 1), np.int32); n = C.c_int32(); radius = C.c_double()
+        self._check(self._lib().uzl_scope_request(self._h, C.c_int32(current), C.byref(radius), C.c_int32(cap), _p(out, c_i32p), C.byref(n)))
+        self.last_total = n.value
+        return radius.value, out[:min(n.value, cap)].copy()
+
+    def select(self, center, radius, have, cap=None):
+        """-> ids within radius of center that are not among have, ascending"""
+        cap = self.n if cap is None else cap
+        c = np.ascontiguousarray(center, np.float64).reshape(3); hv = np.ascontiguousarray(have, np.int32).reshape(-1)
+        out = np.zeros(max(cap, 1), np.int32); n = C.c_int32()
+        self._check(self._lib().uzl_scope_select(self._h, _p(c, c_f64p), C.c_double(radius), C.c_int32(len(hv)), _p(hv, c_i32p) if len(hv) else None,
+                                                 C.c_int32(cap), _p(out, c_i32p), C.byref(n)))
+        self.last_total = n.value
+        return out[:min(n.value, cap)].copy()
+
+    def stats(self):
+        """barrier rounds and strict improvements of the last pass, and whether its distances lived in LDS"""
+        r = C.c_int64(); x = C.c_int64(); l = C.c_int32()
+        self._check(self._lib().uzl_scope_stats(self._h, C.byref(r), C.byref(x), C.byref(l)))
+        return dict(rounds=r.value, relaxations=x.value, in_lds=l.value)
 
 
 class Grid(_Handle):

@@ -7,6 +7,7 @@
 // accept/reject logic of g2o's OptimizationAlgorithmLevenberg [EXT].
 #include "pgo_handle.hpp"
 #include "pgo_lm.hpp"
+#include "scope_types.hpp"
 #include "uzl_streams.hpp"
 
 #include <array>
@@ -900,6 +901,20 @@ int do_optimize_host(uzl_pgo* h, int32_t iterations, uzl_pgo_stats* st)
     if (st) *st = S;
     if (rc != UZL_OK) h->last_error = "PCG hit pcg_max_iter in at least one LM trial";
     return rc;
+}
+
+// Read-only, for uzl_scope_poses_from_pgo (scope_types.hpp): the translations of the current estimates as SoA positions on stream s,
+// under the solver's lock and behind whatever is still queued on the solver's stream.  Nothing of the solver changes.
+int pgo_positions_to(uzl_pgo* h, int32_t device, int32_t n, double* x, double* y, double* z, hipStream_t s)
+{
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (!h->have_graph || !h->cur) return UZL_ERR_STATE;
+    if (h->cfg.device != device || h->n != n) return UZL_ERR_BAD_ARG;
+    if (h->stream) UZL_HIP(hipStreamSynchronize(h->stream));
+    launch_scope_pgo_poses(h->cur, n, x, y, z, s);
+    UZL_HIP(hipGetLastError());
+    UZL_HIP(hipStreamSynchronize(s));
+    return UZL_OK;
 }
 }  // namespace uzl
 
