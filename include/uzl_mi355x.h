@@ -960,6 +960,138 @@ int  uzl_scope_select(uzl_scope* h, const double center[3], double radius, int32
 int  uzl_scope_stats(uzl_scope* h, int64_t* rounds, int64_t* relaxations, int32_t* in_lds);
 
 /* ======================================================================================
+ *  Node merging  (the second half of how the reference keeps its graph bounded)
+ *
+ *  uzl_scope_* drops what lies outside the radius; merging collapses revisited places inside the global
+ *  graph.  GraphSlamNode::mergeTimerCallback (graph_slam/src/graph_slam_node.cpp:665-777) walks
+ *  current_merge_index_ over the nodes, and for a node far enough from the local scope (:696) takes a
+ *  node of SlamGraph::getNodesWithinHops(id, ., 10) (graph_slam_common/src/slam_graph.cpp:231-264) that
+ *  is close (:740) and turned little (:743-747); mergeNodes (:890-1062) folds the younger of the two
+ *  into the older.  Here the search runs on the device and the rewrite is a host-side plan, a pure
+ *  value; no resident handle is rewritten in place: the caller applies the plan to its arrays and hands
+ *  them to the existing *_set_graph / uzl_pgo_add_graph paths.  Node and edge ids are indices in the
+ *  reference's std::map id order, as for uzl_scope_*: node 0 is nodes_.begin(), the root.
+ *
+ *  Contract (parity is against this repository's own restatement, tests/merge_reference.py):
+ *    1. Adjacency of the walk.  An edge takes part iff valid != 0 (only_valid = true by default,
+ *       slam_graph.h:92); `type` is not looked at, laser edges count (unlike getNeighbors).  A node's row
+ *       is its edges in ascending edge index (node.edges_ is a std::set of edge ids, slam_node.h:103).
+ *       A self-loop leads to a visited node and is skipped; parallel edges are harmless.
+ *    2. Visited set.  Exactly the set the recursion of slam_graph.cpp:231-253 marks from `start` with
+ *       max_hops hops: depth first, one visited_ flag per node, the flag tested when the loop reaches
+ *       the edge - after earlier siblings have returned.  It is NOT the breadth-first ball: a node first
+ *       reached with few hops left is marked and never expanded again from a shorter path.  With
+ *       max_hops = 2 and edges 0-1, 1-2, 0-2, 2-3 in that order the walk from 0 marks {0, 1, 2} and
+ *       misses 3; with 0-2 first it reaches 3.  The set is a function of the edge order and a subset
+ *       of the ball.
+ *    3. Geometry.  Distance: sqrt((dx*dx + dy*dy) + dz*dz) < max_distance (:740; the expression and
+ *       association of an edge length of uzl_scope_*, no contraction).  Rotation, [EXT] and
+ *       transcendental-free: pass iff tr(R_a^T R_b) >= 1 + 2 cos(max_rotation_deg * pi / 180), the
+ *       trace being the nine entry-wise products of the two rotation blocks in row-major order summed
+ *       left to right, the right-hand side computed once on the host at create.  In exact arithmetic
+ *       that is Eigen's AngleAxisd(R_a^T R_b).angle() * 180 / pi <= max_rotation_deg (:743-747); Eigen is
+ *       not in the tree, so an angle within rounding of the bound may fall on the other side.
+ *       Start test: |t - center| > radius + scope_margin (:696), strict, the same norm expression.
+ *    4. Qualifying set and partner.  Q(start) = the visited nodes that are not start, not node 0
+ *       (:726) and pass both geometry tests; partner(start) = min Q(start), or -1.  DIVERGENCE: the
+ *       reference takes the first member of Q in the iteration order of a std::unordered_set
+ *       <std::string>, which depends on the standard library's hash.  Every outcome of the reference
+ *       is a member of Q; this library always returns the smallest.  (isMerged, :731, is always false
+ *       for a node that is still in the graph.)
+ *    5. Tick.  uzl_merge_search(first_index, center, radius) finds the smallest i >= first_index that
+ *       passes the start test and has partner(i) >= 0, and returns keep = max(i, partner) (:751-753 keep
+ *       the larger id, whatever the comment there says), drop = min(i, partner), and *next_index = what
+ *       the reference leaves in current_merge_index_: i on a merge, the node count when none is found.
+ *       first_index >= node count is treated as 1 (:677-679); otherwise it is taken as given - with 0 the
+ *       root is an ordinary start, as in the code.  A graph of fewer than 2 nodes finds nothing (:671)
+ *       and leaves *next_index = first_index.
+ *    6. Plan.  uzl_merge_plan restates mergeNodes :919-986 for first = keep, second = drop over the
+ *       handle's current poses and edges: ratio = n_stamps_drop / (n_stamps_keep + n_stamps_drop); the
+ *       new rotation is the slerp of the two quaternions at ratio ([EXT]: Eigen's quaternion from a
+ *       matrix, slerp, angle-axis and back, restated step by step), the new translation
+ *       (1 - ratio) t_keep + ratio t_drop; keep_displacement = new^-1 keep, drop_displacement =
+ *       new^-1 drop.  Every edge of keep takes keep_displacement on keep's side (:943-953).  Every edge
+ *       of drop, in ascending edge index (:960-986): deleted if it joins the two nodes; deleted if an edge
+ *       of the same type already joins keep and its other end, in either direction (existsEdge,
+ *       slam_graph.cpp:407-422 - about presence, so invalid edges are edges too, and it sees the edges
+ *       retargeted earlier in the same loop); otherwise retargeted to keep with drop_displacement on that
+ *       side.  A self-loop of drop that survives is retargeted on its `from` side as the code does and
+ *       still names drop at its `to` end: it goes with the node.
+ *       The plan is host arithmetic, but it reads the two poses where set_poses / poses_from_pgo left
+ *       them - on the device - so it needs a created handle like every other call.
+ *       Sensor-data moves (:993-1045), stamps, the uncertainty minimum and merged_nodes_map_ stay the
+ *       caller's.
+ *
+ *  Device side: merge_near_kernel tests all nodes against all nodes (positions tiled through LDS, the
+ *  rotation only where the distance passes) and flags the starts that have any geometric candidate; it
+ *  builds no lists and no counts.  merge_walk_kernel runs one wave per flagged start: the visited bitmap of
+ *  n bits in LDS, the recursion's stack as one frame per lane, and the 64 lanes working within a step
+ *  (they load the next 64 row entries, and a ballot names the first unvisited one), so a hub costs
+ *  ceil(deg / 64) steps; then the wave reads its bitmap in ascending order and writes the first node that
+ *  qualifies.  The walk is never cut short.  merge_tick_kernel reduces partner[] to the 16 bytes of a tick.
+ *  One path: the bitmaps of a workgroup's 4 waves must fit the LDS of a CU, 4 x 32 KiB, which bounds a
+ *  graph at uzl_merge_max_nodes() = 262,144 nodes; above it uzl_merge_set_graph refuses.
+ * ====================================================================================== */
+#define UZL_MERGE_MAX_HOPS 64
+typedef struct uzl_merge uzl_merge;
+typedef struct uzl_merge_cfg {
+    double  max_distance;         /* 0.25  graph_slam_node.cpp:740                                       */
+    double  max_rotation_deg;     /* 15.   :745                                                          */
+    double  scope_margin;         /* 6.    :696                                                          */
+    int32_t max_hops;             /* 10    :680; 0 .. UZL_MERGE_MAX_HOPS                                 */
+    int32_t device;
+} uzl_merge_cfg;
+/* what uzl_merge_plan does to an edge */
+#define UZL_MERGE_EDGE_UNTOUCHED      0
+#define UZL_MERGE_EDGE_KEEP_FROM      1   /* displacement_from = keep_displacement * displacement_from   */
+#define UZL_MERGE_EDGE_KEEP_TO        2   /* displacement_to   = keep_displacement * displacement_to     */
+#define UZL_MERGE_EDGE_RETARGET_FROM  3   /* from = keep, displacement_from = drop_displacement * ...    */
+#define UZL_MERGE_EDGE_RETARGET_TO    4   /* to   = keep, displacement_to   = drop_displacement * ...    */
+#define UZL_MERGE_EDGE_DELETE         5
+typedef struct uzl_merge_plan_out {
+    double  ratio;
+    double  new_pose[12];             /* pose_ of keep after the merge                                   */
+    double  keep_displacement[12];    /* first_displacement, :928                                        */
+    double  drop_displacement[12];    /* second_displacement, :929                                       */
+    int32_t n_touched;                /* edges whose action is not UNTOUCHED                             */
+    int32_t n_retargeted;
+    int32_t n_deleted;
+    int32_t _pad;
+} uzl_merge_plan_out;
+void uzl_merge_cfg_default(uzl_merge_cfg* cfg);
+/* UZL_ERR_BAD_ARG for a NaN in the config or max_hops outside 0 .. UZL_MERGE_MAX_HOPS; UZL_ERR_NO_DEVICE without a GPU (there is
+ * no CPU fallback for the search) */
+int  uzl_merge_create(const uzl_merge_cfg* cfg, uzl_merge** out);
+void uzl_merge_destroy(uzl_merge* h);
+const char* uzl_merge_last_error(uzl_merge* h);
+/* the one bound of the one path: nodes whose visited bitmap fits a wave's share of the LDS */
+int32_t uzl_merge_max_nodes(void);
+/* poses n x 12, edges as handed to uzl_gate_set_graph (from, to, type, valid are read; the rest ignored).  UZL_ERR_BAD_ARG, and
+ * nothing changed, for an edge that names a node outside the graph or for n_nodes > uzl_merge_max_nodes(). */
+int  uzl_merge_set_graph(uzl_merge* h, int32_t n_nodes, const double* poses, int32_t n_edges, const uzl_gate_edge* edges);
+/* new poses after a solve, from host memory (n_nodes must be the graph's) ... */
+int  uzl_merge_set_poses(uzl_merge* h, int32_t n_nodes, const double* poses);
+/* ... or where the solver left them: a uzl_pgo handle on the same device and of the same node count, no host copy; the same bits as
+ * uzl_pgo_store's poses handed to uzl_merge_set_poses.  Waits for the solver's stream; the solver is only read.  UZL_ERR_STATE for
+ * a solver without a graph. */
+int  uzl_merge_poses_from_pgo(uzl_merge* h, uzl_pgo* solver);
+/* the filter flips SlamEdge::valid_: edge_index[k] (an index into the edges in the order given) takes valid[k] */
+int  uzl_merge_set_valid(uzl_merge* h, int32_t n, const int32_t* edge_index, const uint8_t* valid);
+/* one tick of mergeTimerCallback (contract 5); *keep = *drop = -1: nothing to merge.  UZL_ERR_BAD_ARG for first_index < 0. */
+int  uzl_merge_search(uzl_merge* h, int32_t first_index, const double center[3], double radius, int32_t* keep, int32_t* drop,
+                      int32_t* next_index);
+/* partner(i) of every node, -1 for a node the start test rejects or one without a partner; cap >= node count, returns the node
+ * count */
+int  uzl_merge_partners(uzl_merge* h, const double center[3], double radius, int32_t cap, int32_t* partner);
+/* introspection for the tests: the starts the last search walked from (those with a geometric candidate) and the nodes those
+ * walks marked, the starts themselves included */
+int  uzl_merge_stats(uzl_merge* h, int64_t* starts_walked, int64_t* nodes_visited);
+/* contract 6: edge_action[e] = UZL_MERGE_EDGE_* for every edge of the graph; cap_edges >= edge count, returns the edge count.
+ * UZL_ERR_BAD_ARG unless keep and drop are two different nodes of the graph and the stamp counts are >= 0 and not both 0. */
+int  uzl_merge_plan(uzl_merge* h, int32_t keep, int32_t drop, int32_t n_stamps_keep, int32_t n_stamps_drop, uzl_merge_plan_out* out,
+                    int32_t cap_edges, int8_t* edge_action);
+
+/* ======================================================================================
  *  Occupancy-grid map from the stored laser scans at the solved poses
  *
  *  GraphGridMapper::convertLaserScans2Map (map_projection/src/graph_grid_mapper.cpp:295-400), which

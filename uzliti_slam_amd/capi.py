@@ -202,6 +202,23 @@ class ScopeCfg(C.Structure):
 SCOPE_LDS_NODES = 16384         # scope_types.hpp kScopeLdsNodes = uzl_scope_lds_nodes(): the on-chip bound of a pass
 
 
+class MergeCfg(C.Structure):
+    _fields_ = [("max_distance", C.c_double), ("max_rotation_deg", C.c_double), ("scope_margin", C.c_double),
+                ("max_hops", C.c_int32), ("device", C.c_int32)]
+
+
+class MergePlanOut(C.Structure):
+    _fields_ = [("ratio", C.c_double), ("new_pose", C.c_double * 12), ("keep_displacement", C.c_double * 12),
+                ("drop_displacement", C.c_double * 12), ("n_touched", C.c_int32), ("n_retargeted", C.c_int32),
+                ("n_deleted", C.c_int32), ("_pad", C.c_int32)]
+
+
+MERGE_MAX_NODES = 262144        # merge_types.hpp kMergeMaxNodes = uzl_merge_max_nodes(): a visited bitmap of 32 KiB per wave
+MERGE_MAX_HOPS = 64             # UZL_MERGE_MAX_HOPS
+(MERGE_EDGE_UNTOUCHED, MERGE_EDGE_KEEP_FROM, MERGE_EDGE_KEEP_TO, MERGE_EDGE_RETARGET_FROM, MERGE_EDGE_RETARGET_TO,
+ MERGE_EDGE_DELETE) = range(6)
+
+
 class GridCfg(C.Structure):
     _fields_ = [("resolution", C.c_double), ("range_max", C.c_double), ("occupancy_threshold", C.c_double), ("max_distance", C.c_double),
                 ("known_free_radius", C.c_double), ("min_pass_through", C.c_int32), ("device", C.c_int32), ("max_cells", C.c_int64)]
@@ -338,7 +355,7 @@ def lib():
 
 
 _HANDLES = ("uzl_match", "uzl_pgo", "uzl_pgo_batch", "uzl_filter", "uzl_gate", "uzl_radius", "uzl_places", "uzl_gist")
-_MORE_HANDLES = ("uzl_grid", "uzl_laserline", "uzl_gfr", "uzl_laser", "uzl_depthfilter", "uzl_cloud", "uzl_orb", "uzl_scope")    # declared like _HANDLES; kept apart because tests pin _HANDLES to the first eight
+_MORE_HANDLES = ("uzl_grid", "uzl_laserline", "uzl_gfr", "uzl_laser", "uzl_depthfilter", "uzl_cloud", "uzl_orb", "uzl_scope", "uzl_merge")    # declared like _HANDLES; kept apart because tests pin _HANDLES to the first eight
 
 
 def _declare(L):
@@ -1511,6 +1528,97 @@ class Scope(_Handle):
         r = C.c_int64(); x = C.c_int64(); l = C.c_int32()
         self._check(self._lib().uzl_scope_stats(self._h, C.byref(r), C.byref(x), C.byref(l)))
         return dict(rounds=r.value, relaxations=x.value, in_lds=l.value)
+
+
+def _plan_dict(out, action):
+    return dict(ratio=out.ratio, new_pose=np.array(out.new_pose), keep_displacement=np.array(out.keep_displacement),
+                drop_displacement=np.array(out.drop_displacement), action=action, touched=out.n_touched, retargeted=out.n_retargeted,
+                deleted=out.n_deleted)
+
+
+class Merge(_Handle):
+    """uzl_merge_* (GraphSlamNode::mergeTimerCallback over SlamGraph::getNodesWithinHops, and mergeNodes): which node the merge
+    timer would fold into which, searched on the device, and the rewrite of the graph as a host-side plan.  Node and edge ids are
+    indices in the reference's std::map id order."""
+
+    _prefix, _cfg_type = "uzl_merge", MergeCfg
+
+    def __init__(self, **cfg):
+        super().__init__(**cfg)
+        self.n = self.n_edges = 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def set_graph(self, poses, edges):
+        """poses (n,12); edges: GATE_EDGE_DTYPE array (from, to, type, valid) or None."""
+        P = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
+        E = np.zeros(0, GATE_EDGE_DTYPE) if edges is None else np.ascontiguousarray(edges, GATE_EDGE_DTYPE)
+        self._check(self._lib().uzl_merge_set_graph(self._h, C.c_int32(len(P)), _p(P, c_f64p) if len(P) else None, C.c_int32(len(E)),
+                                                    _p(E, C.c_void_p) if len(E) else None))
+        self.n, self.n_edges = len(P), len(E)
+
+    def set_poses(self, poses):
+        P = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
+        self._check(self._lib().uzl_merge_set_poses(self._h, C.c_int32(len(P)), _p(P, c_f64p) if len(P) else None))
+
+    def poses_from_pgo(self, pgo):
+        """the current estimates of a Pgo handle on the same device, read where they lie"""
+        self._check(self._lib().uzl_merge_poses_from_pgo(self._h, pgo._h))
+
+    def set_valid(self, edge_index, valid):
+        i = np.ascontiguousarray(edge_index, np.int32); v = np.ascontiguousarray(valid, np.uint8)
+        assert i.shape == v.shape
+        self._check(self._lib().uzl_merge_set_valid(self._h, C.c_int32(len(i)), _p(i, c_i32p), _p(v, c_u8p)))
+
+    def search(self, first_index, center, radius):
+        """one tick -> (keep, drop, next_index); keep = drop = -1: nothing to merge"""
+        c = np.ascontiguousarray(center, np.float64).reshape(3)
+        k = C.c_int32(); d = C.c_int32(); nx = C.c_int32()
+        self._check(self._lib().uzl_merge_search(self._h, C.c_int32(first_index), _p(c, c_f64p), C.c_double(radius), C.byref(k), C.byref(d),
+                                                 C.byref(nx)))
+        return k.value, d.value, nx.value
+
+    def partners(self, center, radius):
+        """partner(i) of every node, -1 for a node the start test rejects or one without a partner"""
+        c = np.ascontiguousarray(center, np.float64).reshape(3)
+        out = np.full(max(self.n, 1), -1, np.int32)
+        n = self._check(self._lib().uzl_merge_partners(self._h, _p(c, c_f64p), C.c_double(radius), C.c_int32(self.n), _p(out, c_i32p)))
+        return out[:n]
+
+    def stats(self):
+        """the starts the last search walked from and the nodes those walks marked"""
+        a = C.c_int64(); b = C.c_int64()
+        self._check(self._lib().uzl_merge_stats(self._h, C.byref(a), C.byref(b)))
+        return dict(starts_walked=a.value, nodes_visited=b.value)
+
+    def plan(self, keep, drop, n_stamps_keep=1, n_stamps_drop=1):
+        """mergeNodes for (keep, drop) over the current graph -> dict(ratio, new_pose, keep_displacement, drop_displacement, action
+        [n_edges] int8 of MERGE_EDGE_*, touched, retargeted, deleted, keep, drop)"""
+        out = MergePlanOut(); action = np.zeros(max(self.n_edges, 1), np.int8)
+        ne = self._check(self._lib().uzl_merge_plan(self._h, C.c_int32(keep), C.c_int32(drop), C.c_int32(n_stamps_keep),
+                                                    C.c_int32(n_stamps_drop), C.byref(out), C.c_int32(self.n_edges),
+                                                    action.ctypes.data_as(C.c_void_p)))
+        return dict(_plan_dict(out, action[:ne]), keep=keep, drop=drop)
+
+
+def merge_plan(n_nodes, pose_keep, pose_drop, edges, keep, drop, n_stamps_keep=1, n_stamps_drop=1):
+    """uzl_debug_merge_plan (diagnostic library, host only): the plan of Merge.plan for two poses and an edge list given, without a
+    handle or a device."""
+    L = diag_lib()
+    Tk = np.ascontiguousarray(pose_keep, np.float64).reshape(12); Td = np.ascontiguousarray(pose_drop, np.float64).reshape(12)
+    E = np.zeros(0, GATE_EDGE_DTYPE) if edges is None else np.ascontiguousarray(edges, GATE_EDGE_DTYPE)
+    out = MergePlanOut(); action = np.zeros(max(len(E), 1), np.int8)
+    L.uzl_debug_merge_plan.argtypes = [C.c_int32, c_f64p, c_f64p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                       C.POINTER(MergePlanOut), C.c_void_p]
+    rc = L.uzl_debug_merge_plan(n_nodes, _p(Tk, c_f64p), _p(Td, c_f64p), len(E), _p(E, C.c_void_p) if len(E) else None, keep, drop,
+                                n_stamps_keep, n_stamps_drop, C.byref(out), action.ctypes.data_as(C.c_void_p))
+    if rc < 0:
+        raise UzlError(rc, "uzl_debug_merge_plan")
+    return dict(_plan_dict(out, action[:rc]), keep=keep, drop=drop)
 
 
 class Grid(_Handle):

@@ -5,6 +5,7 @@
 // store = storeImpl.  All arithmetic on poses, measurements and the normal equations runs in the HIP
 // kernels of pgo_kernels.hip; the host only makes the integer/structural decisions and the scalar LM
 // accept/reject logic of g2o's OptimizationAlgorithmLevenberg [EXT].
+#include "merge_types.hpp"
 #include "pgo_handle.hpp"
 #include "pgo_lm.hpp"
 #include "scope_types.hpp"
@@ -912,6 +913,20 @@ int pgo_positions_to(uzl_pgo* h, int32_t device, int32_t n, double* x, double* y
     if (h->cfg.device != device || h->n != n) return UZL_ERR_BAD_ARG;
     if (h->stream) UZL_HIP(hipStreamSynchronize(h->stream));
     launch_scope_pgo_poses(h->cur, n, x, y, z, s);
+    UZL_HIP(hipGetLastError());
+    UZL_HIP(hipStreamSynchronize(s));
+    return UZL_OK;
+}
+
+// Read-only, for uzl_merge_poses_from_pgo (merge_types.hpp): the current estimates as n x 12 [R|t], written by the kernel uzl_pgo_store
+// reads poses back with - so they are the bits a store would hand to the host - under the same lock and waits as above.
+int pgo_poses12_to(uzl_pgo* h, int32_t device, int32_t n, double* out12, hipStream_t s)
+{
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (!h->have_graph || !h->cur) return UZL_ERR_STATE;
+    if (h->cfg.device != device || h->n != n) return UZL_ERR_BAD_ARG;
+    if (h->stream) UZL_HIP(hipStreamSynchronize(h->stream));
+    k_poses_out(h->cur, n, out12, s);
     UZL_HIP(hipGetLastError());
     UZL_HIP(hipStreamSynchronize(s));
     return UZL_OK;

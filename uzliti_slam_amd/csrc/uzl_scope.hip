@@ -10,6 +10,7 @@
 // HBM: positions SoA, uncertainty_, distance_ (bit patterns), the CSR, the pass's edge lengths and node records.  A pass is one
 // upload of nothing (or of a rebuilt CSR), one launch (scope_kernels.hip), one 32-byte download and one wait; the positions arrive
 // from the host (set_poses) or straight from a uzl_pgo handle's pose buffer (poses_from_pgo: one small kernel, no host copy).
+#include "graph_csr.hpp"
 #include "scope_types.hpp"
 #include "uzl_common.hpp"
 #include "uzl_streams.hpp"
@@ -25,7 +26,7 @@ struct uzl_scope : HandleBase {
     uzl_scope_cfg cfg;
     HandleStream stream;
     int32_t n = 0;
-    struct Edge { int32_t from, to, type, valid; };
+    using Edge = GraphEdge;
     std::vector<Edge> edges;
     bool plan_stale = true;                         // edges or flags changed since the CSR and the components were built
     std::vector<int32_t> comp_min;                  // per node: smallest index of its component over all non-laser edges
@@ -98,25 +99,15 @@ void ensure_plan(uzl_scope* h)
     const int32_t n = h->n;
     std::vector<int32_t> parent((size_t)n);
     std::iota(parent.begin(), parent.end(), 0);
-    std::vector<int32_t> row_ptr((size_t)n + 1, 0);
     for (const auto& e : h->edges) {
         if (!joins(e)) continue;
         const int32_t a = find_root(parent, e.from), b = find_root(parent, e.to);
         if (a != b) parent[std::max(a, b)] = std::min(a, b);            // the root of a component is its smallest index
-        if (!walked(e)) continue;
-        row_ptr[(size_t)e.from + 1]++;
-        if (e.to != e.from) row_ptr[(size_t)e.to + 1]++;
     }
     h->comp_min.resize((size_t)n);
     for (int32_t v = 0; v < n; v++) h->comp_min[v] = find_root(parent, v);
-    for (int32_t v = 0; v < n; v++) row_ptr[(size_t)v + 1] += row_ptr[v];
-    const int32_t m = row_ptr[n];
-    std::vector<int32_t> row((size_t)std::max(m, 1)), col(row.size()), fill(row_ptr.begin(), row_ptr.end() - 1);
-    for (const auto& e : h->edges) {
-        if (!walked(e)) continue;
-        int32_t k = fill[e.from]++; row[k] = e.from; col[k] = e.to;
-        if (e.to != e.from) { k = fill[e.to]++; row[k] = e.to; col[k] = e.from; }
-    }
+    std::vector<int32_t> row_ptr, row, col;
+    const int32_t m = build_csr(n, h->edges, walked, row_ptr, &row, col);
     h->m = m;
     h->d_row_ptr.reserve((size_t)n + 1); h->d_row.reserve(row.size()); h->d_col.reserve(row.size()); h->d_w.reserve(row.size());
     UZL_HIP(hipMemcpyAsync(h->d_row_ptr.p, row_ptr.data(), ((size_t)n + 1) * 4, hipMemcpyHostToDevice, s));

@@ -1,0 +1,54 @@
+"""Applying a merge plan (capi.Merge.plan, uzl_merge_plan) to the caller's arrays: no resident handle is rewritten in place, the
+compacted arrays this returns go to the existing set_graph / add_graph calls."""
+import numpy as np
+
+from . import capi
+
+
+def _compose(A, B):
+    """A * B of two 3 x 4 transforms [R|t] (12 doubles, row-major): rows of A times columns of B, summed left to right"""
+    out = np.empty(12)
+    for i in range(3):
+        a0, a1, a2, a3 = float(A[4 * i]), float(A[4 * i + 1]), float(A[4 * i + 2]), float(A[4 * i + 3])
+        for j in range(3):
+            out[4 * i + j] = (a0 * float(B[j]) + a1 * float(B[4 + j])) + a2 * float(B[8 + j])
+        out[4 * i + 3] = ((a0 * float(B[3]) + a1 * float(B[7])) + a2 * float(B[11])) + a3
+    return out
+
+
+def apply_merge_plan(poses, edges, displacements, plan):
+    """poses (n,12); edges: GATE_EDGE_DTYPE array; displacements: (displacement_from (e,12), displacement_to (e,12)) or None for
+    identities; plan: what Merge.plan(keep, drop, ...) returned for this graph.
+    -> (poses (n-1,12), edges, (displacement_from, displacement_to), old_to_new (n) int32) with node `drop` gone, the nodes behind it
+    one index lower (old_to_new[drop] = -1), keep at the plan's new pose, every edge action applied and the deleted edges dropped;
+    the edges keep their order.  An edge that still names `drop` afterwards (a retargeted self-loop of it) goes with the node."""
+    P = np.array(poses, np.float64).reshape(-1, 12)
+    E = np.array(np.ascontiguousarray(edges, capi.GATE_EDGE_DTYPE))
+    n, ne = len(P), len(E)
+    keep, drop, action = int(plan["keep"]), int(plan["drop"]), np.asarray(plan["action"])
+    if not (0 <= keep < n and 0 <= drop < n and keep != drop) or len(action) != ne:
+        raise ValueError("the plan does not belong to this graph")
+    if displacements is None:
+        eye = np.eye(3, 4).reshape(12)
+        D_from, D_to = np.tile(eye, (ne, 1)), np.tile(eye, (ne, 1))
+    else:
+        D_from = np.array(displacements[0], np.float64).reshape(ne, 12)
+        D_to = np.array(displacements[1], np.float64).reshape(ne, 12)
+    old_to_new = np.arange(n, dtype=np.int32)
+    old_to_new[drop + 1:] -= 1
+    old_to_new[drop] = -1
+    P[keep] = plan["new_pose"]
+    for k in np.flatnonzero(action != capi.MERGE_EDGE_UNTOUCHED):
+        a = action[k]
+        if a == capi.MERGE_EDGE_KEEP_FROM:
+            D_from[k] = _compose(plan["keep_displacement"], D_from[k])
+        elif a == capi.MERGE_EDGE_KEEP_TO:
+            D_to[k] = _compose(plan["keep_displacement"], D_to[k])
+        elif a == capi.MERGE_EDGE_RETARGET_FROM:
+            D_from[k] = _compose(plan["drop_displacement"], D_from[k]); E["from"][k] = keep
+        elif a == capi.MERGE_EDGE_RETARGET_TO:
+            D_to[k] = _compose(plan["drop_displacement"], D_to[k]); E["to"][k] = keep
+    alive = (action != capi.MERGE_EDGE_DELETE) & (E["from"] != drop) & (E["to"] != drop)
+    E = E[alive]
+    E["from"] = old_to_new[E["from"]]; E["to"] = old_to_new[E["to"]]
+    return np.delete(P, drop, axis=0), E, (D_from[alive], D_to[alive]), old_to_new
