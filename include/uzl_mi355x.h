@@ -1194,6 +1194,13 @@ int  uzl_grid_set_config(uzl_grid* h, const uzl_grid_cfg* cfg);
 int  uzl_grid_add_scans(uzl_grid* h, int32_t n, const uzl_grid_scan* scans, int32_t* first_scan);
 /* scans stored so far */
 int  uzl_grid_scan_count(uzl_grid* h);
+/* Re-point stored scans at new node indices after the caller has compacted its arrays (old_to_new of apply_merge_plan): stored
+ * scan scan_index[i] gets node = node[i].  node = -1 retires the scan - after a node merge the keep node's old scan and the drop
+ * node's scan, which the merged one (uzl_scanmerge_to_grid) replaces: every later build or extend skips it.  Host records only:
+ * the store stays append-only, the grid built so far is not touched, and a full build is the caller's next step, as after any
+ * change of stored scans.  UZL_ERR_BAD_ARG, nothing changed, for n < 0, a NULL array, an index outside the store or node < -1.
+ * uzl_grid_add_scans still refuses node < 0. */
+int  uzl_grid_renumber_scans(uzl_grid* h, int32_t n, const int32_t* scan_index, const int32_t* node);
 /* Full rebuild, steps 1-6 over every stored scan: the reset branch of convertLaserScans2Map (:308-324).  poses = n_nodes x 12
  * (row-major 3x4 SlamNode::pose_), present = n_nodes flags or NULL.  UZL_ERR_BAD_ARG (handle unchanged) for n_nodes < 0, NULL
  * poses, a non-finite pose entry of a present node, no present node, width * height > max_cells, or a scan whose pose scales
@@ -1492,6 +1499,123 @@ int  uzl_laser_estimate(uzl_laser* h, int32_t n_pairs, const uzl_laser_pair* pai
  * after step 4, dist = d_i of step 4 for a correspondence left after step 3, else 0.  Returns n_beams(to); errors as estimate. */
 int  uzl_laser_correspondences(uzl_laser* h, const uzl_laser_pair* pair, const double* x, int32_t* j1, int32_t* j2, int32_t* valid,
                                double* dist);
+
+/* ======================================================================================
+ *  Node merging: the two nodes' laser scans folded into one, on the device
+ *
+ *  The sensor-data half of GraphSlamNode::mergeNodes (graph_slam/src/graph_slam_node.cpp:993-1045;
+ *  uzl_merge_* finds the pair and plans poses and edges): when keep (first) and drop (second) both
+ *  carry a LaserscanData, the LaserscanDataPtr overload of GraphGridMapper::mergeLaserScans
+ *  (map_projection/src/graph_grid_mapper.cpp:45-133, called at :1002, with scanToPoints /
+ *  scanToIntensities :575-603 and scanMean :605-621) re-projects both scans through their
+ *  displacements, re-bins every point on keep's angular grid and folds the points of one bin in beam
+ *  order.  It is not the (scan, scan, displacement) overload of the laser line's step 8 (:135-212).
+ *  Which sensor of drop merges, moves or is discarded is host logic: uzliti_slam_amd.merge.sensor_moves.
+ *  Every step is f32 or f64 as stated, evaluated in the order written with no fused multiply-add, sqrtf
+ *  correctly rounded; the results equal a NumPy restatement (tests/scanmerge_reference.py) bit for bit.
+ *
+ *  A scan S (a = keep, b = drop): n_beams in 8..4096, angle_min, angle_increment, range_min,
+ *  range_max (f32, from the LaserScan), ranges and intensities (n f32 each), displacement
+ *  (LaserscanData::displacement_, 3x4 row-major f64) and stamp_ns (scan_.header.stamp).  A pair adds
+ *  keep_displacement and drop_displacement as uzl_merge_plan_out gives them.
+ *
+ *  1. Displacements: D_a = keep_displacement * a.displacement (:955), D_b = drop_displacement *
+ *     b.displacement (:999), on the host in f64, each 3-term sum as (a0 b0 + a1 b1) + a2 b2 and the
+ *     left translation added last; then cast entry by entry to f32 (displacement_.cast<float>(), :581).
+ *  2. Points (:575-603).  Reading r of beam i of S is used iff it is not NaN and S.range_min <= r <=
+ *     S.range_max; the intensities pass the same test, upper bound included (:595).  (c_i, s_i) =
+ *     (cos, sin)(theta_i), theta_i = (double)angle_min + (double)i (double)angle_increment, from the
+ *     HOST's libm as a table - the table rule of the occupancy grid's step 3.  x = (float)(c_i (double)r),
+ *     y = (float)(s_i (double)r); q_x = (D[0][0] x + D[0][1] y) + D[0][3] and q_y = (D[1][0] x +
+ *     D[1][1] y) + D[1][3] in f32.  A scan therefore gives two point lists, one of its ranges and one
+ *     of its intensities.  Divergences: the reference accumulates the angle in f32 and calls cosf /
+ *     sinf; the z = 0 term of the product is left out.
+ *  3. Bin and range.  The bin of (q_x, q_y) on a's grid is the laser line's step 6 exactly, with a's
+ *     (c_k, s_k), k = 0..n_a; the result does not depend on a device atan2f.  A point without a bin
+ *     (the origin, a non-finite coordinate) is dropped.  rho = sqrtf(q_x q_x + q_y q_y) in f32.
+ *  4. Start (:53-56): ranges[k] = a.range_max + 1.0f, intensities[k] = 0 for every k.
+ *  5. a's own points (:58-84), in beam order: ranges[bin] = rho for the points of a's ranges,
+ *     intensities[bin] = rho for those of its intensities: per bin the highest beam index wins.
+ *  6. b's points, in beam order.  Ranges (:86-107), cur = ranges[bin]: cur NaN, cur < a.range_min or
+ *     cur > a.range_max -> rho; else fabsf(cur - rho) < 0.1f -> 0.5f (cur + rho); else b.stamp_ns >
+ *     a.stamp_ns -> rho; else unchanged.  Intensities (:109-130): the same without the upper test.
+ *     The chain of means is not associative: a bin's points are folded in beam order, by one lane.
+ *  7. Scan centre (:132): the laser line's step 9 over the merged ranges with lo = a.range_min,
+ *     hi0 = a.range_max and a's table.
+ *  8. The merged scan carries a's message fields (angular grid, limits, stamp) and an identity
+ *     displacement (:52).
+ *
+ *  Scope.  a must lie on a laser-line grid: angle_min = (float)(-pi) and n_beams the n of the laser
+ *  line's step 1 for its angle_increment; anything else is UZL_ERR_UNSUPPORTED.  Every LaserScan in the
+ *  reference's graph comes from extractImageLaserLine (:422-433), so this covers its data; step 6 of
+ *  the laser line is wrong on a partial grid (on a 270-degree grid about half of the points beyond the
+ *  last boundary land in bin n - 1).  b may lie on any finite grid.
+ *  Divergences from the reference, deliberate: its (int)((angle - angle_min) / angle_increment) can
+ *  index past the array (angle = angle_max passes its test); and with an identity displacement every
+ *  point of a lies on a bin boundary, where the reference's own choice between bin i and i - 1 is the
+ *  rounding noise of cosf, sinf and atan2f (a fifth to a half of a scan's points fall on the other side): step
+ *  3's choice is deterministic and as arbitrary.  Away from boundaries the reference's atan2f index
+ *  differs from step 3 in fewer than 1 in 5,000 points (tests/test_scanmerge_reference.py).
+ *
+ *  Device side: one workgroup per pair.  A list is made with one lane per beam, as keys
+ *  bin << 12 | beam with rho as payload, and sorted in LDS; of a's lists the last element of a run is
+ *  the bin's value, of b's lists the lane at a run's head folds its run.  Ranges are finished before
+ *  the intensities reuse the buffers (48 KiB of LDS per workgroup); the tables stay in global memory.
+ *  No float atomics; a pair's result does not depend on the schedule, the other pairs or the batching.
+ * ====================================================================================== */
+typedef struct uzl_scanmerge uzl_scanmerge;
+typedef struct uzl_scanmerge_cfg {
+    int32_t device, _pad;
+} uzl_scanmerge_cfg;
+typedef struct uzl_scanmerge_scan {
+    const float* ranges;          /* n_beams f32 each, borrowed for the call                                     */
+    const float* intensities;
+    int32_t n_beams;
+    float   angle_min, angle_increment, range_min, range_max;
+    int32_t _pad;
+    double  displacement[12];     /* LaserscanData::displacement_, row-major 3x4                                 */
+    int64_t stamp_ns;             /* scan_.header.stamp                                                          */
+} uzl_scanmerge_scan;
+typedef struct uzl_scanmerge_pair {
+    const uzl_scanmerge_scan* keep;   /* a: the scan of the node that stays                                      */
+    const uzl_scanmerge_scan* drop;   /* b                                                                       */
+    double keep_displacement[12];     /* uzl_merge_plan_out.keep_displacement                                    */
+    double drop_displacement[12];     /* uzl_merge_plan_out.drop_displacement                                    */
+} uzl_scanmerge_pair;
+void uzl_scanmerge_cfg_default(uzl_scanmerge_cfg* cfg);
+/* UZL_ERR_NO_DEVICE without a GPU (no CPU fallback) */
+int  uzl_scanmerge_create(const uzl_scanmerge_cfg* cfg, uzl_scanmerge** out);
+void uzl_scanmerge_destroy(uzl_scanmerge* h);
+const char* uzl_scanmerge_last_error(uzl_scanmerge* h);
+/* Steps 1-8 for n_pairs pairs in one launch; replaces the handle's resident result (the merged scans and the call's inputs stay
+ * in HBM until the next run).  A pair's result does not depend on the other pairs or on the batching.  n_pairs = 0 is valid.
+ * Pairs are checked in order, each for UZL_ERR_BAD_ARG first: n_pairs < 0, a NULL array (pairs, keep, drop, ranges, intensities),
+ * n_beams outside 8..4096, a non-finite angle_min / angle_increment / range_min / range_max / displacement entry,
+ * range_min < 0, range_max < range_min; then UZL_ERR_UNSUPPORTED for a keep scan outside the scope above.  On either the handle
+ * is left unchanged. */
+int  uzl_scanmerge_run(uzl_scanmerge* h, int32_t n_pairs, const uzl_scanmerge_pair* pairs);
+/* The merged scan of pair `pair`: ranges, intensities (n_beams(keep) f32 each) and scan_center (3 doubles); any output may be
+ * NULL.  Returns n_beams(keep).  UZL_ERR_STATE before any run, UZL_ERR_BAD_ARG for a pair outside the last run or cap < 0,
+ * UZL_ERR_TRUNCATED when cap is smaller than n_beams(keep). */
+int  uzl_scanmerge_read(uzl_scanmerge* h, int32_t pair, int32_t cap, float* ranges, float* intensities, double* scan_center);
+/* Stage entry: steps 1-3 of one pair of the last run again, over the resident inputs.  which = 0: keep's ranges, 1: keep's
+ * intensities, 2: drop's ranges, 3: drop's intensities.  Per beam of that scan (either output may be NULL): bin on keep's grid
+ * (-1: the reading is unused or its point dropped) and rho (0 where bin = -1).  Returns the scan's n_beams; errors as
+ * uzl_scanmerge_read, and UZL_ERR_BAD_ARG for which outside 0..3.  The resident result is not touched. */
+int  uzl_scanmerge_points(uzl_scanmerge* h, int32_t pair, int32_t which, int32_t cap, int32_t* bin, float* rho);
+/* Append the merged scans to a grid handle's store by one device-to-device copy, as uzl_grid_add_scans would with displacement =
+ * identity, keep's angle_min, angle_increment and range_min, and node = nodes[i] (one per pair, >= 0): the grid built afterwards
+ * equals, bit for bit, the grid built from uzl_scanmerge_read -> uzl_grid_add_scans.  The scans they replace (keep's old one and
+ * drop's) are retired with uzl_grid_renumber_scans.  *first_scan (may be NULL) = index of the first scan in the grid's store.
+ * UZL_ERR_BAD_ARG for a NULL grid, NULL nodes with scans to add, a negative node, or handles on different devices;
+ * UZL_ERR_STATE before any run.  Locks the scan-merge handle, then the grid handle. */
+int  uzl_scanmerge_to_grid(uzl_scanmerge* h, uzl_grid* grid, const int32_t* nodes, int32_t* first_scan);
+/* Device-to-device append of the merged scans to a laser handle's store: their intensities, or their ranges when use_near != 0,
+ * with keep's angular grid and (range_min, range_max).  The store then holds, bit for bit, what uzl_scanmerge_read ->
+ * uzl_laser_add_scans would have put there (the matcher's store is append-only: the caller stops naming the replaced scans).
+ * UZL_ERR_BAD_ARG for a NULL laser handle or handles on different devices; UZL_ERR_STATE before any run.  Locks the scan-merge
+ * handle, then the laser handle. */
+int  uzl_scanmerge_to_laser(uzl_scanmerge* h, uzl_laser* laser, int32_t use_near, int32_t* first_scan);
 
 /* ======================================================================================
  *  Depth refinement and 3-D keypoint lifting: the depth image the front end stores and reads

@@ -219,6 +219,24 @@ MERGE_MAX_HOPS = 64             # UZL_MERGE_MAX_HOPS
  MERGE_EDGE_DELETE) = range(6)
 
 
+class ScanMergeCfg(C.Structure):
+    _fields_ = [("device", C.c_int32), ("_pad", C.c_int32)]
+
+
+class ScanMergeScan(C.Structure):
+    _fields_ = [("ranges", C.POINTER(C.c_float)), ("intensities", C.POINTER(C.c_float)), ("n_beams", C.c_int32),
+                ("angle_min", C.c_float), ("angle_increment", C.c_float), ("range_min", C.c_float), ("range_max", C.c_float),
+                ("_pad", C.c_int32), ("displacement", C.c_double * 12), ("stamp_ns", C.c_int64)]
+
+
+class ScanMergePair(C.Structure):
+    _fields_ = [("keep", C.POINTER(ScanMergeScan)), ("drop", C.POINTER(ScanMergeScan)), ("keep_displacement", C.c_double * 12),
+                ("drop_displacement", C.c_double * 12)]
+
+
+SCANMERGE_KEEP_RANGES, SCANMERGE_KEEP_INTENSITIES, SCANMERGE_DROP_RANGES, SCANMERGE_DROP_INTENSITIES = range(4)
+
+
 class GridCfg(C.Structure):
     _fields_ = [("resolution", C.c_double), ("range_max", C.c_double), ("occupancy_threshold", C.c_double), ("max_distance", C.c_double),
                 ("known_free_radius", C.c_double), ("min_pass_through", C.c_int32), ("device", C.c_int32), ("max_cells", C.c_int64)]
@@ -355,7 +373,7 @@ def lib():
 
 
 _HANDLES = ("uzl_match", "uzl_pgo", "uzl_pgo_batch", "uzl_filter", "uzl_gate", "uzl_radius", "uzl_places", "uzl_gist")
-_MORE_HANDLES = ("uzl_grid", "uzl_laserline", "uzl_gfr", "uzl_laser", "uzl_depthfilter", "uzl_cloud", "uzl_orb", "uzl_scope", "uzl_merge")    # declared like _HANDLES; kept apart because tests pin _HANDLES to the first eight
+_MORE_HANDLES = ("uzl_grid", "uzl_laserline", "uzl_gfr", "uzl_laser", "uzl_depthfilter", "uzl_cloud", "uzl_orb", "uzl_scope", "uzl_merge", "uzl_scanmerge")    # declared like _HANDLES; kept apart because tests pin _HANDLES to the first eight
 
 
 def _declare(L):
@@ -1654,6 +1672,13 @@ class Grid(_Handle):
     def scan_count(self):
         return self._check(lib().uzl_grid_scan_count(self._h))
 
+    def renumber_scans(self, scan_index, node):
+        """stored scan scan_index[i] now belongs to node[i]; -1 retires it (every later build or extend skips it)"""
+        si = np.ascontiguousarray(scan_index, np.int32).reshape(-1); nd = np.ascontiguousarray(node, np.int32).reshape(-1)
+        assert si.shape == nd.shape
+        self._check(lib().uzl_grid_renumber_scans(self._h, C.c_int32(len(si)), _p(si, c_i32p) if len(si) else None,
+                                                  _p(nd, c_i32p) if len(nd) else None))
+
     @staticmethod
     def _poses(poses, present):
         P = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
@@ -1808,6 +1833,90 @@ class Laserline(_Handle):
         """append the resident scans (intensities, or ranges with use_near) to a Laser's store on the device -> index of the first"""
         first = C.c_int32(-1)
         self._check(lib().uzl_laserline_to_laser(self._h, laser._h, C.c_int32(1 if use_near else 0), C.byref(first)))
+        return first.value
+
+
+class ScanMerge(_Handle):
+    """uzl_scanmerge_* (the LaserscanDataPtr overload of GraphGridMapper::mergeLaserScans, map_projection/src/graph_grid_mapper.cpp:
+    45-133, as GraphSlamNode::mergeNodes calls it): the laser scans of (keep, drop) node pairs re-projected, re-binned on keep's grid
+    and folded into one scan per pair, all pairs of a call in one launch."""
+
+    _prefix, _cfg_type = "uzl_scanmerge", ScanMergeCfg
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @staticmethod
+    def pack_scan(s):
+        """s: dict with ranges, intensities (f32, one length), angle_min, angle_increment, range_min, range_max and optionally
+        displacement (12 or 3x4, default identity) and stamp_ns (default 0) -> (ScanMergeScan, the arrays it points into)"""
+        r = np.ascontiguousarray(s["ranges"], np.float32).reshape(-1)
+        it = np.ascontiguousarray(s["intensities"], np.float32).reshape(-1)
+        if len(r) != len(it):
+            raise ValueError("ranges and intensities of a scan have one length")
+        f32p = C.POINTER(C.c_float)
+        g = ScanMergeScan()
+        g.ranges = r.ctypes.data_as(f32p); g.intensities = it.ctypes.data_as(f32p); g.n_beams = len(r)
+        g.angle_min = float(s["angle_min"]); g.angle_increment = float(s["angle_increment"])
+        g.range_min = float(s["range_min"]); g.range_max = float(s["range_max"])
+        g.displacement[:] = np.asarray(s.get("displacement", np.eye(3, 4)), np.float64).reshape(12).tolist()
+        g.stamp_ns = int(s.get("stamp_ns", 0))
+        return g, (r, it)
+
+    @classmethod
+    def pack_pairs(cls, pairs):
+        """pairs: (keep scan, drop scan, keep_displacement, drop_displacement) with the scans as pack_scan takes them
+        -> (ScanMergePair array, what it points into, [(n_beams(keep), n_beams(drop))])"""
+        arr = (ScanMergePair * max(len(pairs), 1))()
+        keep, shape = [], []
+        for i, (a, b, Dk, Dd) in enumerate(pairs):
+            ga, ka = cls.pack_scan(a); gb, kb = cls.pack_scan(b)
+            keep.append((ga, ka, gb, kb))
+            arr[i].keep = C.pointer(ga); arr[i].drop = C.pointer(gb)
+            arr[i].keep_displacement[:] = np.asarray(Dk, np.float64).reshape(12).tolist()
+            arr[i].drop_displacement[:] = np.asarray(Dd, np.float64).reshape(12).tolist()
+            shape.append((ga.n_beams, gb.n_beams))
+        return arr, keep, shape
+
+    _pairs = ()                       # (n_beams(keep), n_beams(drop)) per pair of the resident result
+
+    def run(self, pairs):
+        """merge every pair; the merged scans stay on the device.  pairs: a list as pack_pairs takes it, or what it made of one"""
+        arr, keep, shape = pairs if isinstance(pairs, tuple) else self.pack_pairs(pairs)
+        self._check(lib().uzl_scanmerge_run(self._h, C.c_int32(len(shape)), arr))
+        self._pairs = tuple(shape)
+        return len(shape)
+
+    def read(self, pair):
+        """-> (ranges, intensities: float32 (n_beams(keep),); scan centre: float64 (3,)) of one pair"""
+        n = self._pairs[pair][0] if 0 <= pair < len(self._pairs) else 0
+        f32p = C.POINTER(C.c_float)
+        r = np.zeros(max(n, 1), np.float32); it = np.zeros(max(n, 1), np.float32); ce = np.zeros(3, np.float64)
+        m = self._check(lib().uzl_scanmerge_read(self._h, C.c_int32(pair), C.c_int32(n), _p(r, f32p), _p(it, f32p), _p(ce, c_f64p)))
+        return r[:m], it[:m], ce
+
+    def points(self, pair, which):
+        """stage entry: per beam of list `which` (SCANMERGE_*) of one pair -> (bin int32, -1 = unused or dropped; rho float32)"""
+        n = self._pairs[pair][0 if which < 2 else 1] if 0 <= pair < len(self._pairs) else 0
+        b = np.zeros(max(n, 1), np.int32); rho = np.zeros(max(n, 1), np.float32)
+        m = self._check(lib().uzl_scanmerge_points(self._h, C.c_int32(pair), C.c_int32(which), C.c_int32(n), _p(b, c_i32p),
+                                                   _p(rho, C.POINTER(C.c_float))))
+        return b[:m], rho[:m]
+
+    def to_grid(self, grid, nodes):
+        """append the merged scans to a Grid's store on the device (pair i at node nodes[i]) -> index of the first scan added"""
+        nd = np.ascontiguousarray(nodes, np.int32).reshape(-1)
+        first = C.c_int32(-1)
+        self._check(lib().uzl_scanmerge_to_grid(self._h, grid._h, _p(nd, c_i32p) if len(nd) else None, C.byref(first)))
+        return first.value
+
+    def to_laser(self, laser, use_near=False):
+        """append the merged scans (intensities, or ranges with use_near) to a Laser's store on the device -> index of the first"""
+        first = C.c_int32(-1)
+        self._check(lib().uzl_scanmerge_to_laser(self._h, laser._h, C.c_int32(1 if use_near else 0), C.byref(first)))
         return first.value
 
 

@@ -57,6 +57,11 @@ void launch_grid_stats(const GridStatsArgs& a, int n_scans, hipStream_t s);
 // grid handle's lock; failures are reported through the grid handle's last_error.
 int grid_append_device(uzl_grid* h, int device, int32_t n_scans, int32_t n_beams, const float* d_ranges, float angle_min,
                        float angle_increment, float range_min, const int32_t* nodes, int32_t* first_scan);
+// The same for scans that differ in beam count, grid or range_min (uzl_scanmerge_to_grid): scan i has scans[i].n ranges, and the
+// scans lie one after the other at d_ranges.  One device-to-device copy; the same checks, messages and lock.
+struct DeviceScan;
+int grid_append_device_scans(uzl_grid* h, int device, int32_t n_scans, const DeviceScan* scans, const float* d_ranges,
+                             const int32_t* nodes, int32_t* first_scan);
 
 // The part of the ray cell(o) = (x0, y0) -> (x1, y1) (steps 0..L of contract step 5) inside the cell rectangle [ux0, ux1] x
 // [uy0, uy1]: calls visit(x, y) for exactly those cells, in walk order.  Bresenham's state after k steps in closed form: with

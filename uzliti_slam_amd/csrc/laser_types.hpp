@@ -65,5 +65,10 @@ void launch_laser_icp(const LaserIcpArgs& a, int n_pairs, hipStream_t s);
 // complete, appended as uzl_laser_add_scans appends them.
 int laser_append_device(uzl_laser* h, int device, int32_t n_scans, int32_t n_beams, const float* d_values, float angle_min,
                         float angle_increment, float range_min, float range_max, int32_t* first_scan);
+// The same for scans that differ in beam count, grid or limits (uzl_scanmerge_to_laser): scan i has scans[i].n values, and the
+// scans lie one after the other at d_values.  One device-to-device copy; the same checks, messages and lock.
+struct DeviceScan;
+int laser_append_device_scans(uzl_laser* h, int device, int32_t n_scans, const DeviceScan* scans, const float* d_values,
+                              int32_t* first_scan);
 
 }  // namespace uzl

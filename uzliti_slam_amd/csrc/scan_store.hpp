@@ -10,6 +10,13 @@
 
 namespace uzl {
 
+// One scan that already lies in device memory, as a store takes it from another handle when the scans of a call differ in their
+// grids or limits (grid_append_device_scans, laser_append_device_scans): its n readings follow the previous scan's.
+struct DeviceScan {
+    int32_t n;
+    float angle_min, angle_increment, range_min, range_max;
+};
+
 struct ScanStore {
     int64_t n_values = 0, n_trig = 0;
     std::map<std::tuple<uint32_t, uint32_t, int32_t>, int64_t> tables;   // (angle_min bits, increment bits, n) -> trig_off

@@ -18,7 +18,7 @@ namespace uzl {
 constexpr double kGridMaxRayCells = 16777216.0;   // 2^24: a scan's rays must stay within this many cells of its sensor
 
 struct GridScanHost {
-    int32_t node, n;
+    int32_t node, n;             // node = -1: retired
     double D[12];
     float range_min;
     int64_t ranges_off, trig_off;
@@ -129,7 +129,7 @@ int plan(const std::vector<GridScanHost>& scans, const uzl_grid_cfg& c, const Gr
     struct Box { int32_t x0, y0, x1, y1; };
     std::vector<Box> sbox;                     // per record: tile box (x0 > x1: off the grid)
     for (const GridScanHost& s : scans) {
-        if (s.node >= n_nodes || !adds(present, s.node, first)) continue;
+        if (s.node < 0 || s.node >= n_nodes || !adds(present, s.node, first)) continue;   // node < 0: retired (uzl_grid_renumber_scans)
         double S[12];
         compose(poses + 12 * (size_t)s.node, s.D, S);
         GridScanRec r;
@@ -391,6 +391,19 @@ int uzl_grid_scan_count(uzl_grid* h)
     return (int)h->scans.size();
 }
 
+int uzl_grid_renumber_scans(uzl_grid* h, int32_t n, const int32_t* scan_index, const int32_t* node)
+{
+    UZL_GUARD_BEGIN(h)
+    if (n < 0 || (n > 0 && (!scan_index || !node))) return fail(h, UZL_ERR_BAD_ARG, "bad count or null arrays");
+    for (int32_t i = 0; i < n; i++) {
+        if (scan_index[i] < 0 || (size_t)scan_index[i] >= h->scans.size()) return fail(h, UZL_ERR_BAD_ARG, "scan index outside the store");
+        if (node[i] < -1) return fail(h, UZL_ERR_BAD_ARG, "node below -1");
+    }
+    for (int32_t i = 0; i < n; i++) h->scans[scan_index[i]].node = node[i];   // host records only: the arenas stay as they are
+    return UZL_OK;
+    UZL_GUARD_END(h)
+}
+
 int uzl_grid_build(uzl_grid* h, int32_t n_nodes, const double* poses, const uint8_t* present, uzl_grid_info* info)
 {
     UZL_GUARD_BEGIN(h)
@@ -543,29 +556,53 @@ extern "C" UZL_DIAG_EXPORT int uzl_debug_grid_plan(const uzl_grid_cfg* cfg, cons
 }
 #endif  // UZL_DIAG
 
-// uzl_laserline_to_grid's way into the store (declared in grid_types.hpp): n_scans scans of n_beams ranges each, contiguous in the
-// memory of `device` and complete (the caller has synchronised their producer), appended as uzl_grid_add_scans appends scans
-// with an identity displacement.
-int uzl::grid_append_device(uzl_grid* h, int device, int32_t n_scans, int32_t n_beams, const float* d_ranges, float angle_min,
-                            float angle_increment, float range_min, const int32_t* nodes, int32_t* first_scan)
+// The way into the store for scans that already lie in device memory (declared in grid_types.hpp): n_scans scans, scan i as
+// scan_at(i) describes it, one after the other at d_ranges and complete (the caller has synchronised their producer), appended as
+// uzl_grid_add_scans appends scans with an identity displacement.  Called with the handle's lock held.
+namespace {
+
+template <typename ScanAt>
+int append_device(uzl_grid* h, int device, int32_t n_scans, ScanAt&& scan_at, const float* d_ranges, const int32_t* nodes, int32_t* first_scan)
 {
-    UZL_GUARD_BEGIN(h)
     if (device != h->cfg.device) return fail(h, UZL_ERR_BAD_ARG, "the scans are on another device than the grid");
-    if (n_scans < 0 || n_beams < 0 || (n_scans > 0 && (!nodes || (n_beams > 0 && !d_ranges))))
-        return fail(h, UZL_ERR_BAD_ARG, "bad scan count or null scans");
+    if (n_scans < 0 || (n_scans > 0 && !nodes)) return fail(h, UZL_ERR_BAD_ARG, "bad scan count or null scans");
     static const double I[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
     std::vector<ScanIn> in(n_scans);
+    int64_t total = 0;
     for (int32_t i = 0; i < n_scans; i++) {
-        if (nodes[i] < 0) return fail(h, UZL_ERR_BAD_ARG, "bad scan node / ranges");
-        in[i] = ScanIn{nodes[i], n_beams, I, angle_min, angle_increment, range_min};
+        const DeviceScan s = scan_at(i);
+        if (nodes[i] < 0 || s.n < 0) return fail(h, UZL_ERR_BAD_ARG, "bad scan node / ranges");
+        if (!std::isfinite(s.angle_min) || !std::isfinite(s.angle_increment)) return fail(h, UZL_ERR_BAD_ARG, "non-finite scan angle or displacement");
+        if (!(s.range_min >= 0.f)) return fail(h, UZL_ERR_BAD_ARG, "range_min negative or NaN");
+        in[i] = ScanIn{nodes[i], s.n, I, s.angle_min, s.angle_increment, s.range_min};
+        total += s.n;
     }
-    if (!std::isfinite(angle_min) || !std::isfinite(angle_increment)) return fail(h, UZL_ERR_BAD_ARG, "non-finite scan angle or displacement");
-    if (!(range_min >= 0.f)) return fail(h, UZL_ERR_BAD_ARG, "range_min negative or NaN");
-    const int64_t total = (int64_t)n_scans * n_beams;
+    if (total > 0 && !d_ranges) return fail(h, UZL_ERR_BAD_ARG, "bad scan count or null scans");
     if (h->store.n_values + total >= ((int64_t)1 << 40)) return fail(h, UZL_ERR_BAD_ARG, "too many ranges");
     append(h, in, total, first_scan, [&](float* dst, hipStream_t st) {
         UZL_HIP(hipMemcpyAsync(dst, d_ranges, (size_t)total * 4, hipMemcpyDeviceToDevice, st));
     });
     return UZL_OK;
+}
+
+}  // namespace
+
+// uzl_laserline_to_grid: every scan with the same beam count, grid and range_min
+int uzl::grid_append_device(uzl_grid* h, int device, int32_t n_scans, int32_t n_beams, const float* d_ranges, float angle_min,
+                            float angle_increment, float range_min, const int32_t* nodes, int32_t* first_scan)
+{
+    UZL_GUARD_BEGIN(h)
+    const DeviceScan one{n_beams, angle_min, angle_increment, range_min, 0.f};
+    return append_device(h, device, n_scans, [&](int32_t) { return one; }, d_ranges, nodes, first_scan);
+    UZL_GUARD_END(h)
+}
+
+// uzl_scanmerge_to_grid: scans that differ in beam count, grid or range_min
+int uzl::grid_append_device_scans(uzl_grid* h, int device, int32_t n_scans, const DeviceScan* scans, const float* d_ranges,
+                                  const int32_t* nodes, int32_t* first_scan)
+{
+    UZL_GUARD_BEGIN(h)
+    if (n_scans > 0 && !scans) return fail(h, UZL_ERR_BAD_ARG, "bad scan count or null scans");
+    return append_device(h, device, n_scans, [&](int32_t i) { return scans[i]; }, d_ranges, nodes, first_scan);
     UZL_GUARD_END(h)
 }

@@ -256,20 +256,48 @@ int uzl_laser_correspondences(uzl_laser* h, const uzl_laser_pair* pair, const do
 
 }  // extern "C"
 
+// The way into the store for scans that already lie in device memory (declared in laser_types.hpp): n_scans scans, scan i as
+// scan_at(i) describes it, one after the other at d_values and complete.  Called with the handle's lock held.
+namespace {
+
+template <typename ScanAt>
+int append_device(uzl_laser* h, int device, int32_t n_scans, ScanAt&& scan_at, const float* d_values, int32_t* first_scan)
+{
+    if (device != h->cfg.device) return fail(h, UZL_ERR_BAD_ARG, "the scans are on another device than the laser handle");
+    if (n_scans < 0 || (n_scans > 0 && !d_values)) return fail(h, UZL_ERR_BAD_ARG, "bad scan count or null scans");
+    std::vector<ScanIn> in(n_scans);
+    int64_t total = 0;
+    for (int32_t i = 0; i < n_scans; i++) {
+        const DeviceScan s = scan_at(i);
+        in[i] = ScanIn{s.n, s.angle_min, s.angle_increment, s.range_min, s.range_max};
+        if (int rc = check_scan(h, in[i])) return rc;
+        total += s.n;
+    }
+    if ((int64_t)h->scans.size() + n_scans > INT32_MAX || h->store.n_values + total >= ((int64_t)1 << 40)) return fail(h, UZL_ERR_BAD_ARG, "too many scans");
+    append(h, in, total, first_scan, [&](float* dst, hipStream_t st) {
+        UZL_HIP(hipMemcpyAsync(dst, d_values, (size_t)total * 4, hipMemcpyDeviceToDevice, st));
+    });
+    return UZL_OK;
+}
+
+}  // namespace
+
+// uzl_laserline_to_laser: every scan with the same beam count, grid and limits
 int uzl::laser_append_device(uzl_laser* h, int device, int32_t n_scans, int32_t n_beams, const float* d_values, float angle_min,
                              float angle_increment, float range_min, float range_max, int32_t* first_scan)
 {
     UZL_GUARD_BEGIN(h)
-    if (device != h->cfg.device) return fail(h, UZL_ERR_BAD_ARG, "the scans are on another device than the laser handle");
-    if (n_scans < 0 || (n_scans > 0 && !d_values)) return fail(h, UZL_ERR_BAD_ARG, "bad scan count or null scans");
-    const ScanIn one{n_beams, angle_min, angle_increment, range_min, range_max};
-    if (n_scans > 0)
-        if (int rc = check_scan(h, one)) return rc;
-    const int64_t total = (int64_t)n_scans * n_beams;
-    if ((int64_t)h->scans.size() + n_scans > INT32_MAX || h->store.n_values + total >= ((int64_t)1 << 40)) return fail(h, UZL_ERR_BAD_ARG, "too many scans");
-    append(h, std::vector<ScanIn>(n_scans, one), total, first_scan, [&](float* dst, hipStream_t st) {
-        UZL_HIP(hipMemcpyAsync(dst, d_values, (size_t)total * 4, hipMemcpyDeviceToDevice, st));
-    });
-    return UZL_OK;
+    const DeviceScan one{n_beams, angle_min, angle_increment, range_min, range_max};
+    return append_device(h, device, n_scans, [&](int32_t) { return one; }, d_values, first_scan);
+    UZL_GUARD_END(h)
+}
+
+// uzl_scanmerge_to_laser: scans that differ in beam count, grid or limits
+int uzl::laser_append_device_scans(uzl_laser* h, int device, int32_t n_scans, const DeviceScan* scans, const float* d_values,
+                                   int32_t* first_scan)
+{
+    UZL_GUARD_BEGIN(h)
+    if (n_scans > 0 && !scans) return fail(h, UZL_ERR_BAD_ARG, "bad scan count or null scans");
+    return append_device(h, device, n_scans, [&](int32_t i) { return scans[i]; }, d_values, first_scan);
     UZL_GUARD_END(h)
 }

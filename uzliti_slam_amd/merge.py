@@ -52,3 +52,28 @@ def apply_merge_plan(poses, edges, displacements, plan):
     E = E[alive]
     E["from"] = old_to_new[E["from"]]; E["to"] = old_to_new[E["to"]]
     return np.delete(P, drop, axis=0), E, (D_from[alive], D_to[alive]), old_to_new
+
+
+SENSOR_TYPE_FEATURE, SENSOR_TYPE_BINARY_GIST, SENSOR_TYPE_LASERSCAN = 1, 3, 4        # graph_slam_msgs/msg/SensorData.msg:3-6
+SENSOR_MERGE, SENSOR_MOVE, SENSOR_DISCARD = "merge", "move", "discard"
+
+
+def sensor_moves(keep_types, drop_types):
+    """The sensor-data loop of mergeNodes (graph_slam_node.cpp:993-1045) over the sensor types of the two nodes, in their
+    sensor_data_ order.  -> one (action, j) per sensor of drop:
+      (SENSOR_MERGE, j)    a laser scan: merged into keep's sensor j, the first laser scan of keep's list as it stands then
+                           (capi.ScanMerge; its displacement becomes drop_displacement * displacement first)
+      (SENSOR_MOVE, j)     appended to keep as its sensor j with displacement = drop_displacement * displacement
+      (SENSOR_DISCARD, -1) keep already has features / a gist descriptor, or the type is none of the three
+    keep's list grows while the loop runs: a second laser scan of drop merges into the one just moved."""
+    have = [int(t) for t in keep_types]
+    out = []
+    for t in (int(t) for t in drop_types):
+        if t not in (SENSOR_TYPE_LASERSCAN, SENSOR_TYPE_FEATURE, SENSOR_TYPE_BINARY_GIST):
+            out.append((SENSOR_DISCARD, -1))
+        elif t in have:
+            out.append((SENSOR_MERGE, have.index(t)) if t == SENSOR_TYPE_LASERSCAN else (SENSOR_DISCARD, -1))
+        else:
+            have.append(t)
+            out.append((SENSOR_MOVE, len(have) - 1))
+    return out
