@@ -2653,26 +2653,35 @@ __global__ __launch_bounds__(kCgBlk) void ml_init_pcg_kernel(const PcgArgs A)
     }
     ml_init_kernel_body<1>(pcg_dev(A), pcg_hot(A), A.pbuf[0], A.pbuf[1], A.rg[0]);
 }
-// The compiler fetches an argument where its first use is, block by block - each batch a scalar round trip with a wait of its own in
-// front of the loads behind it.  One asm statement at the kernel's entry that takes every argument of the working path as a register
-// operand makes the fetch ONE batch with one wait.  It returns a zero the compiler cannot see through, which is added to the pointers
-// of the first loads: they cannot be sent before it, and stay what they were - global, uniform, read with scalar loads where they
-// were.  (Not `volatile`, no memory clobber: behind such a statement the row header's slot range and the scalars are no longer fetched
-// with scalar loads.  Not the pointers themselves through the statement: they come back generic, and the loads become flat ones.)
-// (both buffers' addresses and a select: indexing the argument block with `parity` would be a second, dependent scalar load)
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void ml_spmv_pcg_kernel(const PcgArgs A, int parity)
+// ml_spmv: what its FIRST loads and their predicates read - the r.z partials, the stop test's maxima, the done flag with the LM
+// state's ix word, the scalars, the row header - travels in front of the struct as plain pointer and integer parameters.  The build
+// preloads those into SGPRs (Makefile: -amdgpu-kernarg-preload-count), so the first loads are sent at the wave's start, and the
+// compiler's own fetch of the struct's fields runs BESIDE their round trip: its scalar loads share the one wait the done flag and
+// the row header's slot range need anyway, in front of the second batch (diagonal block, z, p, blocks).  No asm statement here: the
+// one ml_cg_comp has below would stand in the entry block with its wait, in front of every load of the body
+// (tests/diag/preload_waits.py counts the waits; tests/test_pcg_preload_isa.py holds them).
+//   ix_at: index of the ix word relative to `flags` (device-resident loop: LmDev::ix behind LmDev::flags; host-driven loop: 0, the
+//   flags word itself and no check) - an integer where a sixth pointer would not fit into the 14 registers a kernel can have preloaded
+//   n_part: the r.z partials AND the grid (AGG = 1: g_ml_spmv = g_ml_rows) - gridDim.x itself lies behind the struct in the segment
+//   (both buffers' addresses and a select: indexing the argument block with `parity` would be a second, dependent scalar load)
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4)))
+void ml_spmv_pcg_kernel(int32_t* flags, double* scal, double* part_b, double* part_c, const int32_t* rowhdr,
+                        int nb, int n_part, int ix_at, int parity, const PcgArgs A)
 {
+    const int grid = (int)gridDim.x;
+    __builtin_assume(grid == n_part);                        // (pcg_spmv: the launch's grid)
     double* const p0 = A.pbuf[0]; double* const p1 = A.pbuf[1];
-    int zero;
-    asm("s_mov_b32 %0, 0 ; ml_spmv: arguments fetched" : "=s"(zero)
-        : "s"(A.flags), "s"(A.lm), "s"(A.scal), "s"(A.part_b), "s"(A.rowhdr), "s"(A.part_a), "s"(A.part_c), "s"(A.hdiag),
-          "s"(A.z), "s"(A.blk), "s"(p0), "s"(p1), "s"(A.ap), "s"(A.geo0), "s"(A.Sg), "s"(A.col), "s"(__double_as_longlong(A.tol2)),
-          "s"(A.nb), "s"(A.n1), "s"(A.diag_owner), "s"(A.g_rows), "s"(A.ix), "s"(parity), "s"((int)gridDim.x));
     PgoDev D = pcg_dev(A);
-    D.flags += zero; D.scal += zero; D.part_b += zero; D.part_c += zero; D.rowhdr += zero;
-    const int32_t* ix_word = (A.lm ? &A.lm->ix : A.flags) + zero;
-    ml_spmv_kernel_body<1, 1, 8>(D, pcg_hot(A), parity ? p1 : p0, parity ? p0 : p1, A.g_rows, A.tol2, ix_word, A.ix, A.lm != nullptr);
+    D.flags = flags; D.scal = scal; D.part_b = part_b; D.part_c = part_c; D.rowhdr = rowhdr; D.nb = nb;
+    ml_spmv_kernel_body<1, 1, 8>(D, pcg_hot(A), parity ? p1 : p0, parity ? p0 : p1, n_part, A.tol2, flags + ix_at, A.ix, A.lm != nullptr);
 }
+// ml_cg_comp sends every operand load at its entry.  The compiler fetches an argument where its first use is, block by block - each
+// batch a scalar round trip with a wait of its own in front of the loads behind it.  One asm statement at the kernel's entry that takes
+// every argument of the working path as a register operand makes the fetch ONE batch with one wait.  It returns a zero the compiler
+// cannot see through, which is added to the pointers of the first loads: they cannot be sent before it, and stay what they were -
+// global, uniform, read with scalar loads where they were.  (Not `volatile`, no memory clobber: behind such a statement the scalars are
+// no longer fetched with scalar loads.  Not the pointers themselves through the statement: they come back generic, and the loads
+// become flat ones.)
 // (kInit, the first application, at compile time: the working launch is then one straight line from its entry to its last operand load)
 template <int kCompU, bool kInit>
 __global__ __launch_bounds__(kCgBlk) void ml_cg_comp_pcg_kernel(const PcgArgs A, int parity)
@@ -2807,7 +2816,11 @@ static PcgArgs make_pcg_args(const LmSlot& S, const LmDev* lm, int ix, double to
 static void pcg_init(const PcgArgs& A, hipStream_t s) { hipLaunchKernelGGL(ml_init_pcg_kernel, dim3(A.g_rows), dim3(kCgBlk), 0, s, A); }
 static void pcg_spmv(const PcgArgs& A, int parity, hipStream_t s, hipEvent_t ev_a = nullptr, hipEvent_t ev_b = nullptr)
 {
-    launch(ml_spmv_pcg_kernel, dim3(A.g_spmv), dim3(512), 0, s, ev_a, ev_b, A, parity);
+    // (the grid is the partial count: pcg_args_shape admits AGG = 1 only, where g_ml_spmv = g_ml_rows - the kernel is told one number)
+    // (ix_at: the device-resident loop's flags are LmDev::flags, a few words in front of LmDev::ix)
+    const int ix_at = A.lm ? (int)((reinterpret_cast<intptr_t>(&A.lm->ix) - reinterpret_cast<intptr_t>(A.flags)) / (intptr_t)sizeof(int32_t)) : 0;
+    launch(ml_spmv_pcg_kernel, dim3(A.g_rows), dim3(512), 0, s, ev_a, ev_b, A.flags, A.scal, A.part_b, A.part_c, A.rowhdr,
+           A.nb, A.g_rows, ix_at, parity, A);
 }
 static void pcg_cg(const PcgArgs& A, int comp_u, int parity, int init, hipStream_t s, hipEvent_t ev_a = nullptr, hipEvent_t ev_b = nullptr)
 {

@@ -134,10 +134,11 @@ struct MlDev {
     double* Sg;                // [n_g][6] restriction of A p at the gather level (written by ml_spmv)
 };
 
-// Hot subset of MlDev passed BY VALUE to the per-iteration kernels.  Kernel arguments are NOT preloaded into registers: the ISA fetches
-// them from the kernel-argument segment with s_load, in batches, each behind an s_waitcnt lgkmcnt(0) - one scalar round trip per batch,
-// and a batch per basic block that first uses a field.  Going through the MlDev pointer costs one more dependent round trip per first
-// use on top.  (The small-graph PCG pair takes PcgArgs below: one batch.)
+// Hot subset of MlDev passed BY VALUE to the per-iteration kernels.  A struct by value is NOT preloaded into registers (the build
+// preloads leading pointer and integer parameters only, csrc/Makefile): the ISA fetches its fields from the kernel-argument segment
+// with s_load, in batches, each behind an s_waitcnt lgkmcnt(0) - one scalar round trip per batch, and a batch per basic block that
+// first uses a field.  Going through the MlDev pointer costs one more dependent round trip per first use on top.  (The small-graph
+// PCG pair takes PcgArgs below: one batch - ml_spmv_pcg_kernel with what its first loads read as preloaded parameters in front.)
 struct MlHot {
     int32_t levels;
     int32_t n[kMlMaxLevels + 1];
