@@ -1230,6 +1230,90 @@ def pgo_structure_plan(stage, **kw):
     raise ValueError(stage)
 
 
+# the rows uzl_debug_lm_pass_plan reads and writes (csrc/uzl_pgo_debug.hip): a view of a snapshot, a slot's track, a pass's plan
+LM_VIEW_INTS = ("phase", "need", "it", "iterations", "sync_rebuild", "pending", "ix", "pcg_last", "st_lm_trials", "max_it", "pcg_its")
+LM_VIEW_DOUBLES = ("last_rel", "refresh_rel", "rate_ref", "rate_last", "rate_drop", "lambda", "lambda_setup0", "lambda_setup1", "tol2")
+LM_TRACK = ("job", "active", "no_history", "solve_passes", "prev_last", "cur_last", "seen_trials")
+LM_PLAN = ("flags", "want", "base", "ix", "ns_steps", "setup_captured", "any_start")
+_LM_PASS_STAGES = dict(plan=0, launches=1, replay=2, host_batches=3, handover=4)
+
+
+def lm_pass_plan(stage, **kw):
+    """uzl_debug_lm_pass_plan (diagnostic library, host only): the host's predictions about the passes of the device-resident LM loop
+    (csrc/pgo_lm_pass.hpp).  A view is a dict over LM_VIEW_INTS + LM_VIEW_DOUBLES (missing keys: 0), a track one over LM_TRACK plus
+    `hist`, the job's per-trial PCG counts of the last optimize; a plan comes back as a dict over LM_PLAN plus `tol2`.  Stages:
+      plan         views, tracks (one per slot), first_solve_its, shape_ns_steps, wrong_ix              -> plan, tracks (afterwards)
+      launches     base, want, eager                                                              -> lead, long_first, n_long, rem_first, rem
+      replay       n_slots, jobs = [dict(no_history, hist)], events = ("plan",) | ("look", slot, view) | ("load", slot, job or -1, view),
+                   first_solve_its, shape_ns_steps, wrong_ix                          -> plans, tracks, first_solve_its, trial_its (per job)
+      host_batches prev, max_it, end_round                                                        -> the host-driven solve's batch sizes
+      handover     old = [dict(gen, prev, cur)] (the last drive's jobs), new_gens                 -> prev (per new job), cur_sizes, hist_gen"""
+    L = diag_lib()
+    i32 = lambda a: np.ascontiguousarray(a if a is not None else [], np.int32).reshape(-1)
+
+    def run(iv, what, dtype=np.int32, vi=None, vd=None, tr=None, hist=None, ev=None):
+        iv = i32(iv)
+        arrs = [None if a is None or len(a) == 0 else a for a in (vi, vd, tr, hist, ev)]
+
+        def call(out, nbytes):
+            rc = L.uzl_debug_lm_pass_plan(C.c_int32(_LM_PASS_STAGES[stage]), _p(iv, c_i32p), _p(arrs[0], c_i32p), _p(arrs[1], c_f64p), _p(arrs[2], c_i32p),
+                                          _p(arrs[3], c_i32p), _p(arrs[4], c_i32p), C.c_int32(what), out.ctypes.data_as(C.c_void_p) if out is not None else None,
+                                          C.byref(nbytes))
+            if rc != UZL_OK:
+                raise UzlError(rc, "uzl_debug_lm_pass_plan(%s, %d)" % (stage, what))
+
+        nbytes = C.c_int64(0)
+        call(None, nbytes)
+        out = np.zeros(nbytes.value // np.dtype(dtype).itemsize, dtype)
+        if nbytes.value:
+            call(out, nbytes)
+        return out
+
+    def views(vs):
+        return (i32([[int(v.get(k, 0)) for k in LM_VIEW_INTS] for v in vs]),
+                np.ascontiguousarray([[float(v.get(k, 0.)) for k in LM_VIEW_DOUBLES] for v in vs], np.float64).reshape(-1))
+
+    def tracks_out(rows):
+        return [dict(zip(LM_TRACK + ("n_hist",), (int(x) for x in r))) for r in rows.reshape(-1, 8)]
+
+    def plans_out(rows, tol2):
+        return [dict(zip(LM_PLAN, (int(x) for x in r)), tol2=float(t)) for r, t in zip(rows.reshape(-1, 7), tol2)]
+
+    def rows_out(flat, n):                       # n rows of {length, values}
+        out, k = [], 0
+        for _ in range(n):
+            out.append([int(x) for x in flat[k + 1:k + 1 + flat[k]]]); k += 1 + int(flat[k])
+        return out
+
+    if stage == "plan":
+        vi, vd = views(kw["views"])
+        tr = i32([[int(t.get(k, 0)) for k in LM_TRACK] + [len(t.get("hist", ()))] for t in kw["tracks"]])
+        hist = i32([c for t in kw["tracks"] for c in t.get("hist", ())])
+        a = dict(iv=[len(kw["views"]), kw.get("first_solve_its", 0), kw.get("shape_ns_steps", 0), 1 if kw.get("wrong_ix") else 0], vi=vi, vd=vd, tr=tr, hist=hist)
+        return dict(plan=plans_out(run(what=0, **a), run(what=1, dtype=np.float64, **a))[0], tracks=tracks_out(run(what=2, **a)))
+    if stage == "launches":
+        return dict(zip(("lead", "long_first", "n_long", "rem_first", "rem"), (int(x) for x in run([kw["base"], kw["want"], 1 if kw["eager"] else 0], 0))))
+    if stage == "replay":
+        jobs, events = kw["jobs"], kw["events"]
+        kinds = dict(plan=0, look=1, load=2)
+        ev = i32([[kinds[e[0]], e[1] if len(e) > 1 else 0, e[2] if e[0] == "load" else 0] for e in events])
+        vi, vd = views([e[-1] if len(e) > 1 else {} for e in events])
+        a = dict(iv=[kw["n_slots"], len(events), len(jobs), kw.get("first_solve_its", 0), kw.get("shape_ns_steps", 0), 1 if kw.get("wrong_ix") else 0], vi=vi, vd=vd,
+                 tr=i32([[1 if j.get("no_history") else 0, len(j.get("hist", ()))] for j in jobs]), hist=i32([c for j in jobs for c in j.get("hist", ())]), ev=ev)
+        h = run(what=3, **a)
+        return dict(plans=plans_out(run(what=0, **a), run(what=1, dtype=np.float64, **a)), tracks=tracks_out(run(what=2, **a)), first_solve_its=int(h[0]),
+                    trial_its=rows_out(h[1:], len(jobs)))
+    if stage == "host_batches":
+        return [int(x) for x in run([kw["prev"], kw["max_it"], kw["end_round"]], 0)]
+    if stage == "handover":
+        old, new = kw["old"], list(kw["new_gens"])
+        a = dict(iv=[len(old), len(new)], vi=i32([j["gen"] for j in old] + new), tr=i32([[len(j["prev"]), len(j["cur"])] for j in old]),
+                 hist=i32([c for j in old for c in list(j["prev"]) + list(j["cur"])]))
+        r = run(what=1, **a)
+        return dict(prev=rows_out(run(what=0, **a), len(new)), cur_sizes=[int(x) for x in r[:len(new)]], hist_gen=[int(x) for x in r[len(new):]])
+    raise ValueError(stage)
+
+
 # --------------------------------------------------------------------------------------- distance loop-closure candidates
 class Radius(_Handle):
     """uzl_radius_* (SlamGraph::getNodesWithinRadius + the caller's filters, graph_slam_node.cpp:272-289)."""

@@ -8,6 +8,7 @@
 #include "pgo_ml_plan.hpp"
 #include "pgo_structure.hpp"
 #include "pgo_lm.hpp"
+#include "pgo_lm_pass.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -232,7 +233,6 @@ void ensure_structure(uzl_pgo* h);                    // gauge + build_structure
 void destroy_pcg_graph(uzl_pgo* h);
 bool ml_async_level(const uzl_pgo* h);
 double ml_rate_drop(const uzl_pgo* h);
-int ml_ns_steps_at(int structure_steps, int lm_iteration);
 void prepare_optimize(uzl_pgo* h);                    // optimizeImpl's front part: gauge + structure (cached), t_start
 void own_streams(uzl_pgo* h, bool drain_borrowed);               // a batch's handle takes streams of its own (uzl_pgo.hip)
 int do_optimize_host(uzl_pgo* h, int32_t iterations, uzl_pgo_stats* st);      // the host-driven loop (sharded / block-Jacobi / profiled solves, anomaly fallback)
@@ -260,7 +260,45 @@ extern const int kUpperNs;                            // Newton-Schulz steps of 
 // by the chi2 rule only while the problem still changes wholesale (kRefreshRelSync), the PCG-rate rule (kRateDrop, pgo_lm.hpp) from then on
 constexpr double kRefreshRel = 1e-3;
 constexpr double kRefreshRelSync = 3e-2;
-constexpr double kLambdaRetake = 32.;                 // lambda grown by this factor since the inverses were taken: take them again
-constexpr int kGraphPairs = 8;                        // one long PCG replay = 2 x kGraphPairs iterations
-constexpr int kShortPairs = 2;                        // ... a short one 2 x kShortPairs
+// (kLambdaRetake, kGraphPairs, kShortPairs and ml_ns_steps_at: pgo_lm_pass.hpp, with the host's other predictions about a solve)
+
+// The head of uzl_pgo_stats: what the structure of the solved graph says, the same for both loops
+inline void stats_head(const uzl_pgo* h, uzl_pgo_stats& S)
+{
+    S.structure_reused = h->last_structure_reused ? 1 : 0;
+    S.n_vertices = h->n; S.n_edges = h->e; S.n_gauge_fixed = h->n_gauge;
+    S.n_eliminated = h->red.on ? h->red.n_int : 0; S.reduced_strong = (h->red.on && h->red.strong) ? 1 : 0;
+}
+
+// Diagnostic build, UZL_PHASES=1: GPU time between the marks a loop sets on the solver's stream (graph replays as in production), summed
+// per mark over the solve and printed after it; UZL_PHASES_EACH=1: every stretch as well.  N marks per round (LM iteration or pass),
+// named by the loop.
+template <int N>
+struct PhaseMarks {
+    std::vector<hipEvent_t> ev;
+    std::vector<int> tag;
+    static bool on() { static const bool v = diag_flag("UZL_PHASES"); return v; }
+    void mark(int t, hipStream_t s)
+    {
+        if (!on()) return;
+        hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return;
+        (void)hipEventRecord(e, s); ev.push_back(e); tag.push_back(t);
+    }
+    // after the stream has been synchronised: "<what> over <rounds> <unit>" and the sums
+    void report(const char* what, int rounds, const char* unit, const char* const (&names)[N])
+    {
+        if (!on() || ev.size() <= 1) return;
+        double acc[N] = {};
+        static const bool each = diag_flag("UZL_PHASES_EACH");
+        for (size_t i = 0; i + 1 < ev.size(); i++) {
+            float ms = 0.f; (void)hipEventElapsedTime(&ms, ev[i], ev[i + 1]); acc[tag[i] % N] += ms;
+            if (each) fprintf(stderr, "%s%d:%.0f", tag[i] == 0 ? "\n[uzl_pgo]   " : " ", tag[i], 1e3 * ms);
+        }
+        if (each) fprintf(stderr, "\n");
+        fprintf(stderr, "[uzl_pgo] %s over %d %s (GPU event time, ms):", what, rounds, unit);
+        for (int k = 0; k < N; k++) fprintf(stderr, "  %s %.3f", names[k], acc[k]);
+        fprintf(stderr, "\n");
+    }
+    ~PhaseMarks() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
+};
 }  // namespace uzl

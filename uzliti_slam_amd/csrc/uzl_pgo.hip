@@ -412,26 +412,18 @@ int uzl::pcg_solve(uzl_pgo* h, int it, bool* converged)
     }
     if (!timed) ensure_pcg_graph(h);
     int launched = 0;
-    // first batch sized from the previous solve (in steps of 2 x kShortPairs iterations), then two short ones, then long ones; the
-    // kernels no-op once `done` is set
-    constexpr int kFirstPct = 95;                                           // the first batch: 95 % of the previous solve's count
-    constexpr int kStep = 2 * kShortPairs;
-    const int kLong = 2 * kGraphPairs;
-    auto round_up = [](int v) { return ((v + kStep - 1) / kStep) * kStep; };
-    // (+ 1: a solve that ends by the stop test after k iterations is declared done by the ml_spmv of iteration k + 1)
-    int want = h->prev_pcg_iters > 0 ? std::max(kStep, round_up((h->prev_pcg_iters * kFirstPct) / 100 + 1)) : kLong;
+    // batches sized by lm_host_batch (pgo_lm_pass.hpp), a look after each; the kernels no-op once `done` is set
     for (int round = 0;; round++) {
-        want = round_up(std::max(1, std::min(want, max_it - launched)));
+        const int want = lm_host_batch(round, h->prev_pcg_iters, max_it, launched);
         if (timed) enqueue_pcg_pairs(h, want / 2, h->timer.on);
         else {
-            for (int i = 0; i < want / kLong; i++) UZL_HIP(hipGraphLaunch(h->mlb[h->ml_ix].graph_exec, s));
-            for (int i = 0; i < (want % kLong + kStep - 1) / kStep; i++) UZL_HIP(hipGraphLaunch(h->mlb[h->ml_ix].graph_exec_s, s));
+            for (int i = 0; i < want / kPcgLong; i++) UZL_HIP(hipGraphLaunch(h->mlb[h->ml_ix].graph_exec, s));
+            for (int i = 0; i < (want % kPcgLong + kPcgStep - 1) / kPcgStep; i++) UZL_HIP(hipGraphLaunch(h->mlb[h->ml_ix].graph_exec_s, s));
         }
         launched += want;
         k_residual_guard(D, s);                                   // a no-op until `done` is set
         fetch_scal(h);
         if (h->h_scal.p->flags[0] || launched >= max_it) break;
-        want = round < 2 ? kStep : kLong;
     }
     UZL_HIP(hipGetLastError());
     *converged = h->h_scal.p->flags[0] != 0 && h->h_scal.p->flags[2] == 0;
@@ -452,15 +444,7 @@ const int kUpperNs = 4;                   // Newton-Schulz steps of the dense le
 // the rate rule where the rebuild is synchronous: with the dense operator of that class a rebuild pays as soon as the rate has fallen to
 // 0.75 of the fresh one (0.6 elsewhere; -3 ... -8 % on eight of nine such shapes, the 30k / 150k graph - no dense operator - +14 %)
 constexpr double kRateDropSyncDense = 0.75;
-// Newton-Schulz steps of a synchronous set-up at LM iteration `it` for a structure that asks for `structure_steps` (4 on large loopy
-// graphs): 2 in the first kNsEarlyIts iterations (against the full count from the start: -3.4 % over fourteen large shapes at the same
-// PCG iteration count; 4 iterations instead of 2 gain on the largest and lose at 10k, 8 lose everywhere; NO step at all in those two - the
-// cycle's operator as it comes - another -2.5 %, not taken: that operator is what the residual guard exists for)
-int ml_ns_steps_at(int structure_steps, int it)
-{
-    constexpr int kNsEarlyIts = 2, kNsEarlySteps = 2;
-    return (structure_steps > 2 && it < kNsEarlyIts) ? kNsEarlySteps : structure_steps;
-}
+// (ml_ns_steps_at, the Newton-Schulz steps of a synchronous set-up at an LM iteration: pgo_lm_pass.hpp)
 double ml_rate_drop(const uzl_pgo* h) { return (!ml_async_level(h) && h->mlp.cl > 0) ? kRateDropSyncDense : kRateDrop; }
 
 // Asynchronous rebuild (second stream, second copy of the hierarchy) pays on the composite level-1 path, and for the reduced system of a
@@ -676,14 +660,12 @@ int do_optimize_host(uzl_pgo* h, int32_t iterations, uzl_pgo_stats* st)
     const auto t0 = h->t_start;
     uzl_pgo_stats S;
     memset(&S, 0, sizeof(S));
-    S.structure_reused = h->last_structure_reused ? 1 : 0;
-    S.n_vertices = h->n; S.n_edges = h->e; S.n_gauge_fixed = h->n_gauge;
+    stats_head(h, S);
     hipStream_t s = h->stream;
     PgoDev& D = h->D;
     PgoDev& Dp = h->Dp;                       // the system the PCG solves: D, or the Schur complement over the separator vertices
     const bool red = h->red.on;
     const SchurDev& SD = h->red.S;
-    S.n_eliminated = red ? h->red.n_int : 0; S.reduced_strong = (red && h->red.strong) ? 1 : 0;
     // (H + lambda I) with the chain interiors eliminated: once per lambda, i.e. per LM trial (pgo_schur.hpp)
     auto schur_reduce = [&]() { kl_schur_reduce(host_slot(h), h->ml_shape, s, &h->timer); };
     const double delta = h->cfg.huber_delta;
@@ -721,16 +703,8 @@ int do_optimize_host(uzl_pgo* h, int32_t iterations, uzl_pgo_stats* st)
         uzl_pgo* h;
         ~DrainRebuild() { if (h->ml_pending) { (void)hipStreamSynchronize(h->stream2); h->ml_pending = false; } }
     } drain{h};
-    // diagnostic build, UZL_PHASES=1: GPU time between phase marks of every LM iteration (events on the solver's stream, graph replays as
-    // in production), printed after the solve
-    static const bool phases_on = diag_flag("UZL_PHASES");
-    std::vector<hipEvent_t> ph_ev;
-    std::vector<int> ph_tag;
-    auto mark = [&](int tag) {
-        if (!phases_on) return;
-        hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return;
-        (void)hipEventRecord(e, s); ph_ev.push_back(e); ph_tag.push_back(tag);
-    };
+    PhaseMarks<4> phases;                      // diagnostic build, UZL_PHASES=1: GPU time between the marks of every LM iteration
+    auto mark = [&](int tag) { phases.mark(tag, s); };
     for (int it = 0; it < iterations; it++) {
         int gl, ga;
         adopted = false;
@@ -883,20 +857,8 @@ int do_optimize_host(uzl_pgo* h, int32_t iterations, uzl_pgo_stats* st)
     S.lambda_final = lambda;
     if (h->ml_pending) { UZL_HIP(hipStreamSynchronize(h->stream2)); h->ml_pending = false; }   // a rebuild nobody will use: let it drain
     UZL_HIP(hipStreamSynchronize(s));
-    if (phases_on && ph_ev.size() > 1) {
-        double acc[4] = {0., 0., 0., 0.};
-        static const char* nm[4] = {"linearise+set-up (0->1)", "solve incl. init (1->2)", "evaluate+round trip (2->3)", "host decision / next (3->0)"};
-        static const bool phases_each = diag_flag("UZL_PHASES_EACH");
-        for (size_t i = 0; i + 1 < ph_ev.size(); i++) {
-            float ms = 0.f; (void)hipEventElapsedTime(&ms, ph_ev[i], ph_ev[i + 1]); acc[ph_tag[i] & 3] += ms;
-            if (phases_each) fprintf(stderr, "%s%d:%.0f", ph_tag[i] == 0 ? "\n[uzl_pgo]   " : " ", ph_tag[i], 1e3 * ms);
-        }
-        if (phases_each) fprintf(stderr, "\n");
-        fprintf(stderr, "[uzl_pgo] phases over %d LM iterations (GPU event time, ms):", S.iterations_done);
-        for (int k = 0; k < 4; k++) fprintf(stderr, "  %s %.3f", nm[k], acc[k]);
-        fprintf(stderr, "\n");
-        for (hipEvent_t e : ph_ev) (void)hipEventDestroy(e);
-    }
+    static const char* const kPhaseNames[4] = {"linearise+set-up (0->1)", "solve incl. init (1->2)", "evaluate+round trip (2->3)", "host decision / next (3->0)"};
+    phases.report("phases", S.iterations_done, "LM iterations", kPhaseNames);
     S.solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     S.structure_ms = h->structure_ms; S.exchange_ms = h->exchange_ms; S.exchange_calls = h->exchange_calls;
     if (st) *st = S;

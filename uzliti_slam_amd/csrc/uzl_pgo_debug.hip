@@ -442,4 +442,153 @@ extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_trial(uzl_pgo* h, const double* dx,
     return UZL_OK;
     UZL_GUARD_END(h)
 }
+
+// ---- the host's pass plan of the device-resident loop without a handle or a device (pgo_lm_pass.hpp; tests/test_lm_pass_plan.py).  One
+//      stage per call, one output array per call, stateless (the stage is recomputed per call); *nbytes: in = the room at `out` (ignored
+//      when out is null), out = the array's size in bytes.  Arrays a stage does not read may be null.
+//   A VIEW (LmPlanView) is one row of vi and one of vd:
+//      vi [11] = {phase, need, it, iterations, sync_rebuild, pending, ix, pcg_last, st_lm_trials, max_it, flags[1]}
+//      vd [9]  = {last_rel, refresh_rel, rate_ref, rate_last, rate_drop, lambda, lambda_setup[0], lambda_setup[1], tol2}
+//   A TRACK (LmSlotTrack) is a row of 8: {job, active, no_history, solve_passes, prev_last, cur_last, seen_trials, n_hist}
+//   A PLAN (LmPassPlan) is a row of 7: {flags, want, base, ix, ns_steps, setup_captured, any_start}, its tol2 apart
+//   stage 0 lm_plan_pass    iv {nS, first_solve_its, shape_ns_steps, wrong_ix}; vi, vd [nS] views; tr [nS] tracks; hist = the slots' history
+//                           rows one after the other (n_hist each).    what 0 plan (i32), 1 tol2 (f64), 2 the tracks afterwards (i32)
+//   stage 1 lm_pcg_launches iv {base, want, eager}.                    what 0 {lead, long_first, n_long, rem_first, rem} (i32)
+//   stage 2 replay          iv {nS, n_ev, Q, first_solve_its, shape_ns_steps, wrong_ix}; tr [Q][2] = {no_history, n_hist} per job; hist = the
+//                           jobs' history rows; ev [n_ev][3] = {kind, slot, job}; vi, vd [n_ev]: the view of event k in row k.
+//                           kind 0: plan a pass; 1: slot's look at this view (lm_track_look); 2: load job (-1: idle) into slot, its state this view
+//                           what 0 the plans in order (i32), 1 their tol2 (f64), 2 the tracks at the end (i32),
+//                           3 {first_solve_its, then per job: trials recorded, their counts} (i32)
+//   stage 3 lm_host_batch   iv {prev_pcg_iters, max_it, end_round}: batches until the solve ends in the look of round end_round or max_it is
+//                           reached.                                    what 0 the batch sizes (i32)
+//   stage 4 lm_history_begin  iv {Q_old, Q_new}; vi = structure generations: Q_old of the last drive, then Q_new of this one; tr [Q_old][2] =
+//                           {n_prev, n_cur}; hist = per old job its trial_its_prev row, then its trial_its_cur row.
+//                           what 0 per new job {n, counts} of trial_its_prev afterwards, 1 {sizes of trial_its_cur [Q_new], hist_gen [Q_new]} (i32)
+extern "C" UZL_DIAG_EXPORT int uzl_debug_lm_pass_plan(int32_t stage, const int32_t* iv, const int32_t* vi, const double* vd, const int32_t* tr, const int32_t* hist,
+                                                     const int32_t* ev, int32_t what, void* out, int64_t* nbytes)
+{
+    if (!iv || !nbytes || what < 0) return UZL_ERR_BAD_ARG;
+    try {
+        std::vector<int32_t> oi; std::vector<double> od;
+        bool f64 = false;
+        auto view = [&](int k) {
+            const int32_t* a = vi + (size_t)k * kPlanViewInts; const double* b = vd + (size_t)k * kPlanViewDoubles;
+            return LmPlanView{a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[8], a[9], a[10], b[0], b[1], b[2], b[3], b[4], b[5], {b[6], b[7]}, b[8]};
+        };
+        auto bad_view = [](const LmPlanView& v) { return v.ix < 0 || v.ix > 1 || v.phase < kLmLin || v.phase > kLmAnomaly; };      // (lambda_setup[ix])
+        auto put_tracks = [&](const std::vector<LmSlotTrack>& T) {
+            for (const LmSlotTrack& t : T) oi.insert(oi.end(), {t.job, t.active ? 1 : 0, t.no_history ? 1 : 0, t.solve_passes, t.prev_last, t.cur_last, t.seen_trials, t.n_hist});
+        };
+        auto put_plan = [&](const LmPassPlan& P) { oi.insert(oi.end(), {P.flags, P.want, P.base, P.ix, P.ns_steps, P.setup_captured ? 1 : 0, P.any_start ? 1 : 0}); };
+        switch (stage) {
+        case 0: {
+            const int nS = iv[0];
+            if (nS < 1 || !vi || !vd || !tr || what > 2) return UZL_ERR_BAD_ARG;
+            std::vector<LmPlanView> V((size_t)nS);
+            std::vector<LmSlotTrack> T((size_t)nS);
+            const int32_t* row = hist;
+            for (int sl = 0; sl < nS; sl++) {
+                const int32_t* t = tr + 8 * (size_t)sl;
+                V[sl] = view(sl);
+                if (bad_view(V[sl]) || t[7] < 0 || (t[7] > 0 && !hist)) return UZL_ERR_BAD_ARG;
+                LmSlotTrack& K = T[sl];
+                K.job = t[0]; K.active = t[1] != 0; K.no_history = t[2] != 0; K.solve_passes = t[3]; K.prev_last = t[4]; K.cur_last = t[5]; K.seen_trials = t[6];
+                K.hist = row; K.n_hist = t[7]; row += t[7];
+            }
+            const LmPassPlan P = lm_plan_pass(V.data(), T.data(), nS, iv[1], iv[2], iv[3] != 0);
+            if (what == 0) put_plan(P); else if (what == 1) { od = {P.tol2}; f64 = true; } else put_tracks(T);
+            break;
+        }
+        case 1: {
+            if (iv[1] < 1 || iv[0] < 0 || what > 0) return UZL_ERR_BAD_ARG;
+            const LmPcgLaunches L = lm_pcg_launches(iv[0], iv[1], iv[2] != 0);
+            oi = {L.lead, L.long_first, L.n_long, L.rem_first, L.rem};
+            break;
+        }
+        case 2: {
+            const int nS = iv[0], n_ev = iv[1], Q = iv[2];
+            if (nS < 1 || n_ev < 0 || Q < 0 || (n_ev > 0 && (!ev || !vi || !vd)) || (Q > 0 && !tr) || what > 3) return UZL_ERR_BAD_ARG;
+            LmPassHistory H;
+            H.first_solve_its = iv[3];
+            H.trial_its_prev.resize((size_t)Q); H.trial_its_cur.resize((size_t)Q);
+            const int32_t* row = hist;
+            for (int j = 0; j < Q; j++) {
+                const int n = tr[2 * j + 1];
+                if (n < 0 || (n > 0 && !hist)) return UZL_ERR_BAD_ARG;
+                H.trial_its_prev[(size_t)j].assign(row, row + n); row += n;
+            }
+            std::vector<LmPlanView> V((size_t)nS, LmPlanView{});
+            std::vector<LmSlotTrack> T((size_t)nS);
+            for (int sl = 0; sl < nS; sl++) V[sl].phase = kLmDone;          // (an unloaded slot: idle)
+            for (int k = 0; k < n_ev; k++) {
+                const int kind = ev[3 * k], sl = ev[3 * k + 1], job = ev[3 * k + 2];
+                if (kind == 0) {
+                    const LmPassPlan P = lm_plan_pass(V.data(), T.data(), nS, H.first_solve_its, iv[4], iv[5] != 0);
+                    if (what == 0) put_plan(P); else if (what == 1) od.push_back(P.tol2);
+                    continue;
+                }
+                if (sl < 0 || sl >= nS || bad_view(view(k))) return UZL_ERR_BAD_ARG;
+                V[sl] = view(k);
+                if (kind == 1) {
+                    if (T[sl].job < 0) return UZL_ERR_BAD_ARG;
+                    (void)lm_track_look(V[sl], T[sl], H);
+                } else if (kind == 2) {
+                    if (job < -1 || job >= Q) return UZL_ERR_BAD_ARG;
+                    lm_track_load(T[sl], job, job >= 0 && tr[2 * job] != 0, H);
+                } else return UZL_ERR_BAD_ARG;
+            }
+            if (what == 1) f64 = true;
+            if (what == 2) put_tracks(T);
+            if (what == 3) {
+                oi.push_back(H.first_solve_its);
+                for (const std::vector<int>& c : H.trial_its_cur) { oi.push_back((int32_t)c.size()); oi.insert(oi.end(), c.begin(), c.end()); }
+            }
+            break;
+        }
+        case 3: {
+            const int prev = iv[0], max_it = iv[1], end_round = iv[2];
+            if (max_it < 1 || what > 0) return UZL_ERR_BAD_ARG;
+            for (int round = 0, launched = 0;; round++) {                   // (pcg_solve's loop, the look's answer scripted)
+                oi.push_back(lm_host_batch(round, prev, max_it, launched));
+                launched += oi.back();
+                if (round >= end_round || launched >= max_it) break;
+            }
+            break;
+        }
+        case 4: {
+            const int Qo = iv[0], Qn = iv[1];
+            if (Qo < 0 || Qn < 0 || (Qo + Qn > 0 && !vi) || (Qo > 0 && !tr) || what > 1) return UZL_ERR_BAD_ARG;
+            LmPassHistory H;
+            const int32_t* row = hist;
+            for (int j = 0; j < Qo; j++) {
+                const int np = tr[2 * j], nc = tr[2 * j + 1];
+                if (np < 0 || nc < 0 || (np + nc > 0 && !hist)) return UZL_ERR_BAD_ARG;
+                H.trial_its_prev.emplace_back(row, row + np); row += np;
+                H.trial_its_cur.emplace_back(row, row + nc); row += nc;
+                H.hist_gen.push_back((uint64_t)vi[j]);
+            }
+            std::vector<uint64_t> gen;
+            for (int j = 0; j < Qn; j++) gen.push_back((uint64_t)vi[Qo + j]);
+            lm_history_begin(H, gen.data(), Qn);
+            if (what == 0) for (const std::vector<int>& c : H.trial_its_prev) { oi.push_back((int32_t)c.size()); oi.insert(oi.end(), c.begin(), c.end()); }
+            else {
+                for (const std::vector<int>& c : H.trial_its_cur) oi.push_back((int32_t)c.size());
+                for (uint64_t g : H.hist_gen) oi.push_back((int32_t)g);
+            }
+            break;
+        }
+        default: return UZL_ERR_BAD_ARG;
+        }
+        const void* src = f64 ? (const void*)od.data() : (const void*)oi.data();
+        const int64_t bytes = f64 ? (int64_t)od.size() * 8 : (int64_t)oi.size() * 4;
+        if (out && bytes) {
+            if (*nbytes < bytes) return UZL_ERR_BAD_ARG;
+            memcpy(out, src, (size_t)bytes);
+        }
+        *nbytes = bytes;
+        return UZL_OK;
+    } catch (const std::bad_alloc&) {
+        return UZL_ERR_OOM;
+    }
+}
 #endif  // UZL_DIAG

@@ -11,8 +11,8 @@
 //     init  = x = 0, r = b, first application of the preconditioner
 //     pcg   = K iterations                                             (no-ops once the solve's `done` flag is set)
 //     tail  = [back-substitution], retraction, chi2 | lm_tail (residual guard, rho, accept / reject, next phase, snapshot for the host)
-// The host enqueues a pass, looks at the snapshot ONCE, and chooses the next pass's segments and K from it.  Its choices are predictions
-// only: lm_head stalls a graph whose pass lacks a segment it needs (kLmNeedSetup) and the next pass brings it; a solve that outlasts
+// The host enqueues a pass, looks at the snapshot ONCE, and chooses the next pass's segments and K from it (lm_plan_pass,
+// pgo_lm_pass.hpp: every rule of that choice, as a value the CPU tests hold).  Its choices are predictions only: lm_head stalls a graph whose pass lacks a segment it needs (kLmNeedSetup) and the next pass brings it; a solve that outlasts
 // its pass goes on in the next.  The DEVICE takes every decision from the graph's own state, so results do not depend on what the host
 // guessed.  Same kernel bodies, same order of operations, same scalar arithmetic (pgo_lm.hpp) as the host-driven loop: tests hold the
 // two to array_equal poses.
@@ -40,13 +40,7 @@ struct LmRun {
     bool join_pending = false;               // a rebuild is in flight on the second stream
     uint64_t gen = ~0ull;                    // single handle: structure generation the slot and the captured segments belong to
     int solves_of_gen = 0;                   // optimizes of the current structure so far (single-graph driver)
-    int first_solve_its = 0;                 // PCG iterations of the first solve of the last optimize (sizes the first pass of the next)
-    // PCG iterations of every trial of the last drive's jobs and of the running one's.  A re-optimisation
-    // of an unchanged graph (uzl_pgo_reset, a timer-driven one) walks through much the same solves, trial for trial: where the count RISES from one trial to
-    // the next (config 2: 24 -> 40 iterations from the first trial to the second) the last solve alone under-predicts and the solve
-    // needs a second and third pass (tail, look and a fresh launch sequence each)
-    std::vector<std::vector<int>> trial_its_prev, trial_its_cur;      // [job][trial]
-    std::vector<uint64_t> hist_gen;          // structure generation of every job the counts belong to (a batch: its graphs in order)
+    LmPassHistory hist;                      // what earlier solves took, trial by trial: sizes the passes of the next drive (pgo_lm_pass.hpp)
     struct Seg { hipGraph_t g = nullptr; hipGraphExec_t x = nullptr; };
     Seg setup, reb, pcg_long[2];            // pcg_long: per hierarchy copy (a one-graph pass's PCG launches carry the copy's arrays by value)
     void drop(Seg& q) { if (q.x) { (void)hipGraphExecDestroy(q.x); q.x = nullptr; } if (q.g) { (void)hipGraphDestroy(q.g); q.g = nullptr; } }
@@ -265,245 +259,195 @@ struct LmDriveOpts {
     const char* cg_name = "ml_cg";
 };
 
-// Solves `jobs` through the slots of R (shape and slot count set up by the caller; structures prepared).  Returns passes enqueued.
-int lm_drive(LmRun* R, std::vector<LmJob>& jobs, const LmDriveOpts& o)
-{
-    hipStream_t s = o.s;
-    const LmShape& sh = R->shape;
-    const int nS = sh.nslots, Q = (int)jobs.size();
-    const bool eager = o.eager;
-    constexpr int kStep = 2 * kShortPairs;
-    const int kLong = 2 * kGraphPairs;
-    // ---- start poses of every job (anomaly fallback); its current estimate goes to pose buffer 0 (accepted steps flip LmDev::cur; an
-    //      earlier solve may have left it in buffer 1)
-    size_t tot = 0;
-    for (LmJob& j : jobs) { j.start_off = tot; tot += (size_t)std::max(j.h->n, 1) * 8; }
-    R->d_start.reserve(tot);
-    for (LmJob& j : jobs) {
-        uzl_pgo* h = j.h;
-        if (h->cur != h->pose_a.p) {
-            UZL_HIP(hipMemcpyAsync(h->pose_a.p, h->cur, sizeof(double) * 8 * (size_t)h->n, hipMemcpyDeviceToDevice, s));
-            h->cur = h->pose_a.p; h->trial = h->pose_b.p;
-        }
-        UZL_HIP(hipMemcpyAsync(R->d_start.p + j.start_off, h->cur, sizeof(double) * 8 * (size_t)h->n, hipMemcpyDeviceToDevice, s));
-    }
-    std::vector<int> slot_job((size_t)nS, -1), solve_passes((size_t)nS, 0), prev_last((size_t)nS, 0), seen_trials((size_t)nS, 0), cur_last((size_t)nS, 0);
-    std::vector<uint32_t> sent((size_t)nS, 0);               // per slot: lm_tail launches enqueued since its load (= the sequence word expected)
-    std::vector<LmHost> snap((size_t)nS);
-    int next_job = 0, n_active = 0;
-    // The next job of the queue into slot sl (stream-ordered behind what the slot ran).  A REFILL keeps the slot's sequence word running
-    // (LmDev::tails starts at what the slot has sent): lm_tail_kernel publishes for every slot in every pass and the look waits for the
-    // unfinished ones only, so the last snapshot of a finished or idle slot may still be on its way to h_pub when the slot is reloaded -
-    // with the sequence restarted at 0 that late write (an old, larger number with phase = done) would pass for the new graph's.  Only
-    // the first load of a drive (everything drained by the previous drive's final synchronize) zeroes the snapshot.
-    auto load_slot = [&](int sl, bool first) {
-        LmDev I;
-        if (next_job < Q) {
-            const int j = next_job++;
-            slot_job[sl] = j;
-            R->slots[sl] = make_slot(jobs[j].h, R->d_lm.p + sl, R->d_pub + sl);
-            UZL_HIP(hipMemcpyAsync(R->d_slots.p + sl, &R->slots[sl], sizeof(LmSlot), hipMemcpyHostToDevice, s));
-            I = initial_state(jobs[j].h, o.iterations);
-            n_active++;
-        } else {
-            slot_job[sl] = -1;
-            I = idle_state();                                // (the slot keeps its last graph's arguments: every kernel no-ops on the state)
-        }
-        if (first) { memset(R->h_pub.p + sl, 0, sizeof(LmHost)); sent[sl] = 0; }
-        I.tails = (int32_t)sent[sl];
-        R->h_init.p[sl] = I;
-        UZL_HIP(hipMemcpyAsync(R->d_lm.p + sl, R->h_init.p + sl, sizeof(LmDev), hipMemcpyHostToDevice, s));
-        memset(&snap[sl], 0, sizeof(LmHost));
-        snap[sl].lm = I;
-        solve_passes[sl] = 0; prev_last[sl] = 0; cur_last[sl] = 0; seen_trials[sl] = 0;
-    };
-    for (int sl = 0; sl < nS; sl++) load_slot(sl, true);
-    R->join_pending = false;
-    {   // the last drive's counts are this drive's history where job j is the same structure again
-        bool same = R->hist_gen.size() == (size_t)Q;
-        for (int j = 0; same && j < Q; j++) same = R->hist_gen[(size_t)j] == jobs[(size_t)j].h->structure_gen;
-        if (same) R->trial_its_prev.swap(R->trial_its_cur); else R->trial_its_prev.clear();
-        R->trial_its_prev.resize((size_t)Q);
-        R->trial_its_cur.assign((size_t)Q, std::vector<int>());
-        R->hist_gen.resize((size_t)Q);
-        for (int j = 0; j < Q; j++) R->hist_gen[(size_t)j] = jobs[(size_t)j].h->structure_gen;
-    }
-    struct Drain {                           // an exception must not leave a rebuild running on stream2 behind the caller's back
-        LmRun* R; hipStream_t s2;
-        ~Drain() { if (R->join_pending) { (void)hipStreamSynchronize(s2); R->join_pending = false; } }
-    } drain{R, o.s2};
-    // diagnostic build, UZL_PHASES=1: GPU time between the segment boundaries of every pass (events on the solver's stream)
-    static const bool phases_on = diag_flag("UZL_PHASES");
-    std::vector<hipEvent_t> ph_ev;
-    std::vector<int> ph_tag;
-    auto mark = [&](int tag) {
-        if (!phases_on) return;
-        hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return;
-        (void)hipEventRecord(e, s); ph_ev.push_back(e); ph_tag.push_back(tag);
-    };
-    int passes = 0;
-    double enq_ms = 0., wait_ms = 0.;
+// what the steps of one drive share
+struct LmDrive {
+    LmRun* R;
+    std::vector<LmJob>& jobs;
+    const LmDriveOpts& o;
+    std::vector<LmSlotTrack> tracks;         // per slot: its job and what the planner remembers of it (pgo_lm_pass.hpp)
+    std::vector<LmPlanView> views;           // ... what the planner reads of its last snapshot
+    std::vector<LmHost> snap;                // ... the snapshot itself
+    std::vector<uint32_t> sent;              // ... lm_tail launches enqueued since its load (= the sequence word expected)
+    int next_job = 0, n_active = 0, passes = 0;
     // The next pass's linearisation goes out right behind a pass's tail, BEFORE the look: hessian_lm_kernel takes nothing from the host
     // (it works on the graphs the tail has left in phase kLmLin and is a no-op for the others), so the GPU builds the Hessian while the
     // host reads the snapshot, chooses the next pass and launches it - otherwise ~12 us of idle GPU per pass (tail -> hessian in the
     // kernel trace).  Not while a rebuild on the second stream still reads H, and a refill sends the linearisation again.
     bool lin_ahead = false;
-    while (n_active > 0) {
+    PhaseMarks<7> phases;                    // diagnostic build, UZL_PHASES=1: GPU time between the segment boundaries of every pass
+    bool timed() const { return o.timer && o.timer->on; }
+};
+
+// Start poses of every job (anomaly fallback); its current estimate goes to pose buffer 0 (accepted steps flip LmDev::cur; an earlier
+// solve may have left it in buffer 1)
+void save_start_poses(LmDrive& d)
+{
+    LmRun* R = d.R;
+    size_t tot = 0;
+    for (LmJob& j : d.jobs) { j.start_off = tot; tot += (size_t)std::max(j.h->n, 1) * 8; }
+    R->d_start.reserve(tot);
+    for (LmJob& j : d.jobs) {
+        uzl_pgo* h = j.h;
+        if (h->cur != h->pose_a.p) {
+            UZL_HIP(hipMemcpyAsync(h->pose_a.p, h->cur, sizeof(double) * 8 * (size_t)h->n, hipMemcpyDeviceToDevice, d.o.s));
+            h->cur = h->pose_a.p; h->trial = h->pose_b.p;
+        }
+        UZL_HIP(hipMemcpyAsync(R->d_start.p + j.start_off, h->cur, sizeof(double) * 8 * (size_t)h->n, hipMemcpyDeviceToDevice, d.o.s));
+    }
+}
+
+// The next job of the queue into slot sl (stream-ordered behind what the slot ran).  A REFILL keeps the slot's sequence word running
+// (LmDev::tails starts at what the slot has sent): lm_tail_kernel publishes for every slot in every pass and the look waits for the
+// unfinished ones only, so the last snapshot of a finished or idle slot may still be on its way to h_pub when the slot is reloaded -
+// with the sequence restarted at 0 that late write (an old, larger number with phase = done) would pass for the new graph's.  Only
+// the first load of a drive (everything drained by the previous drive's final synchronize) zeroes the snapshot.
+void load_slot(LmDrive& d, int sl, bool first)
+{
+    LmRun* R = d.R;
+    hipStream_t s = d.o.s;
+    LmDev I;
+    if (d.next_job < (int)d.jobs.size()) {
+        const int j = d.next_job++;
+        uzl_pgo* h = d.jobs[(size_t)j].h;
+        lm_track_load(d.tracks[sl], j, h->cfg.pass_history == 1, R->hist);
+        R->slots[sl] = make_slot(h, R->d_lm.p + sl, R->d_pub + sl);
+        UZL_HIP(hipMemcpyAsync(R->d_slots.p + sl, &R->slots[sl], sizeof(LmSlot), hipMemcpyHostToDevice, s));
+        I = initial_state(h, d.o.iterations);
+        d.n_active++;
+    } else {
+        lm_track_load(d.tracks[sl], -1, false, R->hist);
+        I = idle_state();                                // (the slot keeps its last graph's arguments: every kernel no-ops on the state)
+    }
+    if (first) { memset(R->h_pub.p + sl, 0, sizeof(LmHost)); d.sent[sl] = 0; }
+    I.tails = (int32_t)d.sent[sl];
+    R->h_init.p[sl] = I;
+    UZL_HIP(hipMemcpyAsync(R->d_lm.p + sl, R->h_init.p + sl, sizeof(LmDev), hipMemcpyHostToDevice, s));
+    memset(&d.snap[sl], 0, sizeof(LmHost));
+    d.snap[sl].lm = I;
+    d.views[sl] = lm_plan_view(I);
+}
+
+// One pass as the plan says: join wait | head | set-up | fork, rebuild, join record | init | PCG | tail | linearise-ahead
+void enqueue_pass(LmDrive& d, const LmPassPlan& P)
+{
+    LmRun* R = d.R;
+    hipStream_t s = d.o.s, s2 = d.o.s2;
+    const bool eager = d.o.eager;
+    d.phases.mark(0, s);
+    if (P.any_start && R->join_pending) { UZL_HIP(hipStreamWaitEvent(s, R->ev_join, 0)); R->join_pending = false; }      // the rebuild of an earlier pass reads H and the poses
+    d.phases.mark(1, s);
+    if (P.any_start) enq_head(R, P.flags, d.lin_ahead, s);
+    d.lin_ahead = false;
+    d.phases.mark(2, s);
+    if (P.flags & kPassSetup) {
+        if (!P.setup_captured) enq_setup(R, 1, P.ns_steps, s);
+        else run_seg(R->setup, eager, s, [&](hipStream_t q) { enq_setup(R, 1, P.ns_steps, q); });
+    }
+    if (P.flags & kPassRebuild) {
+        UZL_HIP(hipEventRecord(R->ev_fork, s));
+        UZL_HIP(hipStreamWaitEvent(s2, R->ev_fork, 0));
+        run_seg(R->reb, eager, s2, [&](hipStream_t q) { enq_setup(R, 0, R->shape.ns_steps, q); });
+        UZL_HIP(hipEventRecord(R->ev_join, s2));
+        R->join_pending = true;
+    }
+    d.phases.mark(3, s);
+    if (P.any_start) enq_init(R, P.ix, s);
+    d.phases.mark(4, s);
+    if (d.timed()) {
+        KernelTimer* tm = d.o.timer;
+        std::vector<hipEvent_t> ev((size_t)4 * P.want);
+        for (int q = 0; q < P.want; q++) { tm->pair(d.o.spmv_name, &ev[4 * q], &ev[4 * q + 1]); tm->pair(d.o.cg_name, &ev[4 * q + 2], &ev[4 * q + 3]); }
+        enq_pcg(R, P.ix, P.tol2, P.base, P.want, s, ev.data());
+    } else {
+        const LmPcgLaunches L = lm_pcg_launches(P.base, P.want, eager);
+        if (L.lead) enq_pcg(R, P.ix, P.tol2, P.base, 1, s);
+        for (int i = 0; i < L.n_long; i++) run_seg(R->pcg_long[P.ix], false, s, [&](hipStream_t q) { enq_pcg(R, P.ix, P.tol2, 0, kPcgLong, q); });
+        if (L.rem > 0) enq_pcg(R, P.ix, P.tol2, L.rem_first, L.rem, s);
+    }
+    d.phases.mark(5, s);
+    enq_tail(R, s);
+    if (!R->join_pending && !d.timed()) { enq_linearize(R, s); d.lin_ahead = true; }
+    d.phases.mark(6, s);
+    d.passes++;
+    for (uint32_t& n : d.sent) n++;
+}
+
+// The look: every unfinished slot's snapshot of the pass just enqueued.  True when a graph got through.
+bool look(LmDrive& d)
+{
+    bool through = false;
+    for (int sl = 0; sl < (int)d.tracks.size(); sl++) {
+        LmSlotTrack& T = d.tracks[sl];
+        if (!T.active) continue;
+        (void)wait_pub(d.o.s, d.R, sl, d.sent[sl], &d.snap[sl]);
+        LmJob& J = d.jobs[(size_t)T.job];
+        const LmDev& v = d.snap[sl].lm;
+        J.passes++;
+        if (d.o.verbose)
+            fprintf(stderr, "[uzl_pgo] pass %d, graph %d -> it %d trial %d phase %d: pcg %d done %d (last solve %d) lambda %.3e chi2 %.9g |r|2/|b|2 %.3e need %d\n", d.passes - 1,
+                    T.job, v.it, v.qmax, v.phase, v.flags[1], v.flags[0], v.pcg_last, v.lambda, v.chi_cur, d.snap[sl].scal[7], v.need);
+        d.views[sl] = lm_plan_view(v);
+        if (lm_track_look(d.views[sl], T, d.R->hist)) {
+            J.last = d.snap[sl]; J.finished = true; J.anomaly = v.phase == kLmAnomaly;
+            d.n_active--; through = true;
+        }
+    }
+    if (d.timed()) { UZL_HIP(hipStreamSynchronize(d.o.s)); d.o.timer->resolve(); }
+    return through;
+}
+
+// A queue longer than the slots is worked off in COHORTS: the slots are refilled when every resident graph is through, so that the
+// residents walk through their LM iterations together - their solves need similar numbers of PCG iterations, and a pass is as long
+// as its longest solve.  Refilling slot by slot mixes converged graphs (4 iterations
+// per solve) with fresh ones (60): measured on 256 queued config-2 graphs through 16 / 64 slots 49 / 69 M edges/s against 60 / 74 M.
+void refill(LmDrive& d)
+{
+    LmRun* R = d.R;
+    // (a rebuild of the outgoing graphs may still read the slot table and their LM state)
+    if (R->join_pending && d.next_job < (int)d.jobs.size()) { UZL_HIP(hipStreamWaitEvent(d.o.s, R->ev_join, 0)); R->join_pending = false; }
+    for (int sl = 0; sl < (int)d.tracks.size(); sl++)
+        if (d.tracks[sl].job >= 0 && !d.tracks[sl].active) load_slot(d, sl, false);
+    d.lin_ahead = false;                                 // (the new graphs were not in their slots when the linearisation ran)
+}
+
+// Solves `jobs` through the slots of R (shape and slot count set up by the caller; structures prepared): plan the next pass from the
+// slots' snapshots (pgo_lm_pass.hpp), enqueue it, look, refill.  Returns passes enqueued.
+int lm_drive(LmRun* R, std::vector<LmJob>& jobs, const LmDriveOpts& o)
+{
+    const int nS = R->shape.nslots;
+    LmDrive d{R, jobs, o, std::vector<LmSlotTrack>((size_t)nS), std::vector<LmPlanView>((size_t)nS), std::vector<LmHost>((size_t)nS), std::vector<uint32_t>((size_t)nS, 0)};
+    save_start_poses(d);
+    {
+        std::vector<uint64_t> gen;
+        for (const LmJob& j : jobs) gen.push_back(j.h->structure_gen);
+        lm_history_begin(R->hist, gen.data(), (int)gen.size());
+    }
+    for (int sl = 0; sl < nS; sl++) load_slot(d, sl, true);
+    R->join_pending = false;
+    struct Drain {                           // an exception must not leave a rebuild running on stream2 behind the caller's back
+        LmRun* R; hipStream_t s2;
+        ~Drain() { if (R->join_pending) { (void)hipStreamSynchronize(s2); R->join_pending = false; } }
+    } drain{R, o.s2};
+    static const bool wrong_ix = diag_flag("UZL_LM_WRONG_IX");      // diagnostic build: a one-graph pass names the other hierarchy copy
+    double enq_ms = 0., wait_ms = 0.;
+    while (d.n_active > 0) {
         const auto tp0 = std::chrono::steady_clock::now();
-        // ---- what this pass carries: predictions from the slots' last snapshots
-        int pf = 0, want = 0;
-        bool any_start = false;
-        for (int sl = 0; sl < nS; sl++) {
-            if (slot_job[sl] < 0 || jobs[slot_job[sl]].finished) continue;      // (a finished graph waits in its slot for its cohort: every kernel no-ops on its state)
-            const LmDev& v = snap[sl].lm;
-            int w;
-            if (v.phase == kLmSolve) {
-                // A solve that outlasted its pass.  Nothing says how much longer it takes, but a launch past the end is a 1.2-us no-op
-                // and another pass is 50 - 100 us of tail, look and restart: a short batch, then half of what the solve has taken so far (round
-                // 4: two batches of 4, then 16s - config 2's second trial, 48 iterations against 30 predicted, took four passes; now three)
-                w = solve_passes[sl] == 0 ? kStep : std::min(std::max(kStep, (v.flags[1] / 2 + 1) & ~1), 4 * kLong);      // (most often it was one launch short: a short batch first)
-                solve_passes[sl]++;
-            } else {
-                any_start = true; solve_passes[sl] = 0;
-                if (v.phase == kLmNeedSetup) pf |= ((v.need & (kNeedNumeric | kNeedTrial)) ? kPassSetup : 0) | ((v.need & kNeedRebuild) ? kPassRebuild : 0);
-                else if (v.phase == kLmLin) {
-                    if (lm_refresh(v.it, v.iterations, v.sync_rebuild != 0, v.last_rel, v.refresh_rel, v.rate_ref, v.rate_last, v.rate_drop))
-                        pf |= (v.it == 0 || v.sync_rebuild) ? kPassSetup : kPassRebuild;
-                    if (v.it > 0 && v.lambda > kLambdaRetake * v.lambda_setup[v.ix ^ (v.pending ? 1 : 0)]) pf |= kPassSetup;
-                } else if (v.phase == kLmRetry) {
-                    if (v.lambda > kLambdaRetake * v.lambda_setup[v.ix]) pf |= kPassSetup;
-                }
-                // The solve's length: the previous solve's count + 1 (a solve that the stop test ends after k iterations is declared done by
-                // the ml_spmv of iteration k + 1): too many is a ~3.5-us no-op per launch, too few another pass.  The
-                // first solve of an optimize has no predecessor: the first solve of the last optimize stands in (same structure or a grown
-                // one: a re-optimisation), a fresh run starts with two long replays.
-                // uzl_pgo_cfg::pass_history = 1: nothing an earlier optimize of this handle learned sizes a pass (the first solve starts with
-                // two long replays, every later one follows its predecessor in the same optimize)
-                const bool no_history = jobs[(size_t)slot_job[sl]].h->cfg.pass_history == 1;
-                // One graph: exactly count + 1 launches (odd or even; a continuation pass picks the parity up from the solve's own
-                // iteration count).  A batch keeps whole pairs: its graphs share the launches' parity.
-                auto up = [&](int count) { return nS == 1 ? count + 1 : ((count + 2) & ~1); };
-                w = v.pcg_last > 0 ? up(v.pcg_last) : ((R->first_solve_its > 0 && !no_history) ? up(R->first_solve_its) : 2 * kLong);
-                // counts that RISE from trial to trial (lambda falls after accepted steps, the system gets harder: chain-like graphs climb by 2
-                // per trial for ten trials, each time one launch short of `last + 2`): extrapolate the last rise
-                if (v.pcg_last > 0 && prev_last[sl] > 0 && v.pcg_last > prev_last[sl]) w = up(v.pcg_last + std::min(v.pcg_last - prev_last[sl], 16));
-                {
-                    const std::vector<int>& hist = R->trial_its_prev[(size_t)slot_job[sl]];
-                    if (!no_history && (size_t)v.st_lm_trials < hist.size()) w = std::max(w, up(hist[(size_t)v.st_lm_trials]));
-                }
-                w = std::min(w, ((v.max_it + 1) & ~1));
-            }
-            want = std::max(want, w);
-        }
-        want = std::max(2, want);
-        // iteration index of the pass's first PCG launch: a single graph's continuation goes on where its solve stands (its count may be
-        // odd); in a batch every pass holds whole pairs, so every solve stands at an even count
-        const int base = (nS == 1 && slot_job[0] >= 0 && snap[0].lm.phase == kLmSolve) ? snap[0].lm.flags[1] : 0;
-        // the hierarchy copy a one-graph pass applies: lm_head_kernel's rule on the snapshot this pass starts from (the kernels hold it
-        // against LmDev::ix and end the solve as an anomaly if it is not the state's).  Diagnostic build, UZL_LM_WRONG_IX=1: the other copy
-        static const bool wrong_ix = diag_flag("UZL_LM_WRONG_IX");
-        const int pass_ix = lm_pass_ix(snap[0].lm.phase, snap[0].lm.ix, snap[0].lm.pending) ^ (wrong_ix ? 1 : 0);
-        const double tol2 = snap[0].lm.tol2;
-        mark(0);
-        if (any_start && R->join_pending) { UZL_HIP(hipStreamWaitEvent(s, R->ev_join, 0)); R->join_pending = false; }      // the rebuild of an earlier pass reads H and the poses
-        mark(1);
-        if (any_start) enq_head(R, pf, lin_ahead, s);
-        lin_ahead = false;
-        mark(2);
-        if (pf & kPassSetup) {
-            // The synchronous set-ups of the first kNsEarlyIts linearisations refine the dense operator with two Newton-Schulz steps where the
-            // structure asks for four (large loopy graphs): the problem still changes wholesale there and a rougher operator costs no PCG
-            // iterations (ml_ns_steps_at, uzl_pgo.hip).  Launched as they are - the captured segment holds the full sequence.
-            const int steps = nS == 1 ? ml_ns_steps_at(R->shape.ns_steps, snap[0].lm.it) : R->shape.ns_steps;
-            if (steps != R->shape.ns_steps) enq_setup(R, 1, steps, s);
-            else run_seg(R->setup, eager, s, [&](hipStream_t q) { enq_setup(R, 1, steps, q); });
-        }
-        if (pf & kPassRebuild) {
-            UZL_HIP(hipEventRecord(R->ev_fork, s));
-            UZL_HIP(hipStreamWaitEvent(o.s2, R->ev_fork, 0));
-            run_seg(R->reb, eager, o.s2, [&](hipStream_t q) { enq_setup(R, 0, R->shape.ns_steps, q); });
-            UZL_HIP(hipEventRecord(R->ev_join, o.s2));
-            R->join_pending = true;
-        }
-        mark(3);
-        if (any_start) enq_init(R, pass_ix, s);
-        mark(4);
-        // short solves are launched kernel by kernel, long ones as captured replays of 2 x kGraphPairs iterations plus a remainder
-        if (o.timer && o.timer->on) {
-            std::vector<hipEvent_t> ev((size_t)4 * want);
-            for (int q = 0; q < want; q++) { o.timer->pair(o.spmv_name, &ev[4 * q], &ev[4 * q + 1]); o.timer->pair(o.cg_name, &ev[4 * q + 2], &ev[4 * q + 3]); }
-            enq_pcg(R, pass_ix, tol2, base, want, s, ev.data());
-        } else {
-            int first = base, left = want;
-            if (!eager && (first & 1)) { enq_pcg(R, pass_ix, tol2, first, 1, s); first++; left--; }      // (the captured replay starts at an even iteration)
-            const int n_long = eager ? 0 : left / kLong, rem = left - n_long * kLong;
-            for (int i = 0; i < n_long; i++) run_seg(R->pcg_long[pass_ix], false, s, [&](hipStream_t q) { enq_pcg(R, pass_ix, tol2, 0, kLong, q); });
-            if (rem > 0) enq_pcg(R, pass_ix, tol2, first + n_long * kLong, rem, s);
-        }
-        mark(5);
-        enq_tail(R, s);
-        if (!R->join_pending && !(o.timer && o.timer->on)) { enq_linearize(R, s); lin_ahead = true; }
-        mark(6);
-        passes++;
-        for (int sl = 0; sl < nS; sl++) sent[sl]++;
+        const int in_slots = d.n_active;
+        const LmPassPlan P = lm_plan_pass(d.views.data(), d.tracks.data(), nS, R->hist.first_solve_its, R->shape.ns_steps, wrong_ix);
+        enqueue_pass(d, P);
         const auto tp1 = std::chrono::steady_clock::now();
-        if (o.verbose) fprintf(stderr, "[uzl_pgo]   pass %d enqueued: segments %d, %d PCG iterations, %d graph(s) in the slots\n", passes - 1, pf, want, n_active);
-        // ---- the look: every slot's snapshot of this pass
-        bool refill = false;
-        for (int sl = 0; sl < nS; sl++) {
-            if (slot_job[sl] < 0 || jobs[slot_job[sl]].finished) continue;
-            (void)wait_pub(s, R, sl, sent[sl], &snap[sl]);
-            LmJob& J = jobs[slot_job[sl]];
-            const LmDev& v = snap[sl].lm;
-            J.passes++;
-            if (o.verbose)
-                fprintf(stderr, "[uzl_pgo] pass %d, graph %d -> it %d trial %d phase %d: pcg %d done %d (last solve %d) lambda %.3e chi2 %.9g |r|2/|b|2 %.3e need %d\n", passes - 1,
-                        slot_job[sl], v.it, v.qmax, v.phase, v.flags[1], v.flags[0], v.pcg_last, v.lambda, v.chi_cur, snap[sl].scal[7], v.need);
-            if (v.st_lm_trials > seen_trials[sl]) { seen_trials[sl] = v.st_lm_trials; prev_last[sl] = cur_last[sl]; cur_last[sl] = v.pcg_last; }      // a trial ended: its count and the one before
-            if (v.st_lm_trials == 1 && v.pcg_last > 0 && slot_job[sl] == 0) R->first_solve_its = v.pcg_last;
-            {
-                std::vector<int>& cur = R->trial_its_cur[(size_t)slot_job[sl]];
-                if (v.st_lm_trials > 0 && (size_t)v.st_lm_trials > cur.size()) cur.resize((size_t)v.st_lm_trials, v.pcg_last);
-            }
-            if (v.phase == kLmDone || v.phase == kLmAnomaly) {
-                J.last = snap[sl]; J.finished = true; J.anomaly = v.phase == kLmAnomaly;
-                n_active--; refill = true;
-            }
-        }
-        if (o.timer && o.timer->on) { UZL_HIP(hipStreamSynchronize(s)); o.timer->resolve(); }
-        // A queue longer than the slots is worked off in COHORTS: the slots are refilled when every resident graph is through, so that the
-        // residents walk through their LM iterations together - their solves need similar numbers of PCG iterations, and a pass is as long
-        // as its longest solve.  Refilling slot by slot mixes converged graphs (4 iterations
-        // per solve) with fresh ones (60): measured on 256 queued config-2 graphs through 16 / 64 slots 49 / 69 M edges/s against 60 / 74 M.
-        if (refill && (n_active == 0 || nS == 1)) {
-            // (a rebuild of the outgoing graphs may still read the slot table and their LM state)
-            if (R->join_pending && next_job < Q) { UZL_HIP(hipStreamWaitEvent(s, R->ev_join, 0)); R->join_pending = false; }
-            for (int sl = 0; sl < nS; sl++)
-                if (slot_job[sl] >= 0 && jobs[slot_job[sl]].finished) load_slot(sl, false);
-            lin_ahead = false;                              // (the new graphs were not in their slots when the linearisation ran)
-        }
+        if (o.verbose) fprintf(stderr, "[uzl_pgo]   pass %d enqueued: segments %d, %d PCG iterations, %d graph(s) in the slots\n", d.passes - 1, P.flags, P.want, in_slots);
+        if (look(d) && (d.n_active == 0 || nS == 1)) refill(d);
         const auto tp2 = std::chrono::steady_clock::now();
         enq_ms += std::chrono::duration<double, std::milli>(tp1 - tp0).count(); wait_ms += std::chrono::duration<double, std::milli>(tp2 - tp1).count();
     }
     UZL_HIP(hipGetLastError());
-    if (o.verbose) fprintf(stderr, "[uzl_pgo] device-resident loop: %d passes, host time enqueueing %.3f ms, waiting for snapshots %.3f ms\n", passes, enq_ms, wait_ms);
+    if (o.verbose) fprintf(stderr, "[uzl_pgo] device-resident loop: %d passes, host time enqueueing %.3f ms, waiting for snapshots %.3f ms\n", d.passes, enq_ms, wait_ms);
     if (R->join_pending) { UZL_HIP(hipStreamSynchronize(o.s2)); R->join_pending = false; }      // a rebuild nobody will use: let it drain
-    UZL_HIP(hipStreamSynchronize(s));
-    if (phases_on && ph_ev.size() > 1) {
-        double acc[7] = {0, 0, 0, 0, 0, 0, 0};
-        static const char* nm[7] = {"wait for the rebuild (0->1)", "linearise + head (1->2)", "set-up / fork (2->3)", "init (3->4)", "pcg (4->5)", "tail (5->6)", "between passes (6->0)"};
-        static const bool each = diag_flag("UZL_PHASES_EACH");
-        for (size_t i = 0; i + 1 < ph_ev.size(); i++) {
-            float ms = 0.f; (void)hipEventElapsedTime(&ms, ph_ev[i], ph_ev[i + 1]); acc[ph_tag[i] % 7] += ms;
-            if (each) fprintf(stderr, "%s%d:%.0f", ph_tag[i] == 0 ? "\n[uzl_pgo]   " : " ", ph_tag[i], 1e3 * ms);
-        }
-        if (each) fprintf(stderr, "\n");
-        fprintf(stderr, "[uzl_pgo] segments over %d passes (GPU event time, ms):", passes);
-        for (int k = 0; k < 7; k++) fprintf(stderr, "  %s %.3f", nm[k], acc[k]);
-        fprintf(stderr, "\n");
-        for (hipEvent_t e : ph_ev) (void)hipEventDestroy(e);
-    }
-    return passes;
+    UZL_HIP(hipStreamSynchronize(o.s));
+    static const char* const kSegmentNames[7] = {"wait for the rebuild (0->1)", "linearise + head (1->2)", "set-up / fork (2->3)", "init (3->4)", "pcg (4->5)", "tail (5->6)", "between passes (6->0)"};
+    d.phases.report("segments", d.passes, "passes", kSegmentNames);
+    return d.passes;
 }
 
 // what a finished job leaves in its handle and in the caller's stats
@@ -517,8 +461,7 @@ void finish_job(LmJob& J, uzl_pgo_stats* st, double wall_ms)
     if (!st) return;
     uzl_pgo_stats S;
     memset(&S, 0, sizeof(S));
-    S.structure_reused = h->last_structure_reused ? 1 : 0;
-    S.n_vertices = h->n; S.n_edges = h->e; S.n_gauge_fixed = h->n_gauge; S.n_eliminated = h->red.on ? h->red.n_int : 0; S.reduced_strong = (h->red.on && h->red.strong) ? 1 : 0;
+    stats_head(h, S);
     S.iterations_done = v.st_iterations_done; S.lm_trials = v.st_lm_trials; S.pcg_iterations = v.st_pcg_iterations;
     S.terminated_early = v.st_terminated_early; S.precond_builds = v.st_precond_builds;
     S.chi2_initial = v.chi2_initial; S.chi2_final = v.chi_cur; S.lambda_final = v.lambda;
@@ -551,7 +494,7 @@ int do_optimize_lm(uzl_pgo* h, int32_t iterations, uzl_pgo_stats* st)
         R->shape = make_shape({h}, 1, false);
         R->gen = h->structure_gen;
         R->solves_of_gen = 0;
-        R->hist_gen.clear();                                       // (a grown graph's solves are not the old graph's: measured on config 5, +5 % per solve with the old counts)
+        R->hist.hist_gen.clear();                                     // (a grown graph's solves are not the old graph's: measured on config 5, +5 % per solve with the old counts)
         h->structure_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ts).count();
     }
     std::vector<LmJob> jobs(1);
