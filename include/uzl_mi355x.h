@@ -365,6 +365,48 @@ int  uzl_pgo_append_graph(uzl_pgo* h,
                           int32_t n_new_edges, const uzl_edge* new_edges,
                           int32_t n_flags, const int32_t* edge_index, const uint8_t* edge_valid);
 
+/* The graph of the last uzl_pgo_add_graph / uzl_pgo_append_graph, SHRUNK in place: the other half of the resident graph.  Nodes leave
+ * the local scope (scopeRequestTimerCallback, graph_slam_node.cpp:578-663 -> removeNode :636-660; uzl_scope_request names them) or one
+ * is folded into another (mergeNodes :890-1062; uzl_merge_plan states it); with the graph resident in HBM the surviving 608-byte edge
+ * records and the estimates close up on the device, and only the index maps of the rewrite cross PCIe.  A handle fed by
+ * uzl_pgo_set_graph is refused with UZL_ERR_BAD_ARG, as by uzl_pgo_append_graph.
+ *   Ops.  op.edge is an input-edge index in the handle's current numbering.  An edge carries at most one op per side:
+ *     UZL_MERGE_EDGE_KEEP_FROM / _TO      displacement_from / _to = xf[op.xf] * displacement_from / _to
+ *     UZL_MERGE_EDGE_RETARGET_FROM / _TO  the same, and from / to = op.node (OLD node numbering)
+ *     UZL_MERGE_EDGE_DELETE               stands alone on its edge
+ *   - the actions of uzl_merge_plan, contract 6 (UZL_MERGE_EDGE_*, below).  The product of two [R|t] is rows times columns, summed left
+ *   to right without contraction: a rotation entry (a0*b0 + a1*b1) + a2*b2, a translation entry ((a0*B3 + a1*B7) + a2*B11) + a3.
+ *   Which edges go.  An edge with a DELETE op, and an edge that after its ops still names a dropped node (removeNode's edge removal,
+ *   :636-660; the plan's "a surviving self-loop of drop goes with the node").  An endpoint outside the graph (-1) stays as it is.
+ *   Compaction.  Surviving nodes and edges keep their relative order, indices close up; the fixed flags, the valid flags and everything
+ *   else of a surviving edge are unchanged.  Sensors stay as given to uzl_pgo_add_graph.
+ *   Poses.  Surviving nodes keep the handle's current estimates bit for bit (as for uzl_pgo_append_graph); pose_nodes[q] (old numbering)
+ *   takes poses[12 q ..], prepared exactly as uzl_pgo_add_graph prepares a node pose, the xy-only projection included.  uzl_pgo_reset
+ *   returns to this state.
+ *   Equivalence.  The result is what uzl_pgo_add_graph on the same handle gives for the rewritten arrays (the old nodes' poses as
+ *   uzl_pgo_store last returned them), with the same skip rules.  The structure and the numbering memory follow the rule of
+ *   uzl_pgo_add_graph: a graph with fewer nodes starts as on a fresh handle, an empty rewrite keeps the structure.
+ *   old_to_new_node [cap_nodes >= old node count] / old_to_new_edge [cap_edges >= old edge count], either may be NULL: the new index of
+ *   every old node / input edge, -1 = dropped / deleted.
+ *   UZL_ERR_BAD_ARG, and nothing changed: a node or edge index out of range; a duplicate in drop_nodes; a pose_nodes entry that is dropped
+ *   or listed twice; two ops on one side of an edge, or DELETE together with another op; xf out of range; RETARGET to a dropped or
+ *   out-of-range node; an unknown action; a capacity below the old count where the pointer is given.  Only copies. */
+typedef struct uzl_pgo_edge_op {
+    int32_t edge;     /* input-edge index in the handle's current numbering (the order of add_graph + append_graph) */
+    int32_t action;   /* UZL_MERGE_EDGE_KEEP_FROM / KEEP_TO / RETARGET_FROM / RETARGET_TO / DELETE */
+    int32_t xf;       /* index into xf[]: the left multiplier of that side's displacement; ignored for DELETE */
+    int32_t node;     /* RETARGET_*: the new endpoint, OLD node numbering; ignored otherwise */
+} uzl_pgo_edge_op;
+typedef struct uzl_pgo_rewrite {
+    int32_t n_drop;  const int32_t* drop_nodes;                       /* nodes that leave, old numbering, distinct */
+    int32_t n_pose;  const int32_t* pose_nodes; const double* poses;  /* n_pose x 12: new current estimates (keep's new_pose) */
+    int32_t n_xf;    const double* xf;                                /* n_xf x 12 [R|t] */
+    int32_t n_ops;   const uzl_pgo_edge_op* ops;
+} uzl_pgo_rewrite;
+int  uzl_pgo_rewrite_graph(uzl_pgo* h, const uzl_pgo_rewrite* rw,
+                           int32_t cap_nodes, int32_t* old_to_new_node,   /* may be NULL; -1 = dropped */
+                           int32_t cap_edges, int32_t* old_to_new_edge);  /* may be NULL; -1 = deleted */
+
 /* Already-flattened form of the same problem (what addGraphImpl leaves inside g2o):
  * poses n x 12, fixed n, ij e x 2, meas e x 12, info e x 36, robust e. */
 int  uzl_pgo_set_graph(uzl_pgo* h, int32_t n, const double* poses, const uint8_t* fixed,
@@ -968,8 +1010,11 @@ int  uzl_scope_stats(uzl_scope* h, int64_t* rounds, int64_t* relaxations, int32_
  *  node of SlamGraph::getNodesWithinHops(id, ., 10) (graph_slam_common/src/slam_graph.cpp:231-264) that
  *  is close (:740) and turned little (:743-747); mergeNodes (:890-1062) folds the younger of the two
  *  into the older.  Here the search runs on the device and the rewrite is a host-side plan, a pure
- *  value; no resident handle is rewritten in place: the caller applies the plan to its arrays and hands
- *  them to the existing *_set_graph / uzl_pgo_add_graph paths.  Node and edge ids are indices in the
+ *  value.  The solver's resident graph takes it in place: the plan's actions are the ops of
+ *  uzl_pgo_rewrite_graph (drop = the dropped node, keep at new_pose, xf = {keep_displacement,
+ *  drop_displacement}), provided this handle's edge order is the solver's input-edge order.  The gate,
+ *  scope and merge handles are not rewritten in place: the caller applies the plan to its arrays and
+ *  hands them to their *_set_graph (120 bytes an edge).  Node and edge ids are indices in the
  *  reference's std::map id order, as for uzl_scope_*: node 0 is nodes_.begin(), the root.
  *
  *  Contract (parity is against this repository's own restatement, tests/merge_reference.py):

@@ -97,6 +97,13 @@ EDGE_DTYPE = np.dtype([("from", "<i4"), ("to", "<i4"), ("type", "<i4"), ("sensor
                        ("sensor_to", "<i4"), ("valid", "<i4"), ("transform", "<f8", (12,)),
                        ("displacement_from", "<f8", (12,)), ("displacement_to", "<f8", (12,)),
                        ("information", "<f8", (36,)), ("diff_time", "<f8")], align=True)
+PGO_EDGE_OP_DTYPE = np.dtype([("edge", "<i4"), ("action", "<i4"), ("xf", "<i4"), ("node", "<i4")])      # uzl_pgo_edge_op
+
+
+class PgoRewrite(C.Structure):
+    """uzl_pgo_rewrite"""
+    _fields_ = [("n_drop", C.c_int32), ("drop_nodes", c_i32p), ("n_pose", C.c_int32), ("pose_nodes", c_i32p), ("poses", c_f64p),
+                ("n_xf", C.c_int32), ("xf", c_f64p), ("n_ops", C.c_int32), ("ops", C.c_void_p)]
 
 class FilterCfg(C.Structure):
     _fields_ = [("max_dt", C.c_double), ("min_size", C.c_double), ("max_cluster_size", C.c_int32),
@@ -687,6 +694,29 @@ class Pgo(_Handle):
                                                C.c_int32(len(fi)), _p(fi, c_i32p), _p(fv, c_u8p)))
         self.n += n; self.e_in += ne
 
+    def rewrite_graph(self, drop_nodes=(), pose_nodes=(), poses=None, xf=None, ops=()):
+        """uzl_pgo_rewrite_graph: the resident graph shrunk in place.  drop_nodes / pose_nodes: old node indices; poses (n_pose, 12);
+        xf (n_xf, 12); ops: rows (edge, action, xf, node) or a PGO_EDGE_OP_DTYPE array.  merge.pgo_rewrite_of_plan / _of_drops make the
+        arguments.  -> (old_to_new_node, old_to_new_edge), -1 = gone."""
+        drop = np.ascontiguousarray(drop_nodes, np.int32).reshape(-1)
+        pn = np.ascontiguousarray(pose_nodes, np.int32).reshape(-1)
+        P = np.ascontiguousarray(poses if poses is not None else [], np.float64).reshape(-1, 12)
+        X = np.ascontiguousarray(xf if xf is not None else [], np.float64).reshape(-1, 12)
+        assert len(P) == len(pn)
+        if isinstance(ops, np.ndarray) and ops.dtype == PGO_EDGE_OP_DTYPE:
+            oa = np.ascontiguousarray(ops)
+        else:
+            rows = np.ascontiguousarray(ops, np.int32).reshape(-1, 4)
+            oa = np.zeros(len(rows), PGO_EDGE_OP_DTYPE)
+            for j, k in enumerate(("edge", "action", "xf", "node")):
+                oa[k] = rows[:, j]
+        rw = PgoRewrite(len(drop), _p(drop, c_i32p), len(pn), _p(pn, c_i32p), _p(P, c_f64p), len(X), _p(X, c_f64p), len(oa), _p(oa, C.c_void_p))
+        node_map = np.empty(max(self.n, 1), np.int32); edge_map = np.empty(max(self.e_in, 1), np.int32)
+        self._check(self._lib().uzl_pgo_rewrite_graph(self._h, C.byref(rw), C.c_int32(self.n), _p(node_map, c_i32p), C.c_int32(self.e_in), _p(edge_map, c_i32p)))
+        node_map, edge_map = node_map[:self.n], edge_map[:self.e_in]
+        self.n = int((node_map >= 0).sum()); self.e_in = int((edge_map >= 0).sum())
+        return node_map, edge_map
+
     def set_graph(self, poses, fixed, ij, meas, info, robust):
         P = np.ascontiguousarray(poses, np.float64).reshape(-1, 12); f = np.ascontiguousarray(fixed, np.uint8)
         ijc = np.ascontiguousarray(ij, np.int32).reshape(-1, 2)
@@ -1228,6 +1258,40 @@ def pgo_structure_plan(stage, **kw):
                 dtype=np.int32)
         return dict(survive=bool(r[0]), grown=bool(r[1]))
     raise ValueError(stage)
+
+
+def pgo_rewrite_plan(n, fixed, in_edges, drop_nodes=(), pose_nodes=(), n_xf=0, ops=()):
+    """uzl_debug_pgo_rewrite_plan (diagnostic library, host only): rewrite_plan of csrc/pgo_structure.hpp, what uzl_pgo_rewrite_graph
+    decides before it touches the device.  fixed [n]; in_edges [e_in, 4] = (from, to, odom, valid); ops rows (edge, action, xf, node).
+    -> dict(n_new, e_new, old_to_new_node, new_to_old_node, old_to_new_edge, new_to_old_edge, rec [e_new, 4] = (from_new, to_new, xf_from,
+    xf_to), in_edges [e_new, 4], fixed); raises UzlError(UZL_ERR_BAD_ARG) for a rewrite the plan refuses."""
+    L = diag_lib()
+    i32 = lambda a: np.ascontiguousarray(a, np.int32).reshape(-1)
+    fx = np.ascontiguousarray(fixed, np.uint8).reshape(-1); ie = i32(in_edges); dr = i32(drop_nodes); pn = i32(pose_nodes); op = i32(ops)
+    iv = i32([n, len(ie) // 4, len(dr), len(pn), n_xf, len(op) // 4])
+    ptr = lambda a, t: _p(a, t) if len(a) else None
+
+    def run(what, dtype):
+        def call(out, nbytes):
+            rc = L.uzl_debug_pgo_rewrite_plan(_p(iv, c_i32p), ptr(fx, c_u8p), ptr(ie, c_i32p), ptr(dr, c_i32p), ptr(pn, c_i32p), ptr(op, c_i32p), C.c_int32(what),
+                                              out.ctypes.data_as(C.c_void_p) if out is not None else None, C.byref(nbytes))
+            if rc != UZL_OK:
+                raise UzlError(rc, "uzl_debug_pgo_rewrite_plan(%d)" % what)
+
+        nbytes = C.c_int64(0)
+        call(None, nbytes)
+        out = np.zeros(nbytes.value // np.dtype(dtype).itemsize, dtype)
+        if nbytes.value:
+            call(out, nbytes)
+        return out
+
+    sz = run(0, np.int32)
+    out = dict(n_new=int(sz[0]), e_new=int(sz[1]))
+    for what, k in enumerate(("old_to_new_node", "new_to_old_node", "old_to_new_edge", "new_to_old_edge", "rec", "in_edges"), 1):
+        out[k] = run(what, np.int32)
+    out["rec"] = out["rec"].reshape(-1, 4); out["in_edges"] = out["in_edges"].reshape(-1, 4)
+    out["fixed"] = run(7, np.uint8)
+    return out
 
 
 # the rows uzl_debug_lm_pass_plan reads and writes (csrc/uzl_pgo_debug.hip): a view of a snapshot, a slot's track, a pass's plan

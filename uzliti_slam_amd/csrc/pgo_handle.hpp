@@ -142,7 +142,12 @@ struct uzl_pgo : uzl::HandleBase {
     DevBuf<uint8_t> d_robust;
     DevBuf<uzl_node> d_nodes;
     DevBuf<uzl_edge> d_edges;
-    PinBuf<PgoHostScal> h_scal;      // pinned + coherent: written by publish_kernel, polled by the host
+    // uzl_pgo_rewrite_graph: the edge buffer the surviving records are compacted into (then swapped with d_edges), the plan's index
+    // arrays [records 4 e | new_to_old_edge e | node sources n], and [xf 12 n_xf | the placed poses 8 n_pose]
+    DevBuf<uzl_edge> d_edges_spare;
+    DevBuf<int32_t> d_rw_idx;
+    DevBuf<double> d_rw_val;
+    PinBuf<PgoHostScal> h_scal;     // pinned + coherent: written by publish_kernel, polled by the host
     PgoHostScal* d_pub = nullptr;    // its device-side address
     uint32_t pub_seq = 0;
     PinBuf<double> h_lambda;

@@ -283,6 +283,73 @@ bool graph_grown(int n_old, const std::vector<uint8_t>& old_fixed, const std::ve
     return n_new >= n_old && (size_t)n_old <= old_fixed.size() && std::equal(old_fixed.begin(), old_fixed.begin() + n_old, new_fixed.begin()) &&
            edges_survive_in_order(old_ij, new_ij, window);
 }
+
+// uzl_pgo_rewrite_graph's host half: validation first (a refused rewrite changes nothing), then the two compactions.  The ops are the
+// actions of uzl_merge_plan (contract 6): KEEP_x multiplies one side's displacement, RETARGET_x also moves that endpoint, DELETE removes;
+// removeNode's edge removal (graph_slam_node.cpp:636-660) is the second rule - an edge that still names a dropped node goes with it.
+RewritePlan rewrite_plan(int n, const std::vector<InEdge>& in_edges, const std::vector<uint8_t>& fixed_in, const RewriteIn& rw)
+{
+    RewritePlan P;
+    const int e_in = (int)in_edges.size();
+    auto refuse = [&](const char* why) { P = RewritePlan(); P.why = why; return P; };
+    std::vector<uint8_t> dropped((size_t)n, 0), posed((size_t)n, 0);
+    for (int32_t v : rw.drop_nodes) {
+        if (v < 0 || v >= n) return refuse("drop_nodes: node index out of range");
+        if (dropped[v]) return refuse("drop_nodes: a node is listed twice");
+        dropped[v] = 1;
+    }
+    for (int32_t v : rw.pose_nodes) {
+        if (v < 0 || v >= n) return refuse("pose_nodes: node index out of range");
+        if (dropped[v]) return refuse("pose_nodes: the node is dropped");
+        if (posed[v]) return refuse("pose_nodes: a node is listed twice");
+        posed[v] = 1;
+    }
+    // per edge: what its ops leave of it
+    struct Touch { int32_t from, to, xf_from = -1, xf_to = -1; bool on_from = false, on_to = false, del = false; };
+    std::vector<Touch> T((size_t)e_in);
+    for (int k = 0; k < e_in; k++) { T[k].from = in_edges[k].from; T[k].to = in_edges[k].to; }
+    for (const RewriteOp& op : rw.ops) {
+        if (op.edge < 0 || op.edge >= e_in) return refuse("ops: edge index out of range");
+        Touch& t = T[op.edge];
+        if (op.action == UZL_MERGE_EDGE_DELETE) {
+            if (t.del || t.on_from || t.on_to) return refuse("ops: DELETE stands alone on its edge");
+            t.del = true;
+            continue;
+        }
+        const bool from_side = op.action == UZL_MERGE_EDGE_KEEP_FROM || op.action == UZL_MERGE_EDGE_RETARGET_FROM;
+        const bool to_side = op.action == UZL_MERGE_EDGE_KEEP_TO || op.action == UZL_MERGE_EDGE_RETARGET_TO;
+        if (!from_side && !to_side) return refuse("ops: unknown action");
+        if (t.del) return refuse("ops: DELETE stands alone on its edge");
+        if (from_side ? t.on_from : t.on_to) return refuse("ops: two ops on one side of an edge");
+        if (op.xf < 0 || op.xf >= rw.n_xf) return refuse("ops: xf index out of range");
+        const bool retarget = op.action == UZL_MERGE_EDGE_RETARGET_FROM || op.action == UZL_MERGE_EDGE_RETARGET_TO;
+        if (retarget && (op.node < 0 || op.node >= n)) return refuse("ops: RETARGET to a node out of range");
+        if (retarget && dropped[op.node]) return refuse("ops: RETARGET to a dropped node");
+        if (from_side) { t.on_from = true; t.xf_from = op.xf; if (retarget) t.from = op.node; }
+        else { t.on_to = true; t.xf_to = op.xf; if (retarget) t.to = op.node; }
+    }
+    P.old_to_new_node.assign((size_t)n, -1);
+    for (int v = 0; v < n; v++) {
+        if (dropped[v]) continue;
+        P.old_to_new_node[v] = (int32_t)P.new_to_old_node.size();
+        P.new_to_old_node.push_back(v);
+        P.fixed_in.push_back(fixed_in[v]);
+    }
+    auto names_dropped = [&](int32_t v) { return v >= 0 && v < n && dropped[v]; };
+    auto renumber = [&](int32_t v) { return (v >= 0 && v < n) ? P.old_to_new_node[v] : v; };
+    P.old_to_new_edge.assign((size_t)e_in, -1);
+    for (int k = 0; k < e_in; k++) {
+        const Touch& t = T[k];
+        if (t.del || names_dropped(t.from) || names_dropped(t.to)) continue;
+        P.old_to_new_edge[k] = (int32_t)P.new_to_old_edge.size();
+        P.new_to_old_edge.push_back(k);
+        P.rec.push_back({renumber(t.from), renumber(t.to), t.xf_from, t.xf_to});
+        InEdge ed = in_edges[k];
+        ed.from = P.rec.back().from_new; ed.to = P.rec.back().to_new;
+        P.in_edges.push_back(ed);
+    }
+    return P;
+}
 }  // namespace uzl
 
 #ifdef UZL_DIAG
@@ -398,6 +465,52 @@ extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_structure_plan(int32_t stage, const
         }
         const void* src = kind == 0 ? (const void*)oi.data() : kind == 1 ? (const void*)ob.data() : kind == 2 ? (const void*)od.data() : (const void*)ol.data();
         const int64_t bytes = kind == 0 ? (int64_t)oi.size() * 4 : kind == 1 ? (int64_t)ob.size() : kind == 2 ? (int64_t)od.size() * 8 : (int64_t)ol.size() * 8;
+        if (out && bytes) {
+            if (*nbytes < bytes) return UZL_ERR_BAD_ARG;
+            memcpy(out, src, (size_t)bytes);
+        }
+        *nbytes = bytes;
+        return UZL_OK;
+    } catch (const std::bad_alloc&) {
+        return UZL_ERR_OOM;
+    }
+}
+
+// rewrite_plan without a handle or a device (tests/test_pgo_rewrite_plan_cpu.py), one output array per call like the hook above.
+//   iv {n, e_in, n_drop, n_pose, n_xf, n_ops}; fixed [n]; in_edges [e_in][4] = {from, to, odom, valid}; drop [n_drop]; pose_nodes [n_pose];
+//   ops [n_ops][4] = {edge, action, xf, node} (uzl_pgo_edge_op).  A rewrite the plan refuses returns UZL_ERR_BAD_ARG, as uzl_pgo_rewrite_graph does.
+//   what 0 {n_new, e_new}, 1 old_to_new_node, 2 new_to_old_node, 3 old_to_new_edge, 4 new_to_old_edge, 5 the surviving edges' records
+//   [e_new][4] = {from_new, to_new, xf_from, xf_to}, 6 the new in_edges [e_new][4] (all i32), 7 the new fixed flags (u8)
+extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_rewrite_plan(const int32_t* iv, const uint8_t* fixed, const int32_t* in_edges, const int32_t* drop, const int32_t* pose_nodes,
+                                                          const int32_t* ops, int32_t what, void* out, int64_t* nbytes)
+{
+    using namespace uzl;
+    if (!iv || !nbytes || what < 0 || what > 7) return UZL_ERR_BAD_ARG;
+    const int n = iv[0], e_in = iv[1], n_drop = iv[2], n_pose = iv[3], n_xf = iv[4], n_ops = iv[5];
+    if (n < 0 || e_in < 0 || n_drop < 0 || n_pose < 0 || n_xf < 0 || n_ops < 0 || (n > 0 && !fixed) || (e_in > 0 && !in_edges) || (n_drop > 0 && !drop) ||
+        (n_pose > 0 && !pose_nodes) || (n_ops > 0 && !ops))
+        return UZL_ERR_BAD_ARG;
+    try {
+        std::vector<InEdge> in((size_t)e_in);
+        for (int k = 0; k < e_in; k++) in[k] = {in_edges[4 * k], in_edges[4 * k + 1], (uint8_t)(in_edges[4 * k + 2] ? 1 : 0), (uint8_t)(in_edges[4 * k + 3] ? 1 : 0), 1.};
+        RewriteIn rw;
+        rw.drop_nodes.assign(drop, drop + n_drop); rw.pose_nodes.assign(pose_nodes, pose_nodes + n_pose); rw.n_xf = n_xf;
+        for (int q = 0; q < n_ops; q++) rw.ops.push_back({ops[4 * q], ops[4 * q + 1], ops[4 * q + 2], ops[4 * q + 3]});
+        const RewritePlan P = rewrite_plan(n, in, std::vector<uint8_t>(fixed, fixed + n), rw);
+        if (P.why) return UZL_ERR_BAD_ARG;
+        std::vector<int32_t> oi;
+        switch (what) {
+        case 0: oi = {(int32_t)P.new_to_old_node.size(), (int32_t)P.new_to_old_edge.size()}; break;
+        case 1: oi = P.old_to_new_node; break;
+        case 2: oi = P.new_to_old_node; break;
+        case 3: oi = P.old_to_new_edge; break;
+        case 4: oi = P.new_to_old_edge; break;
+        case 5: for (const RewriteEdge& r : P.rec) oi.insert(oi.end(), {r.from_new, r.to_new, r.xf_from, r.xf_to}); break;
+        case 6: for (const InEdge& ed : P.in_edges) oi.insert(oi.end(), {ed.from, ed.to, (int32_t)ed.odom, (int32_t)ed.valid}); break;
+        default: break;
+        }
+        const void* src = what == 7 ? (const void*)P.fixed_in.data() : (const void*)oi.data();
+        const int64_t bytes = what == 7 ? (int64_t)P.fixed_in.size() : (int64_t)oi.size() * 4;
         if (out && bytes) {
             if (*nbytes < bytes) return UZL_ERR_BAD_ARG;
             memcpy(out, src, (size_t)bytes);

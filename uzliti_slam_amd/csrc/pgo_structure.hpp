@@ -72,4 +72,26 @@ ExchangeLayout exchange_layout(int nbp, const MlPlan& P);
 bool edges_survive_in_order(const std::vector<int32_t>& old_ij, const std::vector<int32_t>& new_ij, size_t window = 4096);
 bool graph_grown(int n_old, const std::vector<uint8_t>& old_fixed, const std::vector<int32_t>& old_ij, int n_new, const std::vector<uint8_t>& new_fixed,
                  const std::vector<int32_t>& new_ij, size_t window = 4096);
+
+// The resident graph SHRUNK in place (uzl_pgo_rewrite_graph): nodes leave, edges are deleted, retargeted or take a left multiplier on
+// one side's displacement; what survives closes up in its order.  The rewrite as the caller states it (the fields of uzl_pgo_rewrite,
+// minus the values: which multiplier and which pose are indices here) ...
+struct RewriteOp { int32_t edge, action, xf, node; };          // uzl_pgo_edge_op
+struct RewriteIn {
+    std::vector<int32_t> drop_nodes, pose_nodes;
+    int32_t n_xf = 0;
+    std::vector<RewriteOp> ops;
+};
+// ... and what it does to a graph of n nodes with these input edges.  why != nullptr: the rewrite is refused (nothing else is filled).
+// An edge goes if it has a DELETE op or if, after its ops, it still names a dropped node; endpoints outside [0, n) stay as they are.
+struct RewriteEdge { int32_t from_new, to_new, xf_from, xf_to; };      // per surviving edge: its endpoints in the new numbering, the multiplier of either side (-1: untouched)
+struct RewritePlan {
+    const char* why = nullptr;
+    std::vector<int32_t> old_to_new_node, new_to_old_node;     // -1: dropped
+    std::vector<int32_t> old_to_new_edge, new_to_old_edge;     // -1: deleted
+    std::vector<RewriteEdge> rec;                              // [surviving edges]
+    std::vector<InEdge> in_edges;                              // the new graph's, for flatten_edges
+    std::vector<uint8_t> fixed_in;
+};
+RewritePlan rewrite_plan(int n, const std::vector<InEdge>& in_edges, const std::vector<uint8_t>& fixed_in, const RewriteIn& rw);
 }  // namespace uzl

@@ -8,6 +8,7 @@
 #include "merge_types.hpp"
 #include "pgo_handle.hpp"
 #include "pgo_lm.hpp"
+#include "pgo_rewrite.hpp"
 #include "scope_types.hpp"
 #include "uzl_streams.hpp"
 
@@ -1119,6 +1120,81 @@ int uzl_pgo_append_graph(uzl_pgo* h, int32_t n_new_nodes, const uzl_node* new_no
                     h->d_zinv.p, h->d_info.p, s);
     UZL_HIP(hipGetLastError());
     finish_graph(h, old_key);
+    return UZL_OK;
+    UZL_GUARD_END(h)
+}
+
+int uzl_pgo_rewrite_graph(uzl_pgo* h, const uzl_pgo_rewrite* rw, int32_t cap_nodes, int32_t* old_to_new_node, int32_t cap_edges, int32_t* old_to_new_edge)
+{
+    UZL_GUARD_BEGIN(h)
+    if (!rw || rw->n_drop < 0 || rw->n_pose < 0 || rw->n_xf < 0 || rw->n_ops < 0 || (rw->n_drop > 0 && !rw->drop_nodes) ||
+        (rw->n_pose > 0 && (!rw->pose_nodes || !rw->poses)) || (rw->n_xf > 0 && !rw->xf) || (rw->n_ops > 0 && !rw->ops))
+        return fail(h, UZL_ERR_BAD_ARG, "null or negative-size input");
+    if (!h->have_graph || !h->in_ready) return fail(h, UZL_ERR_BAD_ARG, "uzl_pgo_rewrite_graph needs a graph from uzl_pgo_add_graph to shrink");
+    const int32_t n_old = h->n, e_old = h->e_in;
+    if ((old_to_new_node && cap_nodes < n_old) || (old_to_new_edge && cap_edges < e_old)) return fail(h, UZL_ERR_BAD_ARG, "a map's capacity is below the old count");
+    // ---- the plan (pgo_structure.hpp): a refused rewrite has changed nothing
+    RewriteIn in;
+    in.drop_nodes.assign(rw->drop_nodes, rw->drop_nodes + rw->n_drop);
+    in.pose_nodes.assign(rw->pose_nodes, rw->pose_nodes + rw->n_pose);
+    in.n_xf = rw->n_xf;
+    in.ops.resize((size_t)rw->n_ops);
+    for (int q = 0; q < rw->n_ops; q++) in.ops[q] = {rw->ops[q].edge, rw->ops[q].action, rw->ops[q].xf, rw->ops[q].node};
+    RewritePlan P = rewrite_plan(n_old, h->in_edges, h->fixed_in, in);
+    if (P.why) return fail(h, UZL_ERR_BAD_ARG, P.why);
+    const int32_t n_new = (int32_t)P.new_to_old_node.size(), e_new = (int32_t)P.new_to_old_edge.size();
+    UZL_HIP(hipSetDevice(h->cfg.device));
+    const StructureKey old_key = begin_graph(h, n_new);
+    hipStream_t s = h->stream;
+    // ---- the plan on the device: [records | new_to_old_edge | node sources], [xf | placed poses]
+    std::vector<int32_t> idx((size_t)5 * e_new + n_new);
+    static_assert(sizeof(RewriteEdge) == 16, "rewrite_edges_kernel reads a record as one int4");
+    if (e_new) {
+        memcpy(idx.data(), P.rec.data(), sizeof(RewriteEdge) * (size_t)e_new);
+        memcpy(idx.data() + (size_t)4 * e_new, P.new_to_old_edge.data(), sizeof(int32_t) * (size_t)e_new);
+    }
+    int32_t* node_src = idx.data() + (size_t)5 * e_new;
+    for (int v = 0; v < n_new; v++) node_src[v] = P.new_to_old_node[v];
+    for (int q = 0; q < rw->n_pose; q++) node_src[P.old_to_new_node[rw->pose_nodes[q]]] = ~q;
+    std::vector<uzl_node> placed((size_t)rw->n_pose);
+    for (int q = 0; q < rw->n_pose; q++) { memcpy(placed[q].pose, rw->poses + 12 * (size_t)q, sizeof(double) * 12); placed[q].fixed = 0; }
+    h->d_rw_idx.reserve(std::max<size_t>(idx.size(), 1));
+    h->d_rw_val.reserve(std::max<size_t>((size_t)12 * rw->n_xf + (size_t)8 * rw->n_pose, 1));
+    h->d_edges_spare.reserve((size_t)std::max(e_new, 1));
+    h->d_nodes.reserve((size_t)std::max(rw->n_pose, 1));
+    double* d_xf = h->d_rw_val.p;
+    double* d_placed = d_xf + (size_t)12 * rw->n_xf;
+    if (!idx.empty()) UZL_HIP(hipMemcpyAsync(h->d_rw_idx.p, idx.data(), sizeof(int32_t) * idx.size(), hipMemcpyHostToDevice, s));
+    if (rw->n_xf) UZL_HIP(hipMemcpyAsync(d_xf, rw->xf, sizeof(double) * 12 * (size_t)rw->n_xf, hipMemcpyHostToDevice, s));
+    if (rw->n_pose) UZL_HIP(hipMemcpyAsync(h->d_nodes.p, placed.data(), sizeof(uzl_node) * (size_t)rw->n_pose, hipMemcpyHostToDevice, s));
+    // ---- the two compactions, out of place: the edge records into the spare buffer, the estimates into the other pose buffer
+    //      (pose_nodes: prepared as add_graph prepares a node pose, by the same kernel, then placed by the gather)
+    k_prepare_nodes(h->d_nodes.p, rw->n_pose, h->cfg.optimize_xy_only, d_placed, s);
+    {
+        hipEvent_t ea = nullptr, eb = nullptr;
+        if (e_new > 0) h->timer.pair("rewrite_edges", &ea, &eb);
+        k_rewrite_edges(h->d_edges.p, h->d_edges_spare.p, h->d_rw_idx.p + (size_t)4 * e_new, h->d_rw_idx.p, e_new, d_xf, s, ea, eb);
+        ea = eb = nullptr;
+        if (n_new > 0) h->timer.pair("rewrite_nodes", &ea, &eb);
+        k_rewrite_nodes(h->cur, d_placed, h->d_rw_idx.p + (size_t)5 * e_new, n_new, h->trial, s, ea, eb);
+    }
+    std::swap(h->d_edges.p, h->d_edges_spare.p); std::swap(h->d_edges.cap, h->d_edges_spare.cap);
+    std::swap(h->cur, h->trial);
+    // ---- from here on as uzl_pgo_append_graph: the new graph's host side, its system edges, their values from the resident records
+    h->n = n_new; h->e_in = e_new;
+    h->fixed_in.swap(P.fixed_in);
+    h->in_edges.swap(P.in_edges);
+    flatten_edges(h);
+    alloc_problem(h, true);
+    h->d_src.reserve((size_t)std::max(h->e, 1));
+    if (h->e) UZL_HIP(hipMemcpyAsync(h->d_src.p, h->src.data(), sizeof(int32_t) * (size_t)h->e, hipMemcpyHostToDevice, s));
+    k_prepare_edges(h->d_edges.p, h->d_src.p, h->e, h->d_stage.p, h->n_sensors_in, h->cfg.optimize_xy_only, h->cfg.use_odometry_parameters,
+                    h->d_zinv.p, h->d_info.p, s);
+    UZL_HIP(hipGetLastError());
+    finish_graph(h, old_key);                                            // (synchronises: idx / placed are locals)
+    h->timer.resolve();
+    if (old_to_new_node && n_old) memcpy(old_to_new_node, P.old_to_new_node.data(), sizeof(int32_t) * (size_t)n_old);
+    if (old_to_new_edge && e_old) memcpy(old_to_new_edge, P.old_to_new_edge.data(), sizeof(int32_t) * (size_t)e_old);
     return UZL_OK;
     UZL_GUARD_END(h)
 }

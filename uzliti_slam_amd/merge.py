@@ -1,5 +1,6 @@
-"""Applying a merge plan (capi.Merge.plan, uzl_merge_plan) to the caller's arrays: no resident handle is rewritten in place, the
-compacted arrays this returns go to the existing set_graph / add_graph calls."""
+"""Applying a merge plan (capi.Merge.plan, uzl_merge_plan).  apply_merge_plan rewrites the caller's arrays: the compacted arrays it
+returns go to the set_graph of the gate, scope and merge handles (and are the host restatement of the rewrite).  The solver's resident
+graph takes a merge or a scope drop in place: pgo_rewrite_of_plan / pgo_rewrite_of_drops make the arguments of capi.Pgo.rewrite_graph."""
 import numpy as np
 
 from . import capi
@@ -54,7 +55,29 @@ def apply_merge_plan(poses, edges, displacements, plan):
     return np.delete(P, drop, axis=0), E, (D_from[alive], D_to[alive]), old_to_new
 
 
-SENSOR_TYPE_FEATURE, SENSOR_TYPE_BINARY_GIST, SENSOR_TYPE_LASERSCAN = 1, 3, 4        # graph_slam_msgs/msg/SensorData.msg:3-6
+def pgo_rewrite_of_plan(plan):
+    """The merge plan as the arguments of capi.Pgo.rewrite_graph (uzl_pgo_rewrite_graph): the solver's resident graph takes the merge
+    in place, p.rewrite_graph(**pgo_rewrite_of_plan(plan)).  drop leaves, keep takes new_pose, xf = [keep_displacement,
+    drop_displacement], one op per edge the plan touches.
+    Precondition: the edge order of the merge handle the plan came from is the solver's input-edge order (the edges of add_graph, then
+    those of every append_graph, less what earlier rewrites removed) - plan["action"][k] is applied to the solver's input edge k."""
+    keep, drop, action = int(plan["keep"]), int(plan["drop"]), np.asarray(plan["action"])
+    ops = np.zeros(int((action != capi.MERGE_EDGE_UNTOUCHED).sum()), capi.PGO_EDGE_OP_DTYPE)
+    touched = np.flatnonzero(action != capi.MERGE_EDGE_UNTOUCHED)
+    ops["edge"] = touched; ops["action"] = action[touched]; ops["node"] = keep
+    ops["xf"] = np.isin(action[touched], (capi.MERGE_EDGE_RETARGET_FROM, capi.MERGE_EDGE_RETARGET_TO))        # (0 keep_displacement, 1 drop_displacement)
+    return dict(drop_nodes=np.array([drop], np.int32), pose_nodes=np.array([keep], np.int32),
+                poses=np.asarray(plan["new_pose"], np.float64).reshape(1, 12),
+                xf=np.stack([np.asarray(plan["keep_displacement"], np.float64), np.asarray(plan["drop_displacement"], np.float64)]).reshape(2, 12), ops=ops)
+
+
+def pgo_rewrite_of_drops(nodes):
+    """Nodes that leave the local scope (capi.Scope.request) as the arguments of capi.Pgo.rewrite_graph: they go, and with them every
+    edge that names one of them (removeNode, graph_slam_node.cpp:636-660); nothing else is touched."""
+    return dict(drop_nodes=np.ascontiguousarray(nodes, np.int32).reshape(-1))
+
+
+SENSOR_TYPE_FEATURE, SENSOR_TYPE_BINARY_GIST, SENSOR_TYPE_LASERSCAN = 1, 3, 4       # graph_slam_msgs/msg/SensorData.msg:3-6
 SENSOR_MERGE, SENSOR_MOVE, SENSOR_DISCARD = "merge", "move", "discard"
 
 
