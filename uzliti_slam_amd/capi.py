@@ -1305,7 +1305,7 @@ LM_VIEW_INTS = ("phase", "need", "it", "iterations", "sync_rebuild", "pending", 
 LM_VIEW_DOUBLES = ("last_rel", "refresh_rel", "rate_ref", "rate_last", "rate_drop", "lambda", "lambda_setup0", "lambda_setup1", "tol2")
 LM_TRACK = ("job", "active", "no_history", "solve_passes", "prev_last", "cur_last", "seen_trials")
 LM_PLAN = ("flags", "want", "base", "ix", "ns_steps", "setup_captured", "any_start")
-_LM_PASS_STAGES = dict(plan=0, launches=1, replay=2, host_batches=3, handover=4)
+_LM_PASS_STAGES = dict(plan=0, launches=1, replay=2, host_batches=3, handover=4, init_rides=5)
 
 
 def lm_pass_plan(stage, **kw):
@@ -1317,7 +1317,8 @@ def lm_pass_plan(stage, **kw):
       replay       n_slots, jobs = [dict(no_history, hist)], events = ("plan",) | ("look", slot, view) | ("load", slot, job or -1, view),
                    first_solve_its, shape_ns_steps, wrong_ix                          -> plans, tracks, first_solve_its, trial_its (per job)
       host_batches prev, max_it, end_round                                                        -> the host-driven solve's batch sizes
-      handover     old = [dict(gen, prev, cur)] (the last drive's jobs), new_gens                 -> prev (per new job), cur_sizes, hist_gen"""
+      handover     old = [dict(gen, prev, cur)] (the last drive's jobs), new_gens                 -> prev (per new job), cur_sizes, hist_gen
+      init_rides   flags, any_start, pcg_args_pass, reduced                   -> True: the pass's PCG init goes out in the head's launch"""
     L = diag_lib()
     i32 = lambda a: np.ascontiguousarray(a if a is not None else [], np.int32).reshape(-1)
 
@@ -1381,6 +1382,8 @@ def lm_pass_plan(stage, **kw):
                  hist=i32([c for j in old for c in list(j["prev"]) + list(j["cur"])]))
         r = run(what=1, **a)
         return dict(prev=rows_out(run(what=0, **a), len(new)), cur_sizes=[int(x) for x in r[:len(new)]], hist_gen=[int(x) for x in r[len(new):]])
+    if stage == "init_rides":
+        return bool(run([kw["flags"], 1 if kw["any_start"] else 0, 1 if kw["pcg_args_pass"] else 0, 1 if kw["reduced"] else 0], 0)[0])
     raise ValueError(stage)
 
 

@@ -68,7 +68,10 @@ void kl_ml_trial(const LmSlot* sl, const LmShape& sh, int which, int ns_steps, h
 void kl_ml_numeric(const HostSlot& hs, const LmShape& sh, hipStream_t s, KernelTimer* timer, const std::function<void()>& level1_done);
 void kl_ml_trial(const HostSlot& hs, const LmShape& sh, int ns_steps, hipStream_t s, KernelTimer* timer);
 void ml_cg_variant(const MlHot& ml, int agg, size_t lds_full, int32_t* variant, int32_t* comp_u, uint64_t* lds);
-hipError_t kl_ml_init(const LmSlot* sl, const LmSlot* by_value, const LmShape& sh, int ix, hipStream_t s);
+hipError_t kl_ml_init(const LmSlot* sl, const LmSlot* by_value, const LmShape& sh, int ix, bool in_head, hipStream_t s);
+// a one-graph pass of the small-graph class may send its PCG init as further workgroups of the head's launch (lm_init_rides, pgo_lm_pass.hpp)
+bool lm_init_rides_shape(const LmSlot* by_value, const LmShape& sh);
+void kl_lm_head_init(const LmSlot* sl, const LmSlot* by_value, int pass_flags, int ix, hipStream_t s);
 hipError_t kl_ml_pcg_its(const LmSlot* sl, const LmSlot* by_value, const LmShape& sh, int ix, double tol2, int first, int n, hipStream_t s, hipEvent_t* ev = nullptr);
 // the same PCG kernels for the host-driven loop (pgo_types.hpp: HostSlot): init, and the two launches of iteration `parity` one by one
 void kl_ml_pcg_init(const HostSlot& hs, const LmShape& sh, hipStream_t s);

@@ -161,6 +161,15 @@ inline LmPassPlan lm_plan_pass(const LmPlanView* views, LmSlotTrack* tracks, int
     return P;
 }
 
+// Does the PCG init of this pass go out as further workgroups of the head's launch (lm_head_init_pcg_kernel) instead of a launch of
+// its own?  pcg_args_pass: one graph of the small-graph class, launched by value (PcgArgs); reduced: its PCG solves the Schur complement.
+// Not with a synchronous set-up in the pass - it rewrites the geometry of the hierarchy copy in use behind the head, and the init reads
+// it - and not on a reduced system, whose right-hand side the reduction behind the head makes.  (A rebuild runs on the other copy.)
+inline bool lm_init_rides(const LmPassPlan& P, bool pcg_args_pass, bool reduced)
+{
+    return P.any_start && !(P.flags & kPassSetup) && pcg_args_pass && !reduced;
+}
+
 // How a pass's `want` iterations from index `base` go out: short solves are launched kernel by kernel, long ones as captured replays of
 // kPcgLong iterations plus a remainder.  The captured replay starts at an even iteration: one single launch in front where base is odd.
 struct LmPcgLaunches {

@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "pgo_device.hpp"
+#include "pgo_lm_head.hpp"
 #include "uzl_common.hpp"
 
 namespace uzl {
@@ -1322,17 +1323,20 @@ __device__ __forceinline__ double p1_comp(const double* geo, const double* y, in
 }
 
 // x = 0, r = b, p0 = p1 = 0, flags cleared; exact gather-level residual of the own aggregates -> rg
-template <int AGG>
+// (kFlags = false, kThreads = kBlk, bx: the workgroups that ride in the head's launch - lm_head_init_pcg_kernel below.  The head clears
+//  the flags itself there, and lanes past kCgBlk own no row.)
+template <int AGG, bool kFlags = true, int kThreads = kCgBlk>
 __device__ __forceinline__ void ml_init_kernel_body(PgoDev D, MlHot H, double* __restrict__ p0, double* __restrict__ p1,
-                                                        double* __restrict__ rg)
+                                                        double* __restrict__ rg, int bx = blockIdx.x)
 {
     constexpr int kRowsPerBlk = kMlFanout * AGG, kAggPerBlk = AGG;
-    __shared__ double sv[kCgBlk];
-    __shared__ double sw[kCgBlk];
+    static_assert(kThreads >= kCgBlk, "the first 48 * AGG lanes own a (row, component)");
+    __shared__ double sv[kThreads];
+    __shared__ double sw[kThreads];
     __shared__ double sr1[kAggPerBlk * 6];
     const int tid = threadIdx.x;
     const int gl = (AGG == 1 || H.levels < 2) ? 1 : 2;
-    const int a = blockIdx.x * kRowsPerBlk + tid / 6, r = tid % 6;
+    const int a = bx * kRowsPerBlk + tid / 6, r = tid % 6;
     const bool act = tid < kRowsPerBlk * 6 && a < D.nb;
     double rv = 0., geo[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (act) {
@@ -1350,7 +1354,7 @@ __device__ __forceinline__ void ml_init_kernel_body(PgoDev D, MlHot H, double* _
     __syncthreads();
     const int n1 = H.n[1];
     if (tid < kAggPerBlk * 6) {
-        const int la = tid / 6, k = tid % 6, A1 = blockIdx.x * kAggPerBlk + la;
+        const int la = tid / 6, k = tid % 6, A1 = bx * kAggPerBlk + la;
         double s = 0.;
 #pragma unroll
         for (int j = 0; j < kMlFanout; j++) s += sw[(la * kMlFanout + j) * 6 + k];
@@ -1361,12 +1365,12 @@ __device__ __forceinline__ void ml_init_kernel_body(PgoDev D, MlHot H, double* _
     if (gl == 2 && tid < 6) {
         double s = 0.;
         for (int la = 0; la < kAggPerBlk; la++) {
-            const int A1 = blockIdx.x * kAggPerBlk + la;
+            const int A1 = bx * kAggPerBlk + la;
             if (A1 < n1) s += restrict_comp(H.geo[1] + (size_t)A1 * 3, sr1 + la * 6, tid);
         }
-        rg[(size_t)blockIdx.x * 6 + tid] = s;
+        rg[(size_t)bx * 6 + tid] = s;
     }
-    if (blockIdx.x == 0 && tid == 0) { D.flags[0] = 0; D.flags[1] = 0; D.flags[2] = 0; D.flags[3] = 0; D.scal[2] = 1.; }
+    if (kFlags && bx == 0 && tid == 0) { D.flags[0] = 0; D.flags[1] = 0; D.flags[2] = 0; D.flags[3] = 0; D.scal[2] = 1.; }
 }
 
 // A launch that was given another hierarchy copy than the graph's LM state names (pgo_types.hpp: PcgArgs) does no work and ends the
@@ -2653,6 +2657,18 @@ __global__ __launch_bounds__(kCgBlk) void ml_init_pcg_kernel(const PcgArgs A)
     }
     ml_init_kernel_body<1>(pcg_dev(A), pcg_hot(A), A.pbuf[0], A.pbuf[1], A.rg[0]);
 }
+// The head of a one-graph pass with that pass's PCG init beside it: workgroup 0 is lm_head_kernel's, workgroups 1 .. g_rows are
+// ml_init_pcg_kernel's (the shape of ml_top_tiles riding in ml_inverses).  The init workgroups read nothing the head rewrites in this
+// launch: the hierarchy copy comes by value (A.ix, lm_pass_ix on the snapshot the pass starts from - the host holds the state of its
+// one graph exactly), b is the linearisation's, and the flags and rz_prev are the head's to clear (lm_head_decide).  They run whatever
+// the head decides: where it stalls the graph for a set-up segment the next pass initialises again, and a copy that is not the
+// state's is caught by ml_cg_comp_pcg's first application, which still follows.  Not for a pass with a synchronous set-up (it
+// rewrites geo0 of the copy in use behind the head) and not for a Schur-reduced system (b is the reduction's): lm_init_rides.
+__global__ __launch_bounds__(kBlk) void lm_head_init_pcg_kernel(const LmSlot* __restrict__ slots, int pass_flags, const PcgArgs A)
+{
+    if (blockIdx.x == 0) { lm_head_body(slots[0], pass_flags); return; }
+    ml_init_kernel_body<1, false, kBlk>(pcg_dev(A), pcg_hot(A), A.pbuf[0], A.pbuf[1], A.rg[0], (int)blockIdx.x - 1);
+}
 // ml_spmv: what its FIRST loads and their predicates read - the r.z partials, the stop test's maxima, the done flag with the LM
 // state's ix word, the scalars, the row header - travels in front of the struct as plain pointer and integer parameters.  The build
 // preloads those into SGPRs (Makefile: -amdgpu-kernarg-preload-count), so the first loads are sent at the wave's start, and the
@@ -2833,16 +2849,27 @@ static void pcg_cg(const PcgArgs& A, int comp_u, int parity, int init, hipStream
 // x = 0, r = b, first application of the preconditioner - for the graphs whose solve starts in this pass.  by_value: the pass has one
 // graph and `by_value` is its slot (the device table `sl` is what every other twin reads); ix: the hierarchy copy its PCG applies in
 // this pass, as the host predicts it (pgo_lm.hpp: lm_pass_ix) - the small-graph class hands it over by value and checks it on the device
-hipError_t kl_ml_init(const LmSlot* sl, const LmSlot* by_value, const LmShape& sh, int ix, hipStream_t s)
+// in_head: x = 0, r = b went out with the pass's head (kl_lm_head_init): the first application only
+hipError_t kl_ml_init(const LmSlot* sl, const LmSlot* by_value, const LmShape& sh, int ix, bool in_head, hipStream_t s)
 {
     if (by_value && pcg_args_shape(sh)) {
         const PcgArgs A = make_pcg_args(*by_value, by_value->lm, ix, 0.);     // (tol2 is ml_spmv's)
-        pcg_init(A, s); pcg_cg(A, sh.comp_u, 0, 1, s);
+        if (!in_head) pcg_init(A, s);
+        pcg_cg(A, sh.comp_u, 0, 1, s);
         return hipSuccess;
     }
+    if (in_head) return hipErrorInvalidValue;
     if (by_value && sh.nslots == 1) { kl_ml_init_t<LmSlot>(*by_value, sh, s); return kl_ml_cg_t<LmSlot>(*by_value, sh, 0, 1, s); }
     kl_ml_init_t<const LmSlot*>(sl, sh, s);
     return kl_ml_cg_t<const LmSlot*>(sl, sh, 0, 1, s);
+}
+// can a pass of this shape carry its PCG init in the head's launch (lm_init_rides, pgo_lm_pass.hpp, takes the pass's part of the rule)
+bool lm_init_rides_shape(const LmSlot* by_value, const LmShape& sh) { return by_value && pcg_args_shape(sh); }
+// lm_head_kernel and ml_init_pcg_kernel of a one-graph pass in one launch
+void kl_lm_head_init(const LmSlot* sl, const LmSlot* by_value, int pass_flags, int ix, hipStream_t s)
+{
+    const PcgArgs A = make_pcg_args(*by_value, by_value->lm, ix, 0.);
+    hipLaunchKernelGGL(lm_head_init_pcg_kernel, dim3(1 + A.g_rows), dim3(kBlk), 0, s, sl, pass_flags, A);
 }
 // PCG iterations first .. first + n - 1 of a solve (iteration i: p_old = pbuf[i & 1], p_new = pbuf[(i & 1) ^ 1]).  ev (profiling only, may
 // be null): 4 events per iteration - spmv start / stop, cg start / stop (dispatch timestamps; the batch's kernels)

@@ -464,6 +464,8 @@ extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_trial(uzl_pgo* h, const double* dx,
 //   stage 4 lm_history_begin  iv {Q_old, Q_new}; vi = structure generations: Q_old of the last drive, then Q_new of this one; tr [Q_old][2] =
 //                           {n_prev, n_cur}; hist = per old job its trial_its_prev row, then its trial_its_cur row.
 //                           what 0 per new job {n, counts} of trial_its_prev afterwards, 1 {sizes of trial_its_cur [Q_new], hist_gen [Q_new]} (i32)
+//   stage 5 lm_init_rides   iv {flags, any_start, pcg_args_pass, reduced}: a pass with these segments, of a graph launched by value / whose
+//                           PCG solves a Schur complement.             what 0 {1: its PCG init goes out in the head's launch} (i32)
 extern "C" UZL_DIAG_EXPORT int uzl_debug_lm_pass_plan(int32_t stage, const int32_t* iv, const int32_t* vi, const double* vd, const int32_t* tr, const int32_t* hist,
                                                      const int32_t* ev, int32_t what, void* out, int64_t* nbytes)
 {
@@ -575,6 +577,13 @@ extern "C" UZL_DIAG_EXPORT int uzl_debug_lm_pass_plan(int32_t stage, const int32
                 for (const std::vector<int>& c : H.trial_its_cur) oi.push_back((int32_t)c.size());
                 for (uint64_t g : H.hist_gen) oi.push_back((int32_t)g);
             }
+            break;
+        }
+        case 5: {
+            if (what > 0) return UZL_ERR_BAD_ARG;
+            LmPassPlan P;
+            P.flags = iv[0]; P.any_start = iv[1] != 0;
+            oi = {lm_init_rides(P, iv[2] != 0, iv[3] != 0) ? 1 : 0};
             break;
         }
         default: return UZL_ERR_BAD_ARG;

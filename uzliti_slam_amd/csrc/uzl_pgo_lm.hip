@@ -8,7 +8,8 @@
 //     head  = linearise, assemble | lm_head (chi2, lambda_0, adoption, refresh decision, setLambda) | [Schur reduction]
 //     setup = numeric + trial part of the hierarchy copy in use        (first iteration; synchronous rebuilds; lambda grown 32x)
 //     reb   = rebuild of the OTHER copy on the second stream           (lazy refresh: adopted by the next iteration)
-//     init  = x = 0, r = b, first application of the preconditioner
+//     init  = x = 0, r = b, first application of the preconditioner  (x = 0, r = b of one small graph: workgroups of the head's launch,
+//             unless the pass has a set-up segment or the system is Schur-reduced - lm_init_rides, pgo_lm_pass.hpp)
 //     pcg   = K iterations                                             (no-ops once the solve's `done` flag is set)
 //     tail  = [back-substitution], retraction, chi2 | lm_tail (residual guard, rho, accept / reject, next phase, snapshot for the host)
 // The host enqueues a pass, looks at the snapshot ONCE, and chooses the next pass's segments and K from it (lm_plan_pass,
@@ -83,11 +84,14 @@ void enq_linearize(LmRun* R, hipStream_t s)
     const LmShape& sh = R->shape;
     UZL_HIP(kl_linearize(R->d_slots.p, sh.nslots, sh.g_edges, sh.g_asm, s));
 }
-void enq_head(LmRun* R, int pass_flags, bool linearized, hipStream_t s)
+const LmSlot* by_value_slot(LmRun* R) { return (R->shape.nslots == 1 && !R->shape.batch_geometry) ? R->slots.data() : nullptr; }
+// init_ix >= 0: the pass's PCG init rides in the head's launch (lm_init_rides), for hierarchy copy init_ix
+void enq_head(LmRun* R, int pass_flags, bool linearized, int init_ix, hipStream_t s)
 {
     const LmShape& sh = R->shape;
     if (!linearized) enq_linearize(R, s);
-    k_lm_head(R->d_slots.p, sh.nslots, pass_flags, s);
+    if (init_ix >= 0) kl_lm_head_init(R->d_slots.p, by_value_slot(R), pass_flags, init_ix, s);
+    else k_lm_head(R->d_slots.p, sh.nslots, pass_flags, s);
     if (sh.red) kl_schur_reduce(R->d_slots.p, sh, s);
 }
 void enq_setup(LmRun* R, int which, int ns_steps, hipStream_t s)
@@ -95,9 +99,9 @@ void enq_setup(LmRun* R, int which, int ns_steps, hipStream_t s)
     kl_ml_numeric(R->d_slots.p, R->shape, which, s);
     kl_ml_trial(R->d_slots.p, R->shape, which, ns_steps, s);
 }
-const LmSlot* by_value_slot(LmRun* R) { return (R->shape.nslots == 1 && !R->shape.batch_geometry) ? R->slots.data() : nullptr; }
 // ix, tol2: the hierarchy copy of a one-graph pass (lm_pass_ix) and its pcg_tol^2, by value to the small-graph class's launches
-void enq_init(LmRun* R, int ix, hipStream_t s) { UZL_HIP(kl_ml_init(R->d_slots.p, by_value_slot(R), R->shape, ix, s)); }
+// (in_head: x = 0, r = b went out with the head - the first application of the preconditioner is what is left)
+void enq_init(LmRun* R, int ix, bool in_head, hipStream_t s) { UZL_HIP(kl_ml_init(R->d_slots.p, by_value_slot(R), R->shape, ix, in_head, s)); }
 void enq_pcg(LmRun* R, int ix, double tol2, int first, int n, hipStream_t s, hipEvent_t* ev = nullptr)
 {
     UZL_HIP(kl_ml_pcg_its(R->d_slots.p, by_value_slot(R), R->shape, ix, tol2, first, n, s, ev));
@@ -327,7 +331,7 @@ void load_slot(LmDrive& d, int sl, bool first)
     d.views[sl] = lm_plan_view(I);
 }
 
-// One pass as the plan says: join wait | head | set-up | fork, rebuild, join record | init | PCG | tail | linearise-ahead
+// One pass as the plan says: join wait | head [+ init] | set-up | fork, rebuild, join record | init | PCG | tail | linearise-ahead
 void enqueue_pass(LmDrive& d, const LmPassPlan& P)
 {
     LmRun* R = d.R;
@@ -336,7 +340,8 @@ void enqueue_pass(LmDrive& d, const LmPassPlan& P)
     d.phases.mark(0, s);
     if (P.any_start && R->join_pending) { UZL_HIP(hipStreamWaitEvent(s, R->ev_join, 0)); R->join_pending = false; }      // the rebuild of an earlier pass reads H and the poses
     d.phases.mark(1, s);
-    if (P.any_start) enq_head(R, P.flags, d.lin_ahead, s);
+    const bool init_in_head = lm_init_rides(P, lm_init_rides_shape(by_value_slot(R), R->shape), R->shape.red != 0);
+    if (P.any_start) enq_head(R, P.flags, d.lin_ahead, init_in_head ? P.ix : -1, s);
     d.lin_ahead = false;
     d.phases.mark(2, s);
     if (P.flags & kPassSetup) {
@@ -351,7 +356,7 @@ void enqueue_pass(LmDrive& d, const LmPassPlan& P)
         R->join_pending = true;
     }
     d.phases.mark(3, s);
-    if (P.any_start) enq_init(R, P.ix, s);
+    if (P.any_start) enq_init(R, P.ix, init_in_head, s);
     d.phases.mark(4, s);
     if (d.timed()) {
         KernelTimer* tm = d.o.timer;
