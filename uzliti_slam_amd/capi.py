@@ -1387,6 +1387,45 @@ def lm_pass_plan(stage, **kw):
     raise ValueError(stage)
 
 
+# the rows uzl_debug_lm_decide reads and writes (csrc/uzl_pgo_debug.hip): an LM state (LmDev, csrc/pgo_types.hpp)
+LM_STATE_INTS = ("done", "pcg_its", "breakdown", "look", "phase", "cur", "ix", "pass", "init_pass", "schur_pass", "numeric_pass", "trial_pass", "build_pass",
+                 "build_ix", "build_cur", "need", "it", "qmax", "iterations", "max_it", "pending", "adopted", "fresh", "pcg_last", "sync_rebuild", "guarded",
+                 "st_pcg_iterations", "st_lm_trials", "st_precond_builds", "st_iterations_done", "st_terminated_early", "anomaly_code")
+LM_STATE_DOUBLES = ("lambda", "ni", "chi_cur", "last_rel", "lambda_setup0", "lambda_setup1", "rate_ref", "rate_last", "chi2_initial", "tol_f2", "eps_t", "eps_r",
+                    "refresh_rel", "tol2", "lambda_retake", "scal2_3", "rate_drop")
+LM_PHASES = dict(lin=0, solve=1, retry=2, need_setup=3, done=4, anomaly=5)
+LM_NEED_NUMERIC, LM_NEED_TRIAL, LM_NEED_REBUILD = 1, 2, 4
+LM_PASS_SETUP, LM_PASS_REBUILD = 1, 2
+
+
+def lm_decide(stage, state, scal=None, **kw):
+    """uzl_debug_lm_decide (diagnostic library, host only): one application of the LM loop's state machine (csrc/pgo_lm.hpp) to `state`, a
+    dict over LM_STATE_INTS + LM_STATE_DOUBLES (missing keys: 0), and the solve's scalars `scal` [16] (default: zeros).
+      head   red, phase (LM_PHASES), pass_flags, chi, dmax     lm_head_decide, in front of a trial
+      tail   chi_t, sc, ratio                                  lm_tail_decide, lane 0 of lm_tail_kernel behind an evaluated trial
+    -> (the state afterwards, scal afterwards)"""
+    L = diag_lib()
+    si = np.ascontiguousarray([int(state.get(k, 0)) for k in LM_STATE_INTS], np.int32)
+    sd = np.ascontiguousarray([float(state.get(k, 0.)) for k in LM_STATE_DOUBLES], np.float64)
+    sc = np.zeros(16, np.float64)
+    if scal is not None:
+        sc[:] = scal
+    if stage == "head":
+        iv = np.ascontiguousarray([1 if kw.get("red") else 0, int(kw["phase"]), int(kw.get("pass_flags", 0))], np.int32)
+        dv = np.ascontiguousarray([kw.get("chi", 0.), kw.get("dmax", 0.)], np.float64)
+    elif stage == "tail":
+        iv = np.zeros(1, np.int32)
+        dv = np.ascontiguousarray([kw.get("chi_t", 0.), kw.get("sc", 0.), kw.get("ratio", 0.)], np.float64)
+    else:
+        raise ValueError(stage)
+    rc = L.uzl_debug_lm_decide(C.c_int32(dict(head=0, tail=1)[stage]), _p(si, c_i32p), _p(sd, c_f64p), _p(sc, c_f64p), _p(iv, c_i32p), _p(dv, c_f64p))
+    if rc != UZL_OK:
+        raise UzlError(rc, "uzl_debug_lm_decide(%s)" % stage)
+    out = dict(zip(LM_STATE_INTS, (int(x) for x in si)))
+    out.update(zip(LM_STATE_DOUBLES, (float(x) for x in sd)))
+    return out, sc
+
+
 # --------------------------------------------------------------------------------------- distance loop-closure candidates
 class Radius(_Handle):
     """uzl_radius_* (SlamGraph::getNodesWithinRadius + the caller's filters, graph_slam_node.cpp:272-289)."""

@@ -177,7 +177,6 @@ struct uzl_pgo : uzl::HandleBase {
     // structure by the additive fallback (do_optimize_host).  Everything else about the class is read from mlp.
     bool ml_mult = false;            // the dense operator in use is the multiplicative cycle's (pgo_ml_kernels.hip)
     int ml_ns_steps = 0;             // Newton-Schulz refinements of the dense operator per rebuild
-    bool ml_trial_setup = false;     // the preconditioner's per-trial part (sibling inverses, top, dense levels) is due
     // Two complete copies of the preconditioner's numeric state (arena, device descriptor, kernel-argument block, PCG graph): the
     // solver applies copy `ml_ix` while a rebuild for the next LM iteration runs on `stream2` into the other one.
     struct MlBuf {
@@ -188,16 +187,13 @@ struct uzl_pgo : uzl::HandleBase {
         double* l1_span_ptr = nullptr;         // level-1 Galerkin arrays (blk | G | M), all-reduced once per linearisation
         hipGraph_t graph = nullptr; hipGraphExec_t graph_exec = nullptr;        // 2 x kGraphPairs PCG iterations
         hipGraph_t graph_s = nullptr; hipGraphExec_t graph_exec_s = nullptr;    // 2 x kShortPairs: the solves of a converged LM iteration end after 2 - 4
-        double lambda_setup = 0.;              // lambda of the last trial set-up of this copy
     } mlb[2];
     double* ml_dense_ptr[2][kMlMaxLevels + 1] = {};   // host copy of MlDev::Ydense per hierarchy copy
-    int ml_ix = 0;
-    bool ml_pending = false;                   // a rebuild into copy ml_ix ^ 1 is in flight on stream2
+    int ml_ix = 0;                             // = LmDev::ix of the host-driven loop's state (do_optimize_host keeps it in step; host_slot reads it)
     hipStream_t stream2 = nullptr;
     bool streams_borrowed = false;             // stream / stream2 are a batch's (uzl_pgo_batch_create): not this handle's to destroy
     hipEvent_t ev_lin = nullptr, ev_setup = nullptr;
     DevBuf<double> d_scal2;                    // lambda slot (scal[3]) for the kernels of an asynchronous rebuild
-    double lambda_now = 0.;          // lambda of the current trial
     DevBuf<uint8_t> ml_arena;
     size_t ml_copy_stride = 0;                 // bytes between the two hierarchy copies inside ml_arena
     DevBuf<MlDev> d_ml;
@@ -249,7 +245,7 @@ int do_optimize(uzl_pgo* h, int32_t iterations, uzl_pgo_stats* st);           //
 HostSlot host_slot(uzl_pgo* h);                       // the slot twins' slot for this handle, the hierarchy copy in use, the current pose buffer
 void set_lambda(uzl_pgo* h, double lambda, double tol_f2);
 void ml_setup_numeric(uzl_pgo* h, const HostSlot& hs, hipStream_t s, KernelTimer* timer);
-int pcg_solve(uzl_pgo* h, int it, bool* converged);   // one (H + lambda I) dx = b solve in LM iteration `it`; returns PCG iterations used
+int pcg_solve(uzl_pgo* h, LmDev& lm);                 // one (H + lambda I) dx = b solve of the trial `lm` is in; returns lm_solve_verdict (0: converged)
 inline double tol_factor2(const uzl_pgo_cfg& c) { return pgo_tol_f2(c); }
 // ---- the device-resident loop (uzl_pgo_lm.hip)
 struct LmRun;                                          // captured passes + slot table of one handle (or one batch)
@@ -257,6 +253,8 @@ void lm_run_destroy(LmRun* r);
 bool lm_eligible(const uzl_pgo* h);
 int do_optimize_lm(uzl_pgo* h, int32_t iterations, uzl_pgo_stats* st);
 bool lm_batch_eligible(const std::vector<uzl_pgo*>& hs);
+LmDev lm_initial_state(const uzl_pgo* h, int iterations, bool sync_rebuild);      // the state a graph starts its LM loop in (both loops)
+void lm_stats(const LmDev& v, uzl_pgo_stats& S);                                   // ... and what its final state says in the stats
 LmSlot make_slot(const uzl_pgo* h, LmDev* d_lm, LmHost* d_pub);
 LmShape make_shape(const std::vector<uzl_pgo*>& hs, int nslots, bool batch_geometry);
 int batch_optimize_lm(LmRun*& R, const std::vector<uzl_pgo*>& hs, int resident, hipStream_t s, hipStream_t s2, int32_t iterations, bool eager, bool verbose, KernelTimer* timer,

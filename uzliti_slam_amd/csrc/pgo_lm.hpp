@@ -1,8 +1,15 @@
-// pgo_lm.hpp — the scalar decisions of the Levenberg-Marquardt loop, written once for the host-driven loop (uzl_pgo.hip, do_optimize)
-// and the device-resident one (pgo_lm_kernels.hip): g2o's OptimizationAlgorithmLevenberg::solve [EXT], which the reference runs through
-// optimizer_.optimize(iterations) (graph_optimization/src/g2o_optimizer.cpp:148).  Both loops must take the SAME decisions from the same
-// numbers - tests hold their poses to array_equal - so nothing here may depend on who compiles it: no contraction of a * b + c, no
-// library pow / log whose last bit differs between libm and the device library.
+// pgo_lm.hpp — the Levenberg-Marquardt loop's STATE MACHINE, written once: g2o's OptimizationAlgorithmLevenberg::solve [EXT], which the
+// reference runs through optimizer_.optimize(iterations) (graph_optimization/src/g2o_optimizer.cpp:148), as functions over an LmDev
+// (pgo_types.hpp) and the solve's scalar array.  One state machine, two drivers: lane 0 of lm_head_kernel / lm_tail_kernel
+// (pgo_lm_head.hpp, pgo_lm_kernels.hip) applies it to the state on the device, do_optimize_host (uzl_pgo.hip) to a state on the host, and
+// uzl_debug_lm_decide (uzl_pgo_debug.hip) to a state a CPU test wrote (tests/test_lm_decide.py).
+//   lm_head_decide   in front of a trial: lambda_0, adoption of a copy rebuilt ahead, lazy refresh, the lambda-retake rule, `fresh`, the
+//                    stamps (*_pass == pass) that say which segments this pass runs, or a stall for a segment the pass lacks
+//   lm_solve_verdict over a solve the PCG kernels have left: stands / still iterating / which anomaly
+//   lm_trial_decide  over an evaluated trial: counters, PCG rate, rho, accept / reject, retry / next iteration / done / Terminate
+//   lm_tail_decide   the two as lm_tail_kernel's lane 0 applies them
+// Both drivers must take the SAME decisions from the same numbers - tests hold their poses to array_equal - so nothing here may depend
+// on who compiles it: no contraction of a * b + c, no library pow / log whose last bit differs between libm and the device library.
 #pragma once
 #include <cmath>
 #include <hip/hip_runtime.h>
@@ -100,6 +107,116 @@ UZL_HD LmStep lm_step(double current_chi, double temp_chi, double scale_sum, dou
         ni *= 2.;
     }
     return r;
+}
+
+// ---- in front of a trial.  phase: the state's phase when the pass found it; chi, dmax: chi2 and the largest diagonal entry of a fresh
+//      linearisation (read in phase kLmLin only); red: the PCG solves a Schur complement; pass_flags: the segments the pass can run
+//      (LmPassFlags).  scal: PgoDev::scal of the graph, or the host driver's image of it.
+UZL_HD void lm_head_decide(LmDev* lm, double* __restrict__ scal, int red, int phase, double chi, double dmax, int pass_flags)
+{
+    const int p = lm->pass + 1;
+    lm->pass = p;
+    int need = 0;
+    if (phase == kLmLin) {
+        scal[4] = chi; scal[6] = dmax;
+        if (lm->it == 0) {
+            lm->chi_cur = chi; lm->chi2_initial = chi;
+            lm->lambda = 1e-5 * dmax;                        // computeLambdaInit: tau * max diag
+            lm->ni = 2.;
+        }
+        lm->adopted = lm->pending ? 1 : 0;                   // the copy built during the last iteration
+        lm->ix = lm_pass_ix(phase, lm->ix, lm->pending);
+        lm->pending = 0;
+        if (lm_refresh(lm->it, lm->iterations, lm->sync_rebuild != 0, lm->last_rel, lm->refresh_rel, lm->rate_ref, lm->rate_last, lm->rate_drop)) {
+            lm->st_precond_builds++;
+            need |= (lm->it == 0 || lm->sync_rebuild) ? (kNeedNumeric | kNeedTrial) : kNeedRebuild;
+        }
+        lm->qmax = 0;
+        if (red) lm->schur_pass = p;                         // (H + lambda I) with the chain interiors eliminated: per lambda
+    } else if (phase == kLmRetry) {
+        if (red) lm->schur_pass = p;                         // a rejected step moved lambda: the Schur complement with it
+    } else if (phase == kLmNeedSetup) {
+        need = lm->need;                                     // (its Schur reduction ran in the pass that stalled)
+    } else {
+        return;                                              // solving (the pass goes on iterating), done, anomaly
+    }
+    // ---- start of a trial: setLambda, this trial's PCG floor and step accuracy
+    const double lambda = lm->lambda;
+    scal[3] = lambda; scal[8] = lm->tol_f2; scal[12] = lm->eps_t; scal[13] = lm->eps_r;
+    // the lambda-dependent inverses of the hierarchy are kept across trials; after rejected steps lambda grows geometrically and
+    // inverses taken at a much smaller lambda stop being a preconditioner at all
+    if (lambda > lm->lambda_retake * lm->lambda_setup[lm->ix]) need |= kNeedTrial;
+    if (((need & (kNeedNumeric | kNeedTrial)) && !(pass_flags & kPassSetup)) || ((need & kNeedRebuild) && !(pass_flags & kPassRebuild))) {
+        lm->need = need; lm->phase = kLmNeedSetup; lm->flags[0] = 1;              // this pass lacks the segment: the PCG kernels stay no-ops
+        return;
+    }
+    if (need & kNeedRebuild) {                               // into the copy the PCG does not use, with this iteration's lambda; adopted next iteration
+        lm->build_pass = p; lm->build_ix = lm->ix ^ 1; lm->build_cur = lm->cur;
+        lm->scal2[3] = lambda; lm->lambda_setup[lm->ix ^ 1] = lambda; lm->pending = 1;
+    }
+    if (need & kNeedNumeric) lm->numeric_pass = p;
+    if (need & kNeedTrial) { lm->trial_pass = p; lm->lambda_setup[lm->ix] = lambda; }
+    lm->fresh = ((need & kNeedTrial) || (lm->adopted && lm->qmax == 0)) ? 1 : 0;
+    lm->need = 0;
+    lm->init_pass = p;
+    lm->phase = kLmSolve;
+    // The solve's done / iterations / breakdown / look words and rz_prev start here, on the driver's copy of the state: the PCG init of a
+    // one-graph pass may run as further workgroups of the head's launch (lm_head_init_pcg_kernel), where a store of theirs into the
+    // state would race with the head's write-back.  A separate ml_init clears them once more, to the same values.
+    lm->flags[0] = 0; lm->flags[1] = 0; lm->flags[2] = 0; lm->flags[3] = 0;
+    scal[2] = 1.;
+}
+
+// ---- behind a trial's solve, on what the PCG kernels left in LmDev::flags (0 done, 1 iterations, 2 breakdown) and the residual guard's
+//      |r|^2 / |b|^2.  The device-resident loop hands a graph with an anomaly to the host-driven one, which knows the remedies (retake
+//      the inverses, additive operator) and evaluates the trial whatever the verdict.
+enum LmVerdict : int32_t {
+    kLmIterating = -1,        // the solve goes on in the next pass
+    kLmSolved = 0,            // converged, and inside the residual guard where the operator needs one
+    kLmAnomalyCap = 1,        // the PCG hit its cap (LmDev::max_it)
+    kLmAnomalyBreakdown = 2,  // PCG breakdown
+    kLmAnomalyGuard = 3,      // DESIGN.md "Safeguards": the multiplicative operator is not SPD by construction
+    kLmAnomalyIx = 4          // PcgArgs::ix was not the state's (kBreakdownIx)
+};
+UZL_HD int lm_solve_verdict(const LmDev* lm, double ratio)
+{
+    if (!lm->flags[0]) return lm->flags[1] >= lm->max_it ? kLmAnomalyCap : kLmIterating;
+    if (lm->flags[2]) return lm->flags[2] == kBreakdownIx ? kLmAnomalyIx : kLmAnomalyBreakdown;
+    return (lm->guarded && !(ratio <= kResidualGuard)) ? kLmAnomalyGuard : kLmSolved;
+}
+
+// ---- over an evaluated trial: chi_t, sc = chi2 at the trial poses and computeScale; scal[0], scal[1] = r.M^-1 r at the solve's end and
+//      its stop threshold, LmDev::flags[1] = the solve's PCG iterations
+UZL_HD void lm_trial_decide(LmDev* lm, double* __restrict__ scal, double chi_t, double sc)
+{
+    const int its = lm->flags[1];
+    scal[4] = chi_t; scal[5] = sc;
+    lm->st_pcg_iterations += its; lm->st_lm_trials++; lm->pcg_last = its;
+    const double rate = lm_pcg_rate(scal[1], scal[0], its, lm->tol2, lm->tol_f2);
+    if (rate > 0.) { lm->rate_last = rate; if (lm->fresh || lm->rate_ref < 0.) lm->rate_ref = rate; }
+    double lambda = lm->lambda, ni = lm->ni;
+    const LmStep st = lm_step(lm->chi_cur, chi_t, sc, lambda, ni);
+    lm->lambda = lambda; lm->ni = ni;
+    if (st.accepted) { lm->last_rel = st.last_rel; lm->chi_cur = chi_t; lm->cur ^= 1; }      // discardTop
+    const int qmax = lm->qmax + 1;
+    lm->qmax = qmax;
+    if (st.rho < 0 && qmax < 10) lm->phase = kLmRetry;                    // another trial on the same linearisation
+    else {
+        lm->st_iterations_done = lm->it + 1;
+        if (qmax == 10 || st.rho == 0) { lm->st_terminated_early = 1; lm->phase = kLmDone; }      // Terminate
+        else { lm->it += 1; lm->qmax = 0; lm->phase = (lm->it >= lm->iterations) ? kLmDone : kLmLin; }
+    }
+}
+
+// ---- lane 0 of lm_tail_kernel: the verdict, and the decision over the trial when the solve stands.  ratio, chi_t, sc: read only
+//      when the pass's evaluation kernels ran for the graph (solving, done, no breakdown); scal[7] = ratio then
+UZL_HD void lm_tail_decide(LmDev* lm, double* __restrict__ scal, double chi_t, double sc, double ratio)
+{
+    if (lm->phase != kLmSolve) return;
+    const int verdict = lm_solve_verdict(lm, ratio);
+    if (verdict == kLmSolved || verdict == kLmAnomalyGuard) scal[7] = ratio;
+    if (verdict > kLmSolved) { lm->phase = kLmAnomaly; lm->anomaly_code = verdict; lm->flags[0] = 1; }
+    else if (verdict == kLmSolved) lm_trial_decide(lm, scal, chi_t, sc);
 }
 
 }  // namespace uzl

@@ -1,17 +1,19 @@
 // pgo_lm_kernels.hip — the two decision kernels of the device-resident Levenberg-Marquardt loop (pgo_types.hpp: LmDev / LmSlot).
 //
 //   lm_head_kernel : in front of a trial's solve.  For a graph that has just been linearised: chi2 and the largest diagonal entry from
-//                    the block partials (finalize_kernel's sums, same order), lambda_0 in the first iteration (computeLambdaInit),
-//                    adoption of a hierarchy copy that was rebuilt ahead, the lazy-refresh decision (pgo_lm.hpp).  For every graph that
-//                    starts a trial (fresh linearisation, rejected step, or a stalled start): setLambda, the stamps that switch this
-//                    pass's Schur reduction / set-up / rebuild / PCG-init kernels on, phase -> solve.
-//   lm_tail_kernel : behind the evaluation of a trial.  Convergence and residual-guard checks of the solve, chi2 of the trial and
-//                    computeScale from the block partials, rho, accept / reject (pgo_lm.hpp: lm_step), next phase; then the snapshot
-//                    the host polls (LmHost, pinned).
+//                    the block partials (finalize_kernel's sums, same order); then lm_head_decide - lambda_0 in the first iteration
+//                    (computeLambdaInit), adoption of a hierarchy copy that was rebuilt ahead, the lazy-refresh decision, and for every
+//                    graph that starts a trial (fresh linearisation, rejected step, or a stalled start) setLambda, the stamps that
+//                    switch this pass's Schur reduction / set-up / rebuild / PCG-init kernels on, phase -> solve.
+//   lm_tail_kernel : behind the evaluation of a trial.  The residual guard's sums, chi2 of the trial and computeScale from the block
+//                    partials; then lm_tail_decide - the verdict over the solve (cap, breakdown, residual guard), rho, accept / reject
+//                    (lm_step), next phase; then the snapshot the host polls (LmHost, pinned).
 // One workgroup per graph (blockIdx.z = slot).  This is OptimizationAlgorithmLevenberg::solve [EXT] of the reference's
-// optimizer_.optimize(iterations) (graph_optimization/src/g2o_optimizer.cpp:148), decision for decision what uzl_pgo.hip's host-driven
-// loop takes - tests hold the two loops to identical poses.  Compiled with -ffp-contract=off like every file that shares arithmetic
-// with the host.
+// optimizer_.optimize(iterations) (graph_optimization/src/g2o_optimizer.cpp:148).  One state machine, two drivers: the decisions
+// themselves are lm_head_decide / lm_tail_decide of pgo_lm.hpp, which lane 0 of these kernels applies to the staged state and
+// uzl_pgo.hip's host-driven loop to a state of its own - the kernels add the sums the decisions read, the staging and the snapshot.
+// Tests hold the two loops to identical poses (tests/test_lm_loops_gpu.py) and the decisions to known answers on the CPU
+// (tests/test_lm_decide.py).  Compiled with -ffp-contract=off like every file that shares arithmetic with the host.
 #include "pgo_device.hpp"
 #include "pgo_lm.hpp"
 #include "pgo_lm_head.hpp"
@@ -82,34 +84,7 @@ __global__ __launch_bounds__(kTailBlk) void lm_tail_kernel(const LmSlot* __restr
         const uint32_t seq = (uint32_t)(lm->tails + 1);
         lm->tails = (int32_t)seq;
         s_seq = seq;
-        double* __restrict__ scal = sscal;                   // (0, 1 read; 4, 5, 7 written: stored below)
-        if (solving && !done) {
-            if (lm->flags[1] >= lm->max_it) { lm->phase = kLmAnomaly; lm->anomaly_code = 1; lm->flags[0] = 1; }      // PCG hit its cap
-        } else if (solving) {
-            const int its = lm->flags[1];
-            bool conv = lm->flags[2] == 0;
-            if (conv) scal[7] = ratio;
-            if (conv && lm->guarded && !(ratio <= kResidualGuard)) conv = false;      // (DESIGN.md "Safeguards": not SPD by construction)
-            if (!conv) { lm->phase = kLmAnomaly; lm->anomaly_code = lm->flags[2] == kBreakdownIx ? 4 : (lm->flags[2] ? 2 : 3); }      // 4: PcgArgs::ix was not the state's
-            else {
-                scal[4] = chi_t; scal[5] = sc;
-                lm->st_pcg_iterations += its; lm->st_lm_trials++; lm->pcg_last = its;
-                const double rate = lm_pcg_rate(scal[1], scal[0], its, lm->tol2, lm->tol_f2);
-                if (rate > 0.) { lm->rate_last = rate; if (lm->fresh || lm->rate_ref < 0.) lm->rate_ref = rate; }
-                double lambda = lm->lambda, ni = lm->ni;
-                const LmStep st = lm_step(lm->chi_cur, chi_t, sc, lambda, ni);
-                lm->lambda = lambda; lm->ni = ni;
-                if (st.accepted) { lm->last_rel = st.last_rel; lm->chi_cur = chi_t; lm->cur ^= 1; }      // discardTop
-                const int qmax = lm->qmax + 1;
-                lm->qmax = qmax;
-                if (st.rho < 0 && qmax < 10) lm->phase = kLmRetry;                    // another trial on the same linearisation
-                else {
-                    lm->st_iterations_done = lm->it + 1;
-                    if (qmax == 10 || st.rho == 0) { lm->st_terminated_early = 1; lm->phase = kLmDone; }      // Terminate
-                    else { lm->it += 1; lm->qmax = 0; lm->phase = (lm->it >= lm->iterations) ? kLmDone : kLmLin; }
-                }
-            }
-        }
+        lm_tail_decide(lm, sscal, chi_t, sc, ratio);         // (pgo_lm.hpp; scal 0, 1 read; 4, 5, 7 written: stored below)
     }
     __syncthreads();
     // ---- the state back to its place, and the snapshot the host polls: one word per lane.  The snapshot lives in pinned, coherent

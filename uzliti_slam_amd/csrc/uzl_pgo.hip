@@ -102,14 +102,12 @@ constexpr int kProgressEveryBJ = 8;           // block-Jacobi path: PCG iteratio
 // How stale is a kept preconditioner?  Not the iteration count of the last solve (with an absolute stop test that follows the size of
 // the LM step and lambda, not the operator): the CONTRACTION it delivers, nats of r.M^-1 r per PCG iteration.  rz_stop = scal[1] is
 // pcg_tol^2 * tol_f2 * (r_0.M^-1 r_0).  A rebuild is due when the rate has fallen below kRateDrop of what the operator delivered when fresh.
-// (kRateDrop, lm_pcg_rate: pgo_lm.hpp - shared with the device-resident loop)
-inline double pcg_rate(double rz_stop, double rz_end, int its, double tol2, double tol_f2) { return lm_pcg_rate(rz_stop, rz_end, its, tol2, tol_f2); }
+// (kRateDrop and the rule: pgo_lm.hpp)
 }  // namespace
 
 void uzl::set_lambda(uzl_pgo* h, double lambda, double tol_f2)
 {
     k_set_trial(h->D.scal, lambda, tol_f2, pgo_eps_t(h->cfg), pgo_eps_r(h->cfg), h->stream);
-    h->lambda_now = lambda;
 }
 
 namespace {
@@ -283,7 +281,6 @@ void upload_ml(uzl_pgo* h, const MlPlan& P, const int32_t* d_row_ptr, const int3
         B.nsT = M.nsT; B.nsX = M.nsX; B.y1 = cl ? M.Ydense[cl] : nullptr;
         B.rg[0] = reinterpret_cast<double*>(base + o_rga);
         B.rg[1] = reinterpret_cast<double*>(base + o_rgb);
-        B.lambda_setup = 0.;
         MlHot& Hh = B.hot;
         memset(&Hh, 0, sizeof(Hh));
         Hh.levels = L;
@@ -295,7 +292,7 @@ void upload_ml(uzl_pgo* h, const MlPlan& P, const int32_t* d_row_ptr, const int3
         B.l1_span_ptr = M.lv[1].blk;
         h->l1_span = (int64_t)((M.lv[1].M + (size_t)std::max(P.n[1], 1) * 36) - M.lv[1].blk);
     }
-    h->ml_ix = 0; h->ml_pending = false;
+    h->ml_ix = 0;
     UZL_HIP(hipMemcpyAsync(h->d_ml.p, Mh, sizeof(Mh), hipMemcpyHostToDevice, s));
     UZL_HIP(hipStreamSynchronize(s));      // stage / Mh are locals
 }
@@ -390,21 +387,20 @@ void ensure_pcg_graph(uzl_pgo* h)
 
 }  // namespace
 
-// one (H + lambda I) dx = b solve in LM iteration `it`; returns PCG iterations used, sets *converged
-int uzl::pcg_solve(uzl_pgo* h, int it, bool* converged)
+// One (H + lambda I) dx = b solve of the trial the host-driven loop's state `lm` is in: the trial part of the set-up of copy lm.ix first
+// when the state stamps it for this pass (trial_pass == pass), PCG batches up to lm.max_it, the residual guard's ratio.  Leaves the
+// PCG's done / iterations / breakdown words in lm.flags and returns lm_solve_verdict over them (pgo_lm.hpp; 0: converged).
+int uzl::pcg_solve(uzl_pgo* h, LmDev& lm)
 {
     hipStream_t s = h->stream;
     const PgoDev& D = h->Dp;
-    if (D.nb == 0) { *converged = true; h->prev_pcg_iters = 0; h->last_residual_ratio = 0.; return 0; }     // every free vertex was Schur-eliminated: nothing left to iterate on
-    const int max_it = h->cfg.pcg_max_iter > 0 ? h->cfg.pcg_max_iter : 6 * std::max(D.nb, 1);
+    lm.flags[0] = 1; lm.flags[1] = 0; lm.flags[2] = 0; lm.flags[3] = 0;
+    if (D.nb == 0) { h->prev_pcg_iters = 0; h->last_residual_ratio = 0.; return kLmSolved; }     // every free vertex was Schur-eliminated: nothing left to iterate on
+    const int max_it = lm.max_it;
     const bool timed = h->timer.on || h->no_graph || h->sharded;   // per-kernel events, rocprofv3 and the exchange callback need eager launches
     if (h->mlp.levels > 0) {
         const HostSlot hs = host_slot(h);
-        if (h->ml_trial_setup) {
-            kl_ml_trial(hs, h->ml_shape, ml_ns_steps_at(h->ml_ns_steps, it), s, &h->timer);
-            h->ml_trial_setup = false;
-            h->mlb[h->ml_ix].lambda_setup = h->lambda_now;
-        }
+        if (lm.trial_pass == lm.pass) kl_ml_trial(hs, h->ml_shape, ml_ns_steps_at(h->ml_ns_steps, lm.it), s, &h->timer);
         { Timed t(h, "pcg_init"); kl_ml_pcg_init(hs, h->ml_shape, s); }
         { Timed t(h, "ml_cg"); UZL_HIP(kl_ml_cg(hs, h->ml_shape, 0, 1, s)); }
     } else {
@@ -427,16 +423,16 @@ int uzl::pcg_solve(uzl_pgo* h, int it, bool* converged)
         if (h->h_scal.p->flags[0] || launched >= max_it) break;
     }
     UZL_HIP(hipGetLastError());
-    *converged = h->h_scal.p->flags[0] != 0 && h->h_scal.p->flags[2] == 0;
-    // The multiplicative cycle / Newton-Schulz operator is not SPD by construction (see the fallback in do_optimize).  The
+    for (int i = 0; i < 4; i++) lm.flags[i] = h->h_scal.p->flags[i];
+    // The multiplicative cycle / Newton-Schulz operator is not SPD by construction (see the fallback in do_optimize_host).  The
     // recurrence residual r is the true residual of x whatever the preconditioner did, so a solve under that operator which
-    // claims convergence in the M^-1 norm while |r| has not come down by kResidualGuard relative to |b| is refused and the
+    // claims convergence in the M^-1 norm while |r| has not come down by kResidualGuard relative to |b| is refused (lm.guarded) and the
     // caller falls back to the additive operator (a sum of SPD terms, whose M^-1 norm is a norm).
     h->last_residual_ratio = h->h_scal.p->scal[7];
-    if (*converged && (h->ml_mult || h->ml_ns_steps > 0) && !(h->last_residual_ratio <= kResidualGuard)) { *converged = false; h->guard_trips++; }
-    const int iters = h->h_scal.p->flags[1];
-    h->prev_pcg_iters = iters;
-    return iters;
+    const int verdict = lm_solve_verdict(&lm, h->last_residual_ratio);
+    if (verdict == kLmAnomalyGuard) h->guard_trips++;
+    h->prev_pcg_iters = lm.flags[1];
+    return verdict;
 }
 
 
@@ -655,7 +651,13 @@ int do_optimize(uzl_pgo* h, int32_t iterations, uzl_pgo_stats* st)
     }
     return rc;
 }
-// The host-driven loop.  Called through do_optimize (structure prepared, device set), or by do_optimize_lm for a solve that met an anomaly.
+// The host-driven loop: the second driver of the LM state machine (pgo_lm.hpp; the first is the pair of decision kernels of
+// uzl_pgo_lm.hip).  It keeps an LmDev and an image of the solve's scalars on the host, has lm_head_decide / lm_trial_decide take every
+// decision on them, and reads what to launch from the state the way the slot twins do: schur_pass / numeric_pass / trial_pass /
+// build_pass == pass, build_ix, scal2[3], ix, cur.  It can launch any segment at any time, so it offers the head both (kPassSetup |
+// kPassRebuild) and never stalls.  Its own: the launches and round trips, the shard exchanges, the timer, the verbose lines, and the
+// remedies the device-resident loop hands a graph over for.
+// Called through do_optimize (structure prepared, device set), or by do_optimize_lm for a solve that met an anomaly.
 int do_optimize_host(uzl_pgo* h, int32_t iterations, uzl_pgo_stats* st)
 {
     const auto t0 = h->t_start;
@@ -667,8 +669,6 @@ int do_optimize_host(uzl_pgo* h, int32_t iterations, uzl_pgo_stats* st)
     PgoDev& Dp = h->Dp;                       // the system the PCG solves: D, or the Schur complement over the separator vertices
     const bool red = h->red.on;
     const SchurDev& SD = h->red.S;
-    // (H + lambda I) with the chain interiors eliminated: once per lambda, i.e. per LM trial (pgo_schur.hpp)
-    auto schur_reduce = [&]() { kl_schur_reduce(host_slot(h), h->ml_shape, s, &h->timer); };
     const double delta = h->cfg.huber_delta;
     h->timer.reset();
     h->prev_pcg_iters = 0;
@@ -687,9 +687,6 @@ int do_optimize_host(uzl_pgo* h, int32_t iterations, uzl_pgo_stats* st)
         return UZL_OK;
     }
     // optimizer_.optimize(iterations) (:148) -> OptimizationAlgorithmLevenberg::solve [EXT]
-    double lambda = 0., ni = 2., current_chi = 0.;
-    double last_rel = 1e300;
-    double rate_ref = -1., rate_last = -1.;
     // Asynchronous rebuild: from the second LM iteration on a wanted rebuild runs on stream2 into the OTHER copy of the
     // hierarchy while this iteration's PCG still uses the current one (any SPD preconditioner gives the same solution; one
     // that is one linearisation old costs a few iterations, a rebuild on the critical path costs ~0.4 ms).  The copy is
@@ -698,165 +695,126 @@ int do_optimize_host(uzl_pgo* h, int32_t iterations, uzl_pgo_stats* st)
     // (small graphs only: at 10k vertices the rebuild's Newton-Schulz GEMMs take more from the overlapped PCG than they give back:
     // 113.2 -> 115.1 ms; config 2: 11.09 -> 10.67 ms with 540 instead of 517 PCG iterations)
     const bool async_ok = !async_off && h->mlp.levels > 0 && ml_async_level(h) && !h->sharded && !h->timer.on && h->stream2 != nullptr;
-    bool adopted = false;
-    h->ml_ix = 0; h->ml_pending = false;
+    const bool ml = h->mlp.levels > 0;
+    LmDev L = lm_initial_state(h, iterations, !async_ok);
+    L.cur = h->cur == h->pose_b.p ? 1 : 0;     // (the estimate sits in whichever buffer the last solve left it)
+    double scal[16] = {};                      // the host's image of PgoDev::scal, as far as the decisions read and write it
+    h->ml_ix = L.ix;
     struct DrainRebuild {                      // an exception must not leave a rebuild running on stream2 behind the handle's back
-        uzl_pgo* h;
-        ~DrainRebuild() { if (h->ml_pending) { (void)hipStreamSynchronize(h->stream2); h->ml_pending = false; } }
-    } drain{h};
+        uzl_pgo* h; LmDev& L;
+        ~DrainRebuild() { if (L.pending) { (void)hipStreamSynchronize(h->stream2); L.pending = 0; } }
+    } drain{h, L};
     PhaseMarks<4> phases;                      // diagnostic build, UZL_PHASES=1: GPU time between the marks of every LM iteration
     auto mark = [&](int tag) { phases.mark(tag, s); };
-    for (int it = 0; it < iterations; it++) {
-        int gl, ga;
-        adopted = false;
-        mark(0);
-        if (h->ml_pending) {                                                      // the copy built during the last iteration
-            UZL_HIP(hipStreamWaitEvent(s, h->ev_setup, 0));
-            h->ml_ix ^= 1; h->ml_pending = false; adopted = true;
-        }
-        D.pose = h->cur; D.pose_trial = h->trial;
-        Dp.pose = h->cur; Dp.pose_trial = h->trial;
-        // (computeActiveErrors: chi2 of the linearisation point is needed in the first iteration, and by every rank of a sharded solve,
-        //  which exchanges it; later iterations carry the accepted trial's over - as lm_head_kernel does)
-        {                                                                       // computeActiveErrors + buildSystem
-            hipEvent_t ea = nullptr, eb = nullptr;
-            h->timer.pair("linearize", &ea, &eb);                               // (profiling: dispatch timestamps, as rocprofv3 reports the kernel)
-            UZL_HIP(k_hessian(D, h->cur, delta, &gl, &ga, s, it == 0 || h->sharded, ea, eb));
-        }
-        if (h->sharded) {                                                         // H_aa, b: sums over all ranks' edges
-            shard_allreduce(h, h->sys.hdiag.p, (int64_t)h->nb * 42);
-            ga = k_diagmax(D, s);
-        }
-        { Timed t(h, "finalize"); k_finalize(D, gl, 0, ga, 2, s); }
-        shard_allreduce_chi2(h);
-        // The multilevel preconditioner is rebuilt only while the linearisation still moves: any SPD preconditioner
-        // gives the same PCG solution, and once chi2 changes by less than refresh_rel per step the hierarchy of the
-        // previous iteration is as good as a fresh one (geometry + Galerkin + inverses are ~170 us per rebuild).
-        // A rebuild is also forced when the iteration count has grown by a third since the last one.
-        // (an asynchronous rebuild is for the NEXT iteration: none in the last one)
-        const bool refresh = lm_refresh(it, iterations, !async_ok, last_rel, ml_async_level(h) ? kRefreshRel : kRefreshRelSync, rate_ref, rate_last, ml_rate_drop(h));
-        bool launch_async = false;
-        bool fetched = false;
-        if (red) {                                      // the hierarchy is built on the reduced system, which needs lambda: lambda_0 first
-            if (h->sharded && SD.runblk) {              // the runs' chain blocks, summed over the ranks (once per linearisation)
+    // one solve of the trial in front of L, and what the state machine needs of it on the host: scal[0], scal[1]
+    auto solve = [&]() {
+        const int verdict = pcg_solve(h, L);                                      // _solver->solve()
+        scal[0] = h->h_scal.p->scal[0]; scal[1] = h->h_scal.p->scal[1];
+        return verdict;
+    };
+    // a solve that did not stand is solved again with the inverses of copy L.ix taken at this lambda; its PCG iterations stay counted
+    auto solve_again = [&]() {
+        L.st_pcg_iterations += L.flags[1];
+        L.trial_pass = L.pass; L.lambda_setup[L.ix] = L.lambda;
+        return solve();
+    };
+    while (L.phase != kLmDone && L.it < iterations) {
+        const int phase = L.phase;                                               // kLmLin or kLmRetry: this driver never stalls, and remedies its anomalies itself
+        double chi = 0., dmax = 0.;
+        if (phase == kLmLin) {
+            int gl, ga;
+            mark(0);
+            if (L.pending) UZL_HIP(hipStreamWaitEvent(s, h->ev_setup, 0));      // the copy built during the last iteration: the head adopts it
+            D.pose = h->cur; D.pose_trial = h->trial;
+            Dp.pose = h->cur; Dp.pose_trial = h->trial;
+            // (computeActiveErrors: chi2 of the linearisation point is needed in the first iteration, and by every rank of a sharded solve,
+            //  which exchanges it; later iterations carry the accepted trial's over - as lm_head_kernel does)
+            {                                                                       // computeActiveErrors + buildSystem
+                hipEvent_t ea = nullptr, eb = nullptr;
+                h->timer.pair("linearize", &ea, &eb);                               // (profiling: dispatch timestamps, as rocprofv3 reports the kernel)
+                UZL_HIP(k_hessian(D, h->cur, delta, &gl, &ga, s, L.it == 0 || h->sharded, ea, eb));
+            }
+            if (h->sharded) {                                                         // H_aa, b: sums over all ranks' edges
+                shard_allreduce(h, h->sys.hdiag.p, (int64_t)h->nb * 42);
+                ga = k_diagmax(D, s);
+            }
+            { Timed t(h, "finalize"); k_finalize(D, gl, 0, ga, 2, s); }
+            shard_allreduce_chi2(h);
+            if (red && h->sharded && SD.runblk) {           // the runs' chain blocks, summed over the ranks (once per linearisation)
                 k_schur_gather(D, SD, s);
                 shard_allreduce(h, SD.runblk, (int64_t)(SD.n_int + SD.n_runs) * 36);
             }
-            if (it == 0) {
-                fetch_scal(h); fetched = true;
-                current_chi = h->h_scal.p->scal[4];
-                S.chi2_initial = current_chi;
-                lambda = 1e-5 * h->h_scal.p->scal[6];                             // computeLambdaInit: tau * max diag
-                ni = 2.;
+            if (L.it == 0 || h->sharded) {                  // later iterations carry chi2 over from the accepted trial: no round trip
+                fetch_scal(h);
+                chi = h->h_scal.p->scal[4]; dmax = h->h_scal.p->scal[6];
             }
-            k_set_scalar(D.scal + 3, lambda, s);
-            schur_reduce();
         }
-        if (refresh) {
-            S.precond_builds++;
-            if (it == 0 || !async_ok) {
-                if (h->mlp.levels > 0) ml_setup_numeric(h, host_slot(h), s, &h->timer);
-                h->ml_trial_setup = true;
-            } else launch_async = true;                                           // needs this iteration's lambda: below
+        // ---- the head: lambda_0, adoption, refresh, retake, fresh, the stamps of this trial's segments
+        lm_head_decide(&L, scal, red ? 1 : 0, phase, chi, dmax, kPassSetup | kPassRebuild);
+        h->ml_ix = L.ix;                                                          // (host_slot, the captured PCG graphs)
+        if (phase == kLmLin && h->sharded) L.chi_cur = chi;                     // a sharded solve takes the all-reduced chi2 of every linearisation
+        if (!ml) L.lambda_setup[L.ix] = 0.;                                     // block-Jacobi has no inverses to keep: every trial is fresh
+        set_lambda(h, L.lambda, L.tol_f2);                                        // setLambda (+ this trial's PCG floor and step accuracy)
+        if (L.schur_pass == L.pass) {                       // (H + lambda I) with the chain interiors eliminated: once per lambda (pgo_schur.hpp)
+            if (phase == kLmRetry && L.pending) UZL_HIP(hipStreamWaitEvent(s, h->ev_setup, 0));   // (a rebuild running ahead on stream2 still reads the old one)
+            kl_schur_reduce(host_slot(h), h->ml_shape, s, &h->timer);
         }
-        if ((it == 0 || h->sharded) && !fetched) {     // later iterations carry chi2 over from the accepted trial: no round trip
-            fetch_scal(h);
-            current_chi = h->h_scal.p->scal[4];
-        }
-        if (it == 0 && !fetched) {
-            S.chi2_initial = current_chi;
-            lambda = 1e-5 * h->h_scal.p->scal[6];                                 // computeLambdaInit: tau * max diag
-            ni = 2.;
-        }
-        if (launch_async) {
-            const int nb_ix = h->ml_ix ^ 1;
+        if (ml && L.numeric_pass == L.pass) ml_setup_numeric(h, host_slot(h), s, &h->timer);
+        if (L.build_pass == L.pass) {                       // a rebuild ahead, into the other copy, with this iteration's lambda
             UZL_HIP(hipEventRecord(h->ev_lin, s));                                // H, b and the poses of this linearisation are final
             UZL_HIP(hipStreamWaitEvent(h->stream2, h->ev_lin, 0));
             HostSlot hb = host_slot(h);
-            hb.ix = nb_ix;
-            hb.S.Dp.scal = h->d_scal2.p;                                          // the trial loop below moves scal[3] on the main stream
-            k_set_scalar(hb.S.Dp.scal + 3, lambda, h->stream2);
+            hb.ix = L.build_ix; hb.cur = L.build_cur;
+            hb.S.Dp.scal = h->d_scal2.p;                                          // the trials move scal[3] on the main stream
+            k_set_scalar(hb.S.Dp.scal + 3, L.scal2[3], h->stream2);
             ml_setup_numeric(h, hb, h->stream2, nullptr);
             kl_ml_trial(hb, h->ml_shape, h->ml_ns_steps, h->stream2, nullptr);    // (a rebuild that runs ahead: the structure's steps)
-            h->mlb[nb_ix].lambda_setup = lambda;
             UZL_HIP(hipEventRecord(h->ev_setup, h->stream2));
-            h->ml_pending = true;
         }
-        double rho = 0.;
-        int qmax = 0;
-        const double tol_f2 = tol_factor2(h->cfg);
-        mark(1);
-        do {
-            set_lambda(h, lambda, tol_f2);                                        // setLambda (+ this iteration's PCG tolerance)
-            if (red && qmax > 0) {                                                // a rejected step moved lambda: the Schur complement with it
-                if (h->ml_pending) UZL_HIP(hipStreamWaitEvent(s, h->ev_setup, 0));   // (a rebuild running ahead on stream2 still reads the old one)
-                schur_reduce();
-            }
-            bool conv = false;
-            // the lambda-dependent inverses of the hierarchy are kept across trials; after rejected steps lambda grows
-            // geometrically and inverses taken at a much smaller lambda stop being a preconditioner at all
-            if (h->mlp.levels > 0 && lambda > kLambdaRetake * h->mlb[h->ml_ix].lambda_setup) h->ml_trial_setup = true;
-            const bool fresh = h->ml_trial_setup || (adopted && qmax == 0);
-            int pcg_its = pcg_solve(h, it, &conv);                                // _solver->solve()
-            S.pcg_iterations += pcg_its;
-            if (!conv && !fresh && h->mlp.levels > 0) {                            // stale hierarchy: retake the inverses once
-                h->ml_trial_setup = true;
-                pcg_its = pcg_solve(h, it, &conv);
-                S.pcg_iterations += pcg_its;
-            }
-            if (!conv && (h->ml_mult || h->ml_ns_steps > 0)) {
-                if (h->cfg.verbose)
-                    fprintf(stderr, "[uzl_pgo] it %d trial %d lambda %.3e: multiplicative operator refused (pcg %d, rz %.3e, breakdown %d, |r|2/|b|2 %.3e) -> additive\n",
-                            it, qmax, lambda, pcg_its, h->h_scal.p->scal[0], (int)h->h_scal.p->flags[2], h->last_residual_ratio);
-                // The multiplicative cycle / its Newton-Schulz refinement is SPD only while the level-1 smoother contracts
-                // (lambda_max(Y_1 A_1) < 2), which block-Jacobi does not guarantee on every graph: fall back, for the rest
-                // of this handle's structure, to the additive operator (a sum of SPD terms) and solve again.
-                if (h->ml_pending) {                                              // the copy being built on stream2 still holds the
-                    UZL_HIP(hipStreamSynchronize(h->stream2));                    // multiplicative operator: drop it and rebuild
-                    h->ml_pending = false; last_rel = 1e300;                      // synchronously at the next linearisation
-                }
-                h->ml_mult = false; h->ml_ns_steps = 0; h->mult_banned = true;   // (the additive operator takes no refinement steps)
-                for (auto& B : h->mlb) B.hot.Cmat = B.y1;
-                destroy_pcg_graph(h);                                             // MlHot is a by-value kernel argument
-                h->structure_gen++;                                               // (slot tables that carry it are rebuilt: uzl_pgo_lm.hip, batches)
-                h->ml_trial_setup = true;
-                pcg_its = pcg_solve(h, it, &conv);
-                S.pcg_iterations += pcg_its;
-            }
-            {
-                const double rate = pcg_rate(h->h_scal.p->scal[1], h->h_scal.p->scal[0], pcg_its, h->cfg.pcg_tol * h->cfg.pcg_tol, tol_f2);
-                if (rate > 0.) { rate_last = rate; if (fresh || rate_ref < 0.) rate_ref = rate; }
-            }
+        if (phase == kLmLin) mark(1);
+        // ---- the solve, and this driver's remedies for one that does not stand
+        const int it = L.it, trial = L.qmax;
+        const double lambda = L.lambda;
+        int verdict = solve();
+        if (verdict != kLmSolved && !L.fresh && ml) verdict = solve_again();      // stale hierarchy: retake the inverses once
+        if (verdict != kLmSolved && L.guarded) {
             if (h->cfg.verbose)
-                fprintf(stderr, "[uzl_pgo] it %d trial %d lambda %.3e pcg %d  rz_end %.3e  rz_stop %.3e  |r|2/|b|2 %.3e  conv %d  chi2 %.9g\n", it, qmax, lambda, pcg_its,
-                        h->h_scal.p->scal[0], h->h_scal.p->scal[1], h->last_residual_ratio, (int)conv, current_chi);
-            if (!conv) { S.pcg_not_converged++; rc = UZL_ERR_NOT_CONVERGED; }
-            S.lm_trials++;
-            mark(2);
-            if (red) kl_schur_backsub(host_slot(h), h->ml_shape, s, &h->timer);  // dx of the eliminated vertices from the separators'
-            int go, gc;
-            { Timed t(h, "oplus"); go = k_oplus(D, h->cur, h->trial, s); }        // push + update
-            { Timed t(h, "chi2"); gc = k_chi2_trial(D, h->cur, delta, s); }       // computeActiveErrors (at trial poses made on the fly: the arithmetic of the device-resident loop's eval_lm_kernel)
-            { Timed t(h, "finalize"); k_finalize(D, gc, go, 0, 1, s); }
-            shard_allreduce_chi2(h);
-            fetch_scal(h);
-            mark(3);
-            const double temp_chi = h->h_scal.p->scal[4];
-            const LmStep step = lm_step(current_chi, temp_chi, h->h_scal.p->scal[5], lambda, ni);     // rho, lambda, ni (pgo_lm.hpp)
-            rho = step.rho;
-            if (step.accepted) {                                                  // good step
-                last_rel = step.last_rel;
-                current_chi = temp_chi;
-                std::swap(h->cur, h->trial);                                      // discardTop
-            }                                                                     // else pop: h->cur untouched
-            qmax++;
-        } while (rho < 0 && qmax < 10);
-        S.iterations_done = it + 1;
-        if (qmax == 10 || rho == 0) { S.terminated_early = 1; break; }           // Terminate
+                fprintf(stderr, "[uzl_pgo] it %d trial %d lambda %.3e: multiplicative operator refused (pcg %d, rz %.3e, breakdown %d, |r|2/|b|2 %.3e) -> additive\n",
+                        it, trial, lambda, L.flags[1], scal[0], L.flags[2], h->last_residual_ratio);
+            // The multiplicative cycle / its Newton-Schulz refinement is SPD only while the level-1 smoother contracts
+            // (lambda_max(Y_1 A_1) < 2), which block-Jacobi does not guarantee on every graph: fall back, for the rest
+            // of this handle's structure, to the additive operator (a sum of SPD terms) and solve again.
+            if (L.pending) {                                                      // the copy being built on stream2 still holds the
+                UZL_HIP(hipStreamSynchronize(h->stream2));                        // multiplicative operator: drop it and rebuild
+                L.pending = 0; L.last_rel = 1e300;                                // at the next linearisation
+            }
+            h->ml_mult = false; h->ml_ns_steps = 0; h->mult_banned = true;       // (the additive operator takes no refinement steps)
+            L.guarded = 0;
+            for (auto& B : h->mlb) B.hot.Cmat = B.y1;
+            destroy_pcg_graph(h);                                                 // MlHot is a by-value kernel argument
+            h->structure_gen++;                                                   // (slot tables that carry it are rebuilt: uzl_pgo_lm.hip, batches)
+            verdict = solve_again();
+        }
+        if (h->cfg.verbose)
+            fprintf(stderr, "[uzl_pgo] it %d trial %d lambda %.3e pcg %d  rz_end %.3e  rz_stop %.3e  |r|2/|b|2 %.3e  conv %d  chi2 %.9g\n", it, trial, lambda, L.flags[1],
+                    scal[0], scal[1], h->last_residual_ratio, (int)(verdict == kLmSolved), L.chi_cur);
+        // not converged is no anomaly here: the trial is evaluated whatever the verdict, and the caller is told
+        if (verdict != kLmSolved) { S.pcg_not_converged++; rc = UZL_ERR_NOT_CONVERGED; }
+        mark(2);
+        if (red) kl_schur_backsub(host_slot(h), h->ml_shape, s, &h->timer);      // dx of the eliminated vertices from the separators'
+        int go, gc;
+        { Timed t(h, "oplus"); go = k_oplus(D, h->cur, h->trial, s); }            // push + update
+        { Timed t(h, "chi2"); gc = k_chi2_trial(D, h->cur, delta, s); }           // computeActiveErrors (at trial poses made on the fly: the arithmetic of the device-resident loop's eval_lm_kernel)
+        { Timed t(h, "finalize"); k_finalize(D, gc, go, 0, 1, s); }
+        shard_allreduce_chi2(h);
+        fetch_scal(h);
+        mark(3);
+        // ---- the tail's decision over the evaluated trial: rho, lambda, accept / reject, what comes next
+        lm_trial_decide(&L, scal, h->h_scal.p->scal[4], h->h_scal.p->scal[5]);
+        h->cur = L.cur ? h->pose_b.p : h->pose_a.p; h->trial = L.cur ? h->pose_a.p : h->pose_b.p;      // an accepted step: discardTop (else pop)
     }
-    S.chi2_final = current_chi;
-    S.lambda_final = lambda;
-    if (h->ml_pending) { UZL_HIP(hipStreamSynchronize(h->stream2)); h->ml_pending = false; }   // a rebuild nobody will use: let it drain
+    lm_stats(L, S);
+    if (L.pending) { UZL_HIP(hipStreamSynchronize(h->stream2)); L.pending = 0; }   // a rebuild nobody will use: let it drain
     UZL_HIP(hipStreamSynchronize(s));
     static const char* const kPhaseNames[4] = {"linearise+set-up (0->1)", "solve incl. init (1->2)", "evaluate+round trip (2->3)", "host decision / next (3->0)"};
     phases.report("phases", S.iterations_done, "LM iterations", kPhaseNames);

@@ -46,14 +46,13 @@ double debug_lambda(uzl_pgo* h, double lambda)
 HostSlot debug_trial_setup(uzl_pgo* h, double& lambda, int ns_steps)
 {
     lambda = debug_lambda(h, lambda);
-    h->ml_ix = 0; h->ml_pending = false;
+    h->ml_ix = 0;
     debug_reduce(h, lambda);
     set_lambda(h, lambda, tol_factor2(h->cfg));
     if (h->mlp.levels == 0) return HostSlot{};
     const HostSlot hs = host_slot(h);
     ml_setup_numeric(h, hs, h->stream, nullptr);
     kl_ml_trial(hs, h->ml_shape, ns_steps, h->stream, nullptr);
-    h->ml_trial_setup = true;
     return hs;
 }
 }  // namespace
@@ -124,14 +123,16 @@ extern "C" UZL_DIAG_EXPORT int uzl_debug_pgo_solve(uzl_pgo* h, double lambda, do
     if (h->nb == 0 || h->e == 0) { info[1] = 1.; return UZL_OK; }
     PgoDev& D = h->D;
     lambda = debug_lambda(h, lambda);
-    h->ml_ix = 0; h->ml_pending = false;
+    h->ml_ix = 0;
     debug_reduce(h, lambda);
-    if (h->mlp.levels > 0) { ml_setup_numeric(h, host_slot(h), s, nullptr); h->ml_trial_setup = true; }      // (not debug_trial_setup: pcg_solve takes the trial part itself)
+    if (h->mlp.levels > 0) ml_setup_numeric(h, host_slot(h), s, nullptr);      // (not debug_trial_setup: pcg_solve takes the trial part itself)
     set_lambda(h, lambda, tol_factor2(h->cfg));
     h->prev_pcg_iters = 0;
     const int trips0 = h->guard_trips;
-    bool conv = false;
-    const int its = pcg_solve(h, 0, &conv);
+    LmDev L = lm_initial_state(h, 1, true);                   // the first trial of a loop, its trial set-up stamped for this pass
+    L.lambda = lambda; L.trial_pass = L.pass;
+    const bool conv = pcg_solve(h, L) == kLmSolved;
+    const int its = L.flags[1];
     h->prev_pcg_iters = 0;
     if (h->red.on) kl_schur_backsub(host_slot(h), h->ml_shape, s, nullptr);
     const size_t nb = (size_t)h->nb;
@@ -599,5 +600,38 @@ extern "C" UZL_DIAG_EXPORT int uzl_debug_lm_pass_plan(int32_t stage, const int32
     } catch (const std::bad_alloc&) {
         return UZL_ERR_OOM;
     }
+}
+
+// ---- the LM state machine itself without a handle or a device (pgo_lm.hpp; tests/test_lm_decide.py): one application of the head or of
+//      the tail's lane 0 to a state the caller wrote, in place.
+//   A STATE (LmDev) is one row of si and one of sd:
+//      si [32] = {flags[0..3], phase, cur, ix, pass, init_pass, schur_pass, numeric_pass, trial_pass, build_pass, build_ix, build_cur, need,
+//                 it, qmax, iterations, max_it, pending, adopted, fresh, pcg_last, sync_rebuild, guarded, st_pcg_iterations, st_lm_trials,
+//                 st_precond_builds, st_iterations_done, st_terminated_early, anomaly_code}
+//      sd [17] = {lambda, ni, chi_cur, last_rel, lambda_setup[0], lambda_setup[1], rate_ref, rate_last, chi2_initial, tol_f2, eps_t, eps_r,
+//                 refresh_rel, tol2, lambda_retake, scal2[3], rate_drop}
+//   scal [16]: the solve's scalars (PgoDev::scal), in place
+//   stage 0 lm_head_decide   iv {red, phase, pass_flags}; dv {chi, dmax}
+//   stage 1 lm_tail_decide   dv {chi_t, sc, ratio}
+constexpr int kLmStateInts = 32, kLmStateDoubles = 17;
+extern "C" UZL_DIAG_EXPORT int uzl_debug_lm_decide(int32_t stage, int32_t* si, double* sd, double* scal, const int32_t* iv, const double* dv)
+{
+    if (!si || !sd || !scal || !dv || (stage == 0 && !iv) || stage < 0 || stage > 1) return UZL_ERR_BAD_ARG;
+    LmDev L;
+    memset(&L, 0, sizeof(L));
+    int32_t* const I[kLmStateInts] = {&L.flags[0], &L.flags[1], &L.flags[2], &L.flags[3], &L.phase, &L.cur, &L.ix, &L.pass, &L.init_pass, &L.schur_pass, &L.numeric_pass,
+                                      &L.trial_pass, &L.build_pass, &L.build_ix, &L.build_cur, &L.need, &L.it, &L.qmax, &L.iterations, &L.max_it, &L.pending, &L.adopted,
+                                      &L.fresh, &L.pcg_last, &L.sync_rebuild, &L.guarded, &L.st_pcg_iterations, &L.st_lm_trials, &L.st_precond_builds,
+                                      &L.st_iterations_done, &L.st_terminated_early, &L.anomaly_code};
+    double* const F[kLmStateDoubles] = {&L.lambda, &L.ni, &L.chi_cur, &L.last_rel, &L.lambda_setup[0], &L.lambda_setup[1], &L.rate_ref, &L.rate_last, &L.chi2_initial,
+                                        &L.tol_f2, &L.eps_t, &L.eps_r, &L.refresh_rel, &L.tol2, &L.lambda_retake, &L.scal2[3], &L.rate_drop};
+    for (int k = 0; k < kLmStateInts; k++) *I[k] = si[k];
+    for (int k = 0; k < kLmStateDoubles; k++) *F[k] = sd[k];
+    if (L.ix < 0 || L.ix > 1) return UZL_ERR_BAD_ARG;             // (lambda_setup[ix])
+    if (stage == 0) lm_head_decide(&L, scal, iv[0], iv[1], dv[0], dv[1], iv[2]);
+    else lm_tail_decide(&L, scal, dv[0], dv[1], dv[2]);
+    for (int k = 0; k < kLmStateInts; k++) si[k] = *I[k];
+    for (int k = 0; k < kLmStateDoubles; k++) sd[k] = *F[k];
+    return UZL_OK;
 }
 #endif  // UZL_DIAG

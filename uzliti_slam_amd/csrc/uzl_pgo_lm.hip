@@ -2,9 +2,10 @@
 //
 // G2oOptimizer::optimizeImpl (graph_optimization/src/g2o_optimizer.cpp:137-149) hands the graph to optimizer_.optimize(iterations),
 // i.e. g2o's OptimizationAlgorithmLevenberg::solve [EXT]: linearise, then trials (lambda, solve, evaluate, accept / reject) until a step
-// is accepted.  uzl_pgo.hip's do_optimize_host drives that loop from the host, scalar by scalar.  Here the loop's state lives on the
-// device (LmDev), its decisions are taken by two one-workgroup kernels (pgo_lm_kernels.hip), every other kernel is a slot twin that
-// predicates itself on that state, and one trial is a PASS, a fixed sequence of segments:
+// is accepted.  That loop is ONE STATE MACHINE - lm_head_decide / lm_tail_decide over an LmDev, pgo_lm.hpp - WITH TWO DRIVERS.
+// uzl_pgo.hip's do_optimize_host keeps the state on the host and launches what it stamps, scalar round trip by scalar round trip.  Here
+// the state lives on the device, lane 0 of two one-workgroup kernels applies the same two functions to it (pgo_lm_kernels.hip), every
+// other kernel is a slot twin that predicates itself on that state, and one trial is a PASS, a fixed sequence of segments:
 //     head  = linearise, assemble | lm_head (chi2, lambda_0, adoption, refresh decision, setLambda) | [Schur reduction]
 //     setup = numeric + trial part of the hierarchy copy in use        (first iteration; synchronous rebuilds; lambda grown 32x)
 //     reb   = rebuild of the OTHER copy on the second stream           (lazy refresh: adopted by the next iteration)
@@ -15,8 +16,8 @@
 // The host enqueues a pass, looks at the snapshot ONCE, and chooses the next pass's segments and K from it (lm_plan_pass,
 // pgo_lm_pass.hpp: every rule of that choice, as a value the CPU tests hold).  Its choices are predictions only: lm_head stalls a graph whose pass lacks a segment it needs (kLmNeedSetup) and the next pass brings it; a solve that outlasts
 // its pass goes on in the next.  The DEVICE takes every decision from the graph's own state, so results do not depend on what the host
-// guessed.  Same kernel bodies, same order of operations, same scalar arithmetic (pgo_lm.hpp) as the host-driven loop: tests hold the
-// two to array_equal poses.
+// guessed.  Same kernel bodies, same order of operations, the very same decisions (pgo_lm.hpp) as the host-driven loop: tests hold the
+// two to array_equal poses, and both start from lm_initial_state below.
 //
 // One driver serves one graph (uzl_pgo_optimize) and many (uzl_pgo_batch_optimize): R slots, blockIdx.z = slot, a queue of graphs
 // behind them.  Graphs in different phases of their loops share the launches of a pass - none waits for another's trial count - and a
@@ -188,10 +189,9 @@ LmShape make_shape(const std::vector<uzl_pgo*>& hs, int nslots, bool batch_geome
     return sh;
 }
 
-namespace {
-
-// the state a graph starts its loop in
-LmDev initial_state(const uzl_pgo* h, int iterations)
+// The state a graph starts its LM loop in, for both drivers of the state machine (pgo_lm.hpp).  sync_rebuild: every rebuild of the
+// hierarchy runs in front of the solve it serves, none ahead on the second stream
+LmDev lm_initial_state(const uzl_pgo* h, int iterations, bool sync_rebuild)
 {
     LmDev I;
     memset(&I, 0, sizeof(I));
@@ -200,15 +200,23 @@ LmDev initial_state(const uzl_pgo* h, int iterations)
     I.init_pass = I.schur_pass = I.numeric_pass = I.trial_pass = I.build_pass = -1;
     I.iterations = iterations;
     I.max_it = h->cfg.pcg_max_iter > 0 ? h->cfg.pcg_max_iter : 6 * std::max(h->Dp.nb, 1);
-    // (do_optimize_host's async_ok: rebuilds run ahead for the small-graph class only - at 10k vertices the rebuild's GEMMs take more from
-    //  the overlapped PCG than they give back)
-    I.sync_rebuild = ml_async_level(h) ? 0 : 1;
+    I.sync_rebuild = sync_rebuild ? 1 : 0;
     I.guarded = (h->ml_mult || h->ml_ns_steps > 0) ? 1 : 0;
     I.ni = 2.; I.last_rel = 1e300; I.rate_ref = -1.; I.rate_last = -1.;
     I.tol_f2 = pgo_tol_f2(h->cfg); I.eps_t = pgo_eps_t(h->cfg); I.eps_r = pgo_eps_r(h->cfg);
     I.refresh_rel = ml_async_level(h) ? kRefreshRel : kRefreshRelSync; I.rate_drop = ml_rate_drop(h); I.tol2 = h->cfg.pcg_tol * h->cfg.pcg_tol; I.lambda_retake = kLambdaRetake; I.delta = h->cfg.huber_delta;
     return I;
 }
+// what a loop's final state says in uzl_pgo_stats (both drivers)
+void lm_stats(const LmDev& v, uzl_pgo_stats& S)
+{
+    S.iterations_done = v.st_iterations_done; S.lm_trials = v.st_lm_trials; S.pcg_iterations = v.st_pcg_iterations;
+    S.terminated_early = v.st_terminated_early; S.precond_builds = v.st_precond_builds;
+    S.chi2_initial = v.chi2_initial; S.chi2_final = v.chi_cur; S.lambda_final = v.lambda;
+}
+
+namespace {
+
 LmDev idle_state()
 {
     LmDev I;
@@ -316,7 +324,8 @@ void load_slot(LmDrive& d, int sl, bool first)
         lm_track_load(d.tracks[sl], j, h->cfg.pass_history == 1, R->hist);
         R->slots[sl] = make_slot(h, R->d_lm.p + sl, R->d_pub + sl);
         UZL_HIP(hipMemcpyAsync(R->d_slots.p + sl, &R->slots[sl], sizeof(LmSlot), hipMemcpyHostToDevice, s));
-        I = initial_state(h, d.o.iterations);
+        // (rebuilds run ahead for the small-graph class only - at 10k vertices the rebuild's GEMMs take more from the overlapped PCG than they give back)
+        I = lm_initial_state(h, d.o.iterations, !ml_async_level(h));
         d.n_active++;
     } else {
         lm_track_load(d.tracks[sl], -1, false, R->hist);
@@ -467,9 +476,7 @@ void finish_job(LmJob& J, uzl_pgo_stats* st, double wall_ms)
     uzl_pgo_stats S;
     memset(&S, 0, sizeof(S));
     stats_head(h, S);
-    S.iterations_done = v.st_iterations_done; S.lm_trials = v.st_lm_trials; S.pcg_iterations = v.st_pcg_iterations;
-    S.terminated_early = v.st_terminated_early; S.precond_builds = v.st_precond_builds;
-    S.chi2_initial = v.chi2_initial; S.chi2_final = v.chi_cur; S.lambda_final = v.lambda;
+    lm_stats(v, S);
     S.lm_passes = J.passes;
     S.solve_ms = wall_ms;
     S.structure_ms = h->structure_ms;
